@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the GIGA dense inference path on MI355X (driver contract in the task brief).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 With N > 1 and no launcher environment the script starts its own N ranks (`python -m torch.distributed.run`, one per GPU,
 rendezvous on 127.0.0.1) and rank 0 prints the JSON line; under an external `torch.distributed.run` it uses the ranks it
@@ -25,6 +25,9 @@ ONE JSON line (< 6 KB) is printed by rank 0: the contract keys, and
 Everything else -- `roofline.stages` (time, FLOPs and fraction of peak of EVERY kernel), the c4 legs (64 000 grasp queries per
 scene, f16 / f16x3 / mixed), c2 (ii), the c5-shaped training steps with their per-kernel tables, notes -- goes to the side file
 gpurun_out/bench_extra.json (GIGA_BENCH_EXTRA overrides the path), never to stdout: round 5's 31-KB line could not be parsed.
+
+--dump-outputs DIR writes what the LAST timed step returned (rank 0's shard: qual, rot, width, tsdf) as DIR/<name>.npy in
+float32, so that two builds can be compared output for output; the inputs and weights are seeded, identical from run to run.
 """
 import argparse
 import ctypes
@@ -174,7 +177,10 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="scenes per GPU per step")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     launched = "RANK" in os.environ and "MASTER_PORT" in os.environ
     if args.gpus > 1 and not launched:
@@ -289,7 +295,7 @@ def main():
     for i in range(K):
         marks[i].record()
         # even steps bracket the dominant kernel, odd steps the kernel VERDICT r01 names (conv_in + projection)
-        step(probe=(dom if i % 2 == 0 else NAMED_STAGE, evs[i][0], evs[i][1]))
+        last = step(probe=(dom if i % 2 == 0 else NAMED_STAGE, evs[i][0], evs[i][1]))
     marks[K].record()
     barrier()
     elapsed_s = time.perf_counter() - t0
@@ -299,6 +305,9 @@ def main():
         L.giga_event_destroy(a); L.giga_event_destroy(b)
     named_ms = named_ms or dom_ms
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(K)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("qual", "rot", "width", "tsdf"), last)))
+    del last
     if os.environ.get("GIGA_BENCH_DUMP_STEPS"):            # diagnosis: which of the K steps are the slow ones
         print("step_ms", " ".join(f"{v:.4f}" for v in step_ms), "| wall", f"{elapsed_s * 1e3:.4f}", "ms", file=sys.stderr)
     t_elapsed = torch.tensor([elapsed_s], dtype=torch.float64, device=dev)
@@ -402,6 +411,25 @@ def main():
     out["summary"] = summary_of(out)                      # LAST key: every named-config number inside the tail of the line
     print(emit(out), flush=True)
     finish()
+
+
+DUMP_LIMIT = 64 << 20                      # bytes: --dump-outputs keeps a fixed sample of scenes beyond this
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: every output of the timed step as <path>/<name>.npy (float32, scenes along axis 0).  Should they exceed
+    DUMP_LIMIT, the same fixed, seeded sample of scenes is kept of each, and its indices are written to scene_index.npy."""
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in outs.items()}
+    n = len(next(iter(arrs.values())))
+    per_scene = sum(a.nbytes for a in arrs.values()) / n
+    budget = DUMP_LIMIT - 4096                                     # (the .npy headers)
+    if per_scene * n > budget:
+        keep = np.sort(np.random.default_rng(0).choice(n, size=max(1, int(budget // (per_scene + 8))), replace=False))
+        arrs = {k: a[keep] for k, a in arrs.items()}
+        arrs["scene_index"] = keep.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 LINE_LIMIT = 6144                          # bytes: the driver parses ONE line; round 5's 31-KB line came back as parsed = null

@@ -3,6 +3,7 @@
 giga_amd/synth.py (write_training_set) (seed 1), with torch/numpy seeded before every item.
 
     python -m oracle.make_feed_goldens        ->  tests/golden/g12_dataset_items.npz, g13_dataset_items_augmented.npz (augment=True)
+    python -m oracle.make_feed_goldens multi  ->  tests/golden/g15_dataset_items_multi_occ.npz (several occupancy files per scene)
 """
 import os
 import tempfile
@@ -16,6 +17,7 @@ from oracle import ref_bootstrap
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "g12_dataset_items.npz")
 OUT_AUG = os.path.join(os.path.dirname(OUT), "g13_dataset_items_augmented.npz")
+OUT_MULTI = os.path.join(os.path.dirname(OUT), "g15_dataset_items_multi_occ.npz")
 DATASET_SEED, NUM_POINT_OCC, ITEMS = 1, 64, (0, 3, 7, 11, 29)
 
 
@@ -54,5 +56,41 @@ def main():
     print("wrote", OUT_AUG, os.path.getsize(OUT_AUG), "bytes")
 
 
+MULTI_OCC = {"plain": dict(seed=4, occ_files=(2, 4), items=(0, 5, 9, 17, 23), num_point_occ=128, augment=False),
+             "augmented": dict(seed=5, occ_files=(2, 3), items=(1, 6, 12, 20), num_point_occ=96, augment=True)}
+
+
+def multi_occ():
+    """Golden G15: the reference's own items on datasets with several occupancy files per scene, where its random file pick
+    (torch.randint over the directory listing) matters.  The listing order the reference saw is recorded per scene, so a reader
+    can be handed the same list on any file system; grids are recorded by their SHA-256 (they are bit-exact copies)."""
+    import hashlib
+    rec = {}
+    for tag, c in MULTI_OCC.items():
+        with tempfile.TemporaryDirectory() as tmp:
+            root, raw = os.path.join(tmp, "data"), os.path.join(tmp, "raw")
+            make_dataset.write_training_set(root, raw, seed=c["seed"], occ_files=c["occ_files"])
+            n, items = reference_items(root, raw, c["items"], c["num_point_occ"], augment=c["augment"])
+            scenes = sorted(os.listdir(os.path.join(raw, "occ")))
+            listing = [[p.name for p in Path(raw, "occ", sid).glob("*.npz")] for sid in scenes]
+        width = max(len(v) for v in listing)
+        rec[f"{tag}_n"] = n
+        rec[f"{tag}_scene_ids"] = np.array(scenes)
+        rec[f"{tag}_occ_listing"] = np.array([v + [""] * (width - len(v)) for v in listing])
+        for k, (x, (label, rot, w), pos, op, occ) in zip(c["items"], items):
+            x = np.asarray(x)
+            rec[f"{tag}_x_sha256_{k}"] = np.array(hashlib.sha256(np.ascontiguousarray(x).tobytes()).hexdigest())
+            rec[f"{tag}_x_dtype_{k}"] = np.array(str(x.dtype))
+            rec[f"{tag}_x_shape_{k}"] = np.array(x.shape)
+            rec[f"{tag}_label_{k}"] = np.asarray(label); rec[f"{tag}_rot_{k}"] = np.asarray(rot); rec[f"{tag}_width_{k}"] = np.asarray(w)
+            rec[f"{tag}_pos_{k}"] = np.asarray(pos); rec[f"{tag}_occ_points_{k}"] = np.asarray(op); rec[f"{tag}_occ_{k}"] = np.asarray(occ)
+    np.savez_compressed(OUT_MULTI, **rec)
+    print("wrote", OUT_MULTI, os.path.getsize(OUT_MULTI), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    import sys
+    if sys.argv[1:] == ["multi"]:
+        multi_occ()
+    else:
+        main()

@@ -81,24 +81,7 @@ def main():
     torch.set_grad_enabled(True)
     B, M = 4, 2048
     net.train()
-    x4 = torch.from_numpy(synth.tsdf_batch(10, B))
-    pos = torch.from_numpy(synth.query_points(10, B, 1, stream=2))
-    pos_occ = torch.from_numpy(synth.query_points(10, B, M, stream=3))
-    label, rots, width_t, occ = [torch.from_numpy(a) for a in synth.train_labels(10, B, M)]
-    out = net(x4, pos, p_tsdf=pos_occ)
-    # select + loss_fn, scripts/train_giga.py:154-195, evaluated with the reference's formulas
-    q_o, r_o, w_o, o_o = out
-    y_pred = (q_o.squeeze(-1), r_o.squeeze(1), w_o.squeeze(-1), torch.sigmoid(o_o))
-    import torch.nn.functional as F
-    lq = F.binary_cross_entropy(y_pred[0], label, reduction="none")
-    def quat(pr, t):
-        return 1.0 - torch.abs(torch.sum(pr * t, dim=1))
-    lr = torch.min(quat(y_pred[1], rots[:, 0]), quat(y_pred[1], rots[:, 1]))
-    lw = F.mse_loss(40 * y_pred[2], 40 * width_t, reduction="none")
-    lo = F.binary_cross_entropy(y_pred[3], occ, reduction="none").mean(-1)
-    loss = (lq + label * (lr + 0.01 * lw) + lo).mean()
-    net.zero_grad()
-    loss.backward()
+    (q_o, r_o, w_o, _), (lq, lr, lw, lo, loss) = _g4_step(net, B, M)
     g4 = {"weight_seed": WEIGHT_SEED, "first_scene": 10, "B": B, "M": M,
           "loss_qual": lq.mean().item(), "loss_rot": lr.mean().item(),
           "loss_width": lw.mean().item(), "loss_occ": lo.mean().item(), "loss_all": loss.item(),
@@ -141,6 +124,50 @@ def main():
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 
+
+def _g4_step(net, B, M):
+    """G4's train step (scripts/train_giga.py:141-218) on the reference network: forward, select + loss_fn evaluated with the
+    reference's formulas, backward.  Returns the network outputs and (loss_qual, loss_rot, loss_width, loss_occ, loss_all)."""
+    import torch.nn.functional as F
+    x4 = torch.from_numpy(synth.tsdf_batch(10, B))
+    pos = torch.from_numpy(synth.query_points(10, B, 1, stream=2))
+    pos_occ = torch.from_numpy(synth.query_points(10, B, M, stream=3))
+    label, rots, width_t, occ = [torch.from_numpy(a) for a in synth.train_labels(10, B, M)]
+    out = net(x4, pos, p_tsdf=pos_occ)
+    q_o, r_o, w_o, o_o = out
+    y_pred = (q_o.squeeze(-1), r_o.squeeze(1), w_o.squeeze(-1), torch.sigmoid(o_o))
+    lq = F.binary_cross_entropy(y_pred[0], label, reduction="none")
+    def quat(pr, t):
+        return 1.0 - torch.abs(torch.sum(pr * t, dim=1))
+    lr = torch.min(quat(y_pred[1], rots[:, 0]), quat(y_pred[1], rots[:, 1]))
+    lw = F.mse_loss(40 * y_pred[2], 40 * width_t, reduction="none")
+    lo = F.binary_cross_entropy(y_pred[3], occ, reduction="none").mean(-1)
+    loss = (lq + label * (lr + 0.01 * lw) + lo).mean()
+    net.zero_grad()
+    loss.backward()
+    return out, (lq, lr, lw, lo, loss)
+
+
+def conv_in_grad_f64():
+    """Adds grad_conv_in_w_f64 to G4 and G8: the conv_in weight gradient of their train step, its B x 40^3-term sums taken in
+    float64 from the fp32 gradient at the conv_in output.  The fp32 gradient (grad_conv_in_w) carries the summation order of the
+    CPU that made it -- a few 1e-5 on entries of ~3 between thread counts -- which this one does not.
+    python -m oracle.make_goldens conv_in_f64"""
+    for name, fixture in (("giga", "g4_train_step.npz"), ("giga_detach", "g8_detach.npz")):
+        net = ref_bootstrap.load_reference_giga(weights.make_state_dict(WEIGHT_SEED), name=name).train()
+        seen = {}
+        conv = net.encoder.conv_in
+        h1 = conv.register_forward_hook(lambda m, i, o: seen.update(x=i[0].detach()))
+        h2 = conv.register_full_backward_hook(lambda m, gi, go: seen.update(gy=go[0].detach()))
+        with torch.enable_grad():
+            _g4_step(net, 4, 2048)
+        h1.remove(); h2.remove()
+        gw = torch.nn.grad.conv3d_weight(seen["x"].double(), conv.weight.shape, seen["gy"].double(), padding=1)
+        path = os.path.join(OUT, fixture)
+        g = dict(np.load(path, allow_pickle=False))
+        g["grad_conv_in_w_f64"] = gw.numpy()
+        np.savez_compressed(path, **g)
+        print("wrote", path, float(np.abs(gw.numpy() - g["grad_conv_in_w"]).max()))
 
 def g7_generation():
     """G7: the reference's own Generator3D.eval_points (conv_onet/generation.py:326-358, chunked decode_occ on cached
@@ -288,6 +315,58 @@ def g11_train_helpers():
     print("wrote", path, float(loss))
 
 
+PLANE_STRIDE = 8
+
+
+def plane_sample(plane):
+    """Every PLANE_STRIDE-th value of a plane tensor in flat order, the offset rotating through the stride: all scenes, channels
+    and pixel columns are visited."""
+    flat = plane.detach().reshape(-1).numpy()
+    n = flat.size // PLANE_STRIDE
+    return flat[np.arange(n) * PLANE_STRIDE + np.arange(n) % PLANE_STRIDE]
+
+
+def plane_sums(plane):
+    """(B, C, 2) float64: sum and absolute sum of every (scene, channel) image of a (B, C, H, W) plane tensor."""
+    t = plane.detach().double()
+    return torch.stack((t.sum((2, 3)), t.abs().sum((2, 3))), -1).numpy()
+
+
+def g14_reference_network():
+    """G14: what tests/test_oracle_vs_reference.py compares the oracle with -- the reference network's state-dict layout (names
+    and shapes, weight seed 11), its forward (qual, rot, width, tsdf) and encoder planes on 2 realistic scenes from scene 20 x
+    777 points (stream 5, half width 0.55), and the plane-cell indices its coordinate2index(normalize_coordinate(...)) assigns to
+    the 40^3 voxel centres.  Of each plane: every PLANE_STRIDE-th value (plane_sample, see plane_sample()) and the float64 sum and
+    absolute sum of every (scene, channel) image, which keeps the fixture small.  python -m oracle.make_goldens g14"""
+    from giga_amd import synth, weights
+    from oracle import ref_bootstrap
+    sd = weights.make_state_dict(11)
+    net = ref_bootstrap.load_reference_giga(sd)
+    from vgn.ConvONets.common import coordinate2index, normalize_coordinate
+    ref_sd = net.state_dict()
+    shapes = np.zeros((len(ref_sd), 7), np.int64)                 # (rank, dims...) zero-padded
+    for i, v in enumerate(ref_sd.values()):
+        shapes[i, 0] = v.dim()
+        shapes[i, 1:1 + v.dim()] = v.shape
+    x = torch.from_numpy(synth.tsdf_batch(20, 2, realistic=True))
+    p = torch.from_numpy(synth.query_points(20, 2, 777, stream=5, half_width=0.55))
+    with torch.no_grad():
+        qual, rot, width, tsdf = net(x, p, p_tsdf=p)
+        planes = net.encode_inputs(x)
+    lin = torch.linspace(-0.5, 0.5, 40)
+    gx, gy, gz = torch.meshgrid(lin, lin, lin, indexing="ij")
+    vox = torch.stack((gx, gy, gz), -1).reshape(1, -1, 3)
+    idx = {f"index_{k}": coordinate2index(normalize_coordinate(vox.clone(), plane=k, padding=0), 40)[0, 0].numpy().astype(np.int16)
+           for k in ("xz", "xy", "yz")}
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "g14_reference_network.npz")
+    np.savez_compressed(out, weight_seed=11, first_scene=20, n_points=777, stream=5, half_width=0.55,
+                        param_names=np.array(list(ref_sd.keys())), param_shapes=shapes,
+                        qual=qual.numpy(), rot=rot.numpy(), width=width.numpy(), tsdf=tsdf.numpy(),
+                        **{f"plane_{k}_sample": plane_sample(v) for k, v in planes.items()},
+                        **{f"plane_{k}_sums": plane_sums(v) for k, v in planes.items()}, **idx)
+    print("wrote", out, os.path.getsize(out), "bytes")
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     if which in ("all", "main"):
@@ -302,3 +381,7 @@ if __name__ == "__main__":
         g10_planner()
     if which in ("all", "g11"):
         g11_train_helpers()
+    if which in ("all", "conv_in_f64"):
+        conv_in_grad_f64()
+    if which in ("all", "g14"):
+        g14_reference_network()

@@ -84,3 +84,35 @@ def test_contract_line_is_small_and_round_trips(tmp_path):
     full["summary"] = {f"k{i}": "x" * 100 for i in range(100)}
     text = bench.emit(full, path=str(side))
     assert len(text) < bench.LINE_LIMIT and all(k in json.loads(text) for k in bench.CONTRACT_KEYS)
+
+
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per output; beyond the size limit the same fixed sample of scenes is kept of every
+    output (and its indices written), identically from call to call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    outs = {"qual": torch.rand(6, 1), "rot": torch.rand(6, 1, 4, dtype=torch.float64), "width": torch.rand(6, 1),
+            "tsdf": torch.rand(6, 2048, dtype=torch.float16)}
+    bench.dump_outputs(str(tmp_path / "all"), outs)
+    for k, v in outs.items():
+        a = np.load(tmp_path / "all" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, v.float().numpy()), k
+    assert not (tmp_path / "all" / "scene_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4096 + 2 * (4 + 16 + 4 + 2048 * 4 + 8) + 100)      # room for two scenes
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), outs)
+    keep = np.load(tmp_path / "s1" / "scene_index.npy").astype(np.int64)
+    assert len(keep) == 2 and np.array_equal(keep, np.load(tmp_path / "s2" / "scene_index.npy"))
+    total = 0
+    for k, v in outs.items():
+        a = np.load(tmp_path / "s1" / f"{k}.npy")
+        assert np.array_equal(a, v.float().numpy()[keep]) and np.array_equal(a, np.load(tmp_path / "s2" / f"{k}.npy")), k
+        total += os.path.getsize(tmp_path / "s1" / f"{k}.npy")
+    assert total + os.path.getsize(tmp_path / "s1" / "scene_index.npy") <= bench.DUMP_LIMIT
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -1,24 +1,13 @@
 """SURVEY 8f-3, reader half: the batched reader of the reference's training data (giga_amd/dataset.py) against golden G12
-(the reference's own DatasetVoxelOccFile.__getitem__ on the synthetic on-disk dataset of giga_amd/synth.py (write_training_set)) and, when
-/root/reference is present, against the live reference class including the random occupancy-file choice."""
+(the reference's own DatasetVoxelOccFile.__getitem__ on the synthetic on-disk dataset of giga_amd/synth.py (write_training_set)) and
+golden G15 (the same class on datasets with several occupancy files per scene, including its random occupancy-file choice)."""
 import os
 
 import numpy as np
-import pytest
 import torch
 
 from giga_amd import dataset
 from giga_amd import synth as make_dataset
-from oracle import ref_bootstrap
-
-
-def _same_item(a, b):
-    xa, (la, ra, wa), pa, opa, oa = a
-    xb, (lb, rb, wb), pb, opb, ob = b
-    assert np.array_equal(np.asarray(xa), np.asarray(xb)) and np.asarray(xa).dtype == np.asarray(xb).dtype
-    for u, v in ((la, lb), (ra, rb), (wa, wb), (pa, pb), (opa, opb), (oa, ob)):
-        u, v = np.asarray(u), np.asarray(v)
-        assert u.shape == v.shape and u.dtype == v.dtype and np.array_equal(u, v)
 
 
 def test_items_match_golden_g12(tmp_path, golden):
@@ -135,18 +124,47 @@ def test_shared_memory_ring_survives_an_abandoned_epoch(tmp_path):
         ring.close()
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_bootstrap.reference_available(), reason="/root/reference not present")
-def test_items_match_live_reference_class(tmp_path):
-    from oracle.make_feed_goldens import reference_items
+def _multi_occ_case(tmp_path, golden, tag):
+    """The dataset of golden G15's case `tag` rebuilt on disk, a reader over it that lists each scene's occupancy files in the
+    order the reference saw them, and the reference's items."""
+    from oracle.make_feed_goldens import MULTI_OCC
+    g, c = golden("g15_dataset_items_multi_occ.npz"), MULTI_OCC[tag]
     root, raw = str(tmp_path / "data"), str(tmp_path / "raw")
-    make_dataset.write_training_set(root, raw, seed=4, occ_files=(2, 4))          # several occupancy files: the random pick matters
-    idx = (0, 5, 9, 17, 23)
-    _, ref = reference_items(root, raw, idx, 128)
-    ds = dataset.GraspOccDataset(root, raw, num_point_occ=128)
+    make_dataset.write_training_set(root, raw, seed=c["seed"], occ_files=c["occ_files"])   # several occupancy files: the random pick matters
+    ds = dataset.GraspOccDataset(root, raw, num_point_occ=c["num_point_occ"], augment=c["augment"])
+    assert len(ds) == int(g[f"{tag}_n"])
+    for sid, names in zip(g[f"{tag}_scene_ids"], g[f"{tag}_occ_listing"]):
+        listed = sorted(p.name for p in ds.occ_paths(str(sid)))
+        names = [str(f) for f in names if f]
+        assert listed == sorted(names), sid
+        ds._occ_paths[str(sid)] = [ds.raw_root / "occ" / str(sid) / f for f in names]
+    ref = []
+    for k in c["items"]:
+        x = (g[f"{tag}_x_sha256_{k}"], g[f"{tag}_x_dtype_{k}"], g[f"{tag}_x_shape_{k}"])
+        grasp = tuple(g[f"{tag}_{key}_{k}"] for key in ("label", "rot", "width"))
+        ref.append((x, grasp, *(g[f"{tag}_{key}_{k}"] for key in ("pos", "occ_points", "occ"))))
+    return ds, c["items"], ref
+
+
+def _same_item_as_golden(a, b):
+    import hashlib
+    xa, (la, ra, wa), pa, opa, oa = a
+    (sha, dtype, shape), (lb, rb, wb), pb, opb, ob = b
+    xa = np.ascontiguousarray(np.asarray(xa))
+    assert str(xa.dtype) == str(dtype) and xa.shape == tuple(shape)
+    assert hashlib.sha256(xa.tobytes()).hexdigest() == str(sha)
+    for u, v in ((la, lb), (ra, rb), (wa, wb), (pa, pb), (opa, opb), (oa, ob)):
+        u, v = np.asarray(u), np.asarray(v)
+        assert u.shape == v.shape and u.dtype == v.dtype and np.array_equal(u, v)
+
+
+def test_items_match_live_reference_class(tmp_path, golden):
+    """The reference's own DatasetVoxelOccFile items (golden G15, oracle/make_feed_goldens.py multi), random occupancy-file
+    choice included."""
+    ds, idx, ref = _multi_occ_case(tmp_path, golden, "plain")
     for i, r in zip(idx, ref):
         torch.manual_seed(100 + i); np.random.seed(200 + i)
-        _same_item(ds.item(i), r)
+        _same_item_as_golden(ds.item(i), r)
 
 
 def test_augmented_items_match_golden_g13(tmp_path, golden):
@@ -187,15 +205,9 @@ def test_augmented_items_match_golden_g13(tmp_path, golden):
     assert rb[0].shape == (2, 40, 40, 40) and rb[2].shape == (2, 3) and rb[1][1].shape == (2, 2, 4)
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_bootstrap.reference_available(), reason="/root/reference not present")
-def test_augmented_items_match_live_reference_class(tmp_path):
-    from oracle.make_feed_goldens import reference_items
-    root, raw = str(tmp_path / "data"), str(tmp_path / "raw")
-    make_dataset.write_training_set(root, raw, seed=5, occ_files=(2, 3))
-    idx = (1, 6, 12, 20)
-    _, ref = reference_items(root, raw, idx, 96, augment=True)
-    ds = dataset.GraspOccDataset(root, raw, num_point_occ=96, augment=True)
+def test_augmented_items_match_live_reference_class(tmp_path, golden):
+    """As above with augment=True (golden G15)."""
+    ds, idx, ref = _multi_occ_case(tmp_path, golden, "augmented")
     for i, r in zip(idx, ref):
         torch.manual_seed(100 + i); np.random.seed(200 + i)
-        _same_item(ds.item(i), r)
+        _same_item_as_golden(ds.item(i), r)

@@ -4,6 +4,7 @@ uses the closed-form axis mean instead of scatter_mean and torch.where instead o
 so summation order differs slightly from the reference)."""
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from giga_amd import synth, weights
 from oracle import giga_oracle as O
@@ -75,8 +76,24 @@ def test_g3_inference_lattice(golden, sd7):
         assert abs(t.double().sum().item() - s[0]) <= 2e-5 * max(1.0, s[1])
 
 
-def test_g4_train_losses_and_grads(golden, sd7):
+def _conv_in_grad_f64(monkeypatch):
+    """conv_in's weight gradient sums B x 40^3 terms per entry: in fp32 the order of that sum (the CPU, its thread count) moves
+    entries of ~3 by a few 1e-5.  Returns a function that gives it summed in float64 from the fp32 gradient at the conv output
+    of the oracle's last backward (golden key grad_conv_in_w_f64 is the reference's, taken the same way)."""
+    seen = {}
+
+    def conv_in_relu(sd, x):                           # O.conv_in_relu, keeping its input and the gradient at the conv output
+        y = F.conv3d(x[:, None], sd["encoder.conv_in.weight"], sd["encoder.conv_in.bias"], padding=1)
+        y.retain_grad()
+        seen.update(x=x[:, None].detach(), y=y, w=sd["encoder.conv_in.weight"])
+        return F.relu(y)
+    monkeypatch.setattr(O, "conv_in_relu", conv_in_relu)
+    return lambda: torch.nn.grad.conv3d_weight(seen["x"].double(), seen["w"].shape, seen["y"].grad.double(), padding=1)
+
+
+def test_g4_train_losses_and_grads(golden, sd7, monkeypatch):
     g = golden("g4_train_step.npz")
+    grad_conv_in = _conv_in_grad_f64(monkeypatch)
     B, M, s0 = int(g["B"]), int(g["M"]), int(g["first_scene"])
     sd = {k: v.clone().requires_grad_(True) for k, v in sd7.items()}
     x = torch.from_numpy(synth.tsdf_batch(s0, B))
@@ -93,7 +110,9 @@ def test_g4_train_losses_and_grads(golden, sd7):
         got = sd[n].grad.double().norm().item()
         assert abs(got - ref) <= 1e-4 * max(ref, 1e-6) + 1e-9, (n, got, ref)
     close(sd["decoder_qual.fc_out.weight"].grad, g["grad_fc_out_qual"], tol=1e-6)
-    close(sd["encoder.conv_in.weight"].grad, g["grad_conv_in_w"], tol=1e-5)
+    gw = grad_conv_in()
+    close(gw, g["grad_conv_in_w_f64"], tol=1e-5)
+    close(sd["encoder.conv_in.weight"].grad, gw, tol=1e-4)           # autograd's fp32 gradient is that sum
 
 
 def test_g5_edges(golden, sd7):
@@ -118,9 +137,10 @@ def test_g7_generation_eval_points(golden, sd7):
     assert np.abs(got - g["logits"]).max() < 2e-5
 
 
-def test_g8_detach_gradients(golden, sd7):
+def test_g8_detach_gradients(golden, sd7, monkeypatch):
     """giga_detach (networks.py:143-169): the oracle's detach_tsdf gradients == the reference network's."""
     g = golden("g8_detach.npz")
+    grad_conv_in = _conv_in_grad_f64(monkeypatch)
     B, M, s0 = int(g["B"]), int(g["M"]), int(g["first_scene"])
     x = torch.from_numpy(synth.tsdf_batch(s0, B))
     pos = torch.from_numpy(synth.query_points(s0, B, 1, stream=2))
@@ -134,8 +154,10 @@ def test_g8_detach_gradients(golden, sd7):
     for n, ref in zip([str(n) for n in g["grad_names"]], g["grad_norms"]):
         got = sdg[n].grad.double().norm().item()
         assert abs(got - ref) <= 1e-4 * max(ref, 1e-6) + 1e-9, (n, got, ref)
-    ref_w = g["grad_conv_in_w"]
-    assert np.abs(sdg["encoder.conv_in.weight"].grad.numpy() - ref_w).max() < 1e-5 * np.abs(ref_w).max()
+    ref_w = g["grad_conv_in_w_f64"]
+    gw = grad_conv_in().numpy()
+    assert np.abs(gw - ref_w).max() < 1e-5 * np.abs(ref_w).max()
+    assert np.abs(sdg["encoder.conv_in.weight"].grad.numpy() - gw).max() < 1e-4 * np.abs(ref_w).max()   # autograd's fp32 sum
 
 
 def test_g9_ablation_variants(golden):
