@@ -79,6 +79,8 @@ _SIGNATURES = {
                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_decoder_point_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+                                + [ctypes.c_void_p] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "giga_host_register": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
     "giga_host_unregister": (ctypes.c_int, [ctypes.c_void_p]),
     "giga_tsdf_scatter_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),

@@ -15,7 +15,9 @@ unchanged and initialisation matches the reference); all arithmetic runs in the 
 kernels of libgiga_hip.so through `giga_amd._capi`.  Inputs must live on a HIP device: there is no
 CPU path (use the reference for that).  `ConvolutionalOccupancyNetwork.forward` is differentiable
 w.r.t. the parameters (fp32 HIP backward, giga_amd/training.py); the piecewise entry points
-(`encode_inputs`, `decode`, `LocalDecoder.forward`, ...) are inference-only and raise under autograd.
+(`encode_inputs`, `decode`, `LocalDecoder.forward`, ...) are inference-only and raise under autograd while parameters require
+grad.  With frozen parameters, `forward`, `decode`, `decode_occ` and `infer_geo` are differentiable w.r.t. the query points
+(giga_decoder_point_grad; `grad_refine` uses it directly).
 """
 import os
 
@@ -154,10 +156,14 @@ class _PackedWeights:
     def __init__(self):
         self.key = None
         self.blob = None
+        self.bkey = None
+        self.bwd_blob = None
 
     def invalidate(self):
         self.key = None
         self.blob = None
+        self.bkey = None
+        self.bwd_blob = None
 
     def get(self, params, head_present, device):
         device = torch.device(device)
@@ -169,6 +175,19 @@ class _PackedWeights:
             self.blob = _capi.pack_weights(flat, head_present).to(device)
             self.key = key
         return self.blob
+
+    def get_bwd(self, params, head_present, device):
+        """The backward blob (transposed decoder images) of the same weights, cached and keyed like `get`: the point gradients
+        (giga_decoder_point_grad) read both blobs."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        key = (head_present, str(device)) + tuple((p.data_ptr(), p._version) for p in params)
+        if key != self.bkey:
+            flat = _flat_params(params, "cpu")
+            self.bwd_blob = _capi.pack_bwd_weights(flat, head_present).to(device)
+            self.bkey = key
+        return self.bwd_blob
 
 
 def _check_no_grad(module):
@@ -396,6 +415,90 @@ def decode_heads(nhwc, p, blob, head_mask, precision, post, probe=None, folded=F
     return out
 
 
+_HEAD_SLOTS = ("decoder_qual", "decoder_rot", "decoder_width", "decoder_tsdf")
+
+
+def decoder_point_grad(nhwc32, p, blob, bwd_blob, head_mask, douts, want_outputs=False):
+    """d/dp of sum_h <douts[h], head_h(p)> for the heads in `head_mask`, the planes constant (giga_decoder_point_grad, one launch).
+    nhwc32: fp32 FINAL planes [3,B,40,40,32] (not folded); p (B,N,3), or (1,N,3) shared by all B scenes (the gradient is then
+    summed over the scenes); douts: name -> gradient of the post-epilogue output ((B,N), rot (B,N,4)).
+    Returns dp shaped like p, and with want_outputs the post-epilogue head outputs (fp32 decoder values) as a dict."""
+    dev = _capi.device_of(nhwc32, p, blob, bwd_blob)
+    if nhwc32.dtype != torch.float32:
+        raise ValueError("the point gradient reads fp32 planes")
+    B = nhwc32.shape[1]
+    if p.dim() != 3 or p.shape[-1] != 3 or p.shape[0] not in (1, B):
+        raise ValueError(f"expected (B,N,3) or (1,N,3) query points for {B} scenes, got {tuple(p.shape)}")
+    shared = p.shape[0] != B
+    N = p.shape[1]
+    pp = p.detach().float().expand(B, N, 3).contiguous()
+    dp = torch.empty((B, N, 3), device=dev)
+    d, o = [], []
+    for i, name in enumerate(_HEAD_SLOTS):
+        shape = (B, N, 4) if i == 1 else (B, N)
+        g = douts.get(name) if head_mask >> i & 1 else None
+        if head_mask >> i & 1 and g is None:
+            g = torch.zeros(shape, device=dev)
+        d.append(g.detach().float().expand(shape).contiguous() if g is not None else None)
+        o.append(torch.empty(shape, device=dev) if want_outputs and head_mask >> i & 1 else None)
+    if B * N > 0:
+        with torch.cuda.device(dev):
+            _capi.check(_capi.lib().giga_decoder_point_grad(
+                _capi.ptr(nhwc32), _capi.ptr(pp), _capi.ptr(blob), _capi.ptr(bwd_blob), head_mask,
+                *[_capi.ptr(t) for t in d], _capi.ptr(dp), *[_capi.ptr(t) for t in o], B, N, 0, _capi.stream_ptr(dev)),
+                "giga_decoder_point_grad")
+    if shared:
+        dp = dp.sum(0, keepdim=True)
+    dp = dp.to(p.dtype)
+    if want_outputs:
+        return dp, {name: t for name, t in zip(_HEAD_SLOTS, o) if t is not None}
+    return dp
+
+
+def _wants_point_grad(module, *points):
+    """Autograd w.r.t. the query points: grad enabled, some point tensor requires grad, no parameter does."""
+    if not torch.is_grad_enabled() or not any(q is not None and q.requires_grad for q in points):
+        return False
+    return not any(q.requires_grad for q in module.parameters())
+
+
+class _PointGrad(torch.autograd.Function):
+    """p -> the head outputs `run()` computes (the inference path: values unchanged), differentiable w.r.t. p.  The planes
+    are constants; the backward is one giga_decoder_point_grad launch on `grad_src()` = (fp32 final planes, blob, bwd blob)."""
+
+    @staticmethod
+    def forward(ctx, p, run, grad_src, names):
+        outs = run()
+        ctx.grad_src, ctx.names = grad_src, names
+        ctx.save_for_backward(p)
+        return outs
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        (p,) = ctx.saved_tensors
+        douts, mask = {}, 0
+        for nm, g in zip(ctx.names, gouts):
+            mask |= _capi.HEAD_BITS[nm]
+            if g is not None:
+                douts[nm] = g
+        if not douts:
+            return None, None, None, None
+        nhwc32, blob, bwd_blob = ctx.grad_src()
+        return decoder_point_grad(nhwc32, p, blob, bwd_blob, mask, douts), None, None, None
+
+
+class _LazyPlanes:
+    """The fp32 final planes for a point-gradient backward, built on first use and shared by the calls of one forward."""
+
+    def __init__(self, fn):
+        self.fn, self.v = fn, None
+
+    def __call__(self):
+        if self.v is None:
+            self.v = self.fn()
+        return self.v
+
+
 class LocalDecoder(nn.Module):
     """decoder.py:61-206.  forward(p:(B,N,3), c_plane:dict) -> (B,N) if out_dim == 1 else (B,N,out_dim)."""
 
@@ -550,6 +653,16 @@ class ConvolutionalOccupancyNetwork(_ParamListCache, nn.Module):
             self.invalidate_packed()
         return self._packed.get(self._ordered_params(), self._head_present(), device)
 
+    def packed_bwd_blob(self, device):
+        """Backward blob of the current weights (the point gradients need it next to `packed_blob`)."""
+        self.packed_blob(device)                             # (drops both caches after a training step)
+        return self._packed.get_bwd(self._ordered_params(), self._head_present(), device)
+
+    def _final_planes32(self, inputs):
+        """fp32 final planes (no conv_final folding) of `inputs`: what a point gradient differentiates through."""
+        nhwc, _ = self.encoder.encode_nhwc(inputs, blob=self.packed_blob(inputs.device), precision="fp32")
+        return nhwc
+
     # -- reference API ------------------------------------------------------------------------------
     def forward(self, inputs, p, p_tsdf=None, sample=True, _probe=None, **kwargs):
         """models/__init__.py:42-67.  inputs (B,40,40,40); p (B,N,3); p_tsdf (B,M,3) ->
@@ -563,11 +676,22 @@ class ConvolutionalOccupancyNetwork(_ParamListCache, nn.Module):
         # encoder and decoders are called back to back here, so conv_final is folded into the heads' fc_c weights and
         # never launched (GIGA_FOLD_FINAL); encode_inputs / decode keep exchanging the final planes, as the reference does
         nhwc, _ = self.encoder.encode_nhwc(inputs, blob=blob, precision=self.precision, probe=_probe, fold_final=True)
-        g = decode_heads(nhwc, p, blob, 7, self.precision, post=True, folded=True)
-        out = (g["decoder_qual"], g["decoder_rot"], g["decoder_width"])
+
+        def grasp():
+            g = decode_heads(nhwc, p, blob, 7, self.precision, post=True, folded=True)
+            return g["decoder_qual"], g["decoder_rot"], g["decoder_width"]
+
+        def occ():
+            return (decode_heads(nhwc, p_tsdf, blob, 8, self.precision, post=False, folded=True)["decoder_tsdf"],)
+
+        if not _wants_point_grad(self, p, p_tsdf):
+            return grasp() + (occ() if p_tsdf is not None else ())
+        # differentiable w.r.t. the points: same values; the backward re-encodes the final fp32 planes once (the folded planes
+        # above have no transposed fc_c images) and runs one point-gradient launch per point set
+        src = _LazyPlanes(lambda: (self._final_planes32(inputs), blob, self.packed_bwd_blob(inputs.device)))
+        out = _PointGrad.apply(p, grasp, src, _HEAD_SLOTS[:3]) if p.requires_grad else grasp()
         if p_tsdf is not None:
-            t = decode_heads(nhwc, p_tsdf, blob, 8, self.precision, post=False, folded=True)
-            out = out + (t["decoder_tsdf"],)
+            out = out + (_PointGrad.apply(p_tsdf, occ, src, _HEAD_SLOTS[3:]) if p_tsdf.requires_grad else occ())
         return out
 
     def _param_list(self):
@@ -664,7 +788,14 @@ class ConvolutionalOccupancyNetwork(_ParamListCache, nn.Module):
     def _decode_tsdf(self, p, c):
         blob = self.packed_blob(p.device)
         nhwc = _planes_to_nhwc(c, self.precision)
-        return decode_heads(nhwc, p, blob, 8, self.precision, post=False)["decoder_tsdf"]
+
+        def occ():
+            return (decode_heads(nhwc, p, blob, 8, self.precision, post=False)["decoder_tsdf"],)
+
+        if _wants_point_grad(self, p):
+            src = _LazyPlanes(lambda: (_planes_to_nhwc(c, "fp32"), blob, self.packed_bwd_blob(p.device)))
+            return _PointGrad.apply(p, occ, src, _HEAD_SLOTS[3:])[0]
+        return occ()[0]
 
     def decode_occ(self, p, c, **kwargs):
         """models/__init__.py:100-109."""
@@ -677,8 +808,15 @@ class ConvolutionalOccupancyNetwork(_ParamListCache, nn.Module):
         _capi.require_device(p)
         blob = self.packed_blob(p.device)
         nhwc = _planes_to_nhwc(c, self.precision)
-        g = decode_heads(nhwc, p, blob, 7, self.precision, post=True)
-        return g["decoder_qual"], g["decoder_rot"], g["decoder_width"]
+
+        def grasp():
+            g = decode_heads(nhwc, p, blob, 7, self.precision, post=True)
+            return g["decoder_qual"], g["decoder_rot"], g["decoder_width"]
+
+        if _wants_point_grad(self, p):
+            src = _LazyPlanes(lambda: (_planes_to_nhwc(c, "fp32"), blob, self.packed_bwd_blob(p.device)))
+            return _PointGrad.apply(p, grasp, src, _HEAD_SLOTS[:3])
+        return grasp()
 
     def to(self, device):
         """models/__init__.py:126-134."""
@@ -687,10 +825,32 @@ class ConvolutionalOccupancyNetwork(_ParamListCache, nn.Module):
         return model
 
     def grad_refine(self, x, pos, bound_value=0.0125, lr=1e-6, num_step=1):
-        """models/__init__.py:136-164 optimises the query POSITIONS by gradient ascent on the predicted quality; it needs
-        d qual / d p, which the HIP decoder does not produce (its backward yields parameter gradients only)."""
-        raise NotImplementedError("grad_refine needs gradients with respect to the query points; libgiga_hip's backward "
-                                  "computes parameter gradients only (DESIGN.md, out of SURVEY 8's scope)")
+        """models/__init__.py:136-164: move every grasp query uphill on the predicted quality, `num_step` steps of
+        torch.optim.SGD(lr) on -qual.sum() (pos <- pos + lr * d(sum qual)/d pos), clamp to [pos - bound_value, pos + bound_value]
+        after the loop, then run the forward at the refined points.  Returns (qual, pos_refined, rot, width); leaves the
+        module in eval mode, as the reference does.
+        The scene is encoded ONCE (the planes do not depend on pos); a step is one giga_decoder_point_grad launch (qual head)
+        plus one fused update.  The steps run in fp32 whatever `set_precision` says; the final forward uses the model's
+        precision.  Deviation: the reference's `p.requres_grad = False` (sic) leaves its parameters trainable, so its
+        backward also fills their `.grad`; here `.grad` is left untouched."""
+        _capi.require_device(x, pos)
+        self.eval()
+        with torch.no_grad():
+            pos_tmp = pos.detach().clone()
+            l_bound, u_bound = pos - bound_value, pos + bound_value
+            if num_step > 0:
+                if pos.dtype != torch.float32:
+                    raise ValueError("grad_refine runs its steps in fp32: pass float32 positions")
+                blob = self.packed_blob(x.device)
+                bwd_blob = self.packed_bwd_blob(x.device)
+                nhwc32 = self._final_planes32(x)
+                ones = torch.ones(pos.shape[:-1], device=pos.device)
+                for _ in range(num_step):
+                    dq = decoder_point_grad(nhwc32, pos_tmp, blob, bwd_blob, 1, {"decoder_qual": ones})
+                    pos_tmp.add_(dq, alpha=lr)               # SGD on -qual.sum(): pos - lr * (-dq)
+            pos_tmp = torch.maximum(torch.minimum(pos_tmp, u_bound), l_bound)
+            qual, rot, width = self.forward(x, pos_tmp)
+        return qual, pos_tmp, rot, width
 
 
 class ConvolutionalOccupancyNetworkGeometry(_ParamListCache, nn.Module):
@@ -718,12 +878,25 @@ class ConvolutionalOccupancyNetworkGeometry(_ParamListCache, nn.Module):
     def packed_blob(self, device):
         return self._packed.get(self._ordered_params(), 8, device)
 
+    def packed_bwd_blob(self, device):
+        return self._packed.get_bwd(self._ordered_params(), 8, device)
+
     def forward(self, inputs, p, p_tsdf, sample=True, **kwargs):
         _check_no_grad(self)
         _capi.require_device(inputs, p_tsdf)
         blob = self.packed_blob(inputs.device)
         nhwc, _ = self.encoder.encode_nhwc(inputs, blob=blob, precision=self.precision)
-        return decode_heads(nhwc, p_tsdf, blob, 8, self.precision, post=False)["decoder_tsdf"]
+
+        def occ():
+            return (decode_heads(nhwc, p_tsdf, blob, 8, self.precision, post=False)["decoder_tsdf"],)
+
+        if _wants_point_grad(self, p_tsdf):
+            def planes():
+                if nhwc.dtype == torch.float32 and self.precision == "fp32":
+                    return nhwc, blob, self.packed_bwd_blob(inputs.device)
+                return self.encoder.encode_nhwc(inputs, blob=blob, precision="fp32")[0], blob, self.packed_bwd_blob(inputs.device)
+            return _PointGrad.apply(p_tsdf, occ, _LazyPlanes(planes), _HEAD_SLOTS[3:])[0]
+        return occ()[0]
 
     def infer_geo(self, inputs, p_tsdf, **kwargs):
         return self.forward(inputs, None, p_tsdf)
@@ -739,8 +912,15 @@ class ConvolutionalOccupancyNetworkGeometry(_ParamListCache, nn.Module):
     def decode_occ(self, p, c, **kwargs):
         _check_no_grad(self)
         nhwc = _planes_to_nhwc(c, self.precision)
-        logits = decode_heads(nhwc, p, self.packed_blob(p.device), 8, self.precision, post=False)["decoder_tsdf"]
-        return dist.Bernoulli(logits=logits)
+        blob = self.packed_blob(p.device)
+
+        def occ():
+            return (decode_heads(nhwc, p, blob, 8, self.precision, post=False)["decoder_tsdf"],)
+
+        if _wants_point_grad(self, p):
+            src = _LazyPlanes(lambda: (_planes_to_nhwc(c, "fp32"), blob, self.packed_bwd_blob(p.device)))
+            return dist.Bernoulli(logits=_PointGrad.apply(p, occ, src, _HEAD_SLOTS[3:])[0])
+        return dist.Bernoulli(logits=occ()[0])
 
     def to(self, device):
         model = super().to(device)

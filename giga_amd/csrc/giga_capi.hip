@@ -31,6 +31,9 @@ int launch_decoder_backward(const float* planes, const float* p, const uint8_t* 
                             float* grads, int head_present, float* scratch, int B, int N, hipStream_t s, bool writes_planes,
                             SideScope* side);
 int launch_plane_gather(const float* dcbuf, const float* p, float* gplanes, int B, int N, hipStream_t s);
+// giga_decoder_pgrad.hip
+int launch_decoder_point_grad(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob, int head_mask,
+                              const float* const* douts, float* const* outs, float* dp, int B, int N, hipStream_t s);
 // giga_decoder_train16.hip (bf16 decoder of the bf16 training step)
 int launch_dect_forward(const float* planes, const float* p, const uint8_t* blob, int head_mask, float* const* outs, int B, int N,
                         int post, hipStream_t s);
@@ -610,6 +613,25 @@ int giga_backward(const float* tsdf, const void* packed, const void* bwd_packed,
     rc |= launch_encoder_backward(tsdf, blob, bblob, static_cast<const uint8_t*>(enc_workspace_fwd), gplanes, gws,
                                   grads, head_present, B, s, bf16_convs, convin_mask, side);
     return rc;
+}
+
+int giga_decoder_point_grad(const void* planes_nhwc, const float* p, const void* packed, const void* bwd_packed,
+                            int head_mask, const float* dqual, const float* drot, const float* dwidth, const float* dtsdf,
+                            float* dp, float* out_qual, float* out_rot, float* out_width, float* out_tsdf,
+                            int B, int N, int flags, void* stream) {
+    if (head_mask <= 0 || (head_mask & ~15) != 0) return -1;
+    if (B <= 0 || N <= 0) return -1;
+    if (B > GIGA_MAX_SCENES) return -7;
+    if ((long long)B * N >= (1LL << 31)) return -1;         // split_scene's point index is exact below 2^31
+    if (flags != 0) return -5;
+    if (!planes_nhwc || !p || !packed || !bwd_packed || !dp) return -1;
+    const float* douts[NHEADS] = {dqual, drot, dwidth, dtsdf};
+    float* outs[NHEADS] = {out_qual, out_rot, out_width, out_tsdf};
+    for (int h = 0; h < NHEADS; ++h)
+        if ((head_mask >> h & 1) && !douts[h]) return -6;
+    return launch_decoder_point_grad(static_cast<const float*>(planes_nhwc), p, static_cast<const uint8_t*>(packed),
+                                     static_cast<const uint8_t*>(bwd_packed), head_mask, douts, outs, dp, B, N,
+                                     static_cast<hipStream_t>(stream));
 }
 
 /* page-lock (and map for DMA) a host range the caller owns, e.g. a shared-memory batch ring written by reader processes */

@@ -9,10 +9,11 @@ chunk in ONE launch (there is no activation tensor whose size would call for chu
 the device copy of a HOST-resident query set, one chunk in flight at a time), and a regular grid of
 queries takes the lattice path (each plane sampled once per lattice coordinate pair).  Mesh extraction
 (`extract_mesh`, marching cubes via libmcubes) is host code outside the hot path and not part of this package."""
+import numpy as np
 import torch
 
 from . import _capi
-from .convonet import register_lattice
+from .convonet import _planes_to_nhwc, decoder_point_grad, register_lattice
 
 
 class Generator3D:
@@ -48,6 +49,30 @@ class Generator3D:
                          for ch in torch.split(pts, self.points_batch_size, dim=1)]
                 logits = torch.cat(parts, dim=1)
         return logits.squeeze(0) if squeeze else logits
+
+    def estimate_normals(self, vertices, c=None):
+        """generation.py:430-455: normals = -grad_p(occupancy logit) / |.| at the mesh vertices.  vertices: (N,3) numpy array
+        or tensor; c: the planes of ONE scene (`encode`).  Returns a numpy (N,3) float32 array, as the reference does.  The
+        gradient is one giga_decoder_point_grad launch (occupancy head, fp32) per chunk; like `eval_points`, only a
+        host-resident vertex set is split into `points_batch_size` chunks.  Unlike the reference's `backward()`, nothing
+        is accumulated into the parameters' `.grad`."""
+        v = torch.from_numpy(np.asarray(vertices, dtype=np.float32)) if not torch.is_tensor(vertices) else vertices
+        if v.dim() != 2 or v.shape[-1] != 3:
+            raise ValueError(f"expected (N,3) vertices, got {tuple(v.shape)}")
+        model = self.model
+        with torch.no_grad():
+            dev = self.device
+            nhwc = _planes_to_nhwc(c, "fp32")
+            blob, bwd_blob = model.packed_blob(nhwc.device), model.packed_bwd_blob(nhwc.device)
+            chunks = [v] if v.is_cuda or v.shape[0] <= self.points_batch_size else torch.split(v, self.points_batch_size)
+            normals = []
+            for vi in chunks:
+                vi = vi.to(dev, torch.float32).unsqueeze(0)
+                ones = torch.ones(vi.shape[:-1], device=vi.device)
+                ni = -decoder_point_grad(nhwc, vi, blob, bwd_blob, 8, {"decoder_tsdf": ones})
+                ni = ni / torch.norm(ni, dim=-1, keepdim=True)
+                normals.append(ni.squeeze(0).cpu().numpy())
+        return np.concatenate(normals, axis=0) if normals else np.zeros((0, 3), np.float32)
 
     def grid_points(self, resolution, lo=-0.5, hi=0.5):
         """The (1, R^3, 3) regular grid `box_size * make_3d_grid((-0.5,)*3, (0.5,)*3, (R,)*3)` of generation.py:160-165

@@ -154,10 +154,14 @@ class _Lease:
 
 
 class GigaFunction(torch.autograd.Function):
-    """(x, p, p_tsdf, *params) -> (qual, rot, width[, tsdf]) on the HIP kernels, differentiable w.r.t. params."""
+    """(x, p, p_tsdf, *params) -> (qual, rot, width[, tsdf]) on the HIP kernels, differentiable w.r.t. params and, when they
+    require grad, w.r.t. the query points p / p_tsdf (giga_decoder_point_grad on the planes of this step; fp32 decoders only)."""
 
     @staticmethod
     def forward(ctx, state, x, p, p_tsdf, *params):
+        if state.bf16 and state.bf16_dec and (p.requires_grad or (p_tsdf is not None and p_tsdf.requires_grad)):
+            raise NotImplementedError("gradients w.r.t. the query points need the fp32 decoder: the bf16 training decoder "
+                                      "(set_train_precision('bf16')) has no point-gradient kernel; use 'fp32' or 'bf16_convs'")
         L = _capi.lib()
         dev = x.device
         x = x.contiguous().float()
@@ -224,9 +228,17 @@ class GigaFunction(torch.autograd.Function):
                 _capi.stream_ptr(dev)), "giga_backward")
         if state.data_parallel:
             allreduce_mean_(grads, state.group)
+        # gradients w.r.t. the query points: the same planes, blobs and upstream gradients, after the parameter gradients
+        # (which this launch only reads around, so they stay what they are without it)
+        dp = dp_tsdf = None
+        with torch.cuda.device(dev):
+            if ctx.needs_input_grad[2] and state.head_present & 7 and N > 0:
+                dp = _point_grad(sb.nhwc, p, state, state.head_present & 7, douts, B, N)
+            if ctx.needs_input_grad[3] and state.head_present & 8 and M > 0:
+                dp_tsdf = _point_grad(sb.nhwc, p_tsdf, state, 8, douts, B, M)
         lease.release()
         if len(ctx.shapes) == 1 and len(ctx.shapes[0]) == 1:  # flattened module: one gradient for the one flat parameter
-            return (None, None, None, None, grads)
+            return (None, None, dp, dp_tsdf, grads)
         views, at = [], 0
         for shp in ctx.shapes:
             n = 1
@@ -234,7 +246,18 @@ class GigaFunction(torch.autograd.Function):
                 n *= d
             views.append(grads[at:at + n].view(shp))
             at += n
-        return (None, None, None, None) + tuple(views)
+        return (None, None, dp, dp_tsdf) + tuple(views)
+
+
+def _point_grad(nhwc, pts, state, mask, douts, B, N):
+    L = _capi.lib()
+    dev = nhwc.device
+    dp = torch.empty((B, N, 3), device=dev)
+    d = [douts[i] if mask >> i & 1 else None for i in range(4)]
+    _capi.check(L.giga_decoder_point_grad(_capi.ptr(nhwc), _capi.ptr(pts), _capi.ptr(state.blob), _capi.ptr(state.bwd_blob), mask,
+                                          *[_capi.ptr(t) for t in d], _capi.ptr(dp), None, None, None, None, B, N, 0,
+                                          _capi.stream_ptr(dev)), "giga_decoder_point_grad")
+    return dp
 
 
 # ---------------------------------------------------------------------------------------------------------

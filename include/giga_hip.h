@@ -252,6 +252,26 @@ int giga_backward(const float* tsdf, const void* packed, const void* bwd_packed,
                   const float* const* douts, float* grads, size_t n_params, int head_present, int B, int N, int M,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- gradient with respect to the QUERY POINTS (fp32; added within ABI 3) -----------------------------------------------
+ * dp [B*N][3] = d/dp of sum_h <dout_h, head_h(p)> over the heads of head_mask, the planes held constant: what autograd of the
+ * reference LocalDecoder (decoder.py:117-176) gives for p, as ConvolutionalOccupancyNetwork.grad_refine (models/__init__.py:136-164)
+ * and Generator3D.estimate_normals (conv_onet/generation.py:430-455) use it.  The upstream gradients refer to the POST-epilogue
+ * outputs of giga_decoder_forward(..., post = 1): dqual of sigmoid(qual), drot of F.normalize(rot), dwidth / dtsdf of the raw
+ * outputs; [B*N] each ([B*N][4] for drot), non-NULL for every head in head_mask.  A coordinate that common.py:255-260 clamps
+ * contributes no bilinear term (only fc_p's).  dp is overwritten.
+ *   planes_nhwc: fp32 FINAL planes (after conv_final: an encoder call WITHOUT GIGA_FOLD_FINAL, or giga_planes_pack precision 0);
+ *   packed / bwd_packed: the forward and backward blobs of the same weights (giga_pack_weights / giga_pack_bwd_weights);
+ *   out_*: optional (may be NULL) post-epilogue head outputs, bit for bit those of the precision-0 forward kernel;
+ *   flags: reserved, must be 0 (GIGA_FOLD_FINAL is rejected with -5).
+ * One launch (csrc/giga_decoder_pgrad.hip): per 32-point tile the forward chain is recomputed and the gradient chain run in
+ * registers, ending in Wp^T DN0 plus the spatial derivative of the bilinear sample.  Errors before anything is enqueued: -1
+ * (head_mask 0 or outside 0xF, B <= 0, N <= 0, B*N >= 2^31, a NULL plane / point / blob pointer or dp), -6 (a head in head_mask with a
+ * NULL upstream gradient), -7 (B > GIGA_MAX_SCENES), -5 (flags != 0). */
+int giga_decoder_point_grad(const void* planes_nhwc, const float* p, const void* packed, const void* bwd_packed,
+                            int head_mask, const float* dqual, const float* drot, const float* dwidth, const float* dtsdf,
+                            float* dp, float* out_qual, float* out_rot, float* out_width, float* out_tsdf,
+                            int B, int N, int flags, void* stream);
+
 /* ---- input side: page-locking of caller-owned host memory (hipHostRegister / hipHostUnregister), so that batches which
  * reader processes assemble in a shared-memory ring are DMA-ed to the device without a staging copy
  * (giga_amd/feed.py; replaces the pageable `.to(device)` of train_giga.py:141-151). */
