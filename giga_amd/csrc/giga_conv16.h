@@ -139,6 +139,7 @@ __device__ __forceinline__ void conv16_fill(const ConvArgs& a, uint8_t* smem, in
 template <typename T, int KIND, int C0, int C1, int COUT, int H, int W, int NB, bool POOL, bool RELU, int MATH, int MAXW = CONV_NW>
 __device__ __forceinline__ void conv16_run(const ConvArgs& a, uint8_t* smem, int block, int nblocks) {
     constexpr bool SPLIT = MATH == MATH_SPLIT, BF = MATH == MATH_BF16;
+    constexpr bool F16C = SPLIT || (sizeof(T) == 2 && MATH == MATH_NATIVE);   // f16-class: NaN-propagating ReLU / pool
     static_assert(MATH == MATH_NATIVE || sizeof(T) == 4, "split / bf16 modes read and write fp32 activations");
     constexpr int CIN = C0 + C1;
     constexpr int TAPS = KIND == CONV3 ? 9 : KIND == DOWN ? 4 : 1;
@@ -328,7 +329,7 @@ __device__ __forceinline__ void conv16_run(const ConvArgs& a, uint8_t* smem, int
                 float sacc = acc[n][0][e];
                 if (NACC == 2) sacc += acc[n][NACC - 1][e];
                 v[e] = sacc + bv;
-                if (RELU) v[e] = relu(v[e]);
+                if (RELU) v[e] = relu_act<F16C>(v[e]);
                 acc[n][0][e] = 0.f;
                 acc[n][NACC - 1][e] = 0.f;
             }
@@ -349,7 +350,8 @@ __device__ __forceinline__ void conv16_run(const ConvArgs& a, uint8_t* smem, int
                     }
                 }
                 if (POOL) {
-                    const float mx = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+                    const float mx = F16C ? max_f16c(max_f16c(v[0], v[1]), max_f16c(v[2], v[3]))
+                                          : fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
                     const uint32_t pidx = ((uint32_t)img * (H / 2 * (W / 2)) + __umul24(qy >> 1, W / 2) + (qx >> 1)) * COUT + co;
                     store_saddr(reinterpret_cast<T*>(a.out_pool), pidx * (uint32_t)ES, (T)mx);
                 }

@@ -134,7 +134,7 @@ struct C32Stage {
             if constexpr (MODE == C32_NATIVE) {
                 half8 x = __builtin_bit_cast(half8, v[u][0][0]);
 #pragma unroll
-                for (int q = 1; q < NPOS; ++q) x = __builtin_elementwise_max(x, __builtin_bit_cast(half8, v[u][q][0]));
+                for (int q = 1; q < NPOS; ++q) x = __builtin_elementwise_maximum(x, __builtin_bit_cast(half8, v[u][q][0]));   // NaN-propagating (relu_f16c)
                 *reinterpret_cast<half8*>(dst) = x;
                 if constexpr (G::POOLIN) {
                     if (own[u] && a.out_pool) *reinterpret_cast<half8*>(reinterpret_cast<char*>(a.out_pool) + qoff[u]) = x;
@@ -148,7 +148,7 @@ struct C32Stage {
                     for (int q = 1; q < NPOS; ++q) {
                         const f32x4v g = __builtin_bit_cast(f32x4v, v[u][q][e2]);
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) f[e] = __builtin_fmaxf(f[e], g[e]);
+                        for (int e = 0; e < 4; ++e) f[e] = max_f16c(f[e], g[e]);
                     }
 #pragma unroll
                     for (int e = 0; e < 4; ++e) x[4 * e2 + e] = f[e];
@@ -282,7 +282,7 @@ struct C32Tile {
                 const size_t pix = (size_t)G::out_index(o.g, o.y, o.x, sub);
                 float v[16];
 #pragma unroll
-                for (int r = 0; r < 16; ++r) v[r] = RELU ? relu(acc[j][s][r]) : acc[j][s][r];
+                for (int r = 0; r < 16; ++r) v[r] = RELU ? relu_f16c(acc[j][s][r]) : acc[j][s][r];
                 T* dst = reinterpret_cast<T*>(a.out) + pix * G::COUT + 32 * cs + 16 * hi;
                 if constexpr (G::MODE == C32_NATIVE) {
                     half8 h0, h1;
@@ -379,7 +379,7 @@ __device__ __forceinline__ void c32_store_mid(const C32Tile<GA, RELU, NTB>& t, c
             const int cs = (sp * GA::SPW + s) % GA::CS;
             float v[16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = RELU ? relu(t.acc[j][s][r]) : t.acc[j][s][r];
+            for (int r = 0; r < 16; ++r) v[r] = RELU ? relu_f16c(t.acc[j][s][r]) : t.acc[j][s][r];
             uint8_t* d = mid + PR::mid_off(o.orow, o.x, 4 * cs + 2 * hi);
             T* dst = reinterpret_cast<T*>(a.out) + (size_t)GA::out_index(o.g, o.y, o.x, 0) * GA::COUT + 32 * cs + 16 * hi;
             if constexpr (GA::MODE == C32_NATIVE) {

@@ -34,7 +34,9 @@ __device__ __forceinline__ void store_head(const DecArgs& a, int h, long long g,
         }
         *reinterpret_cast<float4*>(o + 4 * g) = make_float4(d0, d1, d2, d3);
     } else {
-        if (id == 0 && a.post) d0 = 1.0f / (1.0f + expf(-d0));
+        // sigmoid; + (d0 - d0) keeps an infinite logit (an overflow of the f16-class arithmetic) visible as NaN instead of
+        // a saturated 0 / 1.  Adds +0 to every finite logit's result: same bits.
+        if (id == 0 && a.post) d0 = 1.0f / (1.0f + expf(-d0)) + (d0 - d0);
         o[g] = d0;
     }
 }

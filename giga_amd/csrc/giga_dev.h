@@ -44,18 +44,30 @@ __device__ __forceinline__ float relu(float x) {
     const int b = __builtin_bit_cast(int, x);
     return __builtin_bit_cast(float, b > 0 ? b : 0);
 }
+// ReLU and max-pool of the f16-class kernels (f16 / f16x3 operands): IEEE maximum, one v_maximum3_f32 on gfx950 like the
+// integer max, but a NaN propagates.  Past the f16 range an operand becomes inf, the next products inf - inf = NaN, and
+// relu() above (NaNs with the sign bit set become 0) or fmaxf (drops a NaN next to a number) would turn that overflow into
+// a finite wrong result.  Bit-identical to relu() / fmaxf for every non-NaN input (maximum(-0, +0) = +0).
+__device__ __forceinline__ float relu_f16c(float x) { return __builtin_elementwise_maximum(x, 0.0f); }
+__device__ __forceinline__ float max_f16c(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+template <bool F16C>
+__device__ __forceinline__ float relu_act(float x) {
+    if constexpr (F16C) return relu_f16c(x);
+    else return relu(x);
+}
 // fmaxf form.  The backward decoder keeps it: with the integer form its register allocation tips over
 // (462 -> 512 VGPRs + 16 spills).
 __device__ __forceinline__ float relu_ieee(float x) { return __builtin_fmaxf(x, 0.f); }
 
 // round-to-nearest f16 then relu (== relu then round) of D registers 8c..8c+7 -> B operand of the next
-// layer's chunk c.  4x v_cvt_pk_f16_f32 + 4x v_pk_max_f16 instead of 16 canonicalising v_max_f32.
+// layer's chunk c.  4x v_cvt_pk_f16_f32 + 4x v_pk_maximum3_f16 instead of 16 canonicalising v_max_f32.
+// NaN-propagating like relu_f16c (v_pk_maximum3_f16; v_pk_max_f16 would drop the NaN of an overflowed layer).
 __device__ __forceinline__ half8 pack_relu8(const f32x16& d, int c) {
     half8 x;
 #pragma unroll
     for (int j = 0; j < 8; ++j) x[j] = (half_t)d[8 * c + j];
     const half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-    return __builtin_elementwise_max(x, z);
+    return __builtin_elementwise_maximum(x, z);
 }
 
 // f16x3 split of relu(D registers 8c..8c+7): hi = f16(x) (round to nearest), lo = f16(x - hi); hi + lo carries x to
@@ -92,7 +104,7 @@ __device__ __forceinline__ void lane16_swap(float& a, float& b) {
 __device__ __forceinline__ void split_relu8(const f32x16& d, int c, half8& hi, half8& lo) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const float x = relu(d[8 * c + j]);
+        const float x = relu_f16c(d[8 * c + j]);
         const half_t h = (half_t)x;
         hi[j] = h;
         lo[j] = (half_t)__builtin_fmaf((float)h, -1.0f, x);

@@ -73,6 +73,7 @@ __global__ __launch_bounds__(512) void convin_project_kernel(   // (512 also for
     float* __restrict__ yz_partial,        // [NXP][B][40(iz)][40(iy)][32] sums over the part's ix
     int B, uint4* __restrict__ relu_mask = nullptr) {
     constexpr int XW = NW * SXW, NT = NW * 64;
+    constexpr bool F16C = SPLIT || sizeof(TOut) == 2;      // f16-class: NaN-propagating ReLU (giga_dev.h relu_f16c)
     // row / slab strides of the staged sub-volume in words: the f16-class instantiations use the layout that makes their 8-tap
     // gather conflict-free (giga_layout.h: ci16_tap), fp32 the compact one (its 4-tap k-steps are conflict-free there)
     constexpr int RS = SPLIT ? CI16_RS : CV_RS, SLAB = SPLIT ? CI16_SLAB : CV_ROWS * CV_RS;
@@ -257,7 +258,7 @@ __global__ __launch_bounds__(512) void convin_project_kernel(   // (512 also for
                         mw[k >> 5] = __builtin_amdgcn_alignbit(mw[k >> 5], __builtin_bit_cast(unsigned, dv), 31);
                     }
                 }
-                const f32x4v v = {relu(d[ip][0]), relu(d[ip][1]), relu(d[ip][2]), relu(d[ip][3])};
+                const f32x4v v = {relu_act<F16C>(d[ip][0]), relu_act<F16C>(d[ip][1]), relu_act<F16C>(d[ip][2]), relu_act<F16C>(d[ip][3])};
                 acc_yz[ip][zg] += v;
                 // pin the accumulation here: the IR sinking pass otherwise moves it to the loop latch and keeps all 100
                 // ReLU outputs of a slice live next to the 100 accumulators (spills)
@@ -324,7 +325,7 @@ __global__ __launch_bounds__(512) void convin_project_kernel(   // (512 also for
                         mw[k >> 5] = __builtin_amdgcn_alignbit(mw[k >> 5], __builtin_bit_cast(unsigned, dv), 31);
                     }
                 }
-                const f32x4v v = {relu(d[ip][0]), relu(d[ip][1]), relu(d[ip][2]), relu(d[ip][3])};
+                const f32x4v v = {relu_act<F16C>(d[ip][0]), relu_act<F16C>(d[ip][1]), relu_act<F16C>(d[ip][2]), relu_act<F16C>(d[ip][3])};
                 acc_yz[ip][zg] += v;
                 asm volatile("" : "+v"(acc_yz[ip][zg]));         // keep the accumulation here (see the split path)
                 const f32x2v h = f32x2v{v[0], v[1]} + f32x2v{v[2], v[3]};

@@ -22,7 +22,13 @@
  *                      and every product W_lo*x_hi + W_hi*x_lo + W_hi*x_hi on the f16 MFMA (~22-bit operands, results
  *                      within 1e-5 of the fp32 path).  Decoder entry points only change arithmetic; planes are fp32
  *                      (as for precision 0); the encoder runs its convolutions (conv_in and the U-Net) in the same split
- *                      arithmetic;
+ *                      arithmetic.  Range: the split carries an operand to 2^-22 relative for 2^-3 <= |v| < 65520; below
+ *                      2^-3 lo is subnormal and the error is 2^-25 absolute; from 65520 up hi = inf.  Measured on He-uniform
+ *                      weights (planes of range ~3 at TSDF scale 1): planes within 3.5e-5 of their range against float64 for
+ *                      TSDF inputs scaled by 2^-8 .. 2^14, decoders for planes of range ~6 scaled by 2^-10 .. 2^12; below,
+ *                      the error doubles per halving of the scale.  Precisions 1 and 2: an activation past the f16 range
+ *                      (65504) gives NaN / inf outputs, never a finite wrong value (the f16-class ReLUs and max-pools
+ *                      propagate NaN; a qual logit of +-inf gives a NaN quality);
  *                  3 = bf16 operands / fp32 accumulate, fp32 activations and planes in memory: the forward of the bf16 training
  *                      step.  Encoder entry points: the U-Net convolutions (fp32 conv_in; see GIGA_BF16_CONVS); giga_decoder_forward:
  *                      every linear layer of the heads (see GIGA_BF16_DECODER; not with GIGA_FOLD_FINAL, not the lattice entry point);

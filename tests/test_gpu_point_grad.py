@@ -183,7 +183,14 @@ def _train_run(net, x, pos, pos_occ, gouts, p_grad):
     return [q.grad.clone() for q in net.parameters()], pg.grad, pt.grad
 
 
-def test_training_path_point_gradients(sd7):
+def test_training_path_point_gradients_leave_parameter_gradients(sd7):
+    """The training autograd function with p / p_tsdf requiring grad: dp and dp_tsdf against float64, and the parameter
+    gradients are what they are without the point gradients.  62 of the 164 parameter gradients are reduced with fp32
+    atomics (the decoders' plane gradient and weight gradients) and change from run to run, some among only a handful of
+    values, so two runs that agree bit for bit do not make a tensor deterministic.  K_BASE runs without point gradients
+    decide it: a tensor equal in all of them must come out bit for bit the same in every run with point gradients; any other
+    tensor must stay within 4x the run-to-run spread."""
+    K_BASE, K_WITH = 32, 4
     net = networks.get_network("giga")
     net.load_state_dict(sd7)
     net = net.to(DEV).train()
@@ -194,20 +201,31 @@ def test_training_path_point_gradients(sd7):
     gen = torch.Generator().manual_seed(5)
     gouts = [torch.randn(s, generator=gen) for s in ((B, N), (B, N, 4), (B, N), (B, M))]
     xd, pd, pod, gd = x.to(DEV), pos.to(DEV), pos_occ.to(DEV), [g.to(DEV) for g in gouts]
-    base_a, none_p, none_t = _train_run(net, xd, pd, pod, gd, False)
-    base_b, _, _ = _train_run(net, xd, pd, pod, gd, False)
-    with_p, dp, dpt = _train_run(net, xd, pd, pod, gd, True)
-    assert none_p is None and none_t is None
-    for a, b, c in zip(base_a, base_b, with_p):
-        if torch.equal(a, b):                              # deterministic tensor: bitwise
-            assert torch.equal(a, c)
+    base = []
+    for _ in range(K_BASE):
+        grads, none_p, none_t = _train_run(net, xd, pd, pod, gd, False)
+        assert none_p is None and none_t is None
+        base.append(grads)
+    with_p = [_train_run(net, xd, pd, pod, gd, True) for _ in range(K_WITH)]
+    names = [n for n, _ in net.named_parameters()]
+    n_det = 0
+    for i, name in enumerate(names):
+        a = base[0][i]
+        runs = [r[i] for r in base]
+        if all(torch.equal(a, r) for r in runs[1:]):        # deterministic tensor: bitwise
+            n_det += 1
+            for c, _, _ in with_p:
+                assert torch.equal(a, c[i]), name
         else:                                              # fp32 atomics: within the run-to-run spread
-            spread = (a - b).abs().max().item()
-            assert (a - c).abs().max().item() <= 4 * spread + 1e-7 * a.abs().max().item()
+            spread = max((a - r).abs().max().item() for r in runs[1:])
+            for c, _, _ in with_p:
+                assert (a - c[i]).abs().max().item() <= 4 * spread + 1e-7 * a.abs().max().item(), name
+    assert n_det > 0
     ref = pgrad_ref.point_grad(sd7, O.encoder_forward(sd7, x), pos, dict(zip(HEADS[:3], gouts[:3])))
     ref_t = pgrad_ref.point_grad(sd7, O.encoder_forward(sd7, x), pos_occ, {"decoder_tsdf": gouts[3]})
-    assert (dp.cpu().double() - ref).abs().max().item() < 1e-3 * ref.abs().max().item()
-    assert (dpt.cpu().double() - ref_t).abs().max().item() < 1e-3 * ref_t.abs().max().item()
+    for _, dp, dpt in with_p:
+        assert (dp.cpu().double() - ref).abs().max().item() < 1e-3 * ref.abs().max().item()
+        assert (dpt.cpu().double() - ref_t).abs().max().item() < 1e-3 * ref_t.abs().max().item()
 
 
 def test_bf16_decoder_training_with_point_grad_raises(sd7):

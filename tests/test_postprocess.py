@@ -151,13 +151,23 @@ def test_planner_hipgraph_replay_matches_eager(sd7):
 def test_planner_matches_reference_planner_golden_g10(golden, sd7):
     """The whole planner call against golden G10 = the reference's VGNImplicit.__call__ (network on the 40^3 lattice,
     process, bound, select, metric conversion) with the same weights: same grasps in the same order."""
+    _planner_matches_g10(golden, sd7, "fp32")
+
+
+@pytest.mark.gpu
+def test_planner_matches_reference_planner_golden_g10_fp16x3(golden, sd7):
+    """The same in 'fp16x3', the recommended mode, with the same asserts."""
+    _planner_matches_g10(golden, sd7, "fp16x3")
+
+
+def _planner_matches_g10(golden, sd7, prec):
     from giga_amd import networks
     from giga_amd.detection import VGNImplicit
     g = golden("g10_planner.npz")
     dev = torch.device("cuda:0")
     net = networks.get_network("giga")
     net.load_state_dict(sd7)
-    net = net.to(dev).eval()
+    net = net.to(dev).eval().set_precision(prec)
     planner = VGNImplicit(None, "giga", net=net, best=True, force_detection=True, qual_th=float(g["qual_th"]),
                           out_th=float(g["out_th"]))
 
