@@ -59,10 +59,11 @@ static __device__ long long g_ci_trace[8 * 64];
 #else
 #define CI_T(idx) do {} while (0)
 #endif
-// MASK (training forward): the sign bits of the pre-activations go to `relu_mask` -- per (scene, workgroup row wy, ix) and lane one
-// 16-byte word, value k = (zg * 5 + ip) * 4 + r of the lane's 100 in word k >> 5, shifted in from the right (v_alignbit: one VALU
-// instruction per value) -- so that the backward (convin_bwd_kernel<.., true>) does not recompute the convolution for its ReLU mask.
-// A set bit = negative (or -0): gradient 0; +0 counts as positive (measure zero).
+// MASK (training forward): one bit per pre-activation z, set when !(z > 0), goes to `relu_mask` -- per (scene, workgroup row wy, ix)
+// and lane one 16-byte word, value k = (zg * 5 + ip) * 4 + r of the lane's 100 in word k >> 5, shifted in from the right
+// (v_alignbit) -- so that the backward (convin_bwd_kernel<.., true>) does not recompute the convolution for its ReLU mask.
+// A set bit = gradient 0: z <= 0 (+0 and -0 included: torch's ReLU backward passes nothing at z = 0, and with zero biases every
+// pre-activation over empty space is exactly 0) or NaN.
 template <typename TOut, int SXW, bool SPLIT = false, int NW = 8, bool LO = true, bool MASK = false>
 __global__ __launch_bounds__(512) void convin_project_kernel(   // (512 also for NW = 4: a 256-thread bound makes the compiler put the MFMA results into AGPRs and copy them out for the epilogue)
     const float* __restrict__ tsdf,        // [B][40][40][40]
@@ -255,7 +256,7 @@ __global__ __launch_bounds__(512) void convin_project_kernel(   // (512 also for
                     for (int r = 0; r < 4; ++r) {
                         const int k = (zg * 5 + ip) * 4 + r;
                         const float dv = d[ip][r];       // (a copy: __builtin_bit_cast of a vector ELEMENT reads element 0 of the vector)
-                        mw[k >> 5] = __builtin_amdgcn_alignbit(mw[k >> 5], __builtin_bit_cast(unsigned, dv), 31);
+                        mw[k >> 5] = __builtin_amdgcn_alignbit(mw[k >> 5], dv > 0.f ? 0u : 0x80000000u, 31);
                     }
                 }
                 const f32x4v v = {relu_act<F16C>(d[ip][0]), relu_act<F16C>(d[ip][1]), relu_act<F16C>(d[ip][2]), relu_act<F16C>(d[ip][3])};
@@ -322,7 +323,7 @@ __global__ __launch_bounds__(512) void convin_project_kernel(   // (512 also for
                     for (int r = 0; r < 4; ++r) {
                         const int k = (zg * 5 + ip) * 4 + r;
                         const float dv = d[ip][r];       // (a copy: __builtin_bit_cast of a vector ELEMENT reads element 0 of the vector)
-                        mw[k >> 5] = __builtin_amdgcn_alignbit(mw[k >> 5], __builtin_bit_cast(unsigned, dv), 31);
+                        mw[k >> 5] = __builtin_amdgcn_alignbit(mw[k >> 5], dv > 0.f ? 0u : 0x80000000u, 31);
                     }
                 }
                 const f32x4v v = {relu_act<F16C>(d[ip][0]), relu_act<F16C>(d[ip][1]), relu_act<F16C>(d[ip][2]), relu_act<F16C>(d[ip][3])};
@@ -739,11 +740,12 @@ __device__ __forceinline__ void bwd_pool_stage(const BwdPool& p, int img0, int p
         const float4 d = *reinterpret_cast<const float4*>(p.dcat + pix * p.cs + p.coff + c);
         const float4 q = *reinterpret_cast<const float4*>(p.Q + qi);
         const float4 g = *reinterpret_cast<const float4*>(p.dQ + qi);
+        const float4 f = pool_first_max(p.S, pix, y, x, p.W, p.C, c, s4, q);      // ties: first maximum of the window only
         float4 o;
-        o.x = s4.x > 0.f ? d.x + (s4.x == q.x ? g.x : 0.f) : 0.f;
-        o.y = s4.y > 0.f ? d.y + (s4.y == q.y ? g.y : 0.f) : 0.f;
-        o.z = s4.z > 0.f ? d.z + (s4.z == q.z ? g.z : 0.f) : 0.f;
-        o.w = s4.w > 0.f ? d.w + (s4.w == q.w ? g.w : 0.f) : 0.f;
+        o.x = s4.x > 0.f ? d.x + (f.x != 0.f ? g.x : 0.f) : 0.f;
+        o.y = s4.y > 0.f ? d.y + (f.y != 0.f ? g.y : 0.f) : 0.f;
+        o.z = s4.z > 0.f ? d.z + (f.z != 0.f ? g.z : 0.f) : 0.f;
+        o.w = s4.w > 0.f ? d.w + (f.w != 0.f ? g.w : 0.f) : 0.f;
         *reinterpret_cast<float4*>(p.dS + pix * p.C + c) = o;
     }
 }

@@ -22,7 +22,8 @@ namespace giga {
 
 // ------------------------------- elementwise ------------------------------------------------------------
 // dS[img][y][x][c] = dCat[img][y][x][coff + c] (skip half of the concat gradient, channel stride cs)
-//                  + (S[y][x][c] == Q[y/2][x/2][c] ? dQ[y/2][x/2][c] : 0)      (MaxPool2d(2,2) backward)
+//                  + (S[y][x][c] is the first of its window == Q[y/2][x/2][c] ? dQ[y/2][x/2][c] : 0)   (MaxPool2d(2,2)
+// backward: ties go to the first maximum in row-major window order, as in torch; giga_bwd_mega.h: pool_first_max)
 // and, S being the ReLU output of the layer below, its backward in the same pass: dS = S > 0 ? dS : 0
 // (one thread per FOUR channels: 16-byte loads and stores; C, cs and coff are multiples of 4)
 __global__ void pool_bwd_add_kernel(float* __restrict__ dS, const float* __restrict__ dcat, int cs, int coff,
@@ -41,11 +42,12 @@ __global__ void pool_bwd_add_kernel(float* __restrict__ dS, const float* __restr
     const float4 d = *reinterpret_cast<const float4*>(dcat + pix * cs + coff + c);
     const float4 q = *reinterpret_cast<const float4*>(Q + qi);
     const float4 g = *reinterpret_cast<const float4*>(dQ + qi);
+    const float4 f = pool_first_max(S, pix, y, x, W, C, c, s, q);
     float4 o;
-    o.x = s.x > 0.f ? d.x + (s.x == q.x ? g.x : 0.f) : 0.f;
-    o.y = s.y > 0.f ? d.y + (s.y == q.y ? g.y : 0.f) : 0.f;
-    o.z = s.z > 0.f ? d.z + (s.z == q.z ? g.z : 0.f) : 0.f;
-    o.w = s.w > 0.f ? d.w + (s.w == q.w ? g.w : 0.f) : 0.f;
+    o.x = s.x > 0.f ? d.x + (f.x != 0.f ? g.x : 0.f) : 0.f;
+    o.y = s.y > 0.f ? d.y + (f.y != 0.f ? g.y : 0.f) : 0.f;
+    o.z = s.z > 0.f ? d.z + (f.z != 0.f ? g.z : 0.f) : 0.f;
+    o.w = s.w > 0.f ? d.w + (f.w != 0.f ? g.w : 0.f) : 0.f;
     *reinterpret_cast<float4*>(dS + pix * C + c) = o;
 }
 
@@ -1177,7 +1179,7 @@ constexpr int CB_RS = 44, CB_ROWS = 12;           // staged sub-volume: (XW+2) x
 constexpr int CB_PART = 27 * 16 + 16;             // floats per workgroup partial: dW^T[tap][ch16], db[ch16]
 constexpr size_t cb_lds_bytes(int sxw) { return (size_t)(8 * sxw + 2) * CB_ROWS * CB_RS * sizeof(float); }
 
-// MASK: the forward (convin_project_kernel<.., MASK = true>, GIGA_CONVIN_MASK) has left the sign bits of the pre-activations -- per
+// MASK: the forward (convin_project_kernel<.., MASK = true>, GIGA_CONVIN_MASK) has left one bit per pre-activation z, set when !(z > 0) -- per
 // (scene, workgroup row, ix) and lane one 16-byte word, value k = (zg * 5 + ip) * 4 + r in word k >> 5 at bit (n - 1 - (k & 31)),
 // n = 32 (4 in the last word) -- and the seven recomputation MFMAs of every unit fall away (8 instead of 15 per unit).
 template <int SXW, bool MASK = false>
@@ -1264,7 +1266,7 @@ __global__ __launch_bounds__(512) void convin_bwd_kernel(const float* __restrict
             for (int r = 0; r < 4; ++r) gx[zg][r] = gxz[((8 * zg + 4 * (g & 1) + r) * RES + ix) * CD + ch];
 #pragma unroll
         for (int zg = 0; zg < 5; ++zg) {
-            // forward recompute: five independent 7-MFMA chains (bias in the C operand, as the forward does) -- or the stored sign bits
+            // forward recompute: five independent 7-MFMA chains (bias in the C operand, as the forward does) -- or the stored mask bits
             f32x4v d[5];
             if constexpr (!MASK) {
 #pragma unroll
@@ -1285,7 +1287,7 @@ __global__ __launch_bounds__(512) void convin_bwd_kernel(const float* __restrict
                     bool pos;
                     if constexpr (MASK) {
                         const int k = (zg * 5 + ip) * 4 + r, wd = k >> 5, bit = (wd == 3 ? 3 : 31) - (k & 31);
-                        pos = ((mwv[wd] >> bit) & 1u) == 0u;                 // sign bit clear
+                        pos = ((mwv[wd] >> bit) & 1u) == 0u;                 // bit clear: z > 0
                     } else {
                         pos = d[ip][r] > 0.f;
                     }

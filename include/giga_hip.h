@@ -170,8 +170,8 @@ int giga_decoder_forward(const void* planes_nhwc, const float* p, const void* pa
  *   this call; the environment variable GIGA_CONV32=1 / 0 does the same for a whole process (the flag of a call wins). */
 #define GIGA_CONV32_UNET 128
 #define GIGA_CONV16_UNET 256
-/* GIGA_CONVIN_MASK, OR-ed into `precision` (0 or 3) of giga_encoder_forward*: a TRAINING forward -- conv_in also stores the sign bits of
- * its pre-activations (10 MB at 32 scenes, in the encoder workspace), and giga_backward called with GIGA_CONVIN_MASK_BWD on that workspace
+/* GIGA_CONVIN_MASK, OR-ed into `precision` (0 or 3) of giga_encoder_forward*: a TRAINING forward -- conv_in also stores its ReLU mask, one
+ * bit per pre-activation z set when !(z > 0) (10 MB at 32 scenes, in the encoder workspace), and giga_backward called with GIGA_CONVIN_MASK_BWD on that workspace
  * takes the ReLU mask of conv_in from them instead of recomputing the convolution (8 instead of 15 MFMAs per unit). */
 #define GIGA_CONVIN_MASK 512
 /* The stride-1 3x3 layers of the U-Net in precision 0 (exact fp32; encoder/unet.py:14-23) run as Winograd F(2x2, 3x3) on the fp32

@@ -4,7 +4,13 @@ tests/test_gpu_batch_limits.py hold the kernels to it).
 
 The encoder is oracle.giga_oracle's, run on a float64 state dict.  The heads are tests/pgrad_ref.py's mlp64 on features
 sampled in float64 at the coordinates the kernels use: normalize_coordinate in fp32 on the fp32 points (its clamps and the
-reference's 1 + 10e-6 divisor are fp32 decisions), everything after it in float64."""
+reference's 1 + 10e-6 divisor are fp32 decisions), everything after it in float64.
+
+train_grads is the training step's float64 reference (parameter gradients by autograd through the same chain;
+tests/test_ref64_backward.py pins it, tests/test_gpu_backward_envelope.py holds the backward kernels to it), and census
+counts the near-ties where fp32 and float64 may legitimately route a gradient differently."""
+import contextlib
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -22,6 +28,9 @@ INPUT_FAMILIES = ("uniform", "realistic", "structured", "adversarial")
 # sensitivity check (tests/test_ref64.py: one U-Net layer with f16 operands moves the planes by >= 4x this; the least
 # sensitive layer, up_convs.0.upconv, by 1.56e-4).
 TOL = {"fp32": 3.5e-5, "fp16x3": 3.5e-5}
+# Per-parameter-tensor tolerance of the fp32 training step against train_grads (max |got - ref| / max |ref|): see
+# tests/test_gpu_backward_envelope.py for the measured worst, tests/test_ref64_backward.py for what it rejects.
+TOL_BWD = 1.25e-4
 
 
 # ---- float64 reference ---------------------------------------------------------------------------------------------
@@ -197,3 +206,107 @@ def f16x3_split(v):
         hi = v.astype(np.float16)
         lo = (v - hi.astype(np.float32)).astype(np.float16)
     return hi.astype(np.float32), lo.astype(np.float32)
+
+
+# ---- float64 training reference --------------------------------------------------------------------------------------
+def head_keys(sd, heads):
+    """The state-dict keys of a model with `heads` (encoder + those heads), in state-dict order."""
+    return [k for k in sd if k.startswith("encoder.") or k.split(".")[0] in heads]
+
+
+def smooth_objective(B, N, M, heads=HEADS, seed=0):
+    """{head: R} of the smooth objective sum_h <out_h, R_h>: fixed N(0, 1) weights scaled by 1 / (points per scene), so
+    every head's share is O(1).  Unlike the training loss it has no saturating term: every output carries gradient."""
+    g = torch.Generator().manual_seed(seed)
+    shape = {"decoder_qual": (B, N), "decoder_rot": (B, N, 4), "decoder_width": (B, N), "decoder_tsdf": (B, M)}
+    return {h: torch.randn(shape[h], generator=g, dtype=torch.float64) / max(1, shape[h][1]) for h in heads}
+
+
+def train_outputs(sd, x, pos, pos_occ, heads=HEADS, detach_tsdf=False):
+    """{head: output} of the model forward (models/__init__.py:42-67) in the dtype of `sd`: sigmoid qual, unit rot, raw width
+    at pos; raw occupancy logits at pos_occ (planes detached first when detach_tsdf).  Coordinates normalised in fp32."""
+    dt = next(iter(sd.values())).dtype
+    planes = O.encoder_forward(sd, torch.as_tensor(x).to(dt))
+    out = {}
+    for h in heads:
+        p = pos_occ if h == "decoder_tsdf" else pos
+        pl = {k: v.detach() for k, v in planes.items()} if h == "decoder_tsdf" and detach_tsdf else planes
+        c = sample_features(p, pl).to(dt)
+        z = mlp64(sd, h, torch.as_tensor(p).to(dt), c)
+        out[h] = torch.sigmoid(z) if h == "decoder_qual" else F.normalize(z, dim=2) if h == "decoder_rot" else z
+    return out
+
+
+def train_grads(sd, x, pos, pos_occ, y=None, heads=HEADS, detach_tsdf=False, objective="loss", dtype=torch.float64):
+    """(parts, grads) of one training step, by autograd in float64 (or `dtype`) through train_outputs.
+    objective "loss": the joint loss O.train_loss(O.train_select(out), y) (all four heads, one grasp query per scene);
+    parts = its five terms.  objective {head: R}: sum_h <out_h, R_h> (smooth_objective); parts = {"objective": value}.
+    grads: {key: gradient} of every parameter of the model with `heads`."""
+    sdg = {k: torch.as_tensor(sd[k]).to(dtype).clone().requires_grad_(True) for k in head_keys(sd, heads)}
+    out = train_outputs(sdg, x, pos, pos_occ, heads, detach_tsdf)
+    if isinstance(objective, str):
+        assert objective == "loss" and tuple(heads) == HEADS, objective
+        loss, d = O.train_loss(O.train_select(tuple(out[h] for h in HEADS)), tuple(torch.as_tensor(t).to(dtype) for t in y))
+        parts = {k: v.item() for k, v in d.items()}
+    else:
+        loss = sum((out[h] * objective[h].to(dtype)).sum() for h in heads)
+        parts = {"objective": loss.item()}
+    loss.backward()
+    return parts, {k: v.grad for k, v in sdg.items()}
+
+
+def grad_err(got, ref):
+    """max |got - ref| / max |ref| of one parameter tensor (inf when got has a non-finite entry)."""
+    g = torch.as_tensor(got).double().cpu()
+    r = torch.as_tensor(ref).double().cpu()
+    if not bool(torch.isfinite(g).all()):
+        return float("inf")
+    return (g - r).abs().max().item() / max(r.abs().max().item(), 1e-30)
+
+
+@contextlib.contextmanager
+def patched_functional(**fns):
+    """Replace torch.nn.functional.<name> for the duration (the oracle and mlp64 look them up at call time): the census'
+    recorders and the sensitivity tests' mutated operators."""
+    saved = {k: getattr(F, k) for k in fns}
+    try:
+        for k, v in fns.items():
+            setattr(F, k, v)
+        yield
+    finally:
+        for k, v in saved.items():
+            setattr(F, k, v)
+
+
+def census(sd, x, pos=None, pos_occ=None, heads=HEADS, rel=1e-6):
+    """Near-ties of one case's float64 forward, where the kernels' fp32 may legitimately route a gradient otherwise:
+    pool_near_ties  2x2 max-pool windows whose two largest values are both positive and 0 < gap <= rel * range(pool input);
+    pool_ties       windows whose maximum is positive and held by >= 2 elements exactly (routed by the tie rule);
+    relu_near_zero  ReLU inputs with 0 < |z| <= rel * range(that ReLU's input);
+    relu_zero       ReLU inputs exactly 0 (whose gradient the ReLU's strict '>' drops)."""
+    n = {"pool_near_ties": 0, "pool_ties": 0, "relu_near_zero": 0, "relu_zero": 0}
+    relu, pool = F.relu, F.max_pool2d
+
+    def rec_relu(z, *a, **k):
+        rng = (z.max() - z.min()).item()
+        n["relu_near_zero"] += int(((z != 0) & (z.abs() <= rel * rng)).sum())
+        n["relu_zero"] += int((z == 0).sum())
+        return relu(z, *a, **k)
+
+    def rec_pool(s, *a, **k):
+        B, C, H, W = s.shape
+        w = s.reshape(B, C, H // 2, 2, W // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(-1, 4)
+        t = w.topk(2, dim=1).values
+        gap, rng = t[:, 0] - t[:, 1], (s.max() - s.min()).item()
+        n["pool_near_ties"] += int(((t[:, 1] > 0) & (gap > 0) & (gap <= rel * rng)).sum())
+        n["pool_ties"] += int(((t[:, 0] > 0) & (gap == 0)).sum())
+        return pool(s, *a, **k)
+
+    sd = {k: torch.as_tensor(sd[k]).double() for k in head_keys(sd, heads)}
+    with torch.no_grad(), patched_functional(relu=rec_relu, max_pool2d=rec_pool):
+        planes = O.encoder_forward(sd, torch.as_tensor(x).double())
+        for h in heads:
+            p = pos_occ if h == "decoder_tsdf" else pos
+            if p is not None and p.shape[1] > 0:
+                mlp64(sd, h, torch.as_tensor(p).double(), sample_features(p, planes))
+    return n

@@ -630,11 +630,11 @@ def test_bf16_weight_gradient_kernels_with_rounded_operands(sd7, B):
 
 
 def test_conv_in_relu_mask_of_the_training_forward(sd7):
-    """GIGA_CONVIN_MASK: the training forward leaves the sign bits of conv_in's pre-activations in the encoder workspace (the
+    """GIGA_CONVIN_MASK: the training forward leaves the ReLU mask of conv_in's pre-activations in the encoder workspace (the
     backward takes its ReLU mask from them instead of recomputing the convolution).  Layout (csrc/giga_encoder.hip): per
     (scene, workgroup row wy = 2 * iy-group + channel half, ix) and lane (j = lane & 15, g = lane >> 4) one 16-byte word; value
     k = (zg * 5 + ip) * 4 + r -- channel 16 (wy & 1) + j, iy = 10 (wy >> 1) + 2 ip + (g >> 1), iz = 8 zg + 4 (g & 1) + r -- in
-    word k >> 5 at bit (n - 1 - (k & 31)), n = 32 (4 in the last word); a set bit = negative.  Against the oracle's Conv3d
+    word k >> 5 at bit (n - 1 - (k & 31)), n = 32 (4 in the last word); a set bit = not positive (no gradient).  Against the oracle's Conv3d
     (voxels.py:36,106-107) for both batch regimes of the kernel (5 x-parts below 32 scenes, 1 from 32 up)."""
     import ctypes
     import torch.nn.functional as F
@@ -658,7 +658,7 @@ def test_conv_in_relu_mask_of_the_training_forward(sd7):
             for wy in range(8):
                 ch = 16 * (wy & 1) + j; iy = 10 * (wy >> 1) + 2 * ip + (g >> 1); iz = 8 * zg + 4 * (g & 1) + r
                 ref = pre[:, ch, :, iy, iz].transpose(1, 2, 0)                # (lanes, B, ix) -> (B, ix, lanes)
-                want = ref < 0
+                want = ~(ref > 0)
                 sure = np.abs(ref) > 1e-5                                     # (fp32 summation order near zero)
                 bad += int(((got[:, wy] != want) & sure).sum()); tot += int(sure.sum())
         assert bad == 0, (B, bad, tot)
