@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the GIGA dense inference path on MI355X (driver contract in the task brief).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-extra] [--no-cpu-baseline]]
 
 With N > 1 and no launcher environment the script starts its own N ranks (`python -m torch.distributed.run`, one per GPU,
 rendezvous on 127.0.0.1) and rank 0 prints the JSON line; under an external `torch.distributed.run` it uses the ranks it
@@ -13,18 +13,24 @@ A "step" is one forward pass of BASELINE.json configs[1] on every rank:
     encoder + decoders in exact fp32 (fp32 MFMA), inputs resident in HBM, outputs left in HBM.
 Scenes are independent, so ranks are pure replicas on different scenes (scene i -> rank i mod N, weak scaling) and the
 timed region has no collective; its two barriers run over gloo.  After it an RCCL group (backend "nccl" over xGMI) does the
-MAX-reduce of the elapsed times, one all_gather of per-rank counters, the all_gather of the real head outputs of all
-N x 32 scenes (BASELINE config c3) and, at N > 1, the data-parallel training step of config c5.
+MAX-reduce of the elapsed times and one all_gather of per-rank counters; with --full also the all_gather of the real head
+outputs of all N x 32 scenes (BASELINE config c3) and, at N > 1, the data-parallel training step of config c5.
 
-ONE JSON line (< 6 KB) is printed by rank 0: the contract keys, and
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs and ONE JSON line (< 6 KB),
+printed by rank 0: the contract keys, and
   roofline      - the headline kernel of the timed workload (scalars only), timed live with HIP events on the launch stream
                   inside the timed steps
-  cpu_baseline  - the CPU oracle (a port of the reference's PyTorch path) on the host cores (N = 1 only)
-  checked_vs_oracle, launches_per_step, rccl_ranks / per_rank_seconds and digests of the c3 / data-parallel c5 legs at N > 1
+  launches_per_step, rccl_ranks / per_rank_seconds at N > 1
   summary       - ms per step and roofline fraction of every BASELINE config the run measured (last key)
-Everything else -- `roofline.stages` (time, FLOPs and fraction of peak of EVERY kernel), the c4 legs (64 000 grasp queries per
-scene, f16 / f16x3 / mixed), c2 (ii), the c5-shaped training steps with their per-kernel tables, notes -- goes to the side file
-gpurun_out/bench_extra.json (GIGA_BENCH_EXTRA overrides the path), never to stdout: round 5's 31-KB line could not be parsed.
+--full adds everything else the benchmark measures or checks: before the timed region the untimed pre-pass (`roofline.stages`:
+time, FLOPs and fraction of peak of EVERY kernel; a plain run makes it only when the U-Net runs one launch per layer, to pick
+the kernel the timed steps bracket), after it `checked_vs_oracle` (scene 0 of the headline step against the CPU oracle), the
+other configs and precisions (the c4 legs: 64 000 grasp queries per scene, f16 / f16x3 / mixed; c2 (ii); c2 in fp16x3; the
+c5-shaped training steps with their per-kernel tables; at N > 1 the c3 gather and the data-parallel c5 step, whose digests join
+the line) and, at N = 1, `cpu_baseline` (the CPU oracle, a port of the reference's PyTorch path, on the host cores).
+--no-extra / --no-cpu-baseline leave the other configs / the CPU baseline out of a --full run.  Everything beyond the line goes
+to the side file bench_extra.json (GIGA_BENCH_EXTRA sets its path, see emit()), never to stdout: round 5's 31-KB line could not
+be parsed.
 
 --dump-outputs DIR writes what the LAST timed step returned (rank 0's shard: qual, rot, width, tsdf) as DIR/<name>.npy in
 float32, so that two builds can be compared output for output; the inputs and weights are seeded, identical from run to run.
@@ -175,8 +181,10 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=32, help="scenes per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the stage pre-pass, the oracle check, the other configs and "
+                                                         "precisions and the CPU baseline (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: without the other configs and precisions")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     args = ap.parse_args()
     if args.steps < 1:
@@ -227,10 +235,6 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # -------- untimed pre-pass: every stage probed, median of seven ---------------------------------------
-    ev_a, ev_b = L.giga_event_create(), L.giga_event_create()
-    dec_ev = (L.giga_event_create(), L.giga_event_create())
-
     def step(probe=None, dec_probe=None):
         """One forward of the workload through the module API (vgn-compatible call)."""
         with torch.no_grad():
@@ -253,32 +257,39 @@ def main():
         _capi.check(L.giga_event_elapsed_ms(a, b, ctypes.byref(ms)), "event")
         return ms.value
 
-    bracket_ms = empty_bracket_ms(L, _capi, dev)          # what an event pair costs with nothing between its records
-    stage_ms = []
-    for st in range(15):
-        reps = []
-        for _ in range(7):
-            step(probe=(st, ev_a, ev_b))
-            reps.append(elapsed(ev_a, ev_b))
-        stage_ms.append(float(np.median(reps)))
-    dec2 = (L.giga_event_create(), L.giga_event_create())
-    dg, dt = [], []
-    for _ in range(7):
-        step(dec_probe=(dec_ev, dec2))
-        dg.append(elapsed(*dec_ev)); dt.append(elapsed(*dec2))
-    dec_grasp_ms, dec_occ_ms = float(np.median(dg)), float(np.median(dt))
     # How the U-Net is launched in the product call: one persistent launch (the default from 8 scenes up in fp32) or one launch per
-    # layer.  Probing a single layer (stages 2..14) forces per-layer launches for that call, so the per-layer table above is always
+    # layer.  Probing a single layer (stages 2..14) forces per-layer launches for that call, so the per-layer table below is always
     # available; the dominant launch of the STEP AS TIMED is the persistent one when it is in use.
+    torch.cuda.synchronize()
     n0 = L.giga_launch_count()
     with torch.no_grad():
         net.encoder.encode_nhwc(x, blob=blob, precision="fp32", fold_final=True)
     persistent_unet = int(L.giga_launch_count() - n0) <= 4         # conv_in, finalize, U-Net
-    reps = []
-    for _ in range(7):
-        step(probe=(UNET_STAGE, ev_a, ev_b))
-        reps.append(elapsed(ev_a, ev_b))
-    unet_ms = float(np.median(reps))
+
+    # -------- untimed pre-pass (--full, or to pick the bracketed kernel of the per-layer form): every stage probed, median of seven
+    stage_ms = dec_grasp_ms = dec_occ_ms = unet_ms = bracket_ms = None
+    if args.full or not persistent_unet:
+        ev_a, ev_b = L.giga_event_create(), L.giga_event_create()
+        dec_ev = (L.giga_event_create(), L.giga_event_create())
+        bracket_ms = empty_bracket_ms(L, _capi, dev)          # what an event pair costs with nothing between its records
+        stage_ms = []
+        for st in range(15):
+            reps = []
+            for _ in range(7):
+                step(probe=(st, ev_a, ev_b))
+                reps.append(elapsed(ev_a, ev_b))
+            stage_ms.append(float(np.median(reps)))
+        dec2 = (L.giga_event_create(), L.giga_event_create())
+        dg, dt = [], []
+        for _ in range(7):
+            step(dec_probe=(dec_ev, dec2))
+            dg.append(elapsed(*dec_ev)); dt.append(elapsed(*dec2))
+        dec_grasp_ms, dec_occ_ms = float(np.median(dg)), float(np.median(dt))
+        reps = []
+        for _ in range(7):
+            step(probe=(UNET_STAGE, ev_a, ev_b))
+            reps.append(elapsed(ev_a, ev_b))
+        unet_ms = float(np.median(reps))
     dom = UNET_STAGE if persistent_unet else pick_headline(stage_ms)
 
     # -------- timed region ----------------------------------------------------------------------------
@@ -346,10 +357,11 @@ def main():
     # that one rank never enters (an exception elsewhere, a wedged RCCL ring) must not cost the scaling run its numbers.
     out = core_result(args, world, B, M, K, T, scenes_per_s, stage_ms, dec_grasp_ms, dec_occ_ms, dom, dom_ms, step_ms, named_ms, bracket_ms,
                       launches_per_step, unet_ms, persistent_unet) if rank == 0 else None
-    if rank == 0:                          # (untimed) scene 0 of the headline step's own output against the CPU oracle
+    if rank == 0 and args.full:            # (untimed) scene 0 of the headline step's own output against the CPU oracle
         out["checked_vs_oracle"] = check_c2_scene(step(), sd, x, pos, pos_occ)
     extra = dict(multi)
-    if dist is not None and not args.no_extra:
+    other_configs = args.full and not args.no_extra
+    if dist is not None and other_configs:
         import threading
 
         def bail():
@@ -384,7 +396,7 @@ def main():
         return
 
     single = world == 1 and dist is None
-    if single and not args.no_extra:
+    if single and other_configs:
         legs = (("c4", lambda: bench_c4_all(net, dev, L, _capi, synth, decode_heads)),
                 ("c2_ii", lambda: bench_c2_ii(net, dev, synth, B)),
                 ("c2_fp16x3", lambda: bench_c2_mode(net, x, pos, pos_occ, "fp16x3")),
@@ -406,7 +418,7 @@ def main():
         out["extra"] = extra
 
     # -------- CPU baseline: the oracle (port of the reference path) on the host cores -------------------
-    if single and not args.no_cpu_baseline:               # rank 0 at N = 1 only
+    if single and args.full and not args.no_cpu_baseline:  # rank 0 at N = 1 only
         out["cpu_baseline"] = cpu_baseline(sd, synth, M)
     out["summary"] = summary_of(out)                      # LAST key: every named-config number inside the tail of the line
     print(emit(out), flush=True)
@@ -524,7 +536,8 @@ def _dig(d, ks):
 
 def core_result(args, world, B, M, K, T, scenes_per_s, stage_ms, dec_grasp_ms, dec_occ_ms, dom, dom_ms, step_ms, named_ms, bracket_ms,
                 launches_per_step=None, unet_ms=None, persistent_unet=False):
-    """The contract keys + roofline of the timed region (rank 0)."""
+    """The contract keys + roofline of the timed region (rank 0); with the pre-pass's numbers (stage_ms not None) also its
+    table of every stage (stage_report)."""
     # HBM bytes per launch: PMC counters cannot be collected from inside this process, so they come from the committed
     # rocprofv3 PMC table of the same workload (tools/gpu_traffic.sh -> profiles/*traffic_c2.json), stamped with the commit
     # and kernel it was measured on; null when the table has no entry for this kernel / batch size.
@@ -537,6 +550,57 @@ def core_result(args, world, B, M, K, T, scenes_per_s, stage_ms, dec_grasp_ms, d
     achieved = dom_flops / (dom_avg_ms * 1e-3) / 1e12
     flop_scene = FLOP_ENCODER + FLOP_GRASP3 * 1 + FLOP_HEAD["tsdf"] * M
     points_per_scene = 1 * 3 + M          # head evaluations per scene
+    out = {
+        "metric": "scenes/sec",
+        "value": scenes_per_s,
+        "unit": "scenes/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": args.warmup,
+        "ms_per_step": T / K * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": "c2: batch=32/GPU synthetic 40^3 TSDF, encoder + 3 grasp heads @1 query + "
+                               "occupancy head @2048 queries/scene (literal train_giga call), fp32 MFMA",
+                   "scenes_per_gpu_per_step": B, "occ_points_per_scene": M, "grasp_points_per_scene": 1,
+                   "parallelism": f"scene-sharded x{world} (scene i -> rank i mod {world}; replicas, no data-path collective)"},
+        "step_ms_median": float(np.median(step_ms)), "step_ms_max": float(np.max(step_ms)),
+        "query_points_per_sec": scenes_per_s * points_per_scene,
+        "algorithmic_tflops": scenes_per_s * flop_scene / 1e12,
+        "roofline": {
+            "kernel": STAGE_NAMES[dom], "bound": "mfma", "achieved": achieved, "peak": PEAK_F32_MATRIX_TFLOPS,
+            "unit": "TFLOP/s", "frac": achieved / PEAK_F32_MATRIX_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
+            "frac_of_measured_peak": achieved / MEASURED_F32_MATRIX_TFLOPS,
+            "avg_launch_ms": dom_avg_ms, "median_launch_ms": float(np.median(dom_ms)), "flops_per_launch": dom_flops,
+            # the persistent U-Net launch in its default form issues fewer FLOPs than it is credited with (Winograd): the matrix pipe's own load
+            "issued_mfma_flops_per_launch": unet_issued_flops(B) if dom == UNET_STAGE else None,
+            "issued_mfma_frac_of_peak": unet_issued_flops(B) / (dom_avg_ms * 1e-3) / 1e12 / PEAK_F32_MATRIX_TFLOPS if dom == UNET_STAGE else None,
+            "note": "fp32-input MFMA (v_mfma_f32_16x16x4_f32 / 32x32x2_f32) peak; `achieved` / `frac` count the ALGORITHMIC direct-convolution FLOPs of SURVEY 8d -- "
+                    "the launch runs its 3x3 layers as Winograd F(2x2, 3x3) and ISSUES issued_mfma_flops_per_launch; events on the launch stream inside the timed steps (even steps); "
+                    "kernel = the longest launch of the step as it is launched: the persistent U-Net launch (twelve layers, "
+                    "algorithmic FLOPs of all of them) when that form is in use, else unet.up0.conv1 unless another stage exceeds "
+                    "1.15x its time (pick_headline)",
+            # the kernel VERDICT r01 named (roofline_frac 0.46 then), measured the same way on the odd steps
+            "r01_kernel": {"kernel": STAGE_NAMES[NAMED_STAGE], "achieved": named_ach, "frac": named_ach / PEAK_F32_MATRIX_TFLOPS,
+                           "frac_of_measured_peak": named_ach / MEASURED_F32_MATRIX_TFLOPS, "avg_launch_ms": named_avg_ms,
+                           "median_launch_ms": float(np.median(named_ms)), "flops_per_launch": named_flops,
+                           "traffic": named_traffic, "traffic_source": named_src},
+        },
+        "launches_per_step": launches_per_step,
+    }
+    if stage_ms is not None:
+        out["roofline"].update(stage_report(B, M, stage_ms, dec_grasp_ms, dec_occ_ms, unet_ms, persistent_unet, bracket_ms))
+        out["stage_note"] = ("unet.conv_final is not launched in this call: the 1x1 convolution is folded into the heads' fc_c weights "
+                             "(GIGA_FOLD_FINAL); its entry is the empty event bracket")
+    return out
+
+
+def stage_report(B, M, stage_ms, dec_grasp_ms, dec_occ_ms, unet_ms, persistent_unet, bracket_ms):
+    """The untimed pre-pass as roofline keys: time, FLOPs, share of the step and fraction of the fp32-MFMA peak of every stage,
+    the U-Net launch, the argmax and worst stage and the FLOP-weighted fraction of the whole step."""
     # shares of the step as it is launched: with the persistent U-Net the twelve layers are one launch of unet_ms
     unet_layers_ms = sum(stage_ms[2:14])
     step_total = sum(stage_ms[:2]) + (unet_ms if persistent_unet else unet_layers_ms) + dec_grasp_ms + dec_occ_ms
@@ -567,62 +631,20 @@ def core_result(args, world, B, M, K, T, scenes_per_s, stage_ms, dec_grasp_ms, d
     if unet_launch and persistent_unet:                       # the launch the step really contains; its twelve layers stay listed beside it
         stages[STAGE_NAMES[UNET_STAGE]] = unet_launch
         argmax_stage = {"kernel": STAGE_NAMES[UNET_STAGE], "ms": unet_launch["ms"], "frac": unet_launch["frac_of_fp32_mfma_peak"]}
-    out = {
-        "metric": "scenes/sec",
-        "value": scenes_per_s,
-        "unit": "scenes/s",
-        "n_gpus": world,
-        "steps": K,
-        "warmup": args.warmup,
-        "ms_per_step": T / K * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": "c2: batch=32/GPU synthetic 40^3 TSDF, encoder + 3 grasp heads @1 query + "
-                               "occupancy head @2048 queries/scene (literal train_giga call), fp32 MFMA",
-                   "scenes_per_gpu_per_step": B, "occ_points_per_scene": M, "grasp_points_per_scene": 1,
-                   "parallelism": f"scene-sharded x{world} (scene i -> rank i mod {world}; replicas, no data-path collective)"},
-        "step_ms_median": float(np.median(step_ms)), "step_ms_max": float(np.max(step_ms)),
-        "query_points_per_sec": scenes_per_s * points_per_scene,
-        "algorithmic_tflops": scenes_per_s * flop_scene / 1e12,
-        "roofline": {
-            "kernel": STAGE_NAMES[dom], "bound": "mfma", "achieved": achieved, "peak": PEAK_F32_MATRIX_TFLOPS,
-            "unit": "TFLOP/s", "frac": achieved / PEAK_F32_MATRIX_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
-            "frac_of_measured_peak": achieved / MEASURED_F32_MATRIX_TFLOPS,
-            "avg_launch_ms": dom_avg_ms, "median_launch_ms": float(np.median(dom_ms)), "flops_per_launch": dom_flops,
-            # the persistent U-Net launch in its default form issues fewer FLOPs than it is credited with (Winograd): the matrix pipe's own load
-            "issued_mfma_flops_per_launch": unet_issued_flops(B) if dom == UNET_STAGE else None,
-            "issued_mfma_frac_of_peak": unet_issued_flops(B) / (dom_avg_ms * 1e-3) / 1e12 / PEAK_F32_MATRIX_TFLOPS if dom == UNET_STAGE else None,
-            # elapsed time of an EMPTY event bracket on the same stream: contained in every *_launch_ms / stage ms of this object
-            # (rocprofv3's kernel durations under profiles/ do not contain it)
-            "empty_event_bracket_ms": bracket_ms,
-            "note": "fp32-input MFMA (v_mfma_f32_16x16x4_f32 / 32x32x2_f32) peak; `achieved` / `frac` count the ALGORITHMIC direct-convolution FLOPs of SURVEY 8d -- "
-                    "the launch runs its 3x3 layers as Winograd F(2x2, 3x3) and ISSUES issued_mfma_flops_per_launch; events on the launch stream inside the timed steps (even steps); "
-                    "kernel = the longest launch of the step as it is launched: the persistent U-Net launch (twelve layers, "
-                    "algorithmic FLOPs of all of them) when that form is in use, else unet.up0.conv1 unless another stage exceeds "
-                    "1.15x its time (pick_headline)",
-            "unet_launch": unet_launch,
-            "stages_note": "the U-Net layers of `stages` are timed as SEPARATE launches (probing one layer switches that call to "
-                           "per-layer launches); inside the persistent launch their shares are scaled pro rata",
-            # the kernel VERDICT r01 named (roofline_frac 0.46 then), measured the same way on the odd steps
-            "r01_kernel": {"kernel": STAGE_NAMES[NAMED_STAGE], "achieved": named_ach, "frac": named_ach / PEAK_F32_MATRIX_TFLOPS,
-                           "frac_of_measured_peak": named_ach / MEASURED_F32_MATRIX_TFLOPS, "avg_launch_ms": named_avg_ms,
-                           "median_launch_ms": float(np.median(named_ms)), "flops_per_launch": named_flops,
-                           "traffic": named_traffic, "traffic_source": named_src},
-            "stages": stages,
-            # The roofline kernel above is the LONGEST launch, which is also the best-tuned one.  Beside it: the true argmax
-            # of the measured stage times, the stage FURTHEST below the roofline among those that take >= 8 % of the step,
-            # and the FLOP-weighted fraction of the whole step (sum of algorithmic FLOPs / sum of stage times).
-            "argmax_stage": argmax_stage, "worst_stage": worst_stage,
-            "step_frac_flop_weighted": step_flops / (step_total * 1e-3) / 1e12 / PEAK_F32_MATRIX_TFLOPS,
-        },
-        "launches_per_step": launches_per_step,
-        "stage_note": "unet.conv_final is not launched in this call: the 1x1 convolution is folded into the heads' fc_c weights "
-                      "(GIGA_FOLD_FINAL); its entry is the empty event bracket",
+    return {
+        # elapsed time of an EMPTY event bracket on the same stream: contained in every *_launch_ms / stage ms of the roofline
+        # (rocprofv3's kernel durations under profiles/ do not contain it)
+        "empty_event_bracket_ms": bracket_ms,
+        "unet_launch": unet_launch,
+        "stages_note": "the U-Net layers of `stages` are timed as SEPARATE launches (probing one layer switches that call to "
+                       "per-layer launches); inside the persistent launch their shares are scaled pro rata",
+        "stages": stages,
+        # The roofline kernel is the LONGEST launch, which is also the best-tuned one.  Beside it: the true argmax
+        # of the measured stage times, the stage FURTHEST below the roofline among those that take >= 8 % of the step,
+        # and the FLOP-weighted fraction of the whole step (sum of algorithmic FLOPs / sum of stage times).
+        "argmax_stage": argmax_stage, "worst_stage": worst_stage,
+        "step_frac_flop_weighted": step_flops / (step_total * 1e-3) / 1e12 / PEAK_F32_MATRIX_TFLOPS,
     }
-    return out
 
 
 def bench_c3_gather(net, x, pos, pos_occ, sharding, dist, rccl, rank, world, B, dev):

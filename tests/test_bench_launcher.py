@@ -1,6 +1,6 @@
 """bench.py's launch contract: `python bench.py --gpus N` starts its own N ranks, WORLD_SIZE must equal --gpus, and the
-whole N > 1 code path (gloo barriers, RCCL group after the timed region, counter all_gather, the c3 output gather, the
-data-parallel c5 step) runs under the launcher at world size 1 on a single-GPU box."""
+whole N > 1 code path (gloo barriers, RCCL group after the timed region, counter all_gather and, with --full, the c3 output
+gather and the data-parallel c5 step) runs under the launcher at world size 1 on a single-GPU box."""
 import json
 import os
 import subprocess
@@ -37,7 +37,7 @@ def test_multi_rank_code_path_at_world_size_one():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "MASTER_PORT", "LOCAL_RANK")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-           "--master-port", "29731", BENCH, "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"]
+           "--master-port", "29731", BENCH, "--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=580, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -51,6 +51,27 @@ def test_multi_rank_code_path_at_world_size_one():
     full = json.load(open(os.path.join(ROOT, out["extra_file"])))          # everything else is in the side file
     assert full["roofline"]["kernel"] in full["roofline"]["stages"]
     assert full["extra"]["c3_gather"]["checksum_qual"] == full["extra"]["c3_gather"]["checksum_qual"]
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_plain_run_is_the_headline_only(tmp_path):
+    """Without --full the run is set-up, warm-up and the timed steps: no oracle check, no CPU baseline, no other configs -- also
+    under the launcher, where the RCCL MAX-reduce of the elapsed times still runs."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "MASTER_PORT", "LOCAL_RANK")}
+    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
+    env["GIGA_BENCH_EXTRA"] = str(tmp_path / "bench_extra.json")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
+           "--master-port", "29733", BENCH, "--gpus", "1", "--steps", "5", "--warmup", "2"]
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=280, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 5 and out["warmup"] == 2 and out["value"] > 0 and out["rccl_ranks"] == 1
+    assert set(out["roofline"]) == {"kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_ms", "flops_per_launch"}
+    for k in ("checked_vs_oracle", "cpu_baseline", "c3_gather", "c5_train_step_fp32_data_parallel", "c5_train_step_bf16_data_parallel"):
+        assert k not in out, k
+    full = json.load(open(tmp_path / "bench_extra.json"))
+    assert set(full["extra"]) == {"rccl_ranks", "per_rank_seconds"}
 
 
 def test_contract_line_is_small_and_round_trips(tmp_path):
@@ -84,6 +105,27 @@ def test_contract_line_is_small_and_round_trips(tmp_path):
     full["summary"] = {f"k{i}": "x" * 100 for i in range(100)}
     text = bench.emit(full, path=str(side))
     assert len(text) < bench.LINE_LIMIT and all(k in json.loads(text) for k in bench.CONTRACT_KEYS)
+
+
+def test_result_without_the_pre_pass(tmp_path):
+    """A plain run makes no stage pre-pass (persistent U-Net): core_result builds the contract keys and the roofline from the timed
+    steps alone; given the pre-pass's numbers (--full) it adds the table of every stage."""
+    import argparse
+    sys.path.insert(0, ROOT)
+    import bench
+    K = 4
+    timed = dict(args=argparse.Namespace(warmup=2), world=1, B=32, M=2048, K=K, T=K * 0.34e-3, scenes_per_s=32 / 0.34e-3,
+                 dom=bench.UNET_STAGE, dom_ms=[0.23, 0.23], step_ms=[0.34] * K, named_ms=[0.04, 0.04], launches_per_step=5,
+                 persistent_unet=True)
+    plain = bench.core_result(stage_ms=None, dec_grasp_ms=None, dec_occ_ms=None, bracket_ms=None, unet_ms=None, **timed)
+    assert "stages" not in plain["roofline"] and "stage_note" not in plain
+    assert abs(plain["ms_per_step"] - 0.34) < 1e-12 and plain["roofline"]["avg_launch_ms"] == 0.23
+    line = json.loads(bench.emit(dict(plain, summary=bench.summary_of(plain)), path=str(tmp_path / "plain.json")))
+    assert all(k in line for k in bench.CONTRACT_KEYS) and set(line["roofline"]) == set(bench.ROOFLINE_KEYS)
+    full = bench.core_result(stage_ms=[0.04, 0.005] + [0.02] * 12 + [0.006], dec_grasp_ms=0.01, dec_occ_ms=0.05, bracket_ms=0.005,
+                             unet_ms=0.23, **timed)
+    assert full["roofline"]["stages"][bench.STAGE_NAMES[bench.UNET_STAGE]]["ms"] == 0.23
+    assert {k: v for k, v in full["roofline"].items() if k in plain["roofline"]} == plain["roofline"]
 
 
 def test_dump_outputs_writes_float32_within_the_limit(tmp_path, monkeypatch):
