@@ -53,6 +53,11 @@ int launch_train_loss_backward(const float* qual, const float* rot, const float*
 // giga_tsdf.hip
 int launch_tsdf_scatter(const int* index, const float* value, const int* offsets, int B, int R, int n, float* grid,
                         int* winner, hipStream_t s);
+// giga_mesh.hip
+size_t mesh_workspace_bytes(int B, int nx, int ny, int nz);
+int launch_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, uint8_t* ws, int* counts, hipStream_t s);
+int launch_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso, double box, const uint8_t* ws, float* vertices,
+                     size_t cap_v, int* triangles, size_t cap_t, int* shortfall, hipStream_t s);
 // giga_encoder.hip
 EncWs enc_workspace(int B, int precision);
 int launch_encoder(const float* tsdf, const uint8_t* blob, void* planes_nhwc, float* planes_nchw, int B,
@@ -694,6 +699,42 @@ int giga_adam_step(float* params, const float* grads, float* exp_avg, float* exp
          reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) return -1;
     return launch_adam_flat(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step,
                             static_cast<hipStream_t>(stream));
+}
+
+// ---- marching cubes (giga_mesh.hip) ----
+// 0 when the shape is supported, else the error code
+static int mesh_shape_check(int B, int nx, int ny, int nz) {
+    if (B < 0 || nx < 2 || ny < 2 || nz < 2) return -1;
+    if (nx > GIGA_MESH_MAX_N || ny > GIGA_MESH_MAX_N || nz > GIGA_MESH_MAX_N) return -1;
+    if (B > GIGA_MAX_SCENES) return -7;
+    if ((long long)B * (nx + 1) * (ny + 1) * (nz + 1) >= (1LL << 31)) return -1;      // cell numbers are 32-bit
+    return 0;
+}
+
+size_t giga_mesh_workspace_bytes(int B, int nx, int ny, int nz) {
+    if (B <= 0 || mesh_shape_check(B, nx, ny, nz) != 0) return 0;
+    return mesh_workspace_bytes(B, nx, ny, nz);
+}
+
+int giga_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, void* workspace, size_t workspace_bytes,
+                    int32_t* counts, void* stream) {
+    if (const int rc = mesh_shape_check(B, nx, ny, nz)) return rc;
+    if (B == 0) return 0;
+    if (!grids || !workspace || !counts || !(iso == iso)) return -1;
+    if (workspace_bytes < giga_mesh_workspace_bytes(B, nx, ny, nz)) return -4;
+    return launch_mesh_count(grids, B, nx, ny, nz, iso, static_cast<uint8_t*>(workspace), counts, static_cast<hipStream_t>(stream));
+}
+
+int giga_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso, double box_size, const void* workspace,
+                   size_t workspace_bytes, float* vertices, size_t cap_v, int32_t* triangles, size_t cap_t, int32_t* shortfall,
+                   void* stream) {
+    if (const int rc = mesh_shape_check(B, nx, ny, nz)) return rc;
+    if (B == 0) return 0;
+    if (!grids || !workspace || !(iso == iso) || !(box_size == box_size)) return -1;
+    if ((cap_v > 0 && !vertices) || (cap_t > 0 && !triangles)) return -6;
+    if (workspace_bytes < giga_mesh_workspace_bytes(B, nx, ny, nz)) return -4;
+    return launch_mesh_emit(grids, B, nx, ny, nz, iso, box_size, static_cast<const uint8_t*>(workspace), vertices, cap_v, triangles,
+                            cap_t, shortfall, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

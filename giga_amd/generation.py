@@ -7,26 +7,52 @@ The reference splits the query set into `points_batch_size` chunks, moves each c
 layout the decoder reads (`PlaneDict.nhwc`, produced once by `encode_inputs`), the fused decoder takes a whole
 chunk in ONE launch (there is no activation tensor whose size would call for chunking: `points_batch_size` only bounds
 the device copy of a HOST-resident query set, one chunk in flight at a time), and a regular grid of
-queries takes the lattice path (each plane sampled once per lattice coordinate pair).  Mesh extraction
-(`extract_mesh`, marching cubes via libmcubes) is host code outside the hot path and not part of this package."""
+queries takes the lattice path (each plane sampled once per lattice coordinate pair).
+
+Mesh extraction (`generate_mesh`, `generate_from_latent`, `extract_mesh`, generation.py:68-148, 360-428) runs on the device
+too: marching cubes is csrc/giga_mesh.hip (the reference pads the grid on the host and calls libmcubes), the vertices stay
+on the device for `estimate_normals`, and the only device-to-host traffic before the final copy of the mesh is the B x 2
+vertex / triangle counts.  MISE (utils/libmise) is NOT built: it exists to save decoder evaluations on a CPU by refining
+only cells next to the surface, and the dense grid of its `to_dense()` shape -- resolution0 * 2**upsampling_steps + 1
+samples per axis, 129^3 by default -- is one decoder launch here.  The mesh equals the reference's wherever MISE evaluated
+every sample next to the surface; it can contain components smaller than a coarse cell, which MISE skips.  Mesh
+refinement (`refinement_step`), simplification (`simplify_nfaces`) and the crop mode (`vol_bound`) are not built."""
+import time
+
 import numpy as np
 import torch
 
 from . import _capi
 from .convonet import _planes_to_nhwc, decoder_point_grad, register_lattice
+from .mesh import Mesh, marching_cubes
 
 
 class Generator3D:
     """generation.py:22-75 (the arguments that matter for the voxel-input GIGA models)."""
 
-    def __init__(self, model, points_batch_size=100000, threshold=0.5, device=None, resolution0=16, **mesh_options):
-        """`threshold`, `upsampling_steps`, `padding`, ... of generation.py:36-58 steer the host-side mesh extraction
-        (marching cubes / MISE), which is outside this package: they are accepted and kept in `mesh_options` untouched."""
+    def __init__(self, model, points_batch_size=100000, threshold=0.5, device=None, resolution0=16, upsampling_steps=3,
+                 with_normals=False, padding=0.1, refinement_step=0, simplify_nfaces=None, sample=False, input_type=None,
+                 vol_info=None, vol_bound=None):
+        """The reference's arguments by name (generation.py:42-49).  `refinement_step > 0` (second-order point gradients) and
+        `simplify_nfaces` (quadric simplification) are not built and raise here; `vol_bound` (crop mode) raises when a mesh
+        is asked for.  `mesh_options` records the mesh arguments as a dict."""
+        if refinement_step:
+            raise NotImplementedError("mesh refinement (refinement_step > 0) is not built")
+        if simplify_nfaces is not None:
+            raise NotImplementedError("mesh simplification (simplify_nfaces) is not built")
+        mesh_options = dict(upsampling_steps=upsampling_steps, with_normals=with_normals, padding=padding,
+                            refinement_step=refinement_step, simplify_nfaces=simplify_nfaces, sample=sample,
+                            input_type=input_type, vol_info=vol_info, vol_bound=vol_bound)
         self.model = model
         self.points_batch_size = int(points_batch_size)
         self.threshold = threshold
+        self.refinement_step = 0
         self.device = device if device is not None else torch.device("cuda")
         self.resolution0 = resolution0
+        self.upsampling_steps = int(upsampling_steps)
+        self.with_normals = bool(with_normals)
+        self.padding = padding
+        self.simplify_nfaces = None
         self.mesh_options = dict(mesh_options)
         self._grids = {}
 
@@ -59,20 +85,20 @@ class Generator3D:
         v = torch.from_numpy(np.asarray(vertices, dtype=np.float32)) if not torch.is_tensor(vertices) else vertices
         if v.dim() != 2 or v.shape[-1] != 3:
             raise ValueError(f"expected (N,3) vertices, got {tuple(v.shape)}")
-        model = self.model
         with torch.no_grad():
-            dev = self.device
             nhwc = _planes_to_nhwc(c, "fp32")
-            blob, bwd_blob = model.packed_blob(nhwc.device), model.packed_bwd_blob(nhwc.device)
             chunks = [v] if v.is_cuda or v.shape[0] <= self.points_batch_size else torch.split(v, self.points_batch_size)
-            normals = []
-            for vi in chunks:
-                vi = vi.to(dev, torch.float32).unsqueeze(0)
-                ones = torch.ones(vi.shape[:-1], device=vi.device)
-                ni = -decoder_point_grad(nhwc, vi, blob, bwd_blob, 8, {"decoder_tsdf": ones})
-                ni = ni / torch.norm(ni, dim=-1, keepdim=True)
-                normals.append(ni.squeeze(0).cpu().numpy())
+            normals = [self._normals_on_device(vi.to(self.device, torch.float32), nhwc).cpu().numpy() for vi in chunks]
         return np.concatenate(normals, axis=0) if normals else np.zeros((0, 3), np.float32)
+
+    def _normals_on_device(self, v, nhwc):
+        """`estimate_normals` for device-resident vertices (N,3) and the fp32 NHWC planes of one scene; the result stays on
+        the device (the mesh path copies vertices and normals to the host together, once)."""
+        blob, bwd_blob = self.model.packed_blob(nhwc.device), self.model.packed_bwd_blob(nhwc.device)
+        vi = v.unsqueeze(0)
+        ones = torch.ones(vi.shape[:-1], device=vi.device)
+        ni = -decoder_point_grad(nhwc, vi, blob, bwd_blob, 8, {"decoder_tsdf": ones})
+        return (ni / torch.norm(ni, dim=-1, keepdim=True)).squeeze(0)
 
     def grid_points(self, resolution, lo=-0.5, hi=0.5):
         """The (1, R^3, 3) regular grid `box_size * make_3d_grid((-0.5,)*3, (0.5,)*3, (R,)*3)` of generation.py:160-165
@@ -95,3 +121,115 @@ class Generator3D:
         with torch.no_grad():
             logits = self.model.decode_occ(self.grid_points(resolution, lo, hi), c).logits
         return logits.view(-1, resolution, resolution, resolution)
+
+    # ---- mesh extraction (generation.py:68-148, 360-428) ---------------------------------------------------------------
+    def grid_resolution(self):
+        """Samples per axis of the value grid: resolution0 for upsampling_steps == 0 (generation.py:117-124), else the
+        shape of MISE.to_dense(), resolution0 * 2**upsampling_steps + 1."""
+        return self.resolution0 if self.upsampling_steps == 0 else self.resolution0 * 2 ** self.upsampling_steps + 1
+
+    def _mesh_points(self, n, box_size):
+        """(1, n^3, 3): `box_size * make_3d_grid((-0.5,)*3, (0.5,)*3, (n,)*3)` with the reference's fp32 arithmetic (the
+        product is rounded after linspace, generation.py:119-121); registered as a lattice where the lattice decoder applies."""
+        key = ("mesh", int(n), float(box_size))
+        g = self._grids.get(key)
+        if g is None:
+            lin = box_size * torch.linspace(-0.5, 0.5, n)
+            x, y, z = torch.meshgrid(lin, lin, lin, indexing="ij")
+            g = torch.stack((x, y, z), dim=-1).float().reshape(1, n ** 3, 3).to(self.device)
+            self._grids[key] = register_lattice(g, lin) if n <= 64 else g
+        return g
+
+    def value_grid(self, c):
+        """Occupancy logits of every scene of `c` on the grid of `_mesh_points(n, 1 + padding)`, n = `grid_resolution()`:
+        (B,n,n,n) on the device.  Up to 64 samples per axis take the lattice decoder, larger grids the generic decoder in one
+        launch over all scenes."""
+        n = self.grid_resolution()
+        p = self._mesh_points(n, 1 + self.padding)
+        B = self._scenes(c)
+        if n > 64:
+            p = p.expand(B, -1, -1)
+        return self.eval_points(p, c).view(B, n, n, n)
+
+    @staticmethod
+    def _scenes(c):
+        """Number of scenes of the planes `c` (a PlaneDict of `encode`, or a reference-style dict of (B,32,40,40) tensors)."""
+        nhwc = getattr(c, "nhwc", None)
+        return int(nhwc.shape[1]) if nhwc is not None else int(next(iter(c.values())).shape[0])
+
+    def _iso(self):
+        return float(np.log(self.threshold) - np.log(1. - self.threshold))
+
+    def _meshes(self, grids, c, stats_dict):
+        """Marching cubes over (B,n,n,n) device grids (+ normals): one set of launches, then one copy per array and scene."""
+        if not torch.is_tensor(grids) or not grids.is_cuda:
+            raise _capi.GigaHipError("mesh extraction runs only on a HIP device (the value grid must be a device tensor); "
+                                     "there is no CPU fallback")
+        if self.mesh_options.get("vol_bound") is not None:
+            raise NotImplementedError("the crop mode (vol_bound) is not built")
+        if grids.shape[0] == 0:
+            return []
+        t0 = time.time()
+        vertices, triangles, counts = marching_cubes(grids, self._iso(), 1 + self.padding)
+        stats_dict["time (marching cubes)"] = time.time() - t0
+        v_end, t_end = counts[:, 0].cumsum(0).tolist(), counts[:, 1].cumsum(0).tolist()
+        normals = None
+        if self.with_normals and v_end[-1] > 0:
+            t0 = time.time()
+            with torch.no_grad():
+                nhwc = _planes_to_nhwc(c, "fp32")
+                normals = torch.empty_like(vertices)
+                for b, (v1, nv) in enumerate(zip(v_end, counts[:, 0].tolist())):
+                    if nv:
+                        normals[v1 - nv:v1] = self._normals_on_device(vertices[v1 - nv:v1], nhwc[:, b:b + 1].contiguous())
+            stats_dict["time (normals)"] = time.time() - t0
+        vertices, faces = vertices.cpu().numpy(), triangles.cpu().numpy().astype(np.int64)
+        normals = normals.cpu().numpy() if normals is not None else None
+        out = []
+        for b in range(grids.shape[0]):
+            v0, f0 = v_end[b] - int(counts[b, 0]), t_end[b] - int(counts[b, 1])
+            if v_end[b] == v0:
+                out.append(Mesh.empty())                       # generation.py:412-414: an empty mesh is returned as it is
+                continue
+            out.append(Mesh(vertices[v0:v_end[b]], faces[f0:t_end[b]], normals[v0:v_end[b]] if normals is not None else None))
+        return out
+
+    def extract_mesh(self, occ_hat, c=None, stats_dict=None):
+        """generation.py:360-428: occ_hat (nx,ny,nz) logits ON THE DEVICE -> Mesh in the model's coordinates,
+        `box_size * (index / (n - 1) - 0.5)`; vertex normals when `with_normals` (c: the planes of this scene)."""
+        if torch.is_tensor(occ_hat) and occ_hat.dim() != 3:
+            raise ValueError(f"expected an (nx,ny,nz) grid, got {tuple(occ_hat.shape)}")
+        return self._meshes(occ_hat.unsqueeze(0) if torch.is_tensor(occ_hat) else occ_hat, c,
+                            stats_dict if stats_dict is not None else {})[0]
+
+    def generate_from_latent(self, c=None, stats_dict=None, **kwargs):
+        """generation.py:102-148 with the dense grid in MISE's place (module docstring)."""
+        if self._scenes(c) != 1:
+            raise ValueError("generate_from_latent takes the planes of one scene; use generate_meshes for a batch")
+        stats_dict = stats_dict if stats_dict is not None else {}
+        t0 = time.time()
+        grid = self.value_grid(c)
+        stats_dict["time (eval points)"] = time.time() - t0
+        return self.extract_mesh(grid[0], c, stats_dict=stats_dict)
+
+    def generate_mesh(self, data, return_stats=True):
+        """generation.py:68-100: data["inputs"] (1,40,40,40) TSDF -> Mesh (and the stats dict).  The times are host times of
+        asynchronous launches; the count readback inside marching cubes is the first point that waits for the device."""
+        self.model.eval()
+        stats_dict = {}
+        t0 = time.time()
+        c = self.encode(data["inputs"])
+        stats_dict["time (encode inputs)"] = time.time() - t0
+        mesh = self.generate_from_latent(c, stats_dict=stats_dict)
+        return (mesh, stats_dict) if return_stats else mesh
+
+    def generate_meshes(self, tsdf_batch):
+        """B scenes (B,40,40,40) -> list of B meshes: one encoder call, one value-grid launch, one set of marching-cubes
+        launches.  Marching cubes and the normals are independent of the batch, so mesh b differs from `generate_mesh` on
+        scene b alone only as far as the planes do: byte for byte equal in the precisions whose encoder is independent of the
+        batch size (fp16x3, fp16); in fp32, whose encoder's summation order follows the batch, the
+        value grids agree at rounding level (well inside the 1e-4 fp32 tolerance), so the vertices move by that much and
+        an edge whose end lies that close to the threshold may be crossed in one mesh and not in the other."""
+        self.model.eval()
+        c = self.encode(tsdf_batch)
+        return self._meshes(self.value_grid(c), c, {})

@@ -354,6 +354,30 @@ int giga_grasp_select(const float* tsdf, const float* qual, const float* rot, co
                       float* cand_score, float* cand_rot, float* cand_width, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ---- mesh extraction: marching cubes on B dense value grids (conv_onet/generation.py:360-393, extract_mesh with
+ * vol_bound None; libmcubes.marching_cubes on the grid padded with -1e6) -----
+ * grids [B][nx][ny][nz] float32 (occupancy logits), 2 <= n <= GIGA_MESH_MAX_N per axis.  The padding by one sample of -1e6
+ * on every side is virtual.  A corner counts as set when value <= iso; every crossed edge of the padded grid gives ONE
+ * vertex at (iso - f1) / (f2 - f1) along it (evaluated in double, stored as float32), already in model coordinates
+ * box_size * (g / (n - 1) - 0.5) with g the fractional grid index in [-1, n].  Triangles are wound as the reference's (the
+ * normal points towards values <= iso).  Two phases, both asynchronous on `stream`, no allocation:
+ *   count : classify + scan.  counts [B][2] int32 (device) = {#vertices, #triangles} of every scene; the workspace keeps
+ *           the offsets and must reach the emit call unchanged (same grids, shape and iso).
+ *   emit  : scenes packed back to back in scene order: vertices [cap_v][3] float32, triangles [cap_t][3] int32 whose
+ *           entries count from the scene's OWN first vertex.  Within a scene the order is cell order (z fastest; edges
+ *           along x, y, z inside a cell), so equal input gives equal bytes.  Nothing is written at or beyond a capacity;
+ *           shortfall [2] int32 (device, may be NULL) receives the number of vertices and triangles that did not fit
+ *           (0, 0 when everything was written).
+ * Errors: -1 null grid / workspace / counts, n < 2 or n > GIGA_MESH_MAX_N, NaN iso, B (nx+1)(ny+1)(nz+1) >= 2^31;
+ * -4 workspace too small; -6 null output with a non-zero capacity; -7 B > GIGA_MAX_SCENES. */
+#define GIGA_MESH_MAX_N 256
+size_t giga_mesh_workspace_bytes(int B, int nx, int ny, int nz);
+int giga_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, void* workspace, size_t workspace_bytes,
+                    int32_t* counts, void* stream);
+int giga_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso, double box_size, const void* workspace,
+                   size_t workspace_bytes, float* vertices, size_t cap_v, int32_t* triangles, size_t cap_t, int32_t* shortfall,
+                   void* stream);
+
 /* Number of kernel launches the library has enqueued in this process so far (all streams): the difference around a call is
  * that call's launch count.  Diagnostic only. */
 unsigned long long giga_launch_count(void);
