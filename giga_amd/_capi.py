@@ -130,6 +130,14 @@ _SIGNATURES = {
     "giga_mesh_emit": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
                                       ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
                                       ctypes.c_void_p, ctypes.c_void_p]),
+    "giga_nn_query_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
+    "giga_nn_query": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_mesh_sample_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
+    "giga_mesh_sample": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int] + [ctypes.c_void_p] * 5
+                         + [ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_mesh_contains_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "giga_mesh_contains": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                                  ctypes.c_size_t, ctypes.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

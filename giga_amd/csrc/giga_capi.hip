@@ -58,6 +58,18 @@ size_t mesh_workspace_bytes(int B, int nx, int ny, int nz);
 int launch_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, uint8_t* ws, int* counts, hipStream_t s);
 int launch_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso, double box, const uint8_t* ws, float* vertices,
                      size_t cap_v, int* triangles, size_t cap_t, int* shortfall, hipStream_t s);
+// giga_eval.hip
+size_t nn_workspace_bytes(int B, int n_src);
+int launch_nn_query(const float* src, const int* src_offsets, const float* tgt, const int* tgt_offsets, int B, float* dist,
+                    int* idx, uint8_t* ws, hipStream_t s);
+size_t sample_workspace_bytes(int B, int n_tri);
+int launch_mesh_sample(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets, int B,
+                       int n, unsigned long long seed, int first_scene, float* points, int* face, float* normals, int* counts,
+                       uint8_t* ws, hipStream_t s);
+size_t contains_workspace_bytes(int B, int n_tri, int n_pts);
+int launch_mesh_contains(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
+                         const double* points, const int* point_offsets, int B, int resolution, uint8_t* inside, uint8_t* ws,
+                         hipStream_t s);
 // giga_encoder.hip
 EncWs enc_workspace(int B, int precision);
 int launch_encoder(const float* tsdf, const uint8_t* blob, void* planes_nhwc, float* planes_nchw, int B,
@@ -735,6 +747,73 @@ int giga_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso
     if (workspace_bytes < giga_mesh_workspace_bytes(B, nx, ny, nz)) return -4;
     return launch_mesh_emit(grids, B, nx, ny, nz, iso, box_size, static_cast<const uint8_t*>(workspace), vertices, cap_v, triangles,
                             cap_t, shortfall, static_cast<hipStream_t>(stream));
+}
+
+// ---- mesh evaluation (giga_eval.hip) ----
+// offsets of a ragged batch (host array of B + 1 entries): starts at 0 and never decreases
+static bool ragged_ok(const int32_t* offs, int B) {
+    if (!offs || offs[0] != 0) return false;
+    for (int b = 0; b < B; ++b)
+        if (offs[b + 1] < offs[b]) return false;
+    return true;
+}
+static int ragged_batch_check(int B) { return B < 0 ? -1 : (B > GIGA_MAX_SCENES ? -7 : 0); }
+
+size_t giga_nn_query_workspace_bytes(int B, int n_src) {
+    if (B <= 0 || B > GIGA_MAX_SCENES || n_src < 0) return 0;
+    return nn_workspace_bytes(B, n_src);
+}
+
+int giga_nn_query(const float* src, const int32_t* src_offsets, const float* tgt, const int32_t* tgt_offsets, int B, float* dist,
+                  int32_t* idx, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = ragged_batch_check(B)) return rc;
+    if (B == 0) return 0;
+    if (!ragged_ok(src_offsets, B) || !ragged_ok(tgt_offsets, B)) return -1;
+    if (src_offsets[B] == 0) return 0;
+    if (!src || (tgt_offsets[B] > 0 && !tgt) || !workspace) return -1;
+    if (!dist || !idx) return -6;
+    if (workspace_bytes < giga_nn_query_workspace_bytes(B, src_offsets[B])) return -4;
+    return launch_nn_query(src, src_offsets, tgt, tgt_offsets, B, dist, idx, static_cast<uint8_t*>(workspace),
+                           static_cast<hipStream_t>(stream));
+}
+
+size_t giga_mesh_sample_workspace_bytes(int B, int n_triangles) {
+    if (B <= 0 || B > GIGA_MAX_SCENES || n_triangles < 0) return 0;
+    return sample_workspace_bytes(B, n_triangles);
+}
+
+int giga_mesh_sample(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                     int B, int n, uint64_t seed, int first_scene, float* points, int32_t* face, float* normals, int32_t* counts,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = ragged_batch_check(B)) return rc;
+    if (n < 0 || first_scene < 0 || (long long)B * n >= (1LL << 31)) return -1;
+    if (B == 0) return 0;
+    if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B)) return -1;
+    if ((vertex_offsets[B] > 0 && !vertices) || (triangle_offsets[B] > 0 && !triangles) || !workspace) return -1;
+    if (!counts || (n > 0 && (!points || !face || !normals))) return -6;
+    if (workspace_bytes < giga_mesh_sample_workspace_bytes(B, triangle_offsets[B])) return -4;
+    return launch_mesh_sample(vertices, vertex_offsets, triangles, triangle_offsets, B, n, seed, first_scene, points, face, normals, counts,
+                              static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+size_t giga_mesh_contains_workspace_bytes(int B, int n_triangles, int n_points) {
+    if (B <= 0 || B > GIGA_MAX_SCENES || n_triangles < 0 || n_points < 0) return 0;
+    return contains_workspace_bytes(B, n_triangles, n_points);
+}
+
+int giga_mesh_contains(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                       const double* points, const int32_t* point_offsets, int B, int resolution, uint8_t* inside, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    if (const int rc = ragged_batch_check(B)) return rc;
+    if (resolution < 2 || resolution > GIGA_CONTAINS_MAX_RESOLUTION) return -1;
+    if (B == 0) return 0;
+    if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B) || !ragged_ok(point_offsets, B)) return -1;
+    if (point_offsets[B] == 0) return 0;
+    if ((vertex_offsets[B] > 0 && !vertices) || (triangle_offsets[B] > 0 && !triangles) || !points || !workspace) return -1;
+    if (!inside) return -6;
+    if (workspace_bytes < giga_mesh_contains_workspace_bytes(B, triangle_offsets[B], point_offsets[B])) return -4;
+    return launch_mesh_contains(vertices, vertex_offsets, triangles, triangle_offsets, points, point_offsets, B, resolution, inside,
+                                static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

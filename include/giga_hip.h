@@ -378,6 +378,52 @@ int giga_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso
                    size_t workspace_bytes, float* vertices, size_t cap_v, int32_t* triangles, size_t cap_t, int32_t* shortfall,
                    void* stream);
 
+/* ---- mesh evaluation on ragged batches (vgn/ConvONets/eval.py:28-232, utils/libmesh/inside_mesh.py) -----
+ * B scenes packed back to back, the layout giga_mesh_emit produces: every `*_offsets` argument is a HOST array of B + 1 int32
+ * that starts at 0 and never decreases; scene b owns rows offsets[b] .. offsets[b+1]-1 of the DEVICE array it belongs to, and a
+ * scene's triangles [.][3] int32 count from the scene's OWN first vertex.  The offsets are read (and copied into the workspace)
+ * before a call returns.  Caller-owned buffers, no allocation, asynchronous on `stream`; every argument is checked before the
+ * first HIP call.  No floating-point atomics: equal input gives equal bytes, and a batch gives scene b the bytes of a call on
+ * scene b alone.
+ * Errors (all three): -1 negative B / count, null input or workspace, offsets that do not start at 0 or decrease, resolution
+ * outside 2 .. GIGA_CONTAINS_MAX_RESOLUTION, B n >= 2^31; -4 workspace too small; -6 null output; -7 B > GIGA_MAX_SCENES.
+ *
+ * giga_nn_query: for every source point [.][3] float32 the nearest target point of the SAME scene, exact brute force on float32
+ * differences, d2 = (dx*dx + dy*dy) + dz*dz with one rounding per operation.  dist [n_src] float32 = sqrt(d2) (Euclidean),
+ * idx [n_src] int32 relative to the scene's first target; ties go to the lowest index; a scene without targets (or whose
+ * distances are all NaN) gives dist = +inf, idx = -1.  workspace: giga_nn_query_workspace_bytes(B, src_offsets[B]).
+ *
+ * giga_mesh_sample: n points per scene, uniform over the scene's surface.  Sample i of scene b draws one Philox-4x32-10 block
+ * with counter (i, first_scene + b, 0, 0) (first_scene >= 0: a call on scene b alone with first_scene = b repeats the batch's
+ * bytes) and key (seed & 0xffffffff, seed >> 32); r0, r1, r2 = words 0, 1, 2 times 2^-32 (double).  Face
+ * areas 0.5 |cross(v1 - v0, v2 - v0)| and their inclusive prefix sums inside the scene are double; the sample lies on the first
+ * face whose prefix sum exceeds r0 * total (a face without area is never chosen; neither is one with an index outside the
+ * scene's vertices or a non-finite area) at (1 - sqrt r1) v0 + sqrt r1 (1 - r2) v1 + sqrt r1 r2 v2, evaluated in double.
+ * Outputs at row b * n + i: points [B n][3] float32, face [B n] int32 (relative to the scene's first face), normals [B n][3]
+ * float32 = cross(v1 - v0, v2 - v0) normalised in double.  counts [B] int32 (device) = n, or 0 for a scene without faces or with
+ * total area 0 (or not finite): NOTHING is written to that scene's rows.  workspace:
+ * giga_mesh_sample_workspace_bytes(B, triangle_offsets[B]).
+ *
+ * giga_mesh_contains: inside [n_points] uint8 = 1 where the query point (points [.][3] FLOAT64, so that float32 and float64 callers
+ * both get the reference's arithmetic) lies inside its scene's mesh, as MeshIntersector(mesh, resolution).query decides it, in
+ * double and in the reference's operand order without fused multiply-adds: triangles and points rescaled by scale =
+ * (resolution - 1) / (bbox_max - bbox_min), translate = 0.5 - scale bbox_min (the scene's own box over the vertices its faces
+ * use); candidates = the triangles whose clamped cell range holds the point's cell (triangle_hash.pyx); a candidate is hit when
+ * det != 0 and 0 < u, v, u + v < |det|; inside = both (#hits with depth >= p.z |n.z|) and (#hits with depth < p.z |n.z|) odd.  A
+ * scene without faces has no inside.  workspace: giga_mesh_contains_workspace_bytes(B, triangle_offsets[B], point_offsets[B]). */
+#define GIGA_CONTAINS_MAX_RESOLUTION 32768
+size_t giga_nn_query_workspace_bytes(int B, int n_src);
+int giga_nn_query(const float* src, const int32_t* src_offsets, const float* tgt, const int32_t* tgt_offsets, int B, float* dist,
+                  int32_t* idx, void* workspace, size_t workspace_bytes, void* stream);
+size_t giga_mesh_sample_workspace_bytes(int B, int n_triangles);
+int giga_mesh_sample(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                     int B, int n, uint64_t seed, int first_scene, float* points, int32_t* face, float* normals, int32_t* counts,
+                     void* workspace, size_t workspace_bytes, void* stream);
+size_t giga_mesh_contains_workspace_bytes(int B, int n_triangles, int n_points);
+int giga_mesh_contains(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                       const double* points, const int32_t* point_offsets, int B, int resolution, uint8_t* inside, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* Number of kernel launches the library has enqueued in this process so far (all streams): the difference around a call is
  * that call's launch count.  Diagnostic only. */
 unsigned long long giga_launch_count(void);
