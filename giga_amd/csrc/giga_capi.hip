@@ -53,6 +53,14 @@ int launch_train_loss_backward(const float* qual, const float* rot, const float*
 // giga_tsdf.hip
 int launch_tsdf_scatter(const int* index, const float* value, const int* offsets, int B, int R, int n, float* grid,
                         int* winner, hipStream_t s);
+size_t tsdf_integrate_workspace_bytes(int B, int n_views);
+int launch_tsdf_integrate(const float* depth, const int* view_offsets, const double* extrinsics, const double* intrinsics, int B,
+                          int W, int H, double length, int R, double sdf_trunc, double depth_scale, double depth_trunc, float* tsdf,
+                          float* weight, float* grid, uint8_t* ws, hipStream_t s);
+size_t tsdf_cloud_workspace_bytes(int B, int R);
+int launch_tsdf_cloud_count(const float* tsdf, const float* weight, int B, int R, uint8_t* ws, int* counts, hipStream_t s);
+int launch_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, double length, const uint8_t* ws, float* points,
+                           size_t cap, int* shortfall, hipStream_t s);
 // giga_mesh.hip
 size_t mesh_workspace_bytes(int B, int nx, int ny, int nz);
 int launch_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, uint8_t* ws, int* counts, hipStream_t s);
@@ -814,6 +822,74 @@ int giga_mesh_contains(const float* vertices, const int32_t* vertex_offsets, con
     if (workspace_bytes < giga_mesh_contains_workspace_bytes(B, triangle_offsets[B], point_offsets[B])) return -4;
     return launch_mesh_contains(vertices, vertex_offsets, triangles, triangle_offsets, points, point_offsets, B, resolution, inside,
                                 static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+
+// ---- depth fusion (giga_tsdf.hip) ----
+static bool tsdf_finite(double x) { return x - x == 0.0; }
+
+static int tsdf_volume_check(int B, int R) {
+    if (B < 0 || R < 2 || R > GIGA_TSDF_MAX_R) return -1;
+    if (B > GIGA_MAX_SCENES) return -7;
+    return 0;
+}
+
+size_t giga_tsdf_integrate_workspace_bytes(int B, int n_views) {
+    if (B <= 0 || B > GIGA_MAX_SCENES || n_views < 0) return 0;
+    return tsdf_integrate_workspace_bytes(B, n_views);
+}
+
+int giga_tsdf_integrate(const float* depth, const int32_t* view_offsets, const double* extrinsics, const double* intrinsics, int B,
+                        int width, int height, double length, int R, double sdf_trunc, double depth_scale, double depth_trunc,
+                        float* tsdf, float* weight, float* grid, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = tsdf_volume_check(B, R)) return rc;
+    if (width < 1 || height < 1 || width > GIGA_TSDF_MAX_IMAGE || height > GIGA_TSDF_MAX_IMAGE) return -1;
+    if (!tsdf_finite(length) || !(length > 0.0) || !tsdf_finite(sdf_trunc) || !(sdf_trunc > 0.0) || !tsdf_finite(depth_scale) ||
+        !(depth_scale > 0.0) || !(depth_trunc == depth_trunc))
+        return -1;
+    if (B == 0) return 0;
+    if (!ragged_ok(view_offsets, B)) return -1;
+    const int n = view_offsets[B];
+    if ((long long)n * width * height >= (1LL << 40)) return -1;
+    if (n > 0) {
+        if (!extrinsics || !intrinsics || !depth) return -1;
+        for (size_t i = 0; i < (size_t)n * 16; ++i)
+            if (!tsdf_finite(extrinsics[i])) return -1;
+        for (size_t i = 0; i < (size_t)n * 4; ++i)
+            if (!tsdf_finite(intrinsics[i])) return -1;
+        for (int v = 0; v < n; ++v)
+            if (intrinsics[4 * (size_t)v] == 0.0 || intrinsics[4 * (size_t)v + 1] == 0.0) return -1;
+    }
+    if (!tsdf || !weight || !workspace) return -1;
+    if (workspace_bytes < giga_tsdf_integrate_workspace_bytes(B, n)) return -4;
+    return launch_tsdf_integrate(depth, view_offsets, extrinsics, intrinsics, B, width, height, length, R, sdf_trunc, depth_scale,
+                                 depth_trunc, tsdf, weight, grid, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+size_t giga_tsdf_cloud_workspace_bytes(int B, int R) {
+    if (B <= 0 || tsdf_volume_check(B, R) != 0) return 0;
+    return tsdf_cloud_workspace_bytes(B, R);
+}
+
+int giga_tsdf_cloud_count(const float* tsdf, const float* weight, int B, int R, void* workspace, size_t workspace_bytes,
+                          int32_t* counts, void* stream) {
+    if (const int rc = tsdf_volume_check(B, R)) return rc;
+    if (B == 0) return 0;
+    if (!tsdf || !weight || !workspace || !counts) return -1;
+    if (workspace_bytes < giga_tsdf_cloud_workspace_bytes(B, R)) return -4;
+    return launch_tsdf_cloud_count(tsdf, weight, B, R, static_cast<uint8_t*>(workspace), counts, static_cast<hipStream_t>(stream));
+}
+
+int giga_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, double length, const void* workspace,
+                         size_t workspace_bytes, float* points, size_t cap, int32_t* shortfall, void* stream) {
+    if (const int rc = tsdf_volume_check(B, R)) return rc;
+    if (!tsdf_finite(length) || !(length > 0.0)) return -1;
+    if (B == 0) return 0;
+    if (!tsdf || !weight || !workspace) return -1;
+    if (cap > 0 && !points) return -6;
+    if (workspace_bytes < giga_tsdf_cloud_workspace_bytes(B, R)) return -4;
+    return launch_tsdf_cloud_emit(tsdf, weight, B, R, length, static_cast<const uint8_t*>(workspace), points, cap, shortfall,
+                                  static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -9,7 +9,10 @@
 // Indices outside [0, R) are ignored on the device (numpy would raise; the Python wrapper checks host-side inputs).
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <vector>
 
 namespace giga {
 
@@ -54,6 +57,294 @@ int launch_tsdf_scatter(const int* index, const float* value, const int* offsets
     const unsigned blocks = (unsigned)((n + 255) / 256);
     GIGA_LAUNCH(tsdf_claim_kernel, dim3(blocks), dim3(256), 0, s, index, offsets, B, R, n, winner);
     GIGA_LAUNCH(tsdf_write_kernel, dim3(blocks), dim3(256), 0, s, index, value, offsets, B, R, n, winner, grid);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Fusion of depth images into the volume: the device counterpart of vgn.perception.TSDFVolume.integrate / get_grid / get_cloud
+// (reference src/vgn/perception.py:63-126), which hand the work to Open3D's UniformTSDFVolume (NoColor).  The arithmetic below
+// restates that algorithm operation by operation (include/giga_hip.h spells it out); every operation is one IEEE rounding --
+// no contraction from here on -- so that a numpy restatement reproduces the bytes (tests/tsdf_emu.py).
+//
+//   integrate  one lane per voxel, z fastest across lanes: the state (tsdf, weight) and the exported grid are read and written
+//              once per call, coalesced.  The lane loops over its scene's views with tsdf and weight in registers: no atomics,
+//              and the result does not depend on the launch shape or on the other scenes of the batch.  The camera of a view is
+//              read through a wave-uniform address (scene = blockIdx.y), so it lives in scalar registers; the only divergent
+//              access is the depth gather, where neighbouring z-voxels project to the same or neighbouring pixels.
+//   cloud      zero crossings between a voxel and its +x, +y, +z neighbour (extract_point_cloud without normals): count
+//              (ballot + popcount inside a wave, LDS across the four waves, per-workgroup sums), scan (one workgroup per scene,
+//              then one wave over the scenes), emit at (scene base + workgroup offset + prefix).  Order: cell order, then axis
+//              0, 1, 2; no atomics decide it (the scheme of giga_mesh.hip).
+#pragma clang fp contract(off)
+
+constexpr int TSDF_BLOCK = 256;
+constexpr int TSDF_WAVES = TSDF_BLOCK / 64;
+constexpr int TSDF_SCAN = 1024;
+constexpr int TSDF_CAM = 20;                  // doubles per view in the workspace: extrinsic [16] row-major, fx, fy, cx, cy
+
+struct TsdfVol {
+    double voxel;                             // length / R
+    float neg_trunc, inv_trunc;               // -float(sdf_trunc), float(1 / sdf_trunc)
+    float depth_scale, depth_trunc;
+    int R, W, H;
+    unsigned cells;                           // R^3
+};
+
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_integrate_kernel(const float* __restrict__ depth, const int* __restrict__ view_offsets,
+                                                                    const double* __restrict__ cams, TsdfVol g,
+                                                                    float* __restrict__ tsdf, float* __restrict__ weight,
+                                                                    float* __restrict__ grid) {
+    const unsigned cell = blockIdx.x * TSDF_BLOCK + threadIdx.x, scene = blockIdx.y;
+    if (cell >= g.cells) return;
+    const unsigned R = (unsigned)g.R;
+    const unsigned z = cell % R, xy = cell / R, y = xy % R, x = xy / R;
+    const double px = ((double)x + 0.5) * g.voxel, py = ((double)y + 0.5) * g.voxel, pz = ((double)z + 0.5) * g.voxel;
+    const size_t at = (size_t)scene * g.cells + cell;
+    float t = tsdf[at], w = weight[at];
+    const int v0 = view_offsets[scene], v1 = view_offsets[scene + 1];
+    const size_t pixels = (size_t)g.W * g.H;
+    const double umax = (double)g.W - 0.0001, vmax = (double)g.H - 0.0001;
+    for (int v = v0; v < v1; ++v) {
+        const double* __restrict__ c = cams + (size_t)v * TSDF_CAM;          // wave-uniform address: scalar loads
+        const double cz = ((c[8] * px + c[9] * py) + c[10] * pz) + c[11];
+        if (!(cz > 0.0)) continue;
+        const double cx = ((c[0] * px + c[1] * py) + c[2] * pz) + c[3];
+        const double cy = ((c[4] * px + c[5] * py) + c[6] * pz) + c[7];
+        const double fx = c[16], fy = c[17], ox = c[18], oy = c[19];
+        const double uf = (cx * fx / cz + ox) + 0.5, vf = (cy * fy / cz + oy) + 0.5;
+        if (!(uf >= 0.0001 && uf < umax && vf >= 0.0001 && vf < vmax)) continue;
+        const int u = (int)uf, r = (int)vf;                                   // 0 <= u < W, 0 <= r < H by the test above
+        float d = depth[(size_t)v * pixels + (size_t)r * g.W + u] / g.depth_scale;
+        if (d >= g.depth_trunc) d = 0.f;
+        if (!(d > 0.f)) continue;
+        const double a = ((double)u - ox) / fx, b = ((double)r - oy) / fy;
+        const float m = (float)sqrt((a * a + b * b) + 1.0);
+        const float sdf = (float)(((double)d - cz) * (double)m);
+        if (!(sdf > g.neg_trunc)) continue;
+        const float s = fminf(1.0f, sdf * g.inv_trunc);
+        t = (t * w + s) / (w + 1.0f);
+        w += 1.0f;
+    }
+    tsdf[at] = t;
+    weight[at] = w;
+    if (grid) grid[at] = (w != 0.f && (double)t >= -0.98 && (double)t < 0.98) ? (float)(((double)t + 1.0) * 0.5) : 0.f;
+}
+
+static size_t tsdf_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct IntegrateWs { size_t offs, cams, total; };
+static IntegrateWs integrate_workspace(int B, int n_views) {
+    IntegrateWs w;
+    w.offs = 0;
+    w.cams = tsdf_align((size_t)(B + 1) * sizeof(int));
+    w.total = w.cams + tsdf_align((size_t)n_views * TSDF_CAM * sizeof(double));
+    return w;
+}
+size_t tsdf_integrate_workspace_bytes(int B, int n_views) { return integrate_workspace(B, n_views).total; }
+
+int launch_tsdf_integrate(const float* depth, const int* view_offsets, const double* extrinsics, const double* intrinsics, int B,
+                          int W, int H, double length, int R, double sdf_trunc, double depth_scale, double depth_trunc, float* tsdf,
+                          float* weight, float* grid, uint8_t* ws, hipStream_t s) {
+    const int n = view_offsets[B];
+    const IntegrateWs w = integrate_workspace(B, n);
+    int* offs = reinterpret_cast<int*>(ws + w.offs);
+    double* cams = reinterpret_cast<double*>(ws + w.cams);
+    // (pageable host memory: the copies have left the caller's arrays when the call returns)
+    if (hipMemcpyAsync(offs, view_offsets, (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return -10;
+    if (n > 0) {
+        std::vector<double> host((size_t)n * TSDF_CAM);
+        for (int v = 0; v < n; ++v) {
+            std::memcpy(&host[(size_t)v * TSDF_CAM], extrinsics + 16 * (size_t)v, 16 * sizeof(double));
+            std::memcpy(&host[(size_t)v * TSDF_CAM + 16], intrinsics + 4 * (size_t)v, 4 * sizeof(double));
+        }
+        if (hipMemcpyAsync(cams, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess) return -10;
+    }
+    TsdfVol g;
+    g.voxel = length / (double)R;
+    g.neg_trunc = -(float)sdf_trunc;
+    g.inv_trunc = (float)(1.0 / sdf_trunc);
+    g.depth_scale = (float)depth_scale;
+    g.depth_trunc = (float)depth_trunc;
+    g.R = R; g.W = W; g.H = H;
+    g.cells = (unsigned)R * R * R;
+    GIGA_LAUNCH(tsdf_integrate_kernel, dim3((g.cells + TSDF_BLOCK - 1) / TSDF_BLOCK, B), dim3(TSDF_BLOCK), 0, s, depth, offs, cams, g,
+                tsdf, weight, grid);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+// ---- zero-crossing points ----
+struct CloudRead { float f0, f1[3]; unsigned flags; unsigned x, y, z; };
+
+__device__ __forceinline__ bool tsdf_valid(float t, float w) { return w != 0.f && (double)t >= -0.98 && (double)t < 0.98; }
+
+// flags bit i: the edge from the cell to its neighbour along axis i holds a point
+__device__ __forceinline__ CloudRead cloud_read(const float* __restrict__ tsdf, const float* __restrict__ weight, unsigned R,
+                                                unsigned cell) {
+    CloudRead c;
+    c.z = cell % R;
+    const unsigned xy = cell / R;
+    c.y = xy % R;
+    c.x = xy / R;
+    c.flags = 0;
+    c.f0 = tsdf[cell];
+    c.f1[0] = c.f1[1] = c.f1[2] = 0.f;
+    if (!tsdf_valid(c.f0, weight[cell])) return c;
+    const unsigned n[3] = {c.x, c.y, c.z}, stride[3] = {R * R, R, 1u};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (n[i] + 1 >= R - 1) continue;
+        const unsigned nb = cell + stride[i];
+        const float f1 = tsdf[nb];
+        if (tsdf_valid(f1, weight[nb]) && c.f0 * f1 < 0.f) { c.flags |= 1u << i; c.f1[i] = f1; }
+    }
+    return c;
+}
+
+// exclusive prefix of the number of set flags over the workgroup's cells, in cell order; the workgroup's total in tot
+__device__ __forceinline__ unsigned cloud_block_scan(unsigned flags, unsigned* wsum, unsigned& tot) {
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const unsigned long long bx = __ballot(flags & 1), by = __ballot(flags & 2), bz = __ballot(flags & 4);
+    unsigned pre = __popcll(bx & lt) + __popcll(by & lt) + __popcll(bz & lt);
+    if (lane == 0) wsum[wave] = __popcll(bx) + __popcll(by) + __popcll(bz);
+    __syncthreads();
+    tot = 0;
+#pragma unroll
+    for (unsigned w = 0; w < TSDF_WAVES; ++w) {
+        if (w < wave) pre += wsum[w];
+        tot += wsum[w];
+    }
+    return pre;
+}
+
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_cloud_count_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight,
+                                                                      unsigned R, unsigned cells, unsigned nblk,
+                                                                      unsigned* __restrict__ blk) {
+    __shared__ unsigned wsum[TSDF_WAVES];
+    const unsigned cell = blockIdx.x * TSDF_BLOCK + threadIdx.x, scene = blockIdx.y;
+    const size_t base = (size_t)scene * cells;
+    const unsigned flags = cell < cells ? cloud_read(tsdf + base, weight + base, R, cell).flags : 0u;
+    unsigned tot;
+    cloud_block_scan(flags, wsum, tot);
+    if (threadIdx.x == 0) blk[(size_t)scene * nblk + blockIdx.x] = tot;
+}
+
+__device__ __forceinline__ unsigned long long tsdf_wave_incl(unsigned long long x, unsigned lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long y = __shfl_up(x, o, 64);
+        if (lane >= (unsigned)o) x += y;
+    }
+    return x;
+}
+
+// workgroup sums of one scene -> exclusive offsets (in place), the scene's total to counts
+__global__ __launch_bounds__(TSDF_SCAN) void tsdf_cloud_scan_kernel(unsigned* __restrict__ blk, unsigned nblk, int* __restrict__ counts) {
+    __shared__ unsigned wsum[TSDF_SCAN / 64];
+    __shared__ unsigned carry;
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned* b = blk + (size_t)blockIdx.x * nblk;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (unsigned base = 0; base < nblk; base += TSDF_SCAN) {
+        const unsigned idx = base + threadIdx.x;
+        const unsigned own = idx < nblk ? b[idx] : 0u;
+        const unsigned inc = (unsigned)tsdf_wave_incl(own, lane);
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        unsigned pre = carry + inc - own, all = 0;
+#pragma unroll
+        for (unsigned w = 0; w < TSDF_SCAN / 64; ++w) {
+            if (w < wave) pre += wsum[w];
+            all += wsum[w];
+        }
+        if (idx < nblk) b[idx] = pre;
+        __syncthreads();
+        if (threadIdx.x == 0) carry += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) counts[blockIdx.x] = (int)carry;
+}
+
+// bases[b] = points of the scenes before b; bases[B] = the total.  One wave.
+__global__ __launch_bounds__(64) void tsdf_cloud_bases_kernel(const int* __restrict__ counts, int B, unsigned long long* __restrict__ bases) {
+    const unsigned lane = threadIdx.x;
+    unsigned long long carry = 0;
+    for (int base = 0; base < B; base += 64) {
+        const int b = base + (int)lane;
+        const unsigned long long n = b < B ? (unsigned)counts[b] : 0u;
+        const unsigned long long inc = tsdf_wave_incl(n, lane);
+        if (b < B) bases[b] = carry + inc - n;
+        carry += __shfl(inc, 63, 64);
+    }
+    if (lane == 0) bases[B] = carry;
+}
+
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_cloud_emit_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight,
+                                                                     unsigned R, unsigned cells, unsigned nblk, double voxel,
+                                                                     const unsigned* __restrict__ blk,
+                                                                     const unsigned long long* __restrict__ bases, int B,
+                                                                     float* __restrict__ points, unsigned long long cap,
+                                                                     int* __restrict__ shortfall) {
+    __shared__ unsigned wsum[TSDF_WAVES];
+    const unsigned cell = blockIdx.x * TSDF_BLOCK + threadIdx.x, scene = blockIdx.y;
+    if (shortfall && blockIdx.x == 0 && scene == 0 && threadIdx.x == 0) {
+        const unsigned long long tot = bases[B], big = 0x7fffffffull;
+        shortfall[0] = (int)(tot > cap ? (tot - cap < big ? tot - cap : big) : 0);
+    }
+    const size_t base = (size_t)scene * cells;
+    CloudRead c;
+    c.flags = 0;
+    if (cell < cells) c = cloud_read(tsdf + base, weight + base, R, cell);
+    unsigned tot;
+    const unsigned pre = cloud_block_scan(c.flags, wsum, tot);
+    if (!c.flags) return;
+    unsigned long long at = bases[scene] + blk[(size_t)scene * nblk + blockIdx.x] + pre;
+    const double p0[3] = {((double)c.x + 0.5) * voxel, ((double)c.y + 0.5) * voxel, ((double)c.z + 0.5) * voxel};
+    const double a0 = fabs((double)c.f0);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (!(c.flags >> i & 1)) continue;
+        if (at < cap) {
+            const double a1 = fabs((double)c.f1[i]);
+            float* o = points + 3 * at;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) o[q] = (float)p0[q];
+            o[i] = (float)((p0[i] * a1 + (p0[i] + voxel) * a0) / (a0 + a1));
+        }
+        ++at;
+    }
+}
+
+struct CloudWs { size_t blk, bases, total; unsigned cells, nblk; };
+static CloudWs cloud_workspace(int B, int R) {
+    CloudWs w;
+    w.cells = (unsigned)R * R * R;
+    w.nblk = (w.cells + TSDF_BLOCK - 1) / TSDF_BLOCK;
+    w.blk = 0;
+    w.bases = tsdf_align((size_t)B * w.nblk * sizeof(unsigned));
+    w.total = w.bases + tsdf_align((size_t)(B + 1) * sizeof(unsigned long long));
+    return w;
+}
+size_t tsdf_cloud_workspace_bytes(int B, int R) { return cloud_workspace(B, R).total; }
+
+int launch_tsdf_cloud_count(const float* tsdf, const float* weight, int B, int R, uint8_t* ws, int* counts, hipStream_t s) {
+    const CloudWs w = cloud_workspace(B, R);
+    unsigned* blk = reinterpret_cast<unsigned*>(ws + w.blk);
+    unsigned long long* bases = reinterpret_cast<unsigned long long*>(ws + w.bases);
+    GIGA_LAUNCH(tsdf_cloud_count_kernel, dim3(w.nblk, B), dim3(TSDF_BLOCK), 0, s, tsdf, weight, (unsigned)R, w.cells, w.nblk, blk);
+    GIGA_LAUNCH(tsdf_cloud_scan_kernel, dim3(B), dim3(TSDF_SCAN), 0, s, blk, w.nblk, counts);
+    GIGA_LAUNCH(tsdf_cloud_bases_kernel, dim3(1), dim3(64), 0, s, counts, B, bases);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int launch_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, double length, const uint8_t* ws, float* points,
+                           size_t cap, int* shortfall, hipStream_t s) {
+    const CloudWs w = cloud_workspace(B, R);
+    GIGA_LAUNCH(tsdf_cloud_emit_kernel, dim3(w.nblk, B), dim3(TSDF_BLOCK), 0, s, tsdf, weight, (unsigned)R, w.cells, w.nblk,
+                length / (double)R, reinterpret_cast<const unsigned*>(ws + w.blk),
+                reinterpret_cast<const unsigned long long*>(ws + w.bases), B, points, (unsigned long long)cap, shortfall);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 

@@ -181,7 +181,8 @@ def grasp_select(tsdf, qual, rot, width, voxel_size=None, out_th=0.5, threshold=
 class VGNImplicit:
     """Device-resident counterpart of the reference planner (detection_implicit.py:17-85): network on the 40^3
     lattice + grasp post-processing, one D->H copy of the selected grasps.  `__call__(state)` keeps the
-    reference's contract (state.tsdf a (1,R,R,R) numpy grid or an object with get_grid()/voxel_size/size) and
+    reference's contract (state.tsdf a (1,R,R,R) numpy grid, an object with get_grid()/voxel_size/size, or a
+    giga_amd.perception.TSDFVolume, whose device grid is taken as it is) and
     returns (grasps, scores, toc) where each grasp is a dict {rotation (xyzw quat), translation (m), width (m)}
     -- the fields of vgn.grasp.Grasp/Transform, which live outside this package.  `plan_batch` is the batched,
     tensor-in form."""
@@ -263,17 +264,24 @@ class VGNImplicit:
         return _grasp_collect(buf, self.force_detection)
 
     def __call__(self, state, scene_mesh=None, aff_kwargs={}):
+        from .perception import TSDFVolume
         tsdf_process = state.tsdf_process if hasattr(state, "tsdf_process") else state.tsdf
-        if isinstance(state.tsdf, np.ndarray):
-            tsdf_vol, voxel_size, size = state.tsdf, 0.3 / self.resolution, 0.3
-        else:
-            tsdf_vol, voxel_size, size = state.tsdf.get_grid(), tsdf_process.voxel_size, state.tsdf.size
-            tsdf_process = tsdf_process.get_grid()
         R = self.resolution
-        tic = time.time()
-        t = torch.from_numpy(np.ascontiguousarray(tsdf_vol, np.float32).reshape(1, R, R, R)).to(self.device)
-        tp = t if tsdf_process is tsdf_vol else torch.from_numpy(
-            np.ascontiguousarray(tsdf_process, np.float32).reshape(1, R, R, R)).to(self.device)
+        if isinstance(state.tsdf, TSDFVolume):                 # fused on the device: the grid never visits the host
+            voxel_size, size = tsdf_process.voxel_size, state.tsdf.size
+            tic = time.time()
+            t = state.tsdf.grid().to(self.device).reshape(1, R, R, R)
+            tp = t if tsdf_process is state.tsdf else tsdf_process.grid().to(self.device).reshape(1, R, R, R)
+        else:
+            if isinstance(state.tsdf, np.ndarray):
+                tsdf_vol, voxel_size, size = state.tsdf, 0.3 / self.resolution, 0.3
+            else:
+                tsdf_vol, voxel_size, size = state.tsdf.get_grid(), tsdf_process.voxel_size, state.tsdf.size
+                tsdf_process = tsdf_process.get_grid()
+            tic = time.time()
+            t = torch.from_numpy(np.ascontiguousarray(tsdf_vol, np.float32).reshape(1, R, R, R)).to(self.device)
+            tp = t if tsdf_process is tsdf_vol else torch.from_numpy(
+                np.ascontiguousarray(tsdf_process, np.float32).reshape(1, R, R, R)).to(self.device)
         sel = self.plan_batch(t, tp, voxel_size)[0]
         toc = time.time() - tic
         k = len(sel["score"])
@@ -281,3 +289,11 @@ class VGNImplicit:
         grasps = [{"rotation": sel["rot"][i], "translation": (sel["position"][i] + 0.5) * size,
                    "width": float(sel["width"][i]) * size} for i in p]
         return grasps, sel["score"][p], toc
+
+    def plan_from_depth(self, depth_imgs, intrinsic, extrinsics, size=0.3):
+        """Depth images (n, H, W) with their extrinsics (any form perception.extrinsic_matrix takes) to grasps: fusion, network
+        and post-processing on the device.  Returns what __call__ returns."""
+        from types import SimpleNamespace
+
+        from .perception import create_tsdf
+        return self(SimpleNamespace(tsdf=create_tsdf(size, self.resolution, depth_imgs, intrinsic, extrinsics, self.device)))

@@ -294,6 +294,53 @@ size_t giga_tsdf_scatter_workspace_bytes(int B, int R);
 int giga_tsdf_scatter(const int32_t* voxel_index, const float* voxel_value, const int32_t* scene_offsets, int B, int R,
                       int n_voxels, float* grid, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- input side: fusion of depth images into the volume (src/vgn/perception.py:63-126: TSDFVolume.integrate, get_grid,
+ * get_cloud, which the reference hands to Open3D's UniformTSDFVolume with NoColor) -----
+ * giga_tsdf_integrate fuses, for B scenes in one launch, scene b's views view_offsets[b] .. view_offsets[b+1]-1 into that scene's
+ * state.  depth [n_views][height][width] float32 (device) holds the images of all scenes back to back.  HOST arrays, read (and
+ * copied into the workspace) before the call returns: view_offsets [B+1] int32, extrinsics [n_views][16] double (task -> camera,
+ * row-major 4x4), intrinsics [n_views][4] double (fx, fy, cx, cy).  The volume is the cube [0, length]^3 with R cells per axis,
+ * voxel_length = length / R; the reference passes sdf_trunc = 4 voxel_length, depth_scale = 1, depth_trunc = 2.  State: tsdf and
+ * weight [B][R][R][R] float32 (device), cell (x, y, z) at x R R + y R + z, read and updated in place (zeros = a new volume; a
+ * later call with further views continues the running average).  Per voxel and view, in view order (E the extrinsic):
+ *     p   = (x + 0.5, y + 0.5, z + 0.5) voxel_length                                          double
+ *     pc  = E[:3,:3] p + E[:3,3], every row ((e0 p.x + e1 p.y) + e2 p.z) + e3                  double; skip unless pc.z > 0
+ *     u_f = pc.x fx / pc.z + cx + 0.5, v_f = pc.y fy / pc.z + cy + 0.5                        double
+ *     skip unless 0.0001 <= u_f < width - 0.0001 and 0.0001 <= v_f < height - 0.0001;  u, v = (int) u_f, (int) v_f
+ *     d   = depth[v][u] / float(depth_scale); d = 0 if d >= float(depth_trunc)                float32; skip unless d > 0
+ *     m   = float(sqrt((((u - cx) / fx)^2 + ((v - cy) / fy)^2) + 1))                          double, rounded once
+ *     sdf = float((double(d) - pc.z) double(m));  skip unless sdf > -float(sdf_trunc)
+ *     t   = min(1, sdf float(1 / sdf_trunc));  tsdf = (tsdf weight + t) / (weight + 1);  weight += 1       float32
+ * with one IEEE rounding per operation (no fused multiply-add).  grid [B][R][R][R] float32 (device, may be NULL) receives in the
+ * same pass the network input that get_grid builds from extract_voxel_grid: float((double(tsdf) + 1) 0.5) where weight != 0 and
+ * -0.98 <= tsdf < 0.98 (compared in double), 0 elsewhere.  One lane per voxel with the views looped inside: no atomics, equal
+ * input gives equal bytes, and a batch gives scene b the bytes of a call on scene b alone.
+ * Every argument is checked before the first HIP call.  Errors: -1 negative B, R outside 2 .. GIGA_TSDF_MAX_R, width or height
+ * outside 1 .. GIGA_TSDF_MAX_IMAGE, length / sdf_trunc / depth_scale not finite or <= 0, NaN depth_trunc, offsets that do not
+ * start at 0 or decrease, a non-finite camera entry, fx or fy equal to 0, null depth / cameras (with views) / state / workspace;
+ * -4 workspace too small (giga_tsdf_integrate_workspace_bytes(B, view_offsets[B])); -7 B > GIGA_MAX_SCENES.  B = 0 returns 0.
+ *
+ * giga_tsdf_cloud_count / giga_tsdf_cloud_emit: the points of extract_point_cloud (no normals, no colours).  A voxel is valid when
+ * weight != 0 and -0.98 <= tsdf < 0.98.  A valid voxel with value f0 at p0 = (x + 0.5, y + 0.5, z + 0.5) voxel_length gives, for
+ * each axis i whose neighbour index n_i + 1 < R - 1, whose neighbour is valid with value f1, and f0 f1 < 0 (float32 product), the
+ * point p0 with component i replaced by (p0_i |f1| + (p0_i + voxel_length) |f0|) / (|f0| + |f1|), evaluated in double and stored
+ * as float32.  Two phases like giga_mesh_count / giga_mesh_emit: count writes counts [B] int32 (device) and keeps the offsets in
+ * the workspace (giga_tsdf_cloud_workspace_bytes(B, R)), which must reach emit unchanged together with the same state; emit
+ * writes points [cap][3] float32, scenes back to back, in cell order and then axis order inside a scene.  Nothing is written at or
+ * beyond cap; shortfall [1] int32 (device, may be NULL) receives the number of points that did not fit.
+ * Errors: -1 as above or null state / workspace / counts; -4; -6 null points with cap > 0; -7. */
+#define GIGA_TSDF_MAX_R 512
+#define GIGA_TSDF_MAX_IMAGE 16384
+size_t giga_tsdf_integrate_workspace_bytes(int B, int n_views);
+int giga_tsdf_integrate(const float* depth, const int32_t* view_offsets, const double* extrinsics, const double* intrinsics, int B,
+                        int width, int height, double length, int R, double sdf_trunc, double depth_scale, double depth_trunc,
+                        float* tsdf, float* weight, float* grid, void* workspace, size_t workspace_bytes, void* stream);
+size_t giga_tsdf_cloud_workspace_bytes(int B, int R);
+int giga_tsdf_cloud_count(const float* tsdf, const float* weight, int B, int R, void* workspace, size_t workspace_bytes,
+                          int32_t* counts, void* stream);
+int giga_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, double length, const void* workspace,
+                         size_t workspace_bytes, float* points, size_t cap, int32_t* shortfall, void* stream);
+
 /* ---- fused training loss (scripts/train_giga.py:154-195: `select` + `loss_fn`, literal call shape N = 1) -----
  * Inputs are the head outputs of the model's forward for one grasp query per scene -- qual [B] (post sigmoid), rot [B][4]
  * (unit), width [B], occ_logits [B][M] (raw; the sigmoid of `select` is part of this function) -- and the labels of
