@@ -30,6 +30,7 @@ DIRECT_CONV = 1024       # GIGA_DIRECT_CONV: precision 0 keeps the direct 3x3 co
 PATH_PERSISTENT, PATH_CONV32, PATH_FUSED_PAIRS, PATH_WINOGRAD = 1, 2, 4, 8          # giga_encoder_last_path()
 MESH_MAX_N = 256         # GIGA_MESH_MAX_N: samples per axis of a marching-cubes grid
 TSDF_MAX_R = 512         # GIGA_TSDF_MAX_R: cells per axis of a fused volume
+RENDER_MAX_IMAGE = 4096  # GIGA_RENDER_MAX_IMAGE: width and height of a rendered depth image
 MAX_SCENES = 3072        # GIGA_MAX_SCENES: scenes per encoder / training call (error -7 beyond)
 HEAD_BITS = {"decoder_qual": 1, "decoder_rot": 2, "decoder_width": 4, "decoder_tsdf": 8}
 PLANES_FP32 = 1024       # GIGA_PLANES_FP32: fp32 planes into the plain-f16 lattice decoder
@@ -147,6 +148,9 @@ _SIGNATURES = {
     "giga_mesh_contains_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "giga_mesh_contains": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                                   ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_depth_render_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "giga_depth_render": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 3 + [ctypes.c_double] * 3 + [ctypes.c_void_p] * 2
+                          + [ctypes.c_size_t, ctypes.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -61,6 +61,11 @@ size_t tsdf_cloud_workspace_bytes(int B, int R);
 int launch_tsdf_cloud_count(const float* tsdf, const float* weight, int B, int R, uint8_t* ws, int* counts, hipStream_t s);
 int launch_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, double length, const uint8_t* ws, float* points,
                            size_t cap, int* shortfall, hipStream_t s);
+// giga_render.hip
+size_t depth_render_workspace_bytes(int B, int n_views);
+int launch_depth_render(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
+                        const int* view_offsets, const double* extrinsics, const double* intrinsics, int B, int W, int H, double near,
+                        double far, double pixel_offset, float* depth, uint8_t* ws, hipStream_t s);
 // giga_mesh.hip
 size_t mesh_workspace_bytes(int B, int nx, int ny, int nz);
 int launch_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, uint8_t* ws, int* counts, hipStream_t s);
@@ -890,6 +895,37 @@ int giga_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, d
     if (workspace_bytes < giga_tsdf_cloud_workspace_bytes(B, R)) return -4;
     return launch_tsdf_cloud_emit(tsdf, weight, B, R, length, static_cast<const uint8_t*>(workspace), points, cap, shortfall,
                                   static_cast<hipStream_t>(stream));
+}
+
+// ---- depth rendering (giga_render.hip) ----
+size_t giga_depth_render_workspace_bytes(int B, int n_views, int n_vertices, int n_triangles) {
+    if (B <= 0 || B > GIGA_MAX_SCENES || n_views < 0 || n_vertices < 0 || n_triangles < 0) return 0;
+    return depth_render_workspace_bytes(B, n_views);
+}
+
+int giga_depth_render(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                      const int32_t* view_offsets, const double* extrinsics, const double* intrinsics, int B, int W, int H, double near,
+                      double far, double pixel_offset, float* depth, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = ragged_batch_check(B)) return rc;
+    if (W < 1 || H < 1 || W > GIGA_RENDER_MAX_IMAGE || H > GIGA_RENDER_MAX_IMAGE) return -1;
+    if (!tsdf_finite(near) || !tsdf_finite(far) || !(near > 0.0) || !(far > near) || !tsdf_finite(pixel_offset)) return -1;
+    if (B == 0) return 0;
+    if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B) || !ragged_ok(view_offsets, B)) return -1;
+    const int n = view_offsets[B];
+    if ((long long)n * W * H >= (1LL << 31)) return -1;
+    if ((vertex_offsets[B] > 0 && !vertices) || (triangle_offsets[B] > 0 && !triangles)) return -1;
+    if (n == 0) return 0;
+    if (!extrinsics || !intrinsics || !workspace) return -1;
+    for (size_t i = 0; i < (size_t)n * 16; ++i)
+        if (!tsdf_finite(extrinsics[i])) return -1;
+    for (size_t i = 0; i < (size_t)n * 4; ++i)
+        if (!tsdf_finite(intrinsics[i])) return -1;
+    for (int v = 0; v < n; ++v)
+        if (intrinsics[4 * (size_t)v] == 0.0 || intrinsics[4 * (size_t)v + 1] == 0.0) return -1;
+    if (!depth) return -6;
+    if (workspace_bytes < giga_depth_render_workspace_bytes(B, n, vertex_offsets[B], triangle_offsets[B])) return -4;
+    return launch_depth_render(vertices, vertex_offsets, triangles, triangle_offsets, view_offsets, extrinsics, intrinsics, B, W, H, near,
+                               far, pixel_offset, depth, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

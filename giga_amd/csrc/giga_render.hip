@@ -1,0 +1,215 @@
+// Depth images of posed triangle meshes: the device counterpart of the depth half of btsim.Camera.render (reference
+// src/vgn/utils/btsim.py:276-337), which the reference hands to PyBullet's renderer.  The semantics are this project's own and are
+// spelled out in include/giga_hip.h (giga_depth_render): a double-precision, watertight ray / triangle test per pixel centre, the
+// minimum accepted camera-space z per pixel, `far` where nothing is hit.  Every operation is one IEEE rounding -- no contraction
+// in this file -- so that a numpy restatement reproduces the bytes (tests/render_emu.py).
+//
+//   one workgroup per (16 x 16 pixel tile, view), one lane per pixel: no atomics decide a pixel.
+//   The workgroup walks its scene's triangles 256 at a time, one triangle per lane: the lane transforms the three vertices into
+//   the camera frame, forms the three edge normals n = P x Q (they do not depend on the pixel) and decides whether ANY pixel of
+//   the tile can accept the triangle.  That decision uses the very numbers the pixels will compute: e(d) = (d.x n.x + d.y n.y) + n.z
+//   is, rounding included, monotone in d.x and in d.y (a rounded product or sum is monotone in each operand), and d is monotone in
+//   the pixel index, so the smallest and largest e over the tile's pixels are its values at two corner pixels.  A pixel is hit
+//   only if U, V, W are all >= 0 or all <= 0; the tile can be skipped when some edge is < 0 on every pixel AND some edge is > 0
+//   on every pixel.  No margin is needed, vertices behind the camera need no special case, and a NaN makes every comparison
+//   false, which keeps the triangle.  The second reason to skip is depth: an accepted z is a convex combination of the three
+//   vertex depths, so all three < near or all three > far cannot be accepted.
+//   Survivors are compacted (ballot + popcount inside a wave, LDS across the four waves, as giga_mesh.hip does) into an LDS list
+//   of 12 doubles each (three normals, three depths).  When the list cannot take another 256 it is flushed: every lane runs the
+//   test of its pixel against each entry; all lanes read the same entry, so the LDS read is a broadcast.
+#include <hip/hip_runtime.h>
+#include "giga_launch.h"
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+namespace giga {
+
+#pragma clang fp contract(off)
+
+constexpr int RENDER_TILE = 16;                   // pixels per tile side
+constexpr int RENDER_BLOCK = RENDER_TILE * RENDER_TILE;
+constexpr int RENDER_WAVES = RENDER_BLOCK / 64;
+constexpr int RENDER_CAP = 384;                   // LDS list: 384 x 96 B = 36 KB (four workgroups per CU)
+constexpr int RENDER_CAM = 20;                    // doubles per view in the workspace: extrinsic [16] row-major, fx, fy, cx, cy
+static_assert(RENDER_CAP >= 2 * RENDER_BLOCK - 128 && RENDER_CAP >= RENDER_BLOCK, "a flush leaves room for one more chunk");
+
+struct RenderTri {                                // what a pixel needs of a triangle (a, b, c in the camera frame)
+    double nbc[3], nca[3], nab[3];                // b x c, c x a, a x b
+    double az, bz, cz;
+};
+
+struct RenderArgs {
+    const float* vertices;
+    const int* triangles;
+    const int* voffs;                             // workspace copies (device)
+    const int* toffs;
+    const int* view_scene;
+    const double* cams;
+    unsigned long long* tested;                   // measurement aid: triangle-tile pairs that survived the culling
+    float* depth;
+    double near, far, pixel_offset;
+    int W, H, tiles_x, tiles;                     // tiles per view
+};
+
+__device__ __forceinline__ void render_cross(const double* P, const double* Q, double* n) {
+    n[0] = P[1] * Q[2] - P[2] * Q[1];
+    n[1] = P[2] * Q[0] - P[0] * Q[2];
+    n[2] = P[0] * Q[1] - P[1] * Q[0];
+}
+
+__device__ __forceinline__ double render_edge(double dx, double dy, const double* n) { return (dx * n[0] + dy * n[1]) + n[2]; }
+
+// smallest and largest e over the pixels of a tile whose directions span [x0, x1] x [y0, y1] (see the head of the file)
+__device__ __forceinline__ void render_edge_range(const double* n, double x0, double x1, double y0, double y1, double& lo, double& hi) {
+    const bool px = n[0] >= 0.0, py = n[1] >= 0.0;
+    lo = render_edge(px ? x0 : x1, py ? y0 : y1, n);
+    hi = render_edge(px ? x1 : x0, py ? y1 : y0, n);
+}
+
+__global__ __launch_bounds__(RENDER_BLOCK) void depth_render_kernel(RenderArgs g) {
+    __shared__ RenderTri list[RENDER_CAP];
+    __shared__ int wcnt[2][RENDER_WAVES];
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int view = (int)(blockIdx.x / (unsigned)g.tiles), tile = (int)(blockIdx.x % (unsigned)g.tiles);
+    const int u0 = (tile % g.tiles_x) * RENDER_TILE, v0 = (tile / g.tiles_x) * RENDER_TILE;
+    const int u = u0 + (int)(tid & (RENDER_TILE - 1)), v = v0 + (int)(tid / RENDER_TILE);
+    const double* __restrict__ c = g.cams + (size_t)view * RENDER_CAM;        // wave-uniform address: scalar loads
+    const double fx = c[16], fy = c[17], ox = c[18], oy = c[19];
+    const double dx = (((double)u + g.pixel_offset) - ox) / fx, dy = (((double)v + g.pixel_offset) - oy) / fy;
+    // directions of the tile's first and last pixel inside the image
+    const int u1 = min(u0 + RENDER_TILE, g.W) - 1, v1 = min(v0 + RENDER_TILE, g.H) - 1;
+    const double xa = (((double)u0 + g.pixel_offset) - ox) / fx, xb = (((double)u1 + g.pixel_offset) - ox) / fx;
+    const double ya = (((double)v0 + g.pixel_offset) - oy) / fy, yb = (((double)v1 + g.pixel_offset) - oy) / fy;
+    const double x0 = fmin(xa, xb), x1 = fmax(xa, xb), y0 = fmin(ya, yb), y1 = fmax(ya, yb);
+
+    const int scene = g.view_scene[view];
+    const int vbase = g.voffs[scene], nv = g.voffs[scene + 1] - vbase;
+    const int t0 = g.toffs[scene], t1 = g.toffs[scene + 1];
+    const float* __restrict__ vert = g.vertices + 3 * (size_t)vbase;
+
+    double best = __builtin_huge_val();
+    int count = 0, parity = 0;                    // entries in the list (the same number in every lane)
+    unsigned long long tested = 0;
+
+    auto flush = [&]() {
+        __syncthreads();
+        for (int s = 0; s < count; ++s) {
+            const RenderTri& t = list[s];         // every lane reads the same entry: broadcast
+            const double U = render_edge(dx, dy, t.nbc), V = render_edge(dx, dy, t.nca), Wd = render_edge(dx, dy, t.nab);
+            const double S = (U + V) + Wd;
+            const bool pos = U >= 0.0 && V >= 0.0 && Wd >= 0.0, neg = U <= 0.0 && V <= 0.0 && Wd <= 0.0;
+            if (S != 0.0 && (pos || neg)) {
+                const double z = ((U * t.az + V * t.bz) + Wd * t.cz) / S;
+                if (z >= g.near && z <= g.far && z < best) best = z;
+            }
+        }
+        tested += (unsigned long long)count;
+        __syncthreads();
+        count = 0;
+    };
+
+    for (int base = t0; base < t1; base += RENDER_BLOCK) {
+        const int tri = base + (int)tid;
+        bool keep = false;
+        RenderTri t;
+        if (tri < t1) {
+            const int* __restrict__ f = g.triangles + 3 * (size_t)tri;
+            const int ia = f[0], ib = f[1], ic = f[2];
+            if ((unsigned)ia < (unsigned)nv && (unsigned)ib < (unsigned)nv && (unsigned)ic < (unsigned)nv) {
+                const int idx[3] = {ia, ib, ic};
+                double p[3][3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const float* __restrict__ q = vert + 3 * (size_t)idx[k];
+                    const double x = (double)q[0], y = (double)q[1], z = (double)q[2];
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) p[k][r] = ((c[4 * r] * x + c[4 * r + 1] * y) + c[4 * r + 2] * z) + c[4 * r + 3];
+                }
+                render_cross(p[1], p[2], t.nbc);
+                render_cross(p[2], p[0], t.nca);
+                render_cross(p[0], p[1], t.nab);
+                t.az = p[0][2]; t.bz = p[1][2]; t.cz = p[2][2];
+                double lo[3], hi[3];
+                render_edge_range(t.nbc, x0, x1, y0, y1, lo[0], hi[0]);
+                render_edge_range(t.nca, x0, x1, y0, y1, lo[1], hi[1]);
+                render_edge_range(t.nab, x0, x1, y0, y1, lo[2], hi[2]);
+                const bool never_pos = hi[0] < 0.0 || hi[1] < 0.0 || hi[2] < 0.0;      // some edge is negative on every pixel
+                const bool never_neg = lo[0] > 0.0 || lo[1] > 0.0 || lo[2] > 0.0;      // some edge is positive on every pixel
+                const bool too_near = t.az < g.near && t.bz < g.near && t.cz < g.near;
+                const bool too_far = t.az > g.far && t.bz > g.far && t.cz > g.far;
+                keep = !(never_pos && never_neg) && !too_near && !too_far;
+            }
+        }
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) wcnt[parity][wave] = __popcll(m);
+        __syncthreads();
+        int at = count + __popcll(m & ((1ull << lane) - 1ull)), total = 0;
+#pragma unroll
+        for (int w = 0; w < RENDER_WAVES; ++w) {
+            const int n = wcnt[parity][w];
+            if (w < (int)wave) at += n;
+            total += n;
+        }
+        if (keep) list[at] = t;                   // at < count + total <= RENDER_CAP
+        count += total;
+        parity ^= 1;
+        if (count > RENDER_CAP - RENDER_BLOCK) flush();
+    }
+    if (count > 0) flush();
+
+    if (u < g.W && v < g.H)
+        g.depth[((size_t)view * g.H + v) * g.W + u] = best <= g.far ? (float)best : (float)g.far;
+    if (tid == 0 && tested) atomicAdd(g.tested, tested);
+}
+
+static size_t render_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct RenderWs { size_t tested, voffs, toffs, view_scene, cams, total; };
+static RenderWs render_workspace(int B, int n_views) {
+    RenderWs w;
+    w.tested = 0;
+    w.voffs = 256;
+    w.toffs = w.voffs + render_align((size_t)(B + 1) * sizeof(int));
+    w.view_scene = w.toffs + render_align((size_t)(B + 1) * sizeof(int));
+    w.cams = w.view_scene + render_align((size_t)n_views * sizeof(int));
+    w.total = w.cams + render_align((size_t)n_views * RENDER_CAM * sizeof(double));
+    return w;
+}
+size_t depth_render_workspace_bytes(int B, int n_views) { return render_workspace(B, n_views).total; }
+
+int launch_depth_render(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
+                        const int* view_offsets, const double* extrinsics, const double* intrinsics, int B, int W, int H, double near,
+                        double far, double pixel_offset, float* depth, uint8_t* ws, hipStream_t s) {
+    const int n = view_offsets[B];
+    const RenderWs w = render_workspace(B, n);
+    // one staging buffer, one copy (pageable host memory: the copy has left it when the call returns)
+    std::vector<uint8_t> host(w.total, 0);
+    std::memcpy(&host[w.voffs], vertex_offsets, (size_t)(B + 1) * sizeof(int));
+    std::memcpy(&host[w.toffs], triangle_offsets, (size_t)(B + 1) * sizeof(int));
+    int* view_scene = reinterpret_cast<int*>(&host[w.view_scene]);
+    for (int b = 0; b < B; ++b)
+        for (int v = view_offsets[b]; v < view_offsets[b + 1]; ++v) view_scene[v] = b;
+    for (int v = 0; v < n; ++v) {
+        std::memcpy(&host[w.cams + (size_t)v * RENDER_CAM * sizeof(double)], extrinsics + 16 * (size_t)v, 16 * sizeof(double));
+        std::memcpy(&host[w.cams + ((size_t)v * RENDER_CAM + 16) * sizeof(double)], intrinsics + 4 * (size_t)v, 4 * sizeof(double));
+    }
+    if (hipMemcpyAsync(ws, host.data(), w.total, hipMemcpyHostToDevice, s) != hipSuccess) return -10;
+    RenderArgs g;
+    g.vertices = vertices;
+    g.triangles = triangles;
+    g.voffs = reinterpret_cast<const int*>(ws + w.voffs);
+    g.toffs = reinterpret_cast<const int*>(ws + w.toffs);
+    g.view_scene = reinterpret_cast<const int*>(ws + w.view_scene);
+    g.cams = reinterpret_cast<const double*>(ws + w.cams);
+    g.tested = reinterpret_cast<unsigned long long*>(ws + w.tested);
+    g.depth = depth;
+    g.near = near; g.far = far; g.pixel_offset = pixel_offset;
+    g.W = W; g.H = H;
+    g.tiles_x = (W + RENDER_TILE - 1) / RENDER_TILE;
+    g.tiles = g.tiles_x * ((H + RENDER_TILE - 1) / RENDER_TILE);
+    GIGA_LAUNCH(depth_render_kernel, dim3((unsigned)g.tiles * (unsigned)n), dim3(RENDER_BLOCK), 0, s, g);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+}  // namespace giga

@@ -1,0 +1,240 @@
+"""Depth images and occupancy labels from triangle meshes on the device: what the reference derives from its simulated scene.
+
+`Camera.render` / `render_depth` / `render_depth_batch` are the depth half of `btsim.Camera.render` (reference
+src/vgn/utils/btsim.py:276-337, PyBullet there) through `giga_depth_render` (csrc/giga_render.hip; semantics in
+include/giga_hip.h): a double-precision watertight ray / triangle test per pixel, `far` where nothing is hit.  `acquire_tsdf` is
+`ClutterRemovalSim.acquire_tsdf` (simulation.py:145-186) on a scene mesh, `write_raw_scenes` the raw files `construct_dataset`
+consumes, `sample_iou_points` / `save_occ` the occupancy labels of utils/implicit.py:78-90 and scripts/save_occ_data_parallel.py
+on top of `giga_mesh_contains`.  Meshes are `(vertices, faces)` pairs of numpy arrays or device tensors (or objects with these
+attributes); loading mesh files stays with the caller.  There is no CPU path: CPU tensors raise `GigaHipError`.
+
+Not reproduced: PyBullet's fill rule at silhouettes, its z-buffer quantisation, RGB, the depth noise models."""
+import json
+import os
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from . import _capi, perception
+from .eval import _device, _hptr, _mesh_devices, _mesh_parts, _offsets, _pack_meshes, mesh_contains_batch
+
+SIM_INTRINSIC = (640, 480, 540.0, 540.0, 320.0, 240.0)       # simulation.py:38: width, height, fx, fy, cx, cy
+SIM_NEAR, SIM_FAR = 0.1, 2.0                                  # simulation.py:39
+
+
+def sim_intrinsic():
+    return perception.CameraIntrinsic(*SIM_INTRINSIC)
+
+
+def scene_mesh(mesh_pose_list):
+    """[(vertices (n, 3), faces (m, 3), scale, pose 4x4), ...] -> one (vertices float32, faces int32) pair: `scale` then `pose`
+    applied in float64, faces re-based: the array form of get_scene_from_mesh_pose_list (utils/implicit.py:53-76)."""
+    verts, faces, base = [], [], 0
+    for v, f, scale, pose in mesh_pose_list:
+        v = np.asarray(v, np.float64).reshape(-1, 3) * np.asarray(scale, np.float64)
+        pose = np.asarray(pose, np.float64).reshape(4, 4)
+        v = v @ pose[:3, :3].T + pose[:3, 3]
+        verts.append(v.astype(np.float32))
+        faces.append(np.asarray(f, np.int64).reshape(-1, 3) + base)
+        base += len(v)
+    if not verts:
+        return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
+    return np.concatenate(verts), np.concatenate(faces).astype(np.int32)
+
+
+# ------------------------------------------------------------------------------------------------ rendering
+def render_depth_batch(meshes, intrinsic, extrinsics_batches, near=SIM_NEAR, far=SIM_FAR, pixel_offset=0.0, device=None, stats=None):
+    """B scenes with ragged view counts in one launch: meshes[b] seen from extrinsics_batches[b] (any extrinsic form).
+    Returns (depth (n_total, H, W) float32 device tensor, view_offsets (B + 1) int32): view k of scene b is image
+    view_offsets[b] + k, the layout `perception.integrate_batch` consumes.  stats (a dict) receives 'tile_pairs', the number of
+    (triangle, 16x16 tile) pairs that survived the kernel's culling (this reads the workspace back: a synchronisation)."""
+    if len(extrinsics_batches) != len(meshes):
+        raise ValueError("one list of extrinsics per mesh")
+    B = len(meshes)
+    tensors = _mesh_devices(meshes)
+    dev = torch.device(device) if device is not None else _device(*tensors)
+    if dev.type != "cuda":
+        raise _capi.GigaHipError("depth rendering runs on a HIP device; there is no CPU fallback")
+    _capi.device_of(*[t for t in tensors if torch.is_tensor(t)], torch.empty(0, device=dev))
+    H, W = int(intrinsic.height), int(intrinsic.width)
+    view_offsets = _offsets([len(e) for e in extrinsics_batches])
+    n = int(view_offsets[-1])
+    depth = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+    if B == 0 or n == 0:
+        return depth, view_offsets
+    v, vo, f, fo = _pack_meshes(meshes, dev)
+    ext = np.ascontiguousarray(np.stack([perception.extrinsic_matrix(e) for batch in extrinsics_batches for e in batch]).reshape(n, 16))
+    cam = np.ascontiguousarray(np.tile(np.array([intrinsic.fx, intrinsic.fy, intrinsic.cx, intrinsic.cy], np.float64), (n, 1)))
+    L = _capi.lib()
+    ws = torch.empty(max(L.giga_depth_render_workspace_bytes(B, n, int(vo[-1]), int(fo[-1])), 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _capi.check(L.giga_depth_render(_capi.ptr(v), _hptr(vo), _capi.ptr(f), _hptr(fo), _hptr(view_offsets), ext.ctypes.data,
+                                        cam.ctypes.data, B, W, H, float(near), float(far), float(pixel_offset), _capi.ptr(depth),
+                                        _capi.ptr(ws), ws.numel(), _capi.stream_ptr(dev)), "giga_depth_render")
+    if stats is not None:
+        stats["tile_pairs"] = stats.get("tile_pairs", 0) + int(ws[:8].cpu().numpy().view(np.uint64)[0])
+    return depth, view_offsets
+
+
+def render_depth(vertices, faces, intrinsic, extrinsics, near=SIM_NEAR, far=SIM_FAR, pixel_offset=0.0, device=None):
+    """(n, H, W) float32 device tensor: one mesh seen from n extrinsics."""
+    return render_depth_batch([(vertices, faces)], intrinsic, [list(extrinsics)], near, far, pixel_offset, device)[0]
+
+
+class Camera(object):
+    """btsim.Camera (btsim.py:276-337) without the RGB image: the mesh is passed in instead of living in a physics world."""
+
+    def __init__(self, intrinsic, near, far):
+        self.intrinsic = intrinsic
+        self.near = near
+        self.far = far
+
+    def render(self, extrinsic, vertices, faces, pixel_offset=0.0, device=None):
+        """extrinsic: the transform from the world to the camera frame, T_cam_world (any extrinsic form).
+        Returns the depth image (H, W) as a float32 device tensor."""
+        return render_depth(vertices, faces, self.intrinsic, [extrinsic], self.near, self.far, pixel_offset, device)[0]
+
+
+# ------------------------------------------------------------------------------------------------ acquire_tsdf
+def acquire_extrinsics(n, N=None, size=0.3, sideview=False):
+    """(n, 4, 4) extrinsics of simulation.py:155-169: top view, n of N cameras on a circle about (size/2, size/2, 0) at
+    theta = pi/6, r = 2 size; sideview, one camera about (size/2, size/2, size/3) at theta = pi/3, phi = -pi/2."""
+    origin = np.eye(4)
+    if sideview:
+        origin[:3, 3] = [size / 2, size / 2, size / 3]
+        theta = np.pi / 3.0
+    else:
+        origin[:3, 3] = [size / 2, size / 2, 0.0]
+        theta = np.pi / 6.0
+    r = 2.0 * size
+    N = N if N else n
+    if sideview:
+        assert n == 1
+        phi_list = [-np.pi / 2.0]
+    else:
+        phi_list = 2.0 * np.pi * np.arange(n) / N
+    return np.stack([perception.camera_on_sphere(origin, r, theta, phi) for phi in phi_list]).reshape(-1, 4, 4)
+
+
+def acquire_tsdf(vertices, faces, n, N=None, resolution=40, size=0.3, sideview=False, lower=None, upper=None, device=None):
+    """simulation.py:145-186 on a scene mesh: render n depth images with the reference's camera, integrate them into a volume of
+    `resolution` and into a second one of 120.  Returns (TSDFVolume, pc, timing): pc the zero-crossing cloud of the second volume
+    ((m, 3) float32 device tensor), cropped to lower <= p <= upper when both are given; timing the wall time of the integration
+    into the first volume.  The images never leave the device."""
+    intrinsic = sim_intrinsic()
+    extrinsics = acquire_extrinsics(n, N, size, sideview)
+    depth = render_depth(vertices, faces, intrinsic, extrinsics, SIM_NEAR, SIM_FAR, 0.0, device)
+    tsdf = perception.TSDFVolume(size, resolution, depth.device)
+    high_res_tsdf = perception.TSDFVolume(size, 120, depth.device)
+    torch.cuda.synchronize(depth.device)
+    tic = time.time()
+    tsdf.integrate_views(depth, intrinsic, extrinsics)
+    torch.cuda.synchronize(depth.device)
+    timing = time.time() - tic
+    high_res_tsdf.integrate_views(depth, intrinsic, extrinsics)
+    pc = high_res_tsdf.get_cloud()
+    if lower is not None and upper is not None:
+        lo = torch.as_tensor(np.asarray(lower, np.float64), device=pc.device)
+        hi = torch.as_tensor(np.asarray(upper, np.float64), device=pc.device)
+        p = pc.double()
+        pc = pc[((p >= lo) & (p <= hi)).all(dim=1)]         # o3d's AxisAlignedBoundingBox crop keeps min <= p <= max
+    return tsdf, pc, timing
+
+
+def acquire_tsdfs(meshes, n, N=None, resolution=40, size=0.3, device=None):
+    """The (B, R, R, R) device grid of B scene meshes, each seen from the top-view circle: one render launch, one fusion launch."""
+    intrinsic = sim_intrinsic()
+    extrinsics = acquire_extrinsics(n, N, size)
+    depth, offs = render_depth_batch(meshes, intrinsic, [extrinsics] * len(meshes), SIM_NEAR, SIM_FAR, 0.0, device)
+    batches = [depth[offs[b]:offs[b + 1]] for b in range(len(meshes))]
+    return perception.fuse_scenes(size, resolution, batches, intrinsic, [extrinsics] * len(meshes), depth.device)[2]
+
+
+def pose_list(extrinsic):
+    """4x4 -> [qx, qy, qz, qw, x, y, z], the reference's Transform.to_list (utils/transform.py)."""
+    from scipy.spatial.transform import Rotation
+    m = perception.extrinsic_matrix(extrinsic)
+    return np.r_[Rotation.from_matrix(m[:3, :3]).as_quat(), m[:3, 3]]
+
+
+def write_raw_scenes(raw_root, scene_ids, meshes, n, N=None, size=0.3, batch=32, device=None):
+    """The raw files scripts/generate_data_parallel.py leaves for construct_dataset: <raw_root>/setup.json (size and intrinsic;
+    other keys of an existing file are kept) and <raw_root>/scenes/<id>.npz with depth_imgs (n, H, W) float32 and extrinsics
+    (n, 7) float32 [qx, qy, qz, qw, x, y, z] (io.write_sensor_data), rendered from the top-view circle, `batch` scenes per launch."""
+    if len(scene_ids) != len(meshes):
+        raise ValueError("one scene id per mesh")
+    if int(batch) < 1:
+        raise ValueError("batch must be at least 1")
+    raw_root = Path(raw_root)
+    (raw_root / "scenes").mkdir(parents=True, exist_ok=True)
+    intrinsic = sim_intrinsic()
+    setup = {}
+    if (raw_root / "setup.json").exists():
+        with (raw_root / "setup.json").open("r") as f:
+            setup = json.load(f)
+    setup.update({"size": size, "intrinsic": intrinsic.to_dict()})
+    with (raw_root / "setup.json").open("w") as f:
+        json.dump(setup, f)
+    extrinsics = acquire_extrinsics(n, N, size)
+    poses = np.stack([pose_list(e) for e in extrinsics]).astype(np.float32) if n else np.zeros((0, 7), np.float32)
+    for at in range(0, len(meshes), int(batch)):
+        chunk = meshes[at:at + int(batch)]
+        depth, offs = render_depth_batch(chunk, intrinsic, [extrinsics] * len(chunk), SIM_NEAR, SIM_FAR, 0.0, device)
+        depth = depth.cpu().numpy()
+        for b, sid in enumerate(scene_ids[at:at + int(batch)]):
+            np.savez_compressed(raw_root / "scenes" / (str(sid) + ".npz"), depth_imgs=depth[offs[b]:offs[b + 1]], extrinsics=poses)
+    return list(scene_ids)
+
+
+# ------------------------------------------------------------------------------------------------ occupancy labels
+def mesh_bounds(mesh_list):
+    """(2, 3) float64: the axis-aligned bounds of all vertices (trimesh's scene.bounds)."""
+    vs = [_mesh_parts(m)[0] for m in mesh_list]
+    vs = [(v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)).reshape(-1, 3).astype(np.float64) for v in vs]
+    v = np.concatenate(vs)
+    return np.stack([v.min(axis=0), v.max(axis=0)])
+
+
+def sample_iou_points(mesh_list, bounds, num_point, padding=0.02, uniform=False, size=0.3, generator=None, device=None):
+    """utils/implicit.py:78-90: num_point uniform points in [-padding, size + padding]^3 (uniform) or in the bounds grown by the
+    padding, and whether each lies inside ANY mesh of the list.  Returns (points (n, 3) float32, occ (n,) bool) on the device.
+    The points come from torch.rand on the device (`generator`: a device generator); the affine map is evaluated in float64 as
+    numpy does and rounded to float32 once, and the containment is tested on those float32 points, so the labels belong to the
+    returned points.  One ragged giga_mesh_contains launch with one scene per mesh."""
+    tensors = [t for t in _mesh_devices(mesh_list) if torch.is_tensor(t)]
+    if generator is not None and device is None:
+        device = generator.device
+    dev = torch.device(device) if device is not None else _device(*tensors)
+    if dev.type != "cuda":
+        raise _capi.GigaHipError("occupancy labels are computed on a HIP device; there is no CPU fallback")
+    points = torch.rand((int(num_point), 3), dtype=torch.float32, device=dev, generator=generator)
+    p = points.double()
+    if uniform:
+        p = p * (size + 2 * padding) - padding
+    else:
+        b = torch.as_tensor(np.asarray(bounds, np.float64).reshape(2, 3), device=dev)
+        p = p * (b[1] + 2 * padding - b[0]) + b[0] - padding
+    points = p.float()
+    occ = torch.zeros(int(num_point), dtype=torch.bool, device=dev)
+    live = [m for m in mesh_list if len(_mesh_parts(m)[1])]
+    if live and num_point:
+        inside, po = mesh_contains_batch(live, [points] * len(live))
+        occ = inside.reshape(len(live), int(num_point)).any(dim=0)
+    return points, occ
+
+
+def save_occ(raw_root, scene_id, mesh_list, num_point_per_file, num_file, uniform=False, generator=None, device=None):
+    """scripts/save_occ_data_parallel.py:16-24 for one scene: <raw_root>/occ/<scene_id>/%04d.npz, each with points
+    (num_point_per_file, 3) float16 and occ (num_point_per_file,) bool: the files giga_amd.dataset reads.  Like the reference it
+    refuses to write into an existing directory."""
+    points, occ = sample_iou_points(mesh_list, mesh_bounds(mesh_list), num_point_per_file * num_file, uniform=uniform,
+                                    generator=generator, device=device)
+    points = points.cpu().numpy().astype(np.float16).reshape(num_file, num_point_per_file, 3)
+    occ = occ.cpu().numpy().reshape(num_file, num_point_per_file)
+    save_root = os.path.join(str(raw_root), "occ", str(scene_id))
+    os.makedirs(save_root)
+    for i in range(num_file):
+        np.savez(os.path.join(save_root, "%04d.npz" % i), points=points[i], occ=occ[i])
+    return save_root

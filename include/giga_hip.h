@@ -341,6 +341,46 @@ int giga_tsdf_cloud_count(const float* tsdf, const float* weight, int B, int R, 
 int giga_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, double length, const void* workspace,
                          size_t workspace_bytes, float* points, size_t cap, int32_t* shortfall, void* stream);
 
+/* ---- input side: depth images of posed triangle meshes (the depth half of btsim.Camera.render, src/vgn/utils/btsim.py:276-337,
+ * which the reference hands to PyBullet) -----
+ * B scenes packed back to back in the ragged layout giga_mesh_emit produces: vertices [.][3] float32 and triangles [.][3] int32
+ * (device), a scene's triangles counting from its OWN first vertex.  HOST arrays, validated before the first HIP call and copied
+ * into the workspace before the call returns: vertex_offsets, triangle_offsets, view_offsets [B+1] int32 (start at 0, never
+ * decrease), extrinsics [n][16] double (task -> camera, row-major 4x4), intrinsics [n][4] double (fx, fy, cx, cy), n =
+ * view_offsets[B].  View k of scene b is image view_offsets[b] + k of depth [n][H][W] float32 (device): the layout
+ * giga_tsdf_integrate consumes.  Everything below is evaluated in double with one IEEE rounding per operation (no fused
+ * multiply-add); E is the view's extrinsic:
+ *   camera-space vertex  a = E (x, y, z, 1) from the float32 vertex, every row ((e0 x + e1 y) + e2 z) + e3.
+ *   pixel ray            pixel (row v, column u) has direction d = ((u + pixel_offset - cx) / fx, (v + pixel_offset - cy) / fy, 1),
+ *                        the numerators evaluated left to right.  pixel_offset = 0 is the convention of giga_tsdf_integrate (pixel u
+ *                        is centred on image coordinate u); 0.5 is OpenGL's.
+ *   edge function        for an ordered vertex pair (P, Q): n = P x Q = (Py Qz - Pz Qy, Pz Qx - Px Qz, Px Qy - Py Qx) and
+ *                        e(P, Q) = (d.x n.x + d.y n.y) + n.z.  e(P, Q) == -e(Q, P) exactly, so two triangles that share an edge
+ *                        decide a ray through that edge consistently.
+ *   hit test             U = e(b, c), V = e(c, a), W = e(a, b), S = (U + V) + W.  The triangle (a, b, c) is hit iff S != 0 and
+ *                        (U, V, W all >= 0 or all <= 0): zero counts as inside (watertight: no cracks on shared edges or
+ *                        vertices), and both faces are visible.
+ *   depth of a hit       z = ((U a.z + V b.z) + W c.z) / S; the hit is accepted iff near <= z <= far.
+ *   output               depth[v][u] = float(min accepted z), or float(far) when no triangle is accepted (with far = 2 = the
+ *                        fusion's depth_trunc, giga_tsdf_integrate ignores such pixels).
+ * A triangle with a vertex index outside its scene is skipped; a triangle with a non-finite vertex is never accepted (its
+ * comparisons are false).  The minimum does not depend on the order: equal input gives equal bytes, and a batch gives scene b
+ * the bytes of a call on scene b alone.  No allocation; asynchronous on `stream`.
+ * Not reproduced: PyBullet's TinyRenderer fill rule at silhouettes, its z-buffer quantisation, its RGB output.
+ * Measurement aid: the first 8 bytes of the workspace hold, after the call, the number of (triangle, 16x16 pixel tile) pairs that
+ * survived the kernel's culling (uint64).
+ * Errors: -1 negative B, W or H outside 1 .. GIGA_RENDER_MAX_IMAGE, near / far / pixel_offset not finite, near <= 0, far <= near,
+ * offsets that are null, do not start at 0 or decrease, n W H >= 2^31, null vertices / triangles (with a non-zero count), null
+ * cameras or workspace (with views), a non-finite camera entry, fx or fy equal to 0; -6 null depth (with views); -4 workspace
+ * smaller than giga_depth_render_workspace_bytes(B, n, vertex_offsets[B], triangle_offsets[B]); -7 B > GIGA_MAX_SCENES.
+ * B = 0 and n = 0 return 0. */
+#define GIGA_RENDER_MAX_IMAGE 4096
+size_t giga_depth_render_workspace_bytes(int B, int n_views, int n_vertices, int n_triangles);
+int giga_depth_render(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                      const int32_t* view_offsets, const double* extrinsics, const double* intrinsics, int B, int W, int H,
+                      double near, double far, double pixel_offset, float* depth, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
 /* ---- fused training loss (scripts/train_giga.py:154-195: `select` + `loss_fn`, literal call shape N = 1) -----
  * Inputs are the head outputs of the model's forward for one grasp query per scene -- qual [B] (post sigmoid), rot [B][4]
  * (unit), width [B], occ_logits [B][M] (raw; the sigmoid of `select` is part of this function) -- and the labels of
