@@ -1295,6 +1295,155 @@ __global__ __launch_bounds__(256) void decoder_f32_tile_kernel(DecArgs a) {
 }
 constexpr size_t DEC32_TILE_LDS = 4 * 32 * 96 * sizeof(float) + NBLK * 4 * 64 * sizeof(float4) + 46 * FRAG;   // 4 gather stages, FC exchange, chain fragments
 
+// ------------------------------- exact fp32 path for ONE query per scene: a GEMV per point, no MFMA ------
+// With N == 1 the 32-point tile above holds one valid point per scene and nothing amortises the weights: the latency of a
+// 32-wide matrix instruction is paid 216 times for columns that are thrown away.  Here a workgroup of four waves computes ONE
+// point of ONE head (grid = P x nheads: 96 workgroups at 32 scenes instead of 3) as a chain of 32-row GEMVs on the VALU.  It
+// reads the SAME packed fragments: lane (n, hi) of a fragment holds four weights of output row n, and the B operand the MFMA
+// would take from lane (point, hi) is known from the slot maps, so lane (n, hi) accumulates row n over ITS k slots with fmaf
+// (feature fragment fq, component c: feature 32 pl + 16 hi + (j & 15), j = 4 fq + c, pl = j >> 4; hidden fragment q,
+// component c: activation 8 q + 4 hi + c) and one v_permlane32_swap adds the two hi halves.  The input vector of a GEMV lives
+// in LDS (the lanes of one hi half read the same four 16-byte words: broadcast reads) and is written by lanes 0..31 after the
+// half-add; DS operations of one wave execute in order, so the chain needs no barrier.
+// Split over the waves as in the tile kernel: FC_b = fc_c[b](c) + aux_b of the five blocks side by side (wave 1 takes two),
+// fragments straight from global / L2 with all 13 loads of a block in flight before the gather; waves 1-3 copy the 45 chain
+// fragments and the C table to LDS by LDS-DMA; ONE barrier; wave 0 walks fc_0 / fc_1 / fc_out.  Every wave gathers only the
+// point's own 96 bilinear features (24 lanes x 4 channels x 4 taps) into a wave-private stage.
+// Summation order differs from both MFMA kernels at the fp32 rounding level (1e-7 relative); on data whose partial sums are
+// all exactly representable the result is order-independent and bit-equal to theirs.
+__device__ __forceinline__ float hi_halves_sum(float v) {     // lane (n, 0) + lane (n, 1), in both lanes, same order in both
+    float lo = v, up = v;
+    lane32_swap(lo, up);                                       // lo = lanes 0..31's value everywhere, up = lanes 32..63's
+    return lo + up;
+}
+constexpr size_t DEC32_POINT_LDS = 46 * FRAG + (4 * 96 + NBLK * 32 + 32) * sizeof(float);   // chain fragments, 4 gather stages, FC exchange, GEMV input
+// Up to this many points the point kernel is the default (launch_decoder).  HIP-event medians of seven, mask 7, point / tile kernel
+// (profiles/dec_point/sweep.txt): P = 32 7.2 / 16.1 us, 256 9.7 / 16.1, 384 13.5 / 16.1, 512 15.0 / 16.2, 768 20.0 / 16.3: the curves
+// cross between 512 and 768; the bound sits at the last size with a margin well outside the run-to-run spread.
+constexpr int DEC32_POINT_MAX_P = 256;
+__global__ __launch_bounds__(256) void decoder_f32_point_kernel(DecArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n = lane & 31, hi = lane >> 5;
+    const int h = blockIdx.y;
+    const long long g = blockIdx.x;                            // the point (grid.x == P)
+    const float4* W = reinterpret_cast<const float4*>(a.blob + a.head_off[h]);          // fragments in global memory
+    const float* planes = reinterpret_cast<const float*>(a.planes);
+    const size_t plane_stride = (size_t)a.B * RES * RES * CD;
+    constexpr int BLKF = 21;                                   // fragments per block: 12 features, 1 aux, 4 fc_0, 4 fc_1
+    uint8_t* CHW = smem;                                       // chain fragments: LDS slots 0 .. 45 as in the tile kernel
+    float* FEAT = reinterpret_cast<float*>(smem + 46 * FRAG) + wave * 96;               // this wave's gathered features
+    float* FCX = reinterpret_cast<float*>(smem + 46 * FRAG) + 4 * 96;                   // FC_b as [blk][32]
+    float* X = FCX + NBLK * 32;                                // input vector of the chain's current GEMV
+    if (wave != 0) {
+        const uint8_t* hb = a.blob + a.head_off[h] + lane * 16;
+        for (int c = wave - 1; c < 46; c += 3) {
+            const int frag = c < 40 ? BLKF * (c >> 3) + 13 + (c & 7) : BLKF * NBLK + (c - 40);     // (c = 45: the C table chunk)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(hb + (size_t)frag * FRAG),
+                                             (__attribute__((address_space(3))) void*)(CHW + c * FRAG), 16, 0, 0);
+        }
+    }
+    // ---- FC fragments of this wave's block(s): wave 0 -> 0, wave 1 -> 1 and 4, wave 2 -> 2, wave 3 -> 3; requested before the gather
+    float4 fa[13], fb[13];
+#pragma unroll
+    for (int q = 0; q < 13; ++q) fa[q] = W[(size_t)(BLKF * wave + q) * 64 + lane];
+    if (wave == 1) {
+#pragma unroll
+        for (int q = 0; q < 13; ++q) fb[q] = W[(size_t)(BLKF * 4 + q) * 64 + lane];
+    }
+    // ---- gather: lane = (plane, four channels), lanes 0 .. 23
+    const float px = a.p[3 * g + 0], py = a.p[3 * g + 1], pz = a.p[3 * g + 2];
+    const float ax0 = hi ? py : px;                            // aux slots (px, py)
+    const float ax1 = hi ? 1.0f : pz;                          // aux slots (pz, 1)
+    const float one0 = hi ? 0.0f : 1.0f;                       // aux slots (1, 0)
+    if (lane < 24) {
+        int b, r;
+        split_scene(g, a.N, a.invN, b, r);
+        const int pl = lane >> 3, qd = lane & 7;
+        const float nx = norm_coord(px), ny = norm_coord(py), nz = norm_coord(pz);
+        // xz: (u,v)=(x,z)  xy: (x,y)  yz: (y,z)      common.py:246-251
+        const Bilin bl = bilin_setup(pl == 2 ? ny : nx, pl == 1 ? ny : nz);
+        const float* base = planes + pl * plane_stride + (size_t)b * RES * RES * CD + 4 * qd;
+        const float4 v00 = *reinterpret_cast<const float4*>(base + (size_t)bl.o00 * CD);
+        const float4 v01 = *reinterpret_cast<const float4*>(base + (size_t)bl.o01 * CD);
+        const float4 v10 = *reinterpret_cast<const float4*>(base + (size_t)bl.o10 * CD);
+        const float4 v11 = *reinterpret_cast<const float4*>(base + (size_t)bl.o11 * CD);
+        // same order as aten's grid_sampler: nw, ne, sw, se
+        float4 o;
+        o.x = fmaf(v11.x, bl.w11, fmaf(v10.x, bl.w10, fmaf(v01.x, bl.w01, v00.x * bl.w00)));
+        o.y = fmaf(v11.y, bl.w11, fmaf(v10.y, bl.w10, fmaf(v01.y, bl.w01, v00.y * bl.w00)));
+        o.z = fmaf(v11.z, bl.w11, fmaf(v10.z, bl.w10, fmaf(v01.z, bl.w01, v00.z * bl.w00)));
+        o.w = fmaf(v11.w, bl.w11, fmaf(v10.w, bl.w10, fmaf(v01.w, bl.w01, v00.w * bl.w00)));
+        *reinterpret_cast<float4*>(FEAT + pl * 32 + 4 * qd) = o;
+    }
+    __builtin_amdgcn_wave_barrier();                           // wave-private stage: DS operations of one wave execute in order
+    float cf[48];
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 v = *reinterpret_cast<const float4*>(FEAT + pl * 32 + 16 * hi + 4 * q);
+            cf[16 * pl + 4 * q + 0] = v.x; cf[16 * pl + 4 * q + 1] = v.y; cf[16 * pl + 4 * q + 2] = v.z; cf[16 * pl + 4 * q + 3] = v.w;
+        }
+    auto fc_block = [&](const float4 (&A)[13]) {                // FC_b[n]: this lane's 48 + 3 k slots, then the other half's
+        float acc = 0.f;
+#pragma unroll
+        for (int q = 0; q < 12; ++q) {
+            acc = fmaf(A[q].x, cf[4 * q + 0], acc);
+            acc = fmaf(A[q].y, cf[4 * q + 1], acc);
+            acc = fmaf(A[q].z, cf[4 * q + 2], acc);
+            acc = fmaf(A[q].w, cf[4 * q + 3], acc);
+        }
+        acc = fmaf(A[12].x, ax0, acc);
+        acc = fmaf(A[12].y, ax1, acc);
+        acc = fmaf(A[12].z, one0, acc);
+        return hi_halves_sum(acc);
+    };
+    float net = fc_block(fa);                                   // FC of this wave's first block
+    if (wave != 0 && hi == 0) FCX[wave * 32 + n] = net;
+    if (wave == 1) {
+        const float f4 = fc_block(fb);
+        if (hi == 0) FCX[4 * 32 + n] = f4;
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);                         // vmcnt(0): this wave's share of the chain fragments has landed
+    __syncthreads();                                            // FC_1 .. FC_4 and the chain's fragments are in LDS
+    if (wave != 0) return;
+    const float4* CW = reinterpret_cast<const float4*>(CHW);
+    const float* ctab_l = reinterpret_cast<const float*>(CHW + 45 * FRAG);
+    // one 32 x 32 GEMV of the chain: X <- relu(x); row n over this lane's 16 k slots from `init`; add the other half's
+    auto gemv = [&](int slot, float x, float init) __attribute__((always_inline)) {
+        if (hi == 0) X[n] = relu(x);
+        __builtin_amdgcn_wave_barrier();
+        float acc = init;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 A = CW[(slot + q) * 64 + lane];
+            const float4 v = *reinterpret_cast<const float4*>(X + 8 * q + 4 * hi);
+            acc = fmaf(A.x, v.x, acc);
+            acc = fmaf(A.y, v.y, acc);
+            acc = fmaf(A.z, v.z, acc);
+            acc = fmaf(A.w, v.w, acc);
+        }
+        __builtin_amdgcn_wave_barrier();
+        return hi_halves_sum(acc);
+    };
+#pragma unroll
+    for (int blk = 0; blk < NBLK; ++blk) {
+        if (blk > 0) net += FCX[blk * 32 + n];
+        const float hh = gemv(blk * 8, net, hi ? 0.0f : ctab_l[blk * 32 + n]);          // fc_0 (+ its bias)
+        net += gemv(blk * 8 + 4, hh, 0.0f);                                             // fc_1 onto the stream
+    }
+    net += hi_halves_sum(CW[40 * 64 + lane].y * ax1);           // + b1 of block 4 (slot "1.0")
+    const float o = gemv(41, net, hi ? 0.0f : ctab_l[NBLK * 32 + n]);                   // fc_out: rows 0 .. 3 are the outputs
+    if (lane < 4) X[lane] = o;
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) {
+        const float4 d = *reinterpret_cast<const float4*>(X);
+        store_head(a, h, g, d.x, d.y, d.z, d.w);
+    }
+}
+
 // ------------------------------- plane repack NCHW fp32 -> NHWC T ---------------------------------
 // Used when the planes arrive through the Python boundary as the reference's (B,32,40,40) tensors
 // (LocalDecoder.forward(p, c_plane), decoder.py:133).  One thread per (image, pixel, 4 channels).
@@ -1409,6 +1558,23 @@ __global__ void lattice_resample_split_kernel(const float* __restrict__ planes, 
 // ------------------------------- launchers ----------------------------------------------------------
 constexpr size_t DEC32_LDS = DEC32_BYTES + 4 * 32 * 96 * sizeof(float);     // weight image + the gather's per-wave stage
 static_assert(DEC32_LDS <= 160 * 1024, "LDS budget of the fp32 decoder");
+// Per-call knobs of the exact-fp32 one-query dispatch (read on every call: A/B runs and cross-checks in one process).
+//   GIGA_DEC32_TILE=0    neither one-query kernel: decoder_f32_kernel, the general kernel
+//   GIGA_DEC32_POINT=0   no point kernel: the tile kernel where its own rule holds
+//   GIGA_DEC32_POINT=n   n > 1: the point kernel up to n points instead of DEC32_POINT_MAX_P (sweeps; at most the tile rule's 3072)
+// Anything else (unset, 1, negative, not a number) leaves the default bound.
+static bool dec32_one_query_kernels() {
+    const char* e = getenv("GIGA_DEC32_TILE");
+    return e ? atoi(e) != 0 : true;
+}
+static long long dec32_point_bound() {
+    const char* e = getenv("GIGA_DEC32_POINT");
+    if (!e) return DEC32_POINT_MAX_P;
+    const int v = atoi(e);
+    if (v == 0 && e[0] == '0') return 0;
+    if (v <= 1) return DEC32_POINT_MAX_P;
+    return v < 3072 ? v : 3072;
+}
 int launch_decoder(const DecArgs& a0, int precision, hipStream_t s, void* ev0, void* ev1) {
     DecArgs a = a0;
     if (a.P <= 0 || a.nheads <= 0) return 0;
@@ -1510,7 +1676,14 @@ int launch_decoder(const DecArgs& a0, int precision, hipStream_t s, void* ev0, v
         auto kern = decoder_f16_kernel<T, false, NW>;
         giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)(2 * DEC16_BYTES));
         GIGA_LAUNCH(kern, dim3(grid), dim3(NW * 64), 2 * DEC16_BYTES, s, a);
-    } else if (!lat && a.N == 1 && tiles * a.nheads <= 96 && [] { const char* e = getenv("GIGA_DEC32_TILE"); return e ? atoi(e) != 0 : true; }()) {
+    } else if (!lat && a.N == 1 && dec32_one_query_kernels() && a.P <= dec32_point_bound()) {
+        // ONE query per scene (train_giga's literal call): one point and head per workgroup, GEMVs on the VALU (no padded MFMA
+        // tile).  DEC32_POINT_MAX_P comes from the sweep against the tile kernel below (profiles/dec_point/sweep.txt).
+        // (Only for N == 1, like the tile kernel below and for the same reason.)
+        auto kern = decoder_f32_point_kernel;
+        giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)DEC32_POINT_LDS);
+        GIGA_LAUNCH(kern, dim3((unsigned)a.P, a.nheads), dim3(256), DEC32_POINT_LDS, s, a);
+    } else if (!lat && a.N == 1 && tiles * a.nheads <= 96 && dec32_one_query_kernels()) {
         // ONE query per scene (train_giga's literal call) and few scenes: one tile and head per workgroup, four waves per chain.
         // (Only for N == 1: the kernel sums the stream in a different order than decoder_f32_kernel, and callers that split a
         // query set into chunks -- Generator3D.eval_points -- rely on a point's result not depending on the chunk it is in.)
