@@ -99,6 +99,11 @@ def _grasp_params(R, voxel_size, out_th, threshold, force_detection, max_filter_
     if voxel_size is None:
         voxel_size = 0.3 / R                                  # detection_implicit.py:41
     lx, ly, lz = bound_limits(voxel_size, limit)
+    # detection_implicit.py:92-95 zero the far margin with qual_vol[-x_lim:] = 0.0 (and [:, -y_lim:]); for a limit of 0 voxels
+    # (voxel_size > 0.02) that slice is the WHOLE array, so the reference returns an all-zero volume and no grasps.  The C ABI
+    # keeps the geometric meaning (lim 0 = no margin), so the reference's result is asked for with a margin of R on that axis.
+    # lim_z == 0 needs nothing: [:, :, :0] is empty.
+    lx, ly = (R if l == 0 else l for l in (lx, ly))
     return _capi.GraspParams(float(gaussian_filter_sigma), min_width, max_width, out_th, LOW_TH, threshold,
                              lx, ly, lz, int(max_filter_size), int(bool(force_detection)))
 

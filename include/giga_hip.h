@@ -415,7 +415,11 @@ int giga_adam_step(float* params, const float* grads, float* exp_avg, float* exp
  *             masked binary dilation of (tsdf > out_th) with mask ~(1e-3 < tsdf < out_th), or where
  *             width < min_width or width > max_width                      (detection_implicit.py:126-141)
  *   bound   : qual = 0 for x < lim_x, x >= R-lim_x, y < lim_y, y >= R-lim_y, z < lim_z; the caller computes
- *             lim = int(limit / voxel_size) as detection_implicit.py:89-91 does
+ *             lim = int(limit / voxel_size) as detection_implicit.py:89-91 does.  The limits are geometric: lim 0 means
+ *             no margin on that axis, lim >= R zeroes the scene.  The reference differs at 0: its far margin is the slice
+ *             qual_vol[-x_lim:] (detection_implicit.py:92-95), which for x_lim == 0 (voxel_size > 0.02) is the whole array,
+ *             so its volume comes out all zero.  A caller that wants the reference's result passes lim = R on an x or y
+ *             axis whose int(limit / voxel_size) is 0, as giga_amd/detection.py does; lim_z == 0 needs no such care
  *   select  : qual < low_th -> 0; if force_detection and no voxel >= threshold the scene is "best only" and
  *             the threshold is skipped, else qual < threshold -> 0; NMS with maximum_filter(size =
  *             max_filter_size, mode reflect); survivors are appended (unordered) to the candidate lists.

@@ -73,3 +73,56 @@ def test_capacity_overflow_is_reported():
     buf.pack.zero_()
     buf.counters[1, 1] = 5                             # more survivors than `cap`: the caller must retry with R^3
     assert _grasp_collect(buf, force_detection=False) is None
+
+
+def _handed_over(q, th, force):
+    """What the device hands over for one scene: every NMS survivor of the thresholded (best-only: LOW_TH) volume as flat
+    indices with their scores, and the number of voxels at or above the threshold."""
+    from scipy import ndimage
+    R = q.shape[0]
+    qq = q.copy(); qq[qq < PO.LOW_TH] = 0
+    n_ge = int((qq >= th).sum())
+    if not (force and n_ge == 0):
+        qq[qq < th] = 0
+    surv = np.argwhere((qq == ndimage.maximum_filter(qq, size=4)) & (qq > 0))
+    flat = (surv[:, 0] * R + surv[:, 1]) * R + surv[:, 2]
+    return flat, qq.reshape(-1)[flat], n_ge
+
+
+def test_large_block_branch_equals_small_block_branch():
+    """40 scenes at cap = 1024 are over the 1 MiB switch: the counters are read first, then the first kmax candidates of
+    every scene.  Same grasps as the one-copy branch gives scene by scene, and the oracle's; one scene has no survivor at
+    all and one is in best-only mode."""
+    R, B, cap, rng = 24, 40, 1024, np.random.default_rng(11)
+    big = _GraspBuffers(B, R, cap, "cpu")
+    big.pack.zero_()
+    assert big.pack.numel() * 4 > (1 << 20) >= _GraspBuffers(1, R, cap, "cpu").pack.numel() * 4
+    EMPTY, BEST = 7, 19
+    vols = [_survivor_volume(seed, R, seed % 2 == 0) for seed in range(1, 7)]
+    scenes = []
+    for b in range(B):
+        q, rot, width = vols[b % 6]
+        th = 2.0 if b == BEST else 0.5 + 0.04 * (b % 4)
+        if b == EMPTY:
+            q = np.zeros_like(q)
+        flat, score, n_ge = _handed_over(q, th, True)
+        _fill(big, b, flat, score, rot, width, n_ge, rng)
+        scenes.append((q, th, n_ge == 0))
+    ks = big.counters[:, 1].numpy()
+    assert ks[EMPTY] == 0 and 0 < ks.max() < cap and len(set(ks.tolist())) > 2      # kmax really slices
+    out = _grasp_collect(big, force_detection=True)
+    assert scenes[EMPTY][2] and scenes[BEST][2] and sum(s[2] for s in scenes) < B // 2
+    for b, (q, th, best_only) in enumerate(scenes):
+        small = _GraspBuffers(1, R, cap, "cpu")
+        small.pack.zero_()
+        small.counters[0] = big.counters[b]
+        for name in ("cand_index", "cand_score", "cand_rot", "cand_width"):
+            getattr(small, name)[0] = getattr(big, name)[b]
+        one = _grasp_collect(small, force_detection=True)[0]
+        idx, sc = PO.select_indices(q, threshold=th, force_detection=True)
+        assert out[b]["best_only"] == one["best_only"] == best_only
+        assert np.array_equal(out[b]["index"], idx) and np.array_equal(out[b]["score"], sc)
+        for key in ("index", "score", "rot", "width"):
+            assert out[b][key].shape == one[key].shape and np.array_equal(out[b][key], one[key]), (b, key)
+    assert len(out[EMPTY]["score"]) == 0 and out[EMPTY]["index"].shape == (0, 3)
+    assert len(out[BEST]["score"]) == 1 and ks[BEST] > 1

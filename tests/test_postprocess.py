@@ -45,6 +45,34 @@ def test_bound_limits():
     assert bound_limits(0.3 / 40) == (2, 2, 7)
 
 
+def test_bound_with_a_limit_of_zero_voxels():
+    """detection_implicit.py:92-95: qual_vol[-x_lim:] = 0.0 with x_lim == 0 is the whole array, so an x or y limit of 0 voxels
+    (voxel_size > 0.02) zeroes the scene; [:, :, :0] is empty, so a z limit of 0 zeroes nothing."""
+    for R in (5, 7, 13):
+        assert post_oracle.bound_limits(0.3 / R)[:2] == (0, 0)
+        assert not post_oracle.bound(np.ones((R, R, R), np.float32), 0.3 / R).any()
+    assert post_oracle.bound_limits(0.3 / 15) == (1, 1, 2)
+    assert post_oracle.bound(np.ones((15, 15, 15), np.float32), 0.3 / 15).sum() == 13 * 13 * 13
+    R = 7
+    for limit in ((0.0, 0.02, 0.055), (0.02, 0.0, 0.055)):           # either axis alone is enough
+        assert post_oracle.bound_limits(0.02, limit)[2] == 2 and 0 in post_oracle.bound_limits(0.02, limit)[:2]
+        assert not post_oracle.bound(np.ones((R, R, R), np.float32), 0.02, limit).any()
+    assert post_oracle.bound_limits(0.02, (0.02, 0.02, 0.0)) == (1, 1, 0)
+    q = post_oracle.bound(np.ones((R, R, R), np.float32), 0.02, (0.02, 0.02, 0.0))
+    keep = np.zeros((R, R, R), bool)
+    keep[1:-1, 1:-1, :] = True
+    assert np.array_equal(q != 0, keep)
+    # the product hands the kernel a margin of R where the reference's slice is the whole array, and only there
+    from giga_amd.detection import _grasp_params
+
+    def lims(R, voxel_size, limit=(0.02, 0.02, 0.055)):
+        p = _grasp_params(R, voxel_size, 0.5, 0.9, False, 4, 1.0, 0.033, 0.233, limit)
+        return p.lim_x, p.lim_y, p.lim_z
+    assert lims(7, None) == (7, 7, 1) and lims(13, None) == (13, 13, 2)
+    assert lims(15, None) == (1, 1, 2) and lims(40, None) == (2, 2, 7) and lims(7, 0.02) == (1, 1, 2)
+    assert lims(7, 0.02, (0.0, 0.02, 0.055)) == (7, 1, 2) and lims(7, 0.02, (0.02, 0.02, 0.0)) == (1, 1, 0)
+
+
 @pytest.mark.gpu
 def test_device_postprocess_matches_reference_goldens():
     from giga_amd.detection import grasp_select
