@@ -910,8 +910,10 @@ namespace giga {
 // =============================== exact fp32 MFMA path ==============================================
 // Same chain on v_mfma_f32_32x32x2_f32 (bitwise an fp32 fma chain).  B operand of MFMA s of a hidden
 // layer is simply relu(D[s]) of the previous layer: no conversion, no data movement.
+// Launched with 256 threads.  The bound of two waves per SIMD caps the kernel at 256 registers, and with that the compiler keeps the
+// MFMA accumulators in VGPRs: a ReLU reads them directly, with no v_accvgpr_read in front.
 template <int T, bool LATTICE>
-__global__ __launch_bounds__(256, 1) void decoder_f32_kernel(DecArgs a) {
+__global__ __launch_bounds__(256, 2) void decoder_f32_kernel(DecArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -933,6 +935,8 @@ __global__ __launch_bounds__(256, 1) void decoder_f32_kernel(DecArgs a) {
         loaded = h_begin;
     }
     bool fresh = true;                                        // the resident image has not been waited for yet
+    int lane_hi = 64 * 64 + lane;                             // this lane's float4 of fragment 64: the second base of the chain's reads
+    asm volatile("" : "+v"(lane_hi));                         // (opaque, or the compiler folds it back into W + a 17-bit constant)
 
     for (int bseq = blockIdx.x; bseq < a.nbatch; bseq += gridDim.x) {
         const int batch = xcd_swizzle(bseq, a.nbatch);        // an XCD works on a contiguous range of points (L2 locality)
@@ -1026,17 +1030,73 @@ __global__ __launch_bounds__(256, 1) void decoder_f32_kernel(DecArgs a) {
                 __syncthreads();
                 fresh = false;
             }
+            // One layer of the chain per tile is an uninterrupted run of MFMAs: an fp32 MFMA does not co-execute with VALU work, and a
+            // VALU instruction alone between two of them costs three times what it costs in a run, so the 16 rectified B
+            // operands of a dense layer are formed in ONE run in front of the layer's 16 MFMAs, never one by one between them.  The
+            // accumulators live in VGPRs (__launch_bounds__ above), so a ReLU is one v_max_i32 with no accumulator-file read in front
+            // of it.  Tiles go one after the other through a layer: while tile 1's MFMAs drain, tile 0's results are long complete and
+            // its ReLU run waits for nothing.  The layer's four A fragments are read once and serve both tiles.  The order of the MFMAs
+            // on each accumulator is the chain's summation order and does not change.
             f32x16 net[T], hh[T];
 #pragma unroll
             for (int t = 0; t < T; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) net[t][r] = 0.f;
             int k = 0;
+            // fragment k of the resident image.  A DS instruction's immediate offset ends at 64 KiB; past it every read would carry
+            // a v_add of its own between two MFMAs, so the upper part of the image is addressed from a second base register.
+            auto frag = [&](int i) { return i < 64 ? W[i * 64 + lane] : W[(i - 64) * 64 + lane_hi]; };
+            // The image is read front to back.  The four fragments behind a dense layer are requested inside the layer, ahead of the
+            // last tile's ReLU run, and have landed when the layer ends; take() hands them out.
+            float4 ahead[4];
+            int ahead0 = -4;
+            auto take = [&](int i) { return i >= ahead0 && i < ahead0 + 4 ? ahead[i - ahead0] : frag(i); };
+            // D = C + A(4 fragments) x relu(src), tile by tile.  The first MFMA takes the layer's bias rows (or the running stream)
+            // as its C operand: no copy into the accumulator first.
+            auto dense = [&](const f32x16 (&src)[T], const f32x16 (&cin)[T], f32x16 (&dst)[T]) {
+                float4 A[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) A[q] = take(k++);
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    float r[16];
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (t == T - 1) {
+                        ahead0 = k;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            if (k + q < DEC32_FRAGS) ahead[q] = frag(k + q);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) r[i] = relu(src[t][i]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    f32x16 acc = cin[t];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        acc = mfma32(A[q].x, r[4 * q + 0], acc);
+                        acc = mfma32(A[q].y, r[4 * q + 1], acc);
+                        acc = mfma32(A[q].z, r[4 * q + 2], acc);
+                        acc = mfma32(A[q].w, r[4 * q + 3], acc);
+                    }
+                    dst[t] = acc;
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            };
+            auto bias_rows = [&](int row, f32x16 (&c)[T]) {     // 32 biases of a layer as an accumulator image, the same for every tile
+                f32x16 c0;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float4 v = *reinterpret_cast<const float4*>(ctab + row * 32 + 8 * q + 4 * hi);
+                    c0[4 * q + 0] = v.x; c0[4 * q + 1] = v.y; c0[4 * q + 2] = v.z; c0[4 * q + 3] = v.w;
+                }
+#pragma unroll
+                for (int t = 0; t < T; ++t) c[t] = c0;
+            };
 #pragma unroll
             for (int blk = 0; blk < NBLK; ++blk) {
 #pragma unroll
                 for (int q = 0; q < 12; ++q) {
-                    const float4 A = W[(k++) * 64 + lane];
+                    const float4 A = take(k++);
 #pragma unroll
                     for (int t = 0; t < T; ++t) {
                         net[t] = mfma32(A.x, cf[t][4 * q + 0], net[t]);
@@ -1046,71 +1106,30 @@ __global__ __launch_bounds__(256, 1) void decoder_f32_kernel(DecArgs a) {
                     }
                 }
                 {
-                    const float4 A = W[(k++) * 64 + lane];
+                    float4 A = take(k++);
+                    if (blk > 0) asm volatile("" : "+v"(A.x));   // keeps the fragment one ds_read_b128 at an immediate offset
                     const float one0 = hi ? 0.0f : 1.0f;       // aux MFMA 2: slots (1, 0)
 #pragma unroll
                     for (int t = 0; t < T; ++t) {
-                        net[t] = mfma32(A.x, ax0[t], net[t]);
+                        // aux MFMA 0 carries fc_p; behind block 0 its fragment is all zeros (giga_pack.cpp) and it is not issued
+                        if (blk == 0) net[t] = mfma32(A.x, ax0[t], net[t]);
                         net[t] = mfma32(A.y, ax1[t], net[t]);
                         net[t] = mfma32(A.z, one0, net[t]);
                     }
                 }
-                f32x16 c0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 v = *reinterpret_cast<const float4*>(ctab + blk * 32 + 8 * q + 4 * hi);
-                    c0[4 * q + 0] = v.x; c0[4 * q + 1] = v.y; c0[4 * q + 2] = v.z; c0[4 * q + 3] = v.w;
-                }
-#pragma unroll
-                for (int t = 0; t < T; ++t) hh[t] = c0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 A = W[(k++) * 64 + lane];
-#pragma unroll
-                    for (int t = 0; t < T; ++t) {
-                        hh[t] = mfma32(A.x, relu(net[t][4 * q + 0]), hh[t]);
-                        hh[t] = mfma32(A.y, relu(net[t][4 * q + 1]), hh[t]);
-                        hh[t] = mfma32(A.z, relu(net[t][4 * q + 2]), hh[t]);
-                        hh[t] = mfma32(A.w, relu(net[t][4 * q + 3]), hh[t]);
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 A = W[(k++) * 64 + lane];
-#pragma unroll
-                    for (int t = 0; t < T; ++t) {
-                        // B operands must be the PRE-update hidden values: hh is not modified here
-                        net[t] = mfma32(A.x, relu(hh[t][4 * q + 0]), net[t]);
-                        net[t] = mfma32(A.y, relu(hh[t][4 * q + 1]), net[t]);
-                        net[t] = mfma32(A.z, relu(hh[t][4 * q + 2]), net[t]);
-                        net[t] = mfma32(A.w, relu(hh[t][4 * q + 3]), net[t]);
-                    }
-                }
+                f32x16 c0[T];
+                bias_rows(blk, c0);
+                dense(net, c0, hh);                             // hh = b0 + fc_0(relu(net))
+                // B operands of fc_1 are the PRE-update hidden values, and net keeps its pre-activations: the residual stream
+                dense(hh, net, net);                            // net += fc_1(relu(hh))
             }
             {
-                const float4 A = W[(k++) * 64 + lane];
+                const float4 A = take(k++);
 #pragma unroll
                 for (int t = 0; t < T; ++t) net[t] = mfma32(A.y, ax1[t], net[t]);   // + b1 of block 4 (slot "1.0")
-                f32x16 c0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 v = *reinterpret_cast<const float4*>(ctab + NBLK * 32 + 8 * q + 4 * hi);
-                    c0[4 * q + 0] = v.x; c0[4 * q + 1] = v.y; c0[4 * q + 2] = v.z; c0[4 * q + 3] = v.w;
-                }
-                f32x16 o[T];
-#pragma unroll
-                for (int t = 0; t < T; ++t) o[t] = c0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 A = W[(k++) * 64 + lane];
-#pragma unroll
-                    for (int t = 0; t < T; ++t) {
-                        o[t] = mfma32(A.x, relu(net[t][4 * q + 0]), o[t]);
-                        o[t] = mfma32(A.y, relu(net[t][4 * q + 1]), o[t]);
-                        o[t] = mfma32(A.z, relu(net[t][4 * q + 2]), o[t]);
-                        o[t] = mfma32(A.w, relu(net[t][4 * q + 3]), o[t]);
-                    }
-                }
+                f32x16 c0[T], o[T];
+                bias_rows(NBLK, c0);
+                dense(net, c0, o);                              // fc_out(relu(net))
 #pragma unroll
                 for (int t = 0; t < T; ++t)
                     if (hi == 0 && valid[t]) store_head(a, h, gidx[t], o[t][0], o[t][1], o[t][2], o[t][3]);
