@@ -28,6 +28,7 @@ CONV32_UNET = 128        # GIGA_CONV32_UNET: the f16-class U-Net on the conv32 k
 CONV16_UNET = 256        # GIGA_CONV16_UNET: ... on the conv16 kernels
 DIRECT_CONV = 1024       # GIGA_DIRECT_CONV: precision 0 keeps the direct 3x3 convolutions (default: Winograd F(2x2, 3x3), csrc/giga_wino.h)
 PATH_PERSISTENT, PATH_CONV32, PATH_FUSED_PAIRS, PATH_WINOGRAD = 1, 2, 4, 8          # giga_encoder_last_path()
+BWD_PATH_PERSISTENT, BWD_PATH_WINOGRAD, BWD_PATH_BF16 = 1, 2, 4                      # giga_backward_last_path()
 MESH_MAX_N = 256         # GIGA_MESH_MAX_N: samples per axis of a marching-cubes grid
 TSDF_MAX_R = 512         # GIGA_TSDF_MAX_R: cells per axis of a fused volume
 RENDER_MAX_IMAGE = 4096  # GIGA_RENDER_MAX_IMAGE: width and height of a rendered depth image
@@ -107,6 +108,7 @@ _SIGNATURES = {
     "giga_launch_probe": (ctypes.c_int, [ctypes.c_ulonglong, ctypes.c_void_p, ctypes.c_void_p]),
     "giga_launch_probe_name": (ctypes.c_char_p, []),
     "giga_encoder_last_path": (ctypes.c_int, []),
+    "giga_backward_last_path": (ctypes.c_int, []),
     "giga_forget_device_state": (None, []),
     "giga_event_create": (ctypes.c_void_p, []),
     "giga_event_destroy": (None, [ctypes.c_void_p]),

@@ -9,8 +9,10 @@
 //     dW[c][tap] = sum_voxels dF[c][v] * tsdf[v + tap] on the MFMA as well.
 // Weight/bias gradients are ACCUMULATED into the flat fp32 gradient buffer (reference state-dict order) with
 // fp32 atomics (summation order is not fixed, as with PyTorch's own CUDA/HIP backward kernels).
+#include "../../include/giga_hip.h"
 #include "giga_conv16.h"
 #include "giga_wino.h"
+#include <atomic>
 #include <functional>
 #include <mutex>
 
@@ -1394,6 +1396,9 @@ void side_streams_forget() {
 // ------------------------------- driver -----------------------------------------------------------------------
 // forward activations: the encoder workspace (giga_encoder.hip::EncWs, fp32).  Gradient workspace carve:
 // (struct BwdWs: giga_bwd_mega.h)
+// what the last backward of this process ran its data-gradient chain on (giga_backward_last_path: tests pin the launch form to it)
+static std::atomic<int> g_last_bwd_path{0};
+
 BwdWs enc_bwd_workspace(int B) {
     const size_t n = 3 * (size_t)B;
     BwdWs w{};
@@ -1426,7 +1431,7 @@ int enc_nxp(int B);
 template <int V> using IC = std::integral_constant<int, V>;
 template <int MATH>
 static int encoder_backward_impl(const float* tsdf, const uint8_t* blob, const uint8_t* bwd_blob, const uint8_t* fws,
-                                 float* gplanes /* [3B][40][40][32], in: dLoss/dPlanes, clobbered */, uint8_t* gws,
+                                 float* gplanes /* [3B][40][40][32], in: dLoss/dPlanes (read only: L12's input and its weight gradient's dY) */, uint8_t* gws,
                                  float* grads /* flat, state-dict order */, int head_present, int B, hipStream_t s, bool convin_mask,
                                  SideScope& side) {
     if (B <= 0) return 0;
@@ -1585,6 +1590,8 @@ static int encoder_backward_impl(const float* tsdf, const uint8_t* blob, const u
         }
         return launch_conv<float, CONV3, C0, 0, COUT, HW, HW, NB, false, false, MATH>(M.layer[stage], s);
     };
+    g_last_bwd_path.store((mega > 0 ? GIGA_BWD_PATH_PERSISTENT : 0) | (mega <= 0 && wino_bwd ? GIGA_BWD_PATH_WINOGRAD : 0) |
+                          (MATH == MATH_BF16 ? GIGA_BWD_PATH_BF16 : 0), std::memory_order_relaxed);
     if (mega <= 0) {
         // one launch per stage, the weight gradient of a layer right behind the launch that produced its dPre (it is still in the
         // Infinity Cache then)
@@ -1656,6 +1663,8 @@ int launch_encoder_backward(const float* tsdf, const uint8_t* blob, const uint8_
 }
 
 }  // namespace giga
+
+extern "C" int giga_backward_last_path(void) { return giga::g_last_bwd_path.load(std::memory_order_relaxed); }
 
 #ifdef GIGA_TRACE
 extern "C" int giga_debug_wgrad3_trace(long long* host_out) {

@@ -537,6 +537,14 @@ void giga_forget_device_state(void);
 #define GIGA_PATH_FUSED_PAIRS 4
 #define GIGA_PATH_WINOGRAD 8
 int giga_encoder_last_path(void);
+/* How the LAST giga_backward call of this process ran the U-Net's data-gradient chain (diagnostic, read-only: tests pin the launch
+ * form to it): an OR of GIGA_BWD_PATH_PERSISTENT (one persistent launch, GIGA_DGRAD_PERSIST=1 at 24 images and above; else one
+ * launch per stage), GIGA_BWD_PATH_WINOGRAD (fp32: the 3x3 layers' data gradients as Winograd F(2x2, 3x3); never with the persistent
+ * launch, which runs the direct kernels) and GIGA_BWD_PATH_BF16 (GIGA_BF16_CONVS: bf16 operands).  0 before the first call. */
+#define GIGA_BWD_PATH_PERSISTENT 1
+#define GIGA_BWD_PATH_WINOGRAD 2
+#define GIGA_BWD_PATH_BF16 4
+int giga_backward_last_path(void);
 /* ---- measurement hooks (bench.py roofline): HIP events recorded on `stream` right before and
  * after ONE kernel launch, so the kernel's duration is measured live on the stream it runs on.
  * probe_stage: 0 conv_in+project, 1 plane_finalize, 2..14 = U-Net layers 0..12 (giga_layout.h kConv), 15 = the whole U-Net.

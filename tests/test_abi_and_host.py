@@ -34,7 +34,9 @@ def test_python_constants_equal_the_header_defines():
     defines = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"^#define\s+(GIGA_[A-Z0-9_]+)\s+(0x[0-9a-fA-F]+|\d+)\s*$", hdr, re.M)}
     for name, value in (("GIGA_FOLD_FINAL", _capi.FOLD_FINAL), ("GIGA_PERSIST_UNET", _capi.PERSIST_UNET),
                         ("GIGA_LAYERWISE_UNET", _capi.LAYERWISE_UNET), ("GIGA_MAX_SCENES", _capi.MAX_SCENES),
-                        ("GIGA_CONV32_UNET", _capi.CONV32_UNET), ("GIGA_CONV16_UNET", _capi.CONV16_UNET)):
+                        ("GIGA_CONV32_UNET", _capi.CONV32_UNET), ("GIGA_CONV16_UNET", _capi.CONV16_UNET),
+                        ("GIGA_BWD_PATH_PERSISTENT", _capi.BWD_PATH_PERSISTENT), ("GIGA_BWD_PATH_WINOGRAD", _capi.BWD_PATH_WINOGRAD),
+                        ("GIGA_BWD_PATH_BF16", _capi.BWD_PATH_BF16)):
         assert defines.get(name) == value, (name, defines.get(name), value)
     flags = _capi.FOLD_FINAL | _capi.PERSIST_UNET | _capi.LAYERWISE_UNET | _capi.CONV32_UNET | _capi.CONV16_UNET
     assert flags & 3 == 0 and bin(flags).count("1") == 5          # distinct bits above the precision values 0..3
@@ -59,6 +61,7 @@ def test_forget_device_state_is_callable_without_a_gpu():
     lib.giga_forget_device_state()
     lib.giga_forget_device_state()
     assert lib.giga_encoder_last_path() in range(8)
+    assert lib.giga_backward_last_path() in range(8)
 
 
 def test_param_counts_and_sizes():

@@ -189,18 +189,34 @@ def test_fp32_backward_matches_float64(case):
         _MEASURED[key] = (w[0], f"{w[1]} ({case_id(case)})")
 
 
+def check_form_cases(persistent):
+    """The reduced sweep inside a child process; giga_backward_last_path() must report the form each case is meant to run:
+    the persistent chain only at 24 images and above (the 3-scene cases are the per-stage form, on Winograd data gradients,
+    under GIGA_DGRAD_PERSIST=1 too), no bit at all on the direct kernels."""
+    from giga_amd import _capi
+    worst = []
+    for c in FORM_CASES:
+        worst.append(check_case(c))
+        path = _capi.lib().giga_backward_last_path()
+        want = (_capi.BWD_PATH_PERSISTENT if 3 * c[3] >= 24 else _capi.BWD_PATH_WINOGRAD) if persistent else 0
+        print(f"BWD {case_id(c)} giga_backward_last_path {path} expected {want}")
+        assert path == want, (case_id(c), path, want)
+    return max(worst)
+
+
 def _in_child(env):
     code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
             "import test_gpu_backward_envelope as T\n"
-            "w = max(T.check_case(c) for c in T.FORM_CASES)\n"
-            "print('worst', w)\nprint('ok')\n") % (ROOT, os.path.join(ROOT, "tests"))
+            "w = T.check_form_cases(%r)\n"
+            "print('worst', w)\nprint('ok')\n") % (ROOT, os.path.join(ROOT, "tests"), "GIGA_DGRAD_PERSIST" in env)
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=1500)
     print(r.stdout[-4000:])
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-3000:] + r.stderr[-3000:]
 
 
 def test_fp32_backward_persistent_dgrad_kernel():
-    """GIGA_DGRAD_PERSIST=1: the data-gradient chain in one persistent kernel (its pool stage: bwd_pool_stage)."""
+    """GIGA_DGRAD_PERSIST=1: the data-gradient chain in one persistent kernel (its pool stage: bwd_pool_stage) -- at 33 scenes;
+    the 3-scene cases are below its 24-image threshold and run one launch per stage (check_form_cases asserts which form ran)."""
     _in_child({"GIGA_DGRAD_PERSIST": "1"})
 
 
