@@ -32,6 +32,7 @@ BWD_PATH_PERSISTENT, BWD_PATH_WINOGRAD, BWD_PATH_BF16 = 1, 2, 4                 
 MESH_MAX_N = 256         # GIGA_MESH_MAX_N: samples per axis of a marching-cubes grid
 TSDF_MAX_R = 512         # GIGA_TSDF_MAX_R: cells per axis of a fused volume
 RENDER_MAX_IMAGE = 4096  # GIGA_RENDER_MAX_IMAGE: width and height of a rendered depth image
+NOISE_MODEL = {"dex": 1, "trans": 2, "norm": 3}          # GIGA_NOISE_DEX / _TRANS / _NORM
 MAX_SCENES = 3072        # GIGA_MAX_SCENES: scenes per encoder / training call (error -7 beyond)
 HEAD_BITS = {"decoder_qual": 1, "decoder_rot": 2, "decoder_width": 4, "decoder_tsdf": 8}
 PLANES_FP32 = 1024       # GIGA_PLANES_FP32: fp32 planes into the plain-f16 lattice decoder
@@ -153,6 +154,9 @@ _SIGNATURES = {
     "giga_depth_render_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "giga_depth_render": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 3 + [ctypes.c_double] * 3 + [ctypes.c_void_p] * 2
                           + [ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_depth_noise_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "giga_depth_noise": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_uint64,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -66,6 +66,10 @@ size_t depth_render_workspace_bytes(int B, int n_views);
 int launch_depth_render(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
                         const int* view_offsets, const double* extrinsics, const double* intrinsics, int B, int W, int H, double near,
                         double far, double pixel_offset, float* depth, uint8_t* ws, hipStream_t s);
+// giga_noise.hip
+size_t depth_noise_workspace_bytes(int n);
+int launch_depth_noise(const float* in, float* out, int n, int W, int H, int model, const double* p, unsigned long long seed,
+                       const unsigned long long* image_ids, uint8_t* ws, hipStream_t s);
 // giga_mesh.hip
 size_t mesh_workspace_bytes(int B, int nx, int ny, int nz);
 int launch_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, uint8_t* ws, int* counts, hipStream_t s);
@@ -926,6 +930,46 @@ int giga_depth_render(const float* vertices, const int32_t* vertex_offsets, cons
     if (workspace_bytes < giga_depth_render_workspace_bytes(B, n, vertex_offsets[B], triangle_offsets[B])) return -4;
     return launch_depth_render(vertices, vertex_offsets, triangles, triangle_offsets, view_offsets, extrinsics, intrinsics, B, W, H, near,
                                far, pixel_offset, depth, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+// ---- depth noise (giga_noise.hip) ----
+static bool noise_positive(double x) { return tsdf_finite(x) && x > 0.0; }
+
+static bool noise_shape_ok(int n, int W, int H, int model) {
+    if (n < 0 || W < 1 || H < 1 || W > GIGA_TSDF_MAX_IMAGE || H > GIGA_TSDF_MAX_IMAGE) return false;
+    if ((long long)n * W * H >= (1LL << 31)) return false;
+    return model >= GIGA_NOISE_DEX && model <= GIGA_NOISE_NORM;
+}
+
+size_t giga_depth_noise_workspace_bytes(int n_images, int width, int height, int model) {
+    if (!noise_shape_ok(n_images, width, height, model) || n_images == 0) return 0;
+    return depth_noise_workspace_bytes(n_images);
+}
+
+int giga_depth_noise(const float* depth_in, float* depth_out, int n_images, int width, int height, int model, const double* params,
+                     unsigned long long seed, const unsigned long long* image_ids, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+    if (!noise_shape_ok(n_images, width, height, model)) return -1;
+    static const double defaults[3][5] = {{1000.0, 0.001, 0.005, 4.0, 0.5}, {1.0, 0.005, 0, 0, 0}, {0.005, 0, 0, 0, 0}};
+    static const int count[3] = {5, 2, 1};
+    double p[5] = {0, 0, 0, 0, 0};
+    for (int i = 0; i < count[model - 1]; ++i) p[i] = params ? params[i] : defaults[model - 1][i];
+    if (model == GIGA_NOISE_DEX) {
+        if (!noise_positive(p[0]) || !noise_positive(p[1]) || !noise_positive(p[2]) || !noise_positive(p[3])) return -1;
+        if (!(p[4] >= 0.0 && p[4] <= 1.0)) return -1;
+        if (p[3] < 1.0 || (double)height < p[3] || (double)width < p[3]) return -1;
+    } else {
+        for (int i = 0; i < count[model - 1]; ++i)
+            if (!noise_positive(p[i])) return -1;
+    }
+    if (n_images == 0) return 0;
+    if (!depth_in || !depth_out || !workspace) return -1;
+    const size_t bytes = (size_t)n_images * width * height * sizeof(float);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(depth_in), b = reinterpret_cast<uintptr_t>(depth_out);
+    if (a < b + bytes && b < a + bytes) return -1;                               // out of place: trans is a gather
+    if (workspace_bytes < giga_depth_noise_workspace_bytes(n_images, width, height, model)) return -4;
+    return launch_depth_noise(depth_in, depth_out, n_images, width, height, model, p, seed, image_ids,
+                              static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 // No float atomics anywhere: equal input gives equal bytes, a batch gives scene b the bytes of a call on scene b alone.
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "giga_philox.h"
 #include <cmath>
 #include <cstdint>
 
@@ -227,19 +228,6 @@ __global__ __launch_bounds__(EV_SCAN) void sample_scan_kernel(double* __restrict
         totals[scene] = usable ? total : 0.0;
         counts[scene] = usable ? n : 0;
     }
-}
-
-struct Philox { unsigned x[4]; };
-__device__ __forceinline__ Philox philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return Philox{{c0, c1, c2, c3}};
 }
 
 __global__ __launch_bounds__(EV_BLOCK) void sample_draw_kernel(const float* __restrict__ vertices, const int* __restrict__ vo,

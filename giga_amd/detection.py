@@ -295,10 +295,13 @@ class VGNImplicit:
                    "width": float(sel["width"][i]) * size} for i in p]
         return grasps, sel["score"][p], toc
 
-    def plan_from_depth(self, depth_imgs, intrinsic, extrinsics, size=0.3):
+    def plan_from_depth(self, depth_imgs, intrinsic, extrinsics, size=0.3, noise=None):
         """Depth images (n, H, W) with their extrinsics (any form perception.extrinsic_matrix takes) to grasps: fusion, network
-        and post-processing on the device.  Returns what __call__ returns."""
+        and post-processing on the device.  noise: a `giga_amd.noise.DepthNoise` applied to the images on the device before the
+        fusion (image k has the id k); None leaves them as they are.  Returns what __call__ returns."""
         from types import SimpleNamespace
 
         from .perception import create_tsdf
+        if noise is not None:
+            depth_imgs = noise.apply(torch.as_tensor(depth_imgs).to(self.device, torch.float32))
         return self(SimpleNamespace(tsdf=create_tsdf(size, self.resolution, depth_imgs, intrinsic, extrinsics, self.device)))

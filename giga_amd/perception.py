@@ -4,7 +4,8 @@
 (`giga_tsdf_integrate`), export the (1, R, R, R) grid the encoder consumes in the same pass and extract the zero-crossing
 point cloud (`giga_tsdf_cloud_count` / `_emit`): the counterpart of `vgn.perception` (reference src/vgn/perception.py:10-137),
 which hands these steps to Open3D.  The arithmetic restates Open3D's UniformTSDFVolume (NoColor) operation by operation
-(include/giga_hip.h); `construct_dataset` is the loop of scripts/construct_dataset_parallel.py on top of it.
+(include/giga_hip.h); `construct_dataset` is the loop of scripts/construct_dataset_parallel.py on top of it, depth noise
+(`giga_amd.noise.DepthNoise`, its `noise=` argument) included.
 
 Dense export of a sparse voxel list that Open3D has already produced on the host:
 
@@ -284,13 +285,30 @@ def _fuse_to_host(size, resolution, depth_batches, intrinsic, extrinsics_batches
     return grid.cpu().numpy(), [points[offsets[b]:offsets[b + 1]] for b in range(len(depth_batches))]
 
 
-def construct_dataset(raw_root, dataset_root, single_view=False, batch=32, add_noise="", resolution=40, device=None):
-    """scripts/construct_dataset_parallel.py without noise: every <raw_root>/scenes/<id>.npz (depth_imgs, extrinsics) becomes
+def _noise_scenes(noise, depth_batches, image_ids, device=None):
+    """noise.apply on the images of several scenes in one launch: depth_batches[b] (V_b, H, W), image_ids one id per image, scenes
+    back to back.  Returns the noised (V_b, H, W) float32 device tensors, one per scene."""
+    device = _device(device)
+    imgs = [torch.as_tensor(d).to(torch.float32) for d in depth_batches]
+    out = noise.apply(torch.cat(imgs).to(device), image_ids)
+    return list(torch.split(out, [len(d) for d in imgs]))
+
+
+def construct_dataset(raw_root, dataset_root, single_view=False, batch=32, add_noise="", resolution=40, device=None, noise=None):
+    """scripts/construct_dataset_parallel.py: every <raw_root>/scenes/<id>.npz (depth_imgs, extrinsics) becomes
     <dataset_root>/scenes/<id>.npz (grid (1, R, R, R), the layout giga_amd.dataset.read_voxel_grid reads) and
     <dataset_root>/point_clouds/<id>.npz (pc, the cloud cropped to the reference's box); `batch` scenes are fused per launch.
+    noise: a `giga_amd.noise.DepthNoise` applied on the device to every depth image that is fused (with single_view: the one
+    view that is used), as the reference's --add-noise does (construct_dataset_parallel.py:21); None leaves the images as they
+    are.  Image `view` of the scene with ordinal s in the sorted file list has the id (s << 16) | view, so a scene's noise does
+    not depend on `batch` (scenes with 65 536 views or more are rejected).  The reference's string flag `add_noise` still
+    raises: it draws from numpy's global generator, and a string carries no seed.
     Returns the scene ids in the order they were written."""
     if add_noise:
-        raise NotImplementedError("add_noise: the reference's noise generators (vgn.utils.misc.apply_noise) cannot be reproduced here")
+        raise NotImplementedError("add_noise: the reference's flag draws from numpy's global generator and carries no seed; pass "
+                                  "noise=giga_amd.noise.DepthNoise(kind, seed) instead")
+    if noise is not None and not callable(getattr(noise, "apply", None)):
+        raise TypeError("noise is a giga_amd.noise.DepthNoise (or None)")
     if int(batch) < 1:
         raise ValueError("batch must be at least 1")
     raw_root, dataset_root = Path(raw_root), Path(dataset_root)
@@ -309,6 +327,11 @@ def construct_dataset(raw_root, dataset_root, single_view=False, batch=32, add_n
                 d, e = data["depth_imgs"], data["extrinsics"]
             depth.append(d[:1] if single_view else d)
             ext.append(e[:1] if single_view else e)
+        if noise is not None:
+            if any(len(d) >= 1 << 16 for d in depth):
+                raise ValueError("a scene with 65 536 or more views has no image ids")
+            ids = [((at + k) << 16) | v for k, d in enumerate(depth) for v in range(len(d))]
+            depth = _noise_scenes(noise, depth, ids, device)
         grids, clouds = _fuse_to_host(size, resolution, depth, intrinsic, ext, device)
         for f, g, pc in zip(chunk, grids, clouds):
             np.savez_compressed(dataset_root / "scenes" / (f.stem + ".npz"), grid=g[None])

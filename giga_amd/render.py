@@ -8,7 +8,10 @@ consumes, `sample_iou_points` / `save_occ` the occupancy labels of utils/implici
 on top of `giga_mesh_contains`.  Meshes are `(vertices, faces)` pairs of numpy arrays or device tensors (or objects with these
 attributes); loading mesh files stays with the caller.  There is no CPU path: CPU tensors raise `GigaHipError`.
 
-Not reproduced: PyBullet's fill rule at silhouettes, its z-buffer quantisation, RGB, the depth noise models."""
+The reference's depth noise (simulation.py:176, `--add-noise`) is the `noise=` argument of `acquire_tsdf` / `acquire_tsdfs`: a
+`giga_amd.noise.DepthNoise`, applied on the device between rendering and fusion.
+
+Not reproduced: PyBullet's fill rule at silhouettes, its z-buffer quantisation, RGB."""
 import json
 import os
 import time
@@ -118,14 +121,17 @@ def acquire_extrinsics(n, N=None, size=0.3, sideview=False):
     return np.stack([perception.camera_on_sphere(origin, r, theta, phi) for phi in phi_list]).reshape(-1, 4, 4)
 
 
-def acquire_tsdf(vertices, faces, n, N=None, resolution=40, size=0.3, sideview=False, lower=None, upper=None, device=None):
+def acquire_tsdf(vertices, faces, n, N=None, resolution=40, size=0.3, sideview=False, lower=None, upper=None, device=None, noise=None):
     """simulation.py:145-186 on a scene mesh: render n depth images with the reference's camera, integrate them into a volume of
     `resolution` and into a second one of 120.  Returns (TSDFVolume, pc, timing): pc the zero-crossing cloud of the second volume
     ((m, 3) float32 device tensor), cropped to lower <= p <= upper when both are given; timing the wall time of the integration
-    into the first volume.  The images never leave the device."""
+    into the first volume.  noise: a `giga_amd.noise.DepthNoise` applied to the rendered images (view k has the image id k) before
+    BOTH volumes integrate them, as simulation.py:172-181 does; None leaves them as rendered.  The images never leave the device."""
     intrinsic = sim_intrinsic()
     extrinsics = acquire_extrinsics(n, N, size, sideview)
     depth = render_depth(vertices, faces, intrinsic, extrinsics, SIM_NEAR, SIM_FAR, 0.0, device)
+    if noise is not None:
+        depth = noise.apply(depth)
     tsdf = perception.TSDFVolume(size, resolution, depth.device)
     high_res_tsdf = perception.TSDFVolume(size, 120, depth.device)
     torch.cuda.synchronize(depth.device)
@@ -143,11 +149,16 @@ def acquire_tsdf(vertices, faces, n, N=None, resolution=40, size=0.3, sideview=F
     return tsdf, pc, timing
 
 
-def acquire_tsdfs(meshes, n, N=None, resolution=40, size=0.3, device=None):
-    """The (B, R, R, R) device grid of B scene meshes, each seen from the top-view circle: one render launch, one fusion launch."""
+def acquire_tsdfs(meshes, n, N=None, resolution=40, size=0.3, device=None, noise=None):
+    """The (B, R, R, R) device grid of B scene meshes, each seen from the top-view circle: one render launch, one fusion launch.
+    noise: a `giga_amd.noise.DepthNoise` applied in one launch in between; view k of mesh b has the image id (b << 16) | k."""
     intrinsic = sim_intrinsic()
     extrinsics = acquire_extrinsics(n, N, size)
     depth, offs = render_depth_batch(meshes, intrinsic, [extrinsics] * len(meshes), SIM_NEAR, SIM_FAR, 0.0, device)
+    if noise is not None and len(depth):
+        if n >= 1 << 16:
+            raise ValueError("65 536 or more views per scene have no image ids")
+        depth = noise.apply(depth, [(b << 16) | k for b in range(len(meshes)) for k in range(n)])
     batches = [depth[offs[b]:offs[b + 1]] for b in range(len(meshes))]
     return perception.fuse_scenes(size, resolution, batches, intrinsic, [extrinsics] * len(meshes), depth.device)[2]
 

@@ -381,6 +381,51 @@ int giga_depth_render(const float* vertices, const int32_t* vertex_offsets, cons
                       double near, double far, double pixel_offset, float* depth, void* workspace, size_t workspace_bytes,
                       void* stream);
 
+/* ---- input side: depth-sensor noise, the dex, trans and norm models of vgn.utils.misc.apply_noise (src/vgn/utils/misc.py:18-69),
+ * which the reference applies to every depth image before fusion (scripts/construct_dataset_parallel.py:21, simulation.py:176) -----
+ * depth_in, depth_out [n][H][W] float32 (device): the layout giga_depth_render writes and giga_tsdf_integrate reads.  Out of
+ * place (trans is a gather): overlapping buffers are an error, depth_in is never written.  model: GIGA_NOISE_DEX / _TRANS / _NORM.
+ * params (HOST, NULL = the reference's defaults): dex {gamma_shape 1000, gamma_scale 0.001, gp_sigma 0.005, gp_scale 4, gp_rate
+ * 0.5}, trans {sigma_p 1, sigma_d 0.005}, norm {sigma 0.005}.  image_ids (HOST [n] uint64, NULL = 0 .. n-1) is copied into the
+ * workspace before the call returns.  Asynchronous on `stream`, no allocation, one launch (more only beyond 2^22 tiles).
+ * Draws are counter based.  Block (b, id, s) is Philox-4x32-10 on the counter (b, id & 0xffffffff, id >> 32, s) with the key
+ * (seed & 0xffffffff, seed >> 32); id the image's id, s the stream: 0 image scalars, 1 GP coarse grid, 2 trans row displacement,
+ * 3 trans column displacement, 4 per-pixel depth noise.  A block's words x0..x3 give two uniforms u(x0, x1), u(x2, x3) with
+ * u(hi, lo) = k 2^-53, k = (hi >> 5) 2^26 + (lo >> 6) (53 bits; 2^-54 in place of k = 0, so 0 < u < 1) and the Box-Muller pair
+ * z0 = rad cos(th), z1 = rad sin(th), rad = sqrt(-2 log u(x0, x1)), th = 6.283185307179586 u(x2, x3).  Element e of a stream is
+ * z(e & 1) of block e >> 1; element r w + c belongs to entry (r, c) of the array the reference fills with randn(h, w).  So an
+ * image's output depends only on seed, its id, W, H, the model and the parameters: not on the batch it sits in, the launch
+ * geometry or the order of calls, and equal input gives equal bytes.  All arithmetic is double with one IEEE rounding per
+ * operation unless stated; log, cos, sin (and pow for gamma_shape < 1) are the only operations whose last bits may differ between
+ * implementations.
+ *   dex    gamma = Marsaglia-Tsang (2000) for shape a, d = a - 1/3, c = 1 / sqrt(9 d): attempt k = 0, 1, .. takes x = z0 of
+ *          image-stream block 1 + 2k and u = u(x0, x1) of block 2 + 2k; v = 1 + c x, rejected if v <= 0; v = v^3; accepted if
+ *          u < 1 - 0.0331 x^4 or log u < 0.5 x^2 + d ((1 - v) + log v); the draw is d v gamma_scale.  At most
+ *          GIGA_NOISE_GAMMA_ATTEMPTS attempts (each accepts with probability > 0.95): after that the draw is d gamma_scale, the
+ *          sampler's value at x = 0.  gamma_shape < 1 draws shape + 1 and multiplies by u(x2, x3)^(1 / shape) of block 0.
+ *          out = in * float(gamma) in float32.  The coin u(x0, x1) of image-stream block 0 is always drawn; if it is below
+ *          gp_rate, a coarse h x w grid, h = int(H / gp_scale), w = int(W / gp_scale), of stream-1 normals times gp_sigma is
+ *          upsampled bilinearly to H x W with the pixel-centre mapping src = (dst + 0.5) (h / H) - 0.5 per axis, taps outside the
+ *          grid reading 0: f = floor(src), t = src - f, value = (1 - ty) ((1 - tx) g[fy][fx] + tx g[fy][fx+1]) + ty ((1 - tx)
+ *          g[fy+1][fx] + tx g[fy+1][fx+1]), and out = float(double(out) + value).  This is skimage.transform.resize(order=1,
+ *          mode="constant", anti_aliasing=False) WITHOUT its final clip to the coarse grid's [min, max]: the clip changes nothing
+ *          when the grid has both signs (always, for practical purposes, at 120 x 160 coarse cells) and is not reproduced.
+ *   trans  r' = clip(rint(r + n1 sigma_p), 0, H - 1), c' = clip(rint(c + n2 sigma_p), 0, W - 1) (rint: half to even; n1, n2
+ *          elements r W + c of streams 2 and 3), out[r][c] = float(double(in[r'][c']) + n3 sigma_d), n3 of stream 4.
+ *   norm   out = float(double(in) + n sigma), n of stream 4.
+ * Every argument is checked before the first HIP call.  Errors: -1 negative n, W or H outside 1 .. GIGA_TSDF_MAX_IMAGE,
+ * n W H >= 2^31, unknown model, a sigma / shape / scale parameter that is not finite or not > 0, gp_rate outside [0, 1], gp_scale
+ * < 1 or above H or W (the coarse grid would be empty), null images or workspace with n > 0, overlapping images; -4 workspace
+ * smaller than giga_depth_noise_workspace_bytes(n, W, H, model).  n = 0 returns 0. */
+#define GIGA_NOISE_DEX 1
+#define GIGA_NOISE_TRANS 2
+#define GIGA_NOISE_NORM 3
+#define GIGA_NOISE_GAMMA_ATTEMPTS 16
+size_t giga_depth_noise_workspace_bytes(int n_images, int width, int height, int model);
+int giga_depth_noise(const float* depth_in, float* depth_out, int n_images, int width, int height, int model, const double* params,
+                     unsigned long long seed, const unsigned long long* image_ids, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 /* ---- fused training loss (scripts/train_giga.py:154-195: `select` + `loss_fn`, literal call shape N = 1) -----
  * Inputs are the head outputs of the model's forward for one grasp query per scene -- qual [B] (post sigmoid), rot [B][4]
  * (unit), width [B], occ_logits [B][M] (raw; the sigmoid of `select` is part of this function) -- and the labels of
