@@ -36,7 +36,7 @@ struct EncWs {
 
 // gradient workspace of the encoder backward (giga_encoder_bwd.hip carves it, giga_capi.hip sizes the caller's buffer with it): ONE
 // definition for both translation units
-struct BwdWs { size_t gA6, gA5, gC1, gA4, gA3, gC0, gS2, gA2, gQ1, gS1, gA1, gQ0, gS0, gA0, gP0, WG, WG3[12], CINP, total; };   // (+ SYNC behind `total`)
+struct BwdWs { size_t gA6, gA5, gC1, gA4, gA3, gC0, gS2, gA2, gQ1, gS1, gA1, gQ0, gS0, gA0, gP0, WG, WG3[12], CINP, total; };
 BwdWs enc_bwd_workspace(int B);
 
 }  // namespace giga

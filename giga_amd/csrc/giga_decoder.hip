@@ -1636,19 +1636,13 @@ int launch_decoder(const DecArgs& a0, int precision, hipStream_t s, void* ev0, v
         const int nslab = a.B * a.R * np;
         int slots = nslab < cap ? nslab : (nslab >= 2 * cap8 && cap8 > 0 ? cap8 : cap);
         a.nbatch = slots;
-        // (tuning knob: GIGA_LAT_NW = 12 | 16 waves per workgroup; 16 = four per SIMD, the default: 0.267 -> 0.257 ms at 32 scenes)
-        const int nw = [] { const char* e = getenv("GIGA_LAT_NW"); return e ? atoi(e) : 16; }();
-        auto go = [&](auto kern, int NWv, size_t lds) {
+        // 16 waves per workgroup, four per SIMD (against 12: 0.267 -> 0.257 ms at 32 scenes)
+        auto go = [&](auto kern, size_t lds) {
             giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)lds);
-            GIGA_LAUNCH(kern, dim3(slots * a.nheads), dim3(NWv * 64), lds, s, a);
+            GIGA_LAUNCH(kern, dim3(slots * a.nheads), dim3(16 * 64), lds, s, a);
         };
-        if (precision == 2) {
-            if (nw == 16) go(decoder_lat_kernel<true, 16, false>, 16, lat_lds_bytes<true, false>(a.R));
-            else go(decoder_lat_kernel<true, 12, false>, 12, lat_lds_bytes<true, false>(a.R));
-        } else {
-            if (nw == 16) go(decoder_lat_kernel<false, 16, true>, 16, lat_lds_bytes<false, true>(a.R));
-            else go(decoder_lat_kernel<false, 12, true>, 12, lat_lds_bytes<false, true>(a.R));
-        }
+        if (precision == 2) go(decoder_lat_kernel<true, 16, false>, lat_lds_bytes<true, false>(a.R));
+        else go(decoder_lat_kernel<false, 16, true>, lat_lds_bytes<false, true>(a.R));
         if (ev0 && ev1) (void)hipEventRecord(static_cast<hipEvent_t>(ev1), s);
         return hipGetLastError() == hipSuccess ? 0 : -10;
     }

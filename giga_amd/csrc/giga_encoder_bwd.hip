@@ -16,16 +16,31 @@
 #include <functional>
 #include <mutex>
 
-#include "giga_bwd_mega.h"
 #include "giga_side.h"
 #include "giga_args.h"
 
 namespace giga {
 
 // ------------------------------- elementwise ------------------------------------------------------------
+// MaxPool2d(2,2) backward routing, torch.max_pool2d's rule: of a window's elements equal to its maximum Q, only the FIRST
+// in row-major order ((0,0), (0,1), (1,0), (1,1)) receives dQ.  (Handing dQ to every tied element multiplies the window's
+// gradient by the number of ties; ties are common where the input is constant, e.g. the empty space of a TSDF.)
+// s = S at pixel pix = (y, x) of an H x W image, channels [c, c + 4); returns 1.f per channel where the element is that one.
+__device__ __forceinline__ float4 pool_first_max(const float* __restrict__ S, size_t pix, int y, int x, int W, int C, int c,
+                                                 float4 s, float4 q) {
+    bool tx = false, ty = false, tz = false, tw = false;        // an earlier element of the window equals q
+    const int r = (y & 1) * 2 + (x & 1);
+    const size_t p0 = pix - (size_t)(y & 1) * W - (x & 1);
+    for (int j = 0; j < r; ++j) {
+        const float4 e = *reinterpret_cast<const float4*>(S + (p0 + (size_t)(j >> 1) * W + (j & 1)) * C + c);
+        tx |= e.x == q.x; ty |= e.y == q.y; tz |= e.z == q.z; tw |= e.w == q.w;
+    }
+    return make_float4(s.x == q.x && !tx ? 1.f : 0.f, s.y == q.y && !ty ? 1.f : 0.f,
+                       s.z == q.z && !tz ? 1.f : 0.f, s.w == q.w && !tw ? 1.f : 0.f);
+}
 // dS[img][y][x][c] = dCat[img][y][x][coff + c] (skip half of the concat gradient, channel stride cs)
 //                  + (S[y][x][c] is the first of its window == Q[y/2][x/2][c] ? dQ[y/2][x/2][c] : 0)   (MaxPool2d(2,2)
-// backward: ties go to the first maximum in row-major window order, as in torch; giga_bwd_mega.h: pool_first_max)
+// backward: ties go to the first maximum in row-major window order, as in torch; pool_first_max)
 // and, S being the ReLU output of the layer below, its backward in the same pass: dS = S > 0 ? dS : 0
 // (one thread per FOUR channels: 16-byte loads and stores; C, cs and coff are multiples of 4)
 __global__ void pool_bwd_add_kernel(float* __restrict__ dS, const float* __restrict__ dcat, int cs, int coff,
@@ -1395,7 +1410,7 @@ void side_streams_forget() {
 
 // ------------------------------- driver -----------------------------------------------------------------------
 // forward activations: the encoder workspace (giga_encoder.hip::EncWs, fp32).  Gradient workspace carve:
-// (struct BwdWs: giga_bwd_mega.h)
+// (struct BwdWs: giga_args.h)
 // what the last backward of this process ran its data-gradient chain on (giga_backward_last_path: tests pin the launch form to it)
 static std::atomic<int> g_last_bwd_path{0};
 
@@ -1419,7 +1434,7 @@ BwdWs enc_bwd_workspace(int B) {
         w.WG3[l] = take((size_t)256 * (nblk < 8 ? nblk : 8) * 32 * 288 + WG3_BIAS_FLOATS);
     }
     w.CINP = take((size_t)B * 8 * 5 * CB_PART);    // conv_in's workgroup partials (their own: the backward runs beside the weight gradients' stream)
-    w.total = at;                                  // (+ MEGA_SYNC_WORDS words behind it: the persistent data-gradient kernel's counters)
+    w.total = at;
     return w;
 }
 
@@ -1528,49 +1543,24 @@ static int encoder_backward_impl(const float* tsdf, const uint8_t* blob, const u
     };
     const size_t n40 = (size_t)nimg * 1600, n20 = (size_t)nimg * 400, n10 = (size_t)nimg * 100;
 
-    // ---- the data-gradient chain.  Stage order L12 L11 L10 L9 L8 L7 L6 L5 L4 [pool1] L3 L2 [pool0] L1 L0: one launch per stage, or
-    // ONE persistent launch (unet_dgrad_mega_kernel, giga_encoder.hip).
-    BwdMegaArgs M{};
-    M.layer[0] = dgrad_args(12, gplanes, 0, G(g.gA6), F(f.A6));          // L12 conv_final (1x1, no activation): gplanes = dOUT
-    M.layer[1] = dgrad_args(11, G(g.gA6), 0, G(g.gA5), F(f.A5));         // L11 up1.conv2: A5 -> A6
-    M.layer[2] = dgrad_args(10, G(g.gA5), 0, G(g.gC1));                  // L10 up1.conv1: cat(U1, S0) -> A5; 64 channels out (dU1 | dS0 skip part)
-    M.layer[3] = dgrad_args(9, G(g.gC1), 64, G(g.gA4), F(f.A4));         // L9 up1.upconv: A4 (20x20x64) -> U1; dU1 = gC1[..., 0:32]
-    M.layer[4] = dgrad_args(8, G(g.gA4), 0, G(g.gA3), F(f.A3));          // L8 up0.conv2: A3 -> A4
-    M.layer[5] = dgrad_args(7, G(g.gA3), 0, G(g.gC0));                   // L7 up0.conv1: cat(U0, S1) -> A3; 128 channels out
-    M.layer[6] = dgrad_args(6, G(g.gC0), 128, G(g.gS2), F(f.S2));        // L6 up0.upconv: S2 (10x10x128) -> U0; dU0 = gC0[..., 0:64]
-    M.layer[7] = dgrad_args(5, G(g.gS2), 0, G(g.gA2), F(f.A2));          // L5 down2.conv2: A2 -> S2
-    M.layer[8] = dgrad_args(4, G(g.gA2), 0, G(g.gQ1));                   // L4 down2.conv1: Q1 -> A2
-    M.pool[0] = BwdPool{G(g.gS1), G(g.gC0), G(g.gQ1), F(f.S1), F(f.Q1), 128, 64, 20, 20, 64};   // dS1 = gC0[..., 64:128] + unpool(dQ1)
-    M.layer[9] = dgrad_args(3, G(g.gS1), 0, G(g.gA1), F(f.A1));          // L3 down1.conv2: A1 -> S1
-    M.layer[10] = dgrad_args(2, G(g.gA1), 0, G(g.gQ0));                  // L2 down1.conv1: Q0 -> A1
-    M.pool[1] = BwdPool{G(g.gS0), G(g.gC1), G(g.gQ0), F(f.S0), F(f.Q0), 64, 32, 40, 40, 32};    // dS0 = gC1[..., 32:64] + unpool(dQ0)
-    M.layer[11] = dgrad_args(1, G(g.gS0), 0, G(g.gA0), F(f.A0));         // L1 down0.conv2: A0 -> S0
-    M.layer[12] = dgrad_args(0, G(g.gA0), 0, G(g.gP0));                  // L0 down0.conv1: P0 -> A0
-    M.sync = reinterpret_cast<unsigned*>(gws + g.total);                  // (behind the workspace proper: enc_bwd_workspace_bytes)
-    // The persistent form is an OPT-IN (GIGA_DGRAD_PERSIST=1): measured at 32 scenes it is SLOWER than the fifteen launches it replaces
-    // (bf16 step 1.016 -> 1.057 ms, fp32 1.824 -> 1.849: the kernel takes 212 us against 194 us for the separate launches, whose
-    // dispatch the queue already hides behind the previous kernel's tail, and fifteen group barriers are not free; the weight gradients,
-    // pushed behind the whole chain, find their dY further down the cache hierarchy: +1-2 us each).  profiles/r05/dgrad_mega.txt
-    static const int env_dgrad_persist = [] { const char* e = getenv("GIGA_DGRAD_PERSIST"); return e ? atoi(e) : 0; }();
-    const int mega = env_dgrad_persist ? launch_unet_dgrad_mega(M, MATH == MATH_BF16, s) : 0;
-    if (mega < 0) rc |= mega;
-    if (mega > 0) {
-        // the weight gradients: every one needs only what the chain has left in memory (dPre of its layer, mask applied) and the
-        // forward's activations
-        wgrad3(12, gplanes, F(f.A6), nullptr, 40);
-        wgrad3(11, G(g.gA6), F(f.A5), nullptr, 40);
-        wgrad3(10, G(g.gA5), F(f.U1), F(f.S0), 40);
-        wgrad_up(9, F(f.A4), G(g.gC1), 64, 20);
-        wgrad3(8, G(g.gA4), F(f.A3), nullptr, 20);
-        wgrad3(7, G(g.gA3), F(f.U0), F(f.S1), 20);
-        wgrad_up(6, F(f.S2), G(g.gC0), 128, 10);
-        wgrad3(5, G(g.gS2), F(f.A2), nullptr, 10);
-        wgrad3(4, G(g.gA2), F(f.Q1), nullptr, 10);
-        wgrad3(3, G(g.gS1), F(f.A1), nullptr, 20);
-        wgrad3(2, G(g.gA1), F(f.Q0), nullptr, 20);
-        wgrad3(1, G(g.gS0), F(f.A0), nullptr, 40);
-        wgrad3(0, G(g.gA0), F(f.P0), nullptr, 40);
-    }
+    // ---- the data-gradient chain.  Stage order L12 L11 L10 L9 L8 L7 L6 L5 L4 [pool1] L3 L2 [pool0] L1 L0: one launch per stage.
+    // (The chain as ONE persistent launch measured slower at 8, 32 and 128 scenes in every training mode: back-to-back launches already
+    // overlap their dispatch with the predecessor's tail, fifteen group barriers are not free, and the weight gradients, pushed behind
+    // the whole chain, find their dY further down the cache hierarchy.  profiles/r05/dgrad_mega.txt)
+    const ConvArgs stage[13] = {
+        dgrad_args(12, gplanes, 0, G(g.gA6), F(f.A6)),         // L12 conv_final (1x1, no activation): gplanes = dOUT
+        dgrad_args(11, G(g.gA6), 0, G(g.gA5), F(f.A5)),        // L11 up1.conv2: A5 -> A6
+        dgrad_args(10, G(g.gA5), 0, G(g.gC1)),                 // L10 up1.conv1: cat(U1, S0) -> A5; 64 channels out (dU1 | dS0 skip part)
+        dgrad_args(9, G(g.gC1), 64, G(g.gA4), F(f.A4)),        // L9 up1.upconv: A4 (20x20x64) -> U1; dU1 = gC1[..., 0:32]
+        dgrad_args(8, G(g.gA4), 0, G(g.gA3), F(f.A3)),         // L8 up0.conv2: A3 -> A4
+        dgrad_args(7, G(g.gA3), 0, G(g.gC0)),                  // L7 up0.conv1: cat(U0, S1) -> A3; 128 channels out
+        dgrad_args(6, G(g.gC0), 128, G(g.gS2), F(f.S2)),       // L6 up0.upconv: S2 (10x10x128) -> U0; dU0 = gC0[..., 0:64]
+        dgrad_args(5, G(g.gS2), 0, G(g.gA2), F(f.A2)),         // L5 down2.conv2: A2 -> S2
+        dgrad_args(4, G(g.gA2), 0, G(g.gQ1)),                  // L4 down2.conv1: Q1 -> A2
+        dgrad_args(3, G(g.gS1), 0, G(g.gA1), F(f.A1)),         // L3 down1.conv2: A1 -> S1
+        dgrad_args(2, G(g.gA1), 0, G(g.gQ0)),                  // L2 down1.conv1: Q0 -> A1
+        dgrad_args(1, G(g.gS0), 0, G(g.gA0), F(f.A0)),         // L1 down0.conv2: A0 -> S0
+        dgrad_args(0, G(g.gA0), 0, G(g.gP0))};                 // L0 down0.conv1: P0 -> A0
     // stage k of the chain is the data gradient of U-Net layer 12 - k
     static constexpr int LAYER_OF_STAGE[13] = {12, 11, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1, 0};
     // fp32 step: the data gradients of the 3x3 layers are stride-1 3x3 convolutions too (flipped taps, channels swapped) and run as
@@ -1579,59 +1569,56 @@ static int encoder_backward_impl(const float* tsdf, const uint8_t* blob, const u
     static const int env_wino_bwd = [] { const char* e = getenv("GIGA_WINOGRAD_BWD"); return e ? atoi(e) : 1; }();
     constexpr bool CAN_WINO_BWD = MATH == MATH_NATIVE;
     const bool wino_bwd = CAN_WINO_BWD && env_wino_bwd != 0;
-    auto dgrad3 = [&](auto c0, auto cout, auto hw, auto nb, int stage, int layer) {
+    auto dgrad3 = [&](auto c0, auto cout, auto hw, auto nb, int k, int layer) {
         constexpr int C0 = decltype(c0)::value, COUT = decltype(cout)::value, HW = decltype(hw)::value, NB = decltype(nb)::value;
         if constexpr (CAN_WINO_BWD) {
             if (wino_bwd) {
-                ConvArgs a = M.layer[stage];
+                ConvArgs a = stage[k];
                 a.w = bwd_blob + bo.wino[layer];
                 return launch_wino<C0, 0, COUT, HW, HW, false, false>(a, s);
             }
         }
-        return launch_conv<float, CONV3, C0, 0, COUT, HW, HW, NB, false, false, MATH>(M.layer[stage], s);
+        return launch_conv<float, CONV3, C0, 0, COUT, HW, HW, NB, false, false, MATH>(stage[k], s);
     };
-    g_last_bwd_path.store((mega > 0 ? GIGA_BWD_PATH_PERSISTENT : 0) | (mega <= 0 && wino_bwd ? GIGA_BWD_PATH_WINOGRAD : 0) |
-                          (MATH == MATH_BF16 ? GIGA_BWD_PATH_BF16 : 0), std::memory_order_relaxed);
-    if (mega <= 0) {
-        // one launch per stage, the weight gradient of a layer right behind the launch that produced its dPre (it is still in the
-        // Infinity Cache then)
-        wgrad3(12, gplanes, F(f.A6), nullptr, 40);
-        rc |= launch_conv<float, CONV1, 32, 0, 32, 40, 40, 2, false, false, MATH>(M.layer[0], s);
-        wgrad3(11, G(g.gA6), F(f.A5), nullptr, 40);
-        rc |= dgrad3(IC<32>{}, IC<32>{}, IC<40>{}, IC<2>{}, 1, LAYER_OF_STAGE[1]);
-        wgrad3(10, G(g.gA5), F(f.U1), F(f.S0), 40);
-        rc |= dgrad3(IC<32>{}, IC<64>{}, IC<40>{}, IC<2>{}, 2, LAYER_OF_STAGE[2]);
-        wgrad_up(9, F(f.A4), G(g.gC1), 64, 20);
-        rc |= launch_conv<float, DOWN, 32, 0, 64, 20, 20, 2, false, false, MATH>(M.layer[3], s);
-        wgrad3(8, G(g.gA4), F(f.A3), nullptr, 20);
-        rc |= dgrad3(IC<64>{}, IC<64>{}, IC<20>{}, IC<1>{}, 4, LAYER_OF_STAGE[4]);
-        wgrad3(7, G(g.gA3), F(f.U0), F(f.S1), 20);
-        rc |= dgrad3(IC<64>{}, IC<128>{}, IC<20>{}, IC<1>{}, 5, LAYER_OF_STAGE[5]);
-        wgrad_up(6, F(f.S2), G(g.gC0), 128, 10);
-        rc |= launch_conv<float, DOWN, 64, 0, 128, 10, 10, 1, false, false, MATH>(M.layer[6], s);
-        wgrad3(5, G(g.gS2), F(f.A2), nullptr, 10);
-        rc |= dgrad3(IC<128>{}, IC<128>{}, IC<10>{}, IC<1>{}, 7, LAYER_OF_STAGE[7]);
-        wgrad3(4, G(g.gA2), F(f.Q1), nullptr, 10);
-        rc |= dgrad3(IC<128>{}, IC<64>{}, IC<10>{}, IC<1>{}, 8, LAYER_OF_STAGE[8]);
-        {
-            const size_t tot = n20 * 64 / 4;
-            GIGA_LAUNCH(pool_bwd_add_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, G(g.gS1),
-                               G(g.gC0), 128, 64, G(g.gQ1), F(f.S1), F(f.Q1), nimg, 20, 20, 64);
-        }
-        wgrad3(3, G(g.gS1), F(f.A1), nullptr, 20);
-        rc |= dgrad3(IC<64>{}, IC<64>{}, IC<20>{}, IC<1>{}, 9, LAYER_OF_STAGE[9]);
-        wgrad3(2, G(g.gA1), F(f.Q0), nullptr, 20);
-        rc |= dgrad3(IC<64>{}, IC<32>{}, IC<20>{}, IC<2>{}, 10, LAYER_OF_STAGE[10]);
-        {
-            const size_t tot = n40 * 32 / 4;
-            GIGA_LAUNCH(pool_bwd_add_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, G(g.gS0),
-                               G(g.gC1), 64, 32, G(g.gQ0), F(f.S0), F(f.Q0), nimg, 40, 40, 32);
-        }
-        wgrad3(1, G(g.gS0), F(f.A0), nullptr, 40);
-        rc |= dgrad3(IC<32>{}, IC<32>{}, IC<40>{}, IC<2>{}, 11, LAYER_OF_STAGE[11]);
-        wgrad3(0, G(g.gA0), F(f.P0), nullptr, 40);
-        rc |= dgrad3(IC<32>{}, IC<32>{}, IC<40>{}, IC<2>{}, 12, LAYER_OF_STAGE[12]);
+    g_last_bwd_path.store((wino_bwd ? GIGA_BWD_PATH_WINOGRAD : 0) | (MATH == MATH_BF16 ? GIGA_BWD_PATH_BF16 : 0), std::memory_order_relaxed);
+    // one launch per stage, the weight gradient of a layer right behind the launch that produced its dPre (it is still in the
+    // Infinity Cache then)
+    wgrad3(12, gplanes, F(f.A6), nullptr, 40);
+    rc |= launch_conv<float, CONV1, 32, 0, 32, 40, 40, 2, false, false, MATH>(stage[0], s);
+    wgrad3(11, G(g.gA6), F(f.A5), nullptr, 40);
+    rc |= dgrad3(IC<32>{}, IC<32>{}, IC<40>{}, IC<2>{}, 1, LAYER_OF_STAGE[1]);
+    wgrad3(10, G(g.gA5), F(f.U1), F(f.S0), 40);
+    rc |= dgrad3(IC<32>{}, IC<64>{}, IC<40>{}, IC<2>{}, 2, LAYER_OF_STAGE[2]);
+    wgrad_up(9, F(f.A4), G(g.gC1), 64, 20);
+    rc |= launch_conv<float, DOWN, 32, 0, 64, 20, 20, 2, false, false, MATH>(stage[3], s);
+    wgrad3(8, G(g.gA4), F(f.A3), nullptr, 20);
+    rc |= dgrad3(IC<64>{}, IC<64>{}, IC<20>{}, IC<1>{}, 4, LAYER_OF_STAGE[4]);
+    wgrad3(7, G(g.gA3), F(f.U0), F(f.S1), 20);
+    rc |= dgrad3(IC<64>{}, IC<128>{}, IC<20>{}, IC<1>{}, 5, LAYER_OF_STAGE[5]);
+    wgrad_up(6, F(f.S2), G(g.gC0), 128, 10);
+    rc |= launch_conv<float, DOWN, 64, 0, 128, 10, 10, 1, false, false, MATH>(stage[6], s);
+    wgrad3(5, G(g.gS2), F(f.A2), nullptr, 10);
+    rc |= dgrad3(IC<128>{}, IC<128>{}, IC<10>{}, IC<1>{}, 7, LAYER_OF_STAGE[7]);
+    wgrad3(4, G(g.gA2), F(f.Q1), nullptr, 10);
+    rc |= dgrad3(IC<128>{}, IC<64>{}, IC<10>{}, IC<1>{}, 8, LAYER_OF_STAGE[8]);
+    {
+        const size_t tot = n20 * 64 / 4;
+        GIGA_LAUNCH(pool_bwd_add_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, G(g.gS1),
+                           G(g.gC0), 128, 64, G(g.gQ1), F(f.S1), F(f.Q1), nimg, 20, 20, 64);
     }
+    wgrad3(3, G(g.gS1), F(f.A1), nullptr, 20);
+    rc |= dgrad3(IC<64>{}, IC<64>{}, IC<20>{}, IC<1>{}, 9, LAYER_OF_STAGE[9]);
+    wgrad3(2, G(g.gA1), F(f.Q0), nullptr, 20);
+    rc |= dgrad3(IC<64>{}, IC<32>{}, IC<20>{}, IC<2>{}, 10, LAYER_OF_STAGE[10]);
+    {
+        const size_t tot = n40 * 32 / 4;
+        GIGA_LAUNCH(pool_bwd_add_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, G(g.gS0),
+                           G(g.gC1), 64, 32, G(g.gQ0), F(f.S0), F(f.Q0), nimg, 40, 40, 32);
+    }
+    wgrad3(1, G(g.gS0), F(f.A0), nullptr, 40);
+    rc |= dgrad3(IC<32>{}, IC<32>{}, IC<40>{}, IC<2>{}, 11, LAYER_OF_STAGE[11]);
+    wgrad3(0, G(g.gA0), F(f.P0), nullptr, 40);
+    rc |= dgrad3(IC<32>{}, IC<32>{}, IC<40>{}, IC<2>{}, 12, LAYER_OF_STAGE[12]);
     flush();
     rc |= launch_wgrad3_reduce_all(RED, ws);
     // conv_in + projection

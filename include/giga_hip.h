@@ -149,8 +149,7 @@ int giga_decoder_forward(const void* planes_nhwc, const float* p, const void* pa
  * once: keep those to four concurrent encoder calls, or pass GIGA_LAYERWISE_UNET.  The kernel also assumes that every XCD
  * receives an eighth of the grid (no CU mask on the stream, a whole MI355X: 256 CUs -- checked -- in one partition).  A barrier
  * that is not released within 20 s of wall clock (s_memrealtime) traps instead of returning stale data or hanging the device.
- *   GIGA_LAYERWISE_UNET, OR-ed into `precision` of giga_encoder_forward*: one launch per layer (A/B comparisons; the environment
- *   variable GIGA_UNET_PERSIST=0 does the same for a whole process).
+ *   GIGA_LAYERWISE_UNET, OR-ed into `precision` of giga_encoder_forward*: one launch per layer (A/B comparisons).
  *   GIGA_PERSIST_UNET: the persistent launch also where the default keeps per-layer launches (precisions 0 / 3 below 8 scenes). */
 #define GIGA_PERSIST_UNET 32
 #define GIGA_LAYERWISE_UNET 64
@@ -167,7 +166,7 @@ int giga_decoder_forward(const void* planes_nhwc, const float* p, const void* pa
  * and after the conv32 launch runs, which costs sustained large-batch steps more than the kernel gains.  A scene's low-order bits
  * therefore depend on whether its batch has more than 16 scenes -- force one kernel where that matters:
  *   GIGA_CONV32_UNET / GIGA_CONV16_UNET, OR-ed into `precision` (1 or 2) of giga_encoder_forward*: force the one or the other for
- *   this call; the environment variable GIGA_CONV32=1 / 0 does the same for a whole process (the flag of a call wins). */
+ *   this call. */
 #define GIGA_CONV32_UNET 128
 #define GIGA_CONV16_UNET 256
 /* GIGA_CONVIN_MASK, OR-ed into `precision` (0 or 3) of giga_encoder_forward*: a TRAINING forward -- conv_in also stores its ReLU mask, one
@@ -583,9 +582,9 @@ void giga_forget_device_state(void);
 #define GIGA_PATH_WINOGRAD 8
 int giga_encoder_last_path(void);
 /* How the LAST giga_backward call of this process ran the U-Net's data-gradient chain (diagnostic, read-only: tests pin the launch
- * form to it): an OR of GIGA_BWD_PATH_PERSISTENT (one persistent launch, GIGA_DGRAD_PERSIST=1 at 24 images and above; else one
- * launch per stage), GIGA_BWD_PATH_WINOGRAD (fp32: the 3x3 layers' data gradients as Winograd F(2x2, 3x3); never with the persistent
- * launch, which runs the direct kernels) and GIGA_BWD_PATH_BF16 (GIGA_BF16_CONVS: bf16 operands).  0 before the first call. */
+ * form to it; the chain is always one launch per stage): an OR of GIGA_BWD_PATH_WINOGRAD (fp32: the 3x3 layers' data gradients as
+ * Winograd F(2x2, 3x3)) and GIGA_BWD_PATH_BF16 (GIGA_BF16_CONVS: bf16 operands).  0 before the first call.
+ * GIGA_BWD_PATH_PERSISTENT is no longer reported (the chain as one persistent launch was removed); its value stays reserved. */
 #define GIGA_BWD_PATH_PERSISTENT 1
 #define GIGA_BWD_PATH_WINOGRAD 2
 #define GIGA_BWD_PATH_BF16 4

@@ -26,7 +26,7 @@ with torch.no_grad():
     ref = O.model_forward(sd, torch.from_numpy(synth.tsdf_batch(1000, 1)), O.inference_lattice())
 ms = ctypes.c_float()
 rows = []
-MODES = tuple(os.environ.get("DEC_LAT_MODES", "0,1").split(","))
+MODES = tuple(os.environ.get("DEC_LAT_MODES", "0,1").split(","))      # values of GIGA_DEC_LAT
 sizes = [int(v) for v in (sys.argv[1].split(",") if len(sys.argv) > 1 else "4,8,32,128".split(","))]
 for prec in ("fp16", "fp16x3"):
     net.set_precision(prec)
@@ -38,8 +38,7 @@ for prec in ("fp16", "fp16x3"):
         res, times = {}, {m: [] for m in MODES}
 
         def setmode(mode):
-            os.environ["GIGA_DEC_LAT"] = mode.split("n")[0]     # "1n16": separable kernel with 16 waves per workgroup
-            os.environ["GIGA_LAT_NW"] = mode.split("n")[1] if "n" in mode else "12"
+            os.environ["GIGA_DEC_LAT"] = mode
 
         with torch.no_grad():
             setmode(MODES[-1])
@@ -60,7 +59,7 @@ for prec in ("fp16", "fp16x3"):
                     res[mode] = (0.0, {k: v.clone() for k, v in out.items()})
         for mode in MODES:
             res[mode] = (float(np.median(times[mode])), res[mode][1])
-        os.environ.pop("GIGA_DEC_LAT", None); os.environ.pop("GIGA_LAT_NW", None)
+        os.environ.pop("GIGA_DEC_LAT", None)
         t0, o0 = res["0"]
         fl = B * 64000 * FLOP_GRASP3
         names = ("decoder_qual", "decoder_rot", "decoder_width")

@@ -3,10 +3,10 @@ the fp32 step against float64 autograd, over the weight and input families of re
 one-x-part form) and 33 scenes; the joint loss through the fused giga_loss and a smooth objective (fixed random weights on
 every output, nothing saturates) with 1 and 3 grasp queries; 64, 300 and 2048 occupancy queries (the plane gradient switches
 from atomics to the binned gather at 256) with queries on the cube's faces and corners, outside it and many in one cell;
-the models giga, giga_aff (no occupancy head), giga_geo (occupancy head only) and giga_detach.  The persistent data-gradient
-kernel (GIGA_DGRAD_PERSIST=1) and the direct data-gradient convolutions (GIGA_WINOGRAD_BWD=0) run a reduced sweep in a child
-process each (both are read once per process).  The bf16 step at the c5 shape is held to float64 on 'structured' and
-'adversarial' inputs by the bounds of tests/test_gpu_training.py::test_bf16_training_step_at_the_c5_shape.
+the models giga, giga_aff (no occupancy head), giga_geo (occupancy head only) and giga_detach.  The direct data-gradient
+convolutions (GIGA_WINOGRAD_BWD=0) run a reduced sweep in a child process (the variable is read once per process).  The
+bf16 step at the c5 shape is held to float64 on 'structured' and 'adversarial' inputs by the bounds of
+tests/test_gpu_training.py::test_bf16_training_step_at_the_c5_shape.
 
 Error: max |got - ref| / max |ref| per parameter tensor (ref64.grad_err).  The 'structured' and 'adversarial' families have
 large constant regions, where 2x2 max-pool windows hold tied maxima: the backward must route each window's gradient to its
@@ -189,16 +189,15 @@ def test_fp32_backward_matches_float64(case):
         _MEASURED[key] = (w[0], f"{w[1]} ({case_id(case)})")
 
 
-def check_form_cases(persistent):
+def check_form_cases():
     """The reduced sweep inside a child process; giga_backward_last_path() must report the form each case is meant to run:
-    the persistent chain only at 24 images and above (the 3-scene cases are the per-stage form, on Winograd data gradients,
-    under GIGA_DGRAD_PERSIST=1 too), no bit at all on the direct kernels."""
+    no bit at all on the direct kernels."""
     from giga_amd import _capi
     worst = []
     for c in FORM_CASES:
         worst.append(check_case(c))
         path = _capi.lib().giga_backward_last_path()
-        want = (_capi.BWD_PATH_PERSISTENT if 3 * c[3] >= 24 else _capi.BWD_PATH_WINOGRAD) if persistent else 0
+        want = 0
         print(f"BWD {case_id(c)} giga_backward_last_path {path} expected {want}")
         assert path == want, (case_id(c), path, want)
     return max(worst)
@@ -207,17 +206,11 @@ def check_form_cases(persistent):
 def _in_child(env):
     code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
             "import test_gpu_backward_envelope as T\n"
-            "w = T.check_form_cases(%r)\n"
-            "print('worst', w)\nprint('ok')\n") % (ROOT, os.path.join(ROOT, "tests"), "GIGA_DGRAD_PERSIST" in env)
+            "w = T.check_form_cases()\n"
+            "print('worst', w)\nprint('ok')\n") % (ROOT, os.path.join(ROOT, "tests"))
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=1500)
     print(r.stdout[-4000:])
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-3000:] + r.stderr[-3000:]
-
-
-def test_fp32_backward_persistent_dgrad_kernel():
-    """GIGA_DGRAD_PERSIST=1: the data-gradient chain in one persistent kernel (its pool stage: bwd_pool_stage) -- at 33 scenes;
-    the 3-scene cases are below its 24-image threshold and run one launch per stage (check_form_cases asserts which form ran)."""
-    _in_child({"GIGA_DGRAD_PERSIST": "1"})
 
 
 def test_fp32_backward_direct_dgrad_convolutions():

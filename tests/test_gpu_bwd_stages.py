@@ -12,12 +12,13 @@ gradient only read them), which L12's own check and conv_final's bias gradient (
 Also checked, with unrounded operands (they run the fp32 MFMA in both steps): the weight and bias gradients of the two
 ConvTranspose layers and conv_final, which the layer-by-layer test of the 3x3 weight gradients does not walk.
 
-Forms: one launch per stage in process (bf16: launch_conv<..., MATH_BF16>; fp32: Winograd F(2x2, 3x3) data gradients);
-GIGA_WINOGRAD_BWD=0 (fp32 direct kernels) and GIGA_DGRAD_PERSIST=1 (unet_dgrad_mega_kernel, bf16 and fp32) in one child
-process each, since both variables are read once per process.  giga_backward_last_path() must report the form every case
-expects.  Shapes (scenes -> images): 3 -> 9 (no multiple of 8: conv_wg_map's plain mapping; below the persistent threshold),
-8 -> 24 (XCD-local mapping; the threshold: one image per group), 9 -> 27 (32 groups for 27 images: groups that return before
-any barrier), 11 -> 33 (one group owns two images).  'he-7' weights, 'uniform' inputs at every size, 'structured' inputs
+Forms: one launch per stage in process (bf16: launch_conv<..., MATH_BF16>; fp32: Winograd F(2x2, 3x3) data gradients), and
+GIGA_WINOGRAD_BWD=0 (fp32 direct kernels) in a child process, since the variable is read once per process.  A second child
+sets every environment switch the library no longer reads to its former non-default value and must run the same forms as a
+process without them.  giga_backward_last_path() must report the form every case expects.  Shapes (scenes -> images): 3 -> 9
+(no multiple of 8: conv_wg_map's plain mapping; the training forward's per-layer launches), 8 -> 24 (XCD-local mapping; the
+forward's persistent launch from here up: one image per group), 9 -> 27 (32 groups for 27 images: groups that return before any
+barrier), 11 -> 33 (one group owns two images).  'he-7' weights, 'uniform' inputs at every size, 'structured' inputs
 (pool ties, large zero regions of the masks) at 3 and 11 scenes; a smooth objective, 64 occupancy queries, one grasp query.
 
 Tolerances (bwd_stage_ref.tol_bf16 / tol_fp32; tests/test_bwd_stage_host.py shows that each rejects every one-stage bug it
@@ -41,11 +42,13 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_GRASP, M_OCC = 1, 64
-P, W, BF = _capi.BWD_PATH_PERSISTENT, _capi.BWD_PATH_WINOGRAD, _capi.BWD_PATH_BF16
+W, BF = _capi.BWD_PATH_WINOGRAD, _capi.BWD_PATH_BF16
 # (scenes, input family) per form
 PER_STAGE = [(3, "uniform"), (8, "uniform"), (9, "uniform"), (11, "uniform"), (3, "structured"), (11, "structured")]
 DIRECT = [(3, "uniform"), (8, "uniform"), (3, "structured")]
-PERSISTENT = [(8, "uniform"), (9, "uniform"), (11, "uniform"), (11, "structured")]
+# the switches of decided experiments, removed with the losing paths: (variable, its former non-default value)
+RETIRED = {"GIGA_DGRAD_PERSIST": "1", "GIGA_BF16_CONVIN": "0", "GIGA_UNET_PERSIST": "0", "GIGA_CONV_XCD": "0", "GIGA_CONV32": "0",
+           "GIGA_LAT_NW": "12"}
 
 
 def run_step(prec, B, ifam):
@@ -142,12 +145,17 @@ def test_backward_stages_one_launch_per_stage(prec, B, ifam):
     _note("per-stage", prec, check_step(prec, B, ifam, BF if prec == "bf16" else W, "per-stage"))
 
 
-def _in_child(env, cases, form):
+def _in_child(env, cases, form, enc_path=None):
+    """check_step for every case in a child process with `env`; enc_path: bits giga_encoder_last_path() must report after
+    the last case (its training forward)."""
     code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
             "import test_gpu_bwd_stages as T\n"
             "for prec, B, ifam, path in %r:\n"
             "    T.check_step(prec, B, ifam, path, %r)\n"
-            "print('ok')\n") % (ROOT, os.path.join(ROOT, "tests"), cases, form)
+            "enc = T._capi.lib().giga_encoder_last_path()\n"
+            "print('ENCODER PATH', enc)\n"
+            "assert %r is None or enc & %r == %r, enc\n"
+            "print('ok')\n") % (ROOT, os.path.join(ROOT, "tests"), cases, form, enc_path, enc_path, enc_path)
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
     print(r.stdout[-12000:])
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-3000:] + r.stderr[-3000:]
@@ -159,8 +167,9 @@ def test_backward_stages_direct_dgrad_convolutions():
     _in_child({"GIGA_WINOGRAD_BWD": "0"}, [("fp32", B, f, 0) for B, f in DIRECT], "direct")
 
 
-def test_backward_stages_persistent_dgrad_kernel():
-    """GIGA_DGRAD_PERSIST=1: unet_dgrad_mega_kernel<MATH_BF16> and <MATH_NATIVE> (pool stages: bwd_pool_stage) at 24, 27 and 33
-    images -- one image per group, groups without an image, one group with two."""
-    _in_child({"GIGA_DGRAD_PERSIST": "1"},
-              [(prec, B, f, P | (BF if prec == "bf16" else 0)) for prec in ("bf16", "fp32") for B, f in PERSISTENT], "persistent")
+def test_retired_switches_are_not_read():
+    """Every removed environment switch at its former non-default value (RETIRED): the 8-scene bf16 step -- 24 images, the size
+    from which one of them moved the data-gradient chain into a persistent launch and another kept the forward on per-layer
+    launches -- runs one launch per stage on bf16 operands (BWD_PATH_BF16 alone) behind a persistent forward, within the
+    per-stage tolerances."""
+    _in_child(RETIRED, [("bf16", 8, "uniform", BF)], "retired-switches", enc_path=_capi.PATH_PERSISTENT)

@@ -556,8 +556,9 @@ def test_flat_adam_matches_torch_adam(wd):
 
 @pytest.mark.parametrize("B", [2, 32])
 def test_bf16_weight_gradient_kernels_with_rounded_operands(sd7, B):
-    """Every bf16 3x3 weight-gradient kernel (csrc/giga_encoder_bwd.hip: conv3_wgrad_bf16_kernel and the tap-per-wave variant
-    conv3_wgrad_bf16_taps_kernel, selected per layer) held to what it is supposed to compute, layer by layer, on the operands the
+    """Every bf16 3x3 weight-gradient kernel that runs (csrc/giga_encoder_bwd.hip: the tap-per-wave conv3_wgrad_bf16_taps_kernel for
+    the layers with at most four 32x32 blocks, the output-split conv3_wgrad_bf16_ns_kernel for the wider ones) held to what it is
+    supposed to compute, layer by layer, on the operands the
     GPU itself used:  dW[co][ci][ky][kx] = sum over images and pixels of bf16(dY[y, x, co]) * bf16(X[y + ky - 1, x + kx - 1, ci])
     with fp32 accumulation, X zero outside the image (encoder/unet.py:14-23: padding 1) -- so a dropped tap at an image border, a
     wrong strip boundary or a stale operand shows as a large relative error of ONE tap, which the 2 % whole-network bound of
