@@ -447,6 +447,21 @@ int giga_planes_unpack(const void* planes_nhwc, float* planes_nchw, int B, int p
     return launch_planes_unpack(planes_nhwc, planes_nchw, B, precision, static_cast<hipStream_t>(stream));
 }
 
+// the head list of a decoder launch: the heads of `head_mask` in order, each with its image in the packed blob and its output.
+// -6: a requested head has no output
+static int dec_args_heads(DecArgs& a, int head_mask, float* const (&outs)[NHEADS], const PackOff& ko, int precision, bool fold) {
+    a.nheads = 0;
+    for (int h = 0; h < NHEADS; ++h) {
+        if (!(head_mask >> h & 1)) continue;
+        if (!outs[h]) return -6;
+        a.head_id[a.nheads] = h;
+        a.head_off[a.nheads] = head_image_offset(ko, h, precision, fold);
+        a.out[a.nheads] = outs[h];
+        ++a.nheads;
+    }
+    return 0;
+}
+
 int giga_decoder_forward_probe(const void* planes_nhwc, const float* p, const void* packed, int head_mask,
                                float* qual, float* rot, float* width, float* occ, int B, int N, int precision,
                                int post, void* stream, void* ev_start, void* ev_stop);
@@ -478,18 +493,10 @@ int giga_decoder_forward_probe(const void* planes_nhwc, const float* p, const vo
         if (ev_stop && hipEventRecord(static_cast<hipEvent_t>(ev_stop), s3) != hipSuccess) return -10;
         return rc3;
     }
-    const PackOff ko = pack_offsets();
     DecArgs a{};
     a.planes = planes_nhwc; a.p = p; a.blob = static_cast<const uint8_t*>(packed);
     float* outs[NHEADS] = {qual, rot, width, occ};
-    for (int h = 0; h < NHEADS; ++h) {
-        if (!(head_mask >> h & 1)) continue;
-        if (!outs[h]) return -6;
-        a.head_id[a.nheads] = h;
-        a.head_off[a.nheads] = head_image_offset(ko, h, precision, fold);
-        a.out[a.nheads] = outs[h];
-        ++a.nheads;
-    }
+    if (const int rc = dec_args_heads(a, head_mask, outs, pack_offsets(), precision, fold)) return rc;
     a.B = B; a.N = N; a.P = (long long)B * N; a.post = post;
     return launch_decoder(a, precision, static_cast<hipStream_t>(stream), ev_start, ev_stop);
 }
@@ -513,21 +520,13 @@ int giga_decoder_forward_lattice(const void* planes_nhwc, const float* lin, cons
     if (!planes_nhwc || !lin || !packed || !workspace) return -1;
     if (workspace_bytes < giga_lattice_workspace_bytes(B, R, precision)) return -4;
     float* outs[NHEADS] = {qual, rot, width, occ};
-    for (int h = 0; h < NHEADS; ++h)
-        if ((head_mask >> h & 1) && !outs[h]) return -6;      // before anything is enqueued
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = launch_lattice_resample(planes_nhwc, lin, workspace, B, R, precision, s, planes32);
-    if (rc) return rc;
-    const PackOff ko = pack_offsets();
     DecArgs a{};
+    int rc = dec_args_heads(a, head_mask, outs, pack_offsets(), precision, fold);      // (-6 before anything is enqueued)
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = launch_lattice_resample(planes_nhwc, lin, workspace, B, R, precision, s, planes32);
+    if (rc) return rc;
     a.planes = workspace; a.p = nullptr; a.blob = static_cast<const uint8_t*>(packed);
-    for (int h = 0; h < NHEADS; ++h) {
-        if (!(head_mask >> h & 1)) continue;
-        a.head_id[a.nheads] = h;
-        a.head_off[a.nheads] = head_image_offset(ko, h, precision, fold);
-        a.out[a.nheads] = outs[h];
-        ++a.nheads;
-    }
     a.B = B; a.N = R * R * R; a.P = (long long)B * a.N; a.post = post; a.lin = lin; a.R = R;
     return launch_decoder(a, precision, s, ev_start, ev_stop);
 }

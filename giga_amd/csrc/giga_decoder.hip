@@ -16,7 +16,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "giga_dev.h"
+#include "giga_dec_common.h"
 #include "giga_args.h"
 
 namespace giga {
@@ -50,14 +50,6 @@ __device__ __forceinline__ void store_head(const DecArgs& a, int h, long long g,
 // barrier per step; it is both "image s has landed" and "everyone left image s-1".
 constexpr int DEC16_CHUNKS = (int)(DEC16_BYTES / FRAG);      // 59
 
-template <int NW, int CHUNKS = DEC16_CHUNKS>
-__device__ __forceinline__ void dma_head_image(const uint8_t* src, uint8_t* lds_dst, int wave, int lane) {
-    for (int c = wave; c < CHUNKS; c += NW)
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)(src + (size_t)c * FRAG + lane * 16),
-            (__attribute__((address_space(3))) void*)(lds_dst + c * FRAG), 16, 0, 0);
-}
-
 template <int T, bool LATTICE, int NW>
 __global__ __launch_bounds__(NW * 64) void decoder_f16_kernel(DecArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -85,7 +77,7 @@ __global__ __launch_bounds__(NW * 64) void decoder_f16_kernel(DecArgs a) {
     const int max_phase = a.nheads > 1 ? ((NW / 4 - 1) < (a.nheads - 1) ? (NW / 4 - 1) : (a.nheads - 1)) : 0;
     const int nsteps = work_steps + max_phase;
 
-    dma_head_image<NW>(a.blob + a.head_off[0], smem, wave, lane);
+    lds_dma_frags<NW, DEC16_CHUNKS>(a.blob + a.head_off[0], smem, wave, lane);
 
     half8 cf[T][6], ax[T];
     long long gidx[T];
@@ -111,7 +103,7 @@ __global__ __launch_bounds__(NW * 64) void decoder_f16_kernel(DecArgs a) {
         // ragged last round) only keeps the image pipeline going
         const long long tile0 = tile_lo + ((long long)(ls / a.nheads) * NW + wave) * T;
         if (ls < 0 || ls >= work_steps || tile0 >= tile_hi) {
-            if (dma_next) dma_head_image<NW>(dma_src, dma_dst, wave, lane);
+            if (dma_next) lds_dma_frags<NW, DEC16_CHUNKS>(dma_src, dma_dst, wave, lane);
             continue;
         }
         const bool new_round = ls % a.nheads == 0;
@@ -131,14 +123,7 @@ __global__ __launch_bounds__(NW * 64) void decoder_f16_kernel(DecArgs a) {
                 const int ix = div_magic(r, a.mR2), rz = r - ix * R2;
                 const int iy = div_magic(rz, a.mR), iz = rz - iy * R;
                 const float px = a.lin[ix], py = a.lin[iy], pz = a.lin[iz];
-                half_t xh = (half_t)px, yh = (half_t)py, zh = (half_t)pz;
-                half8 av = {xh, yh, zh, (half_t)0, (half_t)0, (half_t)0, (half_t)0, (half_t)0};
-                if (hi == 0) {
-                    av[3] = (half_t)1.0f;
-                    av[4] = (half_t)(px - (float)xh); av[5] = (half_t)(py - (float)yh);
-                    av[6] = (half_t)(pz - (float)zh); av[7] = (half_t)1.0f;
-                }
-                ax[t] = av;
+                ax[t] = aux_half8(px, py, pz, hi);
                 const half_t* base = planes + (size_t)b * R2 * CD + 8 * hi;
                 const int off[3] = {iz * R + ix, iy * R + ix, iz * R + iy};   // (H,W): xz->(z,x) xy->(y,x) yz->(z,y)
 #pragma unroll
@@ -172,15 +157,7 @@ __global__ __launch_bounds__(NW * 64) void decoder_f16_kernel(DecArgs a) {
                 int b, rdummy;
                 split_scene(gidx[t], a.N, a.invN, b, rdummy);
                 const float nx = norm_coord(px), ny = norm_coord(py), nz = norm_coord(pz);
-                // aux chunk: [p_hi(3), 1, p_lo(3), 1] on hi=0 lanes, [p_hi(3), 0...] on hi=1 lanes
-                half_t xh = (half_t)px, yh = (half_t)py, zh = (half_t)pz;
-                half8 av = {xh, yh, zh, (half_t)0, (half_t)0, (half_t)0, (half_t)0, (half_t)0};
-                if (hi == 0) {
-                    av[3] = (half_t)1.0f;
-                    av[4] = (half_t)(px - (float)xh); av[5] = (half_t)(py - (float)yh);
-                    av[6] = (half_t)(pz - (float)zh); av[7] = (half_t)1.0f;
-                }
-                ax[t] = av;
+                ax[t] = aux_half8(px, py, pz, hi);
                 // xz: (u,v)=(x,z)  xy: (x,y)  yz: (y,z)      common.py:246-251
                 bl[t][0] = bilin_setup(nx, nz);
                 bl[t][1] = bilin_setup(nx, ny);
@@ -217,7 +194,7 @@ __global__ __launch_bounds__(NW * 64) void decoder_f16_kernel(DecArgs a) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (dma_next) dma_head_image<NW>(dma_src, dma_dst, wave, lane);
+        if (dma_next) lds_dma_frags<NW, DEC16_CHUNKS>(dma_src, dma_dst, wave, lane);
         // ---------------- MFMA chain of head h out of buffer s&1 --------------------------------------
         {
             const half8* W = reinterpret_cast<const half8*>(buf);
@@ -340,7 +317,7 @@ __global__ __launch_bounds__(NW * 64) void decoder_f16s_kernel(DecArgs a) {
         slot = xcd * spx + k / a.nheads;
     }
     DEC_T(0);
-    dma_head_image<NW, NCH>(a.blob + a.head_off[hsel], smem, wave, lane);
+    lds_dma_frags<NW, NCH>(a.blob + a.head_off[hsel], smem, wave, lane);
     DEC_T(1);
 
     const long long tiles_total = (a.P + 31) / 32;
@@ -399,16 +376,7 @@ __global__ __launch_bounds__(NW * 64) void decoder_f16s_kernel(DecArgs a) {
             }
 #pragma unroll
             for (int t = 0; t < T; ++t) {
-                // aux chunk: [p_hi(3), 1, p_lo(3), 1] on hi=0 lanes, [p_hi(3), 0...] on hi=1 lanes (exact by itself)
-                const float px = pxs[t], py = pys[t], pz = pzs[t];
-                half_t xh = (half_t)px, yh = (half_t)py, zh = (half_t)pz;
-                half8 av = {xh, yh, zh, (half_t)0, (half_t)0, (half_t)0, (half_t)0, (half_t)0};
-                if (hi == 0) {
-                    av[3] = (half_t)1.0f;
-                    av[4] = (half_t)(px - (float)xh); av[5] = (half_t)(py - (float)yh);
-                    av[6] = (half_t)(pz - (float)zh); av[7] = (half_t)1.0f;
-                }
-                ax[t] = av;
+                ax[t] = aux_half8(pxs[t], pys[t], pzs[t], hi);
             }
             if constexpr (!LATTICE) {
                 // ---------------- generic gather: per (tile, plane, channel half) the lane's 8 channels of the 4 bilinear
@@ -766,7 +734,7 @@ __global__ __launch_bounds__(NW * 64) void decoder_lat_kernel(DecArgs a) {
                 const half_t h = (half_t)acc[r];
                 const half_t l = (half_t)((acc[r] - (float)h) * LAT_LO_SCALE);
                 const half2v pr = {h, l};
-                *reinterpret_cast<half2v*>(g + (8 * (r >> 2) + 4 * hi + (r & 3)) * 16) = pr;
+                *reinterpret_cast<half2v*>(g + drow(r, hi) * 16) = pr;
             }
         }
     };
@@ -931,7 +899,7 @@ __global__ __launch_bounds__(256, 2) void decoder_f32_kernel(DecArgs a) {
     // across point batches while the head does not change (single-head launches: the occupancy path).
     int loaded = -1;
     if ((int)blockIdx.x < a.nbatch && h_begin < h_end) {
-        dma_head_image<4, (int)(DEC32_BYTES / FRAG)>(a.blob + a.head_off[h_begin], smem, wave, lane);
+        lds_dma_frags<4, (int)(DEC32_BYTES / FRAG)>(a.blob + a.head_off[h_begin], smem, wave, lane);
         loaded = h_begin;
     }
     bool fresh = true;                                        // the resident image has not been waited for yet
@@ -971,57 +939,19 @@ __global__ __launch_bounds__(256, 2) void decoder_f32_kernel(DecArgs a) {
                     }
                 }
             } else {
-            // ---------------- generic gather, line-friendly.  A load instruction in which every lane fetches 16 B of
-            // its OWN point touches 64 different cache lines; the gather of a 256-point batch then took a third of the
-            // kernel (the CU's texture path handles a few lines per clock).  Here four adjacent lanes fetch the four
-            // 16-B quads of one (point, channel half), i.e. one whole 64-B line per four lanes, interpolate them, and
-            // the tile is transposed to the operand layout (lane = point) through a wave-private LDS stage.
+            // ---------------- generic gather, line-friendly (gather_staged48), through a wave-private stage behind the image
             const float pxo = a.p[3 * g + 0], pyo = a.p[3 * g + 1], pzo = a.p[3 * g + 2];
             ax0[t] = hi ? pyo : pxo;     // aux MFMA 0: slots (px, py)
             ax1[t] = hi ? 1.0f : pzo;    // aux MFMA 1: slots (pz, 1)
             float* S = reinterpret_cast<float*>(smem + DEC32_BYTES) + wave * (32 * 96);      // [point][96]
             const long long tile0 = ((long long)batch * 4 * T + wave * T + t) * 32;
-#pragma unroll
-            for (int part = 0; part < 4; ++part) {
-                const int pair = part * 16 + (lane >> 2), pt = pair >> 1, hf = pair & 1, qd = lane & 3;
-                long long gp = tile0 + pt;
-                if (gp >= a.P) gp = a.P - 1;
-                int bp, rp;
-                split_scene(gp, a.N, a.invN, bp, rp);
-                const float nx = norm_coord(a.p[3 * gp + 0]), ny = norm_coord(a.p[3 * gp + 1]), nz = norm_coord(a.p[3 * gp + 2]);
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) {
-                    // xz: (u,v)=(x,z)  xy: (x,y)  yz: (y,z)      common.py:246-251
-                    const Bilin bl = bilin_setup(pl == 2 ? ny : nx, pl == 1 ? ny : nz);
-                    const float* base = planes + pl * plane_stride + (size_t)bp * RES * RES * CD + 16 * hf + 4 * qd;
-                    const float4 v00 = *reinterpret_cast<const float4*>(base + (size_t)bl.o00 * CD);
-                    const float4 v01 = *reinterpret_cast<const float4*>(base + (size_t)bl.o01 * CD);
-                    const float4 v10 = *reinterpret_cast<const float4*>(base + (size_t)bl.o10 * CD);
-                    const float4 v11 = *reinterpret_cast<const float4*>(base + (size_t)bl.o11 * CD);
-                    // same order as aten's grid_sampler: nw, ne, sw, se
-                    float4 o;
-                    o.x = fmaf(v11.x, bl.w11, fmaf(v10.x, bl.w10, fmaf(v01.x, bl.w01, v00.x * bl.w00)));
-                    o.y = fmaf(v11.y, bl.w11, fmaf(v10.y, bl.w10, fmaf(v01.y, bl.w01, v00.y * bl.w00)));
-                    o.z = fmaf(v11.z, bl.w11, fmaf(v10.z, bl.w10, fmaf(v01.z, bl.w01, v00.z * bl.w00)));
-                    o.w = fmaf(v11.w, bl.w11, fmaf(v10.w, bl.w10, fmaf(v01.w, bl.w01, v00.w * bl.w00)));
-                    *reinterpret_cast<float4*>(S + pt * 96 + pl * 32 + 16 * hf + 4 * qd) = o;
-                }
-            }
-            // wave-private stage: DS operations of one wave execute in order, no barrier needed
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 v = *reinterpret_cast<const float4*>(S + n * 96 + pl * 32 + 16 * hi + 4 * q);
-                    cf[t][16 * pl + 4 * q + 0] = v.x; cf[t][16 * pl + 4 * q + 1] = v.y;
-                    cf[t][16 * pl + 4 * q + 2] = v.z; cf[t][16 * pl + 4 * q + 3] = v.w;
-                }
+            gather_staged48(S, planes, plane_stride, a.p, tile0, a.P, a.N, a.invN, lane, cf[t]);
             }
         }
         for (int h = h_begin; h < h_end; ++h) {
             if (loaded != h) {
                 __syncthreads();                              // everyone left the previous weight image
-                dma_head_image<4, (int)(DEC32_BYTES / FRAG)>(a.blob + a.head_off[h], smem, wave, lane);
+                lds_dma_frags<4, (int)(DEC32_BYTES / FRAG)>(a.blob + a.head_off[h], smem, wave, lane);
                 loaded = h;
                 fresh = true;
             }
@@ -1083,12 +1013,7 @@ __global__ __launch_bounds__(256, 2) void decoder_f32_kernel(DecArgs a) {
                 }
             };
             auto bias_rows = [&](int row, f32x16 (&c)[T]) {     // 32 biases of a layer as an accumulator image, the same for every tile
-                f32x16 c0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 v = *reinterpret_cast<const float4*>(ctab + row * 32 + 8 * q + 4 * hi);
-                    c0[4 * q + 0] = v.x; c0[4 * q + 1] = v.y; c0[4 * q + 2] = v.z; c0[4 * q + 3] = v.w;
-                }
+                const f32x16 c0 = ctab_row(ctab, row, hi);
 #pragma unroll
                 for (int t = 0; t < T; ++t) c[t] = c0;
             };
@@ -1186,40 +1111,7 @@ __global__ __launch_bounds__(256) void decoder_f32_tile_kernel(DecArgs a) {
     float cf[48];
     const float ax0 = hi ? a.p[3 * g + 1] : a.p[3 * g + 0];     // aux MFMA 0: slots (px, py)
     const float ax1 = hi ? 1.0f : a.p[3 * g + 2];               // aux MFMA 1: slots (pz, 1)
-    {
-        float* S = reinterpret_cast<float*>(smem) + wave * (32 * 96);      // [point][96]
-#pragma unroll
-        for (int part = 0; part < 4; ++part) {
-            const int pair = part * 16 + (lane >> 2), pt = pair >> 1, hf = pair & 1, qd = lane & 3;
-            long long gp = tile0 + pt;
-            if (gp >= a.P) gp = a.P - 1;
-            int bp, rp;
-            split_scene(gp, a.N, a.invN, bp, rp);
-            const float nx = norm_coord(a.p[3 * gp + 0]), ny = norm_coord(a.p[3 * gp + 1]), nz = norm_coord(a.p[3 * gp + 2]);
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
-                const Bilin bl = bilin_setup(pl == 2 ? ny : nx, pl == 1 ? ny : nz);
-                const float* base = planes + pl * plane_stride + (size_t)bp * RES * RES * CD + 16 * hf + 4 * qd;
-                const float4 v00 = *reinterpret_cast<const float4*>(base + (size_t)bl.o00 * CD);
-                const float4 v01 = *reinterpret_cast<const float4*>(base + (size_t)bl.o01 * CD);
-                const float4 v10 = *reinterpret_cast<const float4*>(base + (size_t)bl.o10 * CD);
-                const float4 v11 = *reinterpret_cast<const float4*>(base + (size_t)bl.o11 * CD);
-                float4 o;
-                o.x = fmaf(v11.x, bl.w11, fmaf(v10.x, bl.w10, fmaf(v01.x, bl.w01, v00.x * bl.w00)));
-                o.y = fmaf(v11.y, bl.w11, fmaf(v10.y, bl.w10, fmaf(v01.y, bl.w01, v00.y * bl.w00)));
-                o.z = fmaf(v11.z, bl.w11, fmaf(v10.z, bl.w10, fmaf(v01.z, bl.w01, v00.z * bl.w00)));
-                o.w = fmaf(v11.w, bl.w11, fmaf(v10.w, bl.w10, fmaf(v01.w, bl.w01, v00.w * bl.w00)));
-                *reinterpret_cast<float4*>(S + pt * 96 + pl * 32 + 16 * hf + 4 * qd) = o;
-            }
-        }
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 v = *reinterpret_cast<const float4*>(S + n * 96 + pl * 32 + 16 * hi + 4 * q);
-                cf[16 * pl + 4 * q + 0] = v.x; cf[16 * pl + 4 * q + 1] = v.y; cf[16 * pl + 4 * q + 2] = v.z; cf[16 * pl + 4 * q + 3] = v.w;
-            }
-    }
+    gather_staged48(reinterpret_cast<float*>(smem) + wave * (32 * 96), planes, plane_stride, a.p, tile0, a.P, a.N, a.invN, lane, cf);
     const float one0 = hi ? 0.0f : 1.0f;                        // aux MFMA 2: slots (1, 0)
     auto fc_block = [&](const float4 (&A)[13]) {                // FC_b: 12 feature fragments + the aux fragment, from zero
         f32x16 acc;
@@ -1262,12 +1154,7 @@ __global__ __launch_bounds__(256) void decoder_f32_tile_kernel(DecArgs a) {
                     net[4 * q] += v.x; net[4 * q + 1] += v.y; net[4 * q + 2] += v.z; net[4 * q + 3] += v.w;
                 }
             }
-            f32x16 hh;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 v = *reinterpret_cast<const float4*>(ctab_l + blk * 32 + 8 * q + 4 * hi);
-                hh[4 * q + 0] = v.x; hh[4 * q + 1] = v.y; hh[4 * q + 2] = v.z; hh[4 * q + 3] = v.w;
-            }
+            f32x16 hh = ctab_row(ctab_l, blk, hi);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float4 A = CW[(blk * 8 + q) * 64 + lane];
@@ -1295,12 +1182,7 @@ __global__ __launch_bounds__(256) void decoder_f32_tile_kernel(DecArgs a) {
     if (wave == 0) {
         chain_block(NBLK - 1);
         net = mfma32(CW[40 * 64 + lane].y, ax1, net);           // + b1 of block 4 (slot "1.0")
-        f32x16 o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 v = *reinterpret_cast<const float4*>(ctab_l + NBLK * 32 + 8 * q + 4 * hi);
-            o[4 * q + 0] = v.x; o[4 * q + 1] = v.y; o[4 * q + 2] = v.z; o[4 * q + 3] = v.w;
-        }
+        f32x16 o = ctab_row(ctab_l, NBLK, hi);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float4 A = CW[(41 + q) * 64 + lane];
@@ -1384,17 +1266,7 @@ __global__ __launch_bounds__(256) void decoder_f32_point_kernel(DecArgs a) {
         // xz: (u,v)=(x,z)  xy: (x,y)  yz: (y,z)      common.py:246-251
         const Bilin bl = bilin_setup(pl == 2 ? ny : nx, pl == 1 ? ny : nz);
         const float* base = planes + pl * plane_stride + (size_t)b * RES * RES * CD + 4 * qd;
-        const float4 v00 = *reinterpret_cast<const float4*>(base + (size_t)bl.o00 * CD);
-        const float4 v01 = *reinterpret_cast<const float4*>(base + (size_t)bl.o01 * CD);
-        const float4 v10 = *reinterpret_cast<const float4*>(base + (size_t)bl.o10 * CD);
-        const float4 v11 = *reinterpret_cast<const float4*>(base + (size_t)bl.o11 * CD);
-        // same order as aten's grid_sampler: nw, ne, sw, se
-        float4 o;
-        o.x = fmaf(v11.x, bl.w11, fmaf(v10.x, bl.w10, fmaf(v01.x, bl.w01, v00.x * bl.w00)));
-        o.y = fmaf(v11.y, bl.w11, fmaf(v10.y, bl.w10, fmaf(v01.y, bl.w01, v00.y * bl.w00)));
-        o.z = fmaf(v11.z, bl.w11, fmaf(v10.z, bl.w10, fmaf(v01.z, bl.w01, v00.z * bl.w00)));
-        o.w = fmaf(v11.w, bl.w11, fmaf(v10.w, bl.w10, fmaf(v01.w, bl.w01, v00.w * bl.w00)));
-        *reinterpret_cast<float4*>(FEAT + pl * 32 + 4 * qd) = o;
+        *reinterpret_cast<float4*>(FEAT + pl * 32 + 4 * qd) = bilerp(base, bl);
     }
     __builtin_amdgcn_wave_barrier();                           // wave-private stage: DS operations of one wave execute in order
     float cf[48];
@@ -1558,14 +1430,8 @@ __global__ void lattice_resample_split_kernel(const float* __restrict__ planes, 
     float v[8];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        const float4 v00 = *reinterpret_cast<const float4*>(src + (size_t)bl.o00 * CD + 4 * q);
-        const float4 v01 = *reinterpret_cast<const float4*>(src + (size_t)bl.o01 * CD + 4 * q);
-        const float4 v10 = *reinterpret_cast<const float4*>(src + (size_t)bl.o10 * CD + 4 * q);
-        const float4 v11 = *reinterpret_cast<const float4*>(src + (size_t)bl.o11 * CD + 4 * q);
-        v[4 * q + 0] = fmaf(v11.x, bl.w11, fmaf(v10.x, bl.w10, fmaf(v01.x, bl.w01, v00.x * bl.w00)));
-        v[4 * q + 1] = fmaf(v11.y, bl.w11, fmaf(v10.y, bl.w10, fmaf(v01.y, bl.w01, v00.y * bl.w00)));
-        v[4 * q + 2] = fmaf(v11.z, bl.w11, fmaf(v10.z, bl.w10, fmaf(v01.z, bl.w01, v00.z * bl.w00)));
-        v[4 * q + 3] = fmaf(v11.w, bl.w11, fmaf(v10.w, bl.w10, fmaf(v01.w, bl.w01, v00.w * bl.w00)));
+        const float4 o = bilerp(src, bl, 4 * q);
+        v[4 * q + 0] = o.x; v[4 * q + 1] = o.y; v[4 * q + 2] = o.z; v[4 * q + 3] = o.w;
     }
     half8 h, l;
     split8(v, h, l);

@@ -7,7 +7,8 @@
 //      every block (net_i') and every hidden activation (h_i) in registers;
 //   2. swap the LDS image to the TRANSPOSED matrices (backward blob) and run the gradient chain
 //         G = DN[i+1];  DH[i] = (W1_i^T G) * (h_i > 0);  DN[i] = G + (W0_i^T DH[i]) * (net_i' > 0);  dc += Wc_i^T DN[i]
-//      in the same transposed layout (lane = point, registers = features), so again no cross-lane traffic;
+//      in the same transposed layout (lane = point, registers = features), so again no cross-lane traffic
+//      (1 and 2 are giga_dec_common.h's dec32_recompute / dec32_dn5 / dec32_grad_chain, shared with decoder_pgrad_kernel);
 //   3. write the (dY, X) pairs of every linear layer to HBM as [point][32] rows and scatter dc into the
 //      plane gradients with the bilinear weights (fp32 atomics, like aten's grid_sampler backward; transposed
 //      through LDS so that an atomic instruction touches 128-byte runs of channels).
@@ -15,7 +16,7 @@
 // (MFMA 32x32x2 over pairs of points, operands straight from HBM, one atomic per gradient element per block).
 #include "giga_args.h"
 #include "giga_side.h"
-#include "giga_dev.h"
+#include "giga_dec_common.h"
 
 namespace giga {
 
@@ -45,13 +46,6 @@ struct DecBwdArgs {
     int heads_per_wg;           // heads handled by one workgroup (blockIdx.y selects the group): 1 when the point batches cannot fill the chip
 };
 
-template <int CHUNKS>
-__device__ __forceinline__ void dma_image4(const uint8_t* src, uint8_t* lds_dst, int wave, int lane) {
-    for (int c = wave; c < CHUNKS; c += 4)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)c * FRAG + lane * 16),
-                                         (__attribute__((address_space(3))) void*)(lds_dst + c * FRAG), 16, 0, 0);
-}
-
 // write a D-layout register image (lane = point n, registers = features drow(r,hi)) as row `g` of a [P][32] array
 __device__ __forceinline__ void store_rows(float* arr, long long g, int hi, const f32x16& v, bool ok) {
     if (!ok) return;
@@ -60,6 +54,13 @@ __device__ __forceinline__ void store_rows(float* arr, long long g, int hi, cons
         *reinterpret_cast<float4*>(arr + g * 32 + 8 * q + 4 * hi) =
             make_float4(v[4 * q + 0], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
 }
+
+// the chain's tap: tensor `slot` of the head's scratch arrays (DB_NARR above), this lane's row
+struct RowTap {
+    static constexpr bool active = true;
+    float* S; size_t AS; long long g; int hi; bool valid;
+    __device__ __forceinline__ void operator()(int slot, const f32x16& v) const { store_rows(S + slot * AS, g, hi, v, valid); }
+};
 
 __global__ __launch_bounds__(256, 1) void decoder_bwd_kernel(DecBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -83,21 +84,7 @@ __global__ __launch_bounds__(256, 1) void decoder_bwd_kernel(DecBwdArgs a) {
         Bilin bl[3];
         bl[0] = bilin_setup(nx, nz); bl[1] = bilin_setup(nx, ny); bl[2] = bilin_setup(ny, nz);
         float cf[48];
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-            const float* base = a.planes + pl * plane_stride + (size_t)b * RES * RES * CD + 16 * hi;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 v00 = *reinterpret_cast<const float4*>(base + (size_t)bl[pl].o00 * CD + 4 * q);
-                const float4 v01 = *reinterpret_cast<const float4*>(base + (size_t)bl[pl].o01 * CD + 4 * q);
-                const float4 v10 = *reinterpret_cast<const float4*>(base + (size_t)bl[pl].o10 * CD + 4 * q);
-                const float4 v11 = *reinterpret_cast<const float4*>(base + (size_t)bl[pl].o11 * CD + 4 * q);
-                cf[16 * pl + 4 * q + 0] = fmaf(v11.x, bl[pl].w11, fmaf(v10.x, bl[pl].w10, fmaf(v01.x, bl[pl].w01, v00.x * bl[pl].w00)));
-                cf[16 * pl + 4 * q + 1] = fmaf(v11.y, bl[pl].w11, fmaf(v10.y, bl[pl].w10, fmaf(v01.y, bl[pl].w01, v00.y * bl[pl].w00)));
-                cf[16 * pl + 4 * q + 2] = fmaf(v11.z, bl[pl].w11, fmaf(v10.z, bl[pl].w10, fmaf(v01.z, bl[pl].w01, v00.z * bl[pl].w00)));
-                cf[16 * pl + 4 * q + 3] = fmaf(v11.w, bl[pl].w11, fmaf(v10.w, bl[pl].w10, fmaf(v01.w, bl[pl].w01, v00.w * bl[pl].w00)));
-            }
-        }
+        gather_direct48(a.planes, plane_stride, b, bl, hi, cf);
         // X of fc_c / fc_p: rows of C [P][96] (feature pl*32 + 16*hi + s) and PP [P][32]
         if (valid) {
 #pragma unroll
@@ -129,76 +116,16 @@ __global__ __launch_bounds__(256, 1) void decoder_bwd_kernel(DecBwdArgs a) {
             const size_t AS = (size_t)a.P * 32;                     // array stride
             // ================= 1. forward recompute (fragment order of giga_pack.cpp::pack_head32) ==========
             __syncthreads();
-            dma_image4<(int)(DEC32_BYTES / FRAG)>(a.blob + a.head_off[h], smem, wave, lane);
+            lds_dma_frags<4, (int)(DEC32_BYTES / FRAG)>(a.blob + a.head_off[h], smem, wave, lane);
             __builtin_amdgcn_s_waitcnt(0x0F70);
             __syncthreads();
             const float* ctab = reinterpret_cast<const float*>(smem + (size_t)DEC32_FRAGS * FRAG);
             // the backward chain needs only the SIGNS of the pre-activations: 16 bits per lane and tensor instead of 16
-            // registers; the activations themselves (X of the weight-gradient GEMMs) leave as soon as they exist
+            // registers; the activations themselves (X of the weight-gradient GEMMs) leave through the tap as soon as they exist
+            const RowTap tap{S, AS, g, hi, valid};
             unsigned mnet[NBLK + 1], mhid[NBLK];
             f32x16 net;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) net[r] = 0.f;
-            int k = 0;
-#pragma unroll
-            for (int blk = 0; blk < NBLK; ++blk) {
-#pragma unroll
-                for (int q = 0; q < 12; ++q) {
-                    const float4 A = W[(k++) * 64 + lane];
-                    net = mfma32(A.x, cf[4 * q + 0], net); net = mfma32(A.y, cf[4 * q + 1], net);
-                    net = mfma32(A.z, cf[4 * q + 2], net); net = mfma32(A.w, cf[4 * q + 3], net);
-                }
-                {
-                    const float4 A = W[(k++) * 64 + lane];
-                    net = mfma32(A.x, ax0, net); net = mfma32(A.y, ax1, net); net = mfma32(A.z, ax2, net);
-                }
-                {
-                    f32x16 t;
-                    unsigned m = 0;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { t[r] = relu_ieee(net[r]); m |= (net[r] > 0.f ? 1u : 0u) << r; }
-                    mnet[blk] = m;
-                    store_rows(S + (11 + blk) * AS, g, hi, t, valid);          // XN[blk]
-                }
-                f32x16 hcur;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 v = *reinterpret_cast<const float4*>(ctab + blk * 32 + 8 * q + 4 * hi);
-                    hcur[4 * q + 0] = v.x; hcur[4 * q + 1] = v.y; hcur[4 * q + 2] = v.z; hcur[4 * q + 3] = v.w;
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 A = W[(k++) * 64 + lane];
-                    hcur = mfma32(A.x, relu_ieee(net[4 * q + 0]), hcur); hcur = mfma32(A.y, relu_ieee(net[4 * q + 1]), hcur);
-                    hcur = mfma32(A.z, relu_ieee(net[4 * q + 2]), hcur); hcur = mfma32(A.w, relu_ieee(net[4 * q + 3]), hcur);
-                }
-                {
-                    f32x16 t;
-                    unsigned m = 0;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { t[r] = relu_ieee(hcur[r]); m |= (hcur[r] > 0.f ? 1u : 0u) << r; }
-                    mhid[blk] = m;
-                    store_rows(S + (16 + blk) * AS, g, hi, t, valid);          // XH[blk]
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 A = W[(k++) * 64 + lane];
-                    net = mfma32(A.x, relu_ieee(hcur[4 * q + 0]), net); net = mfma32(A.y, relu_ieee(hcur[4 * q + 1]), net);
-                    net = mfma32(A.z, relu_ieee(hcur[4 * q + 2]), net); net = mfma32(A.w, relu_ieee(hcur[4 * q + 3]), net);
-                }
-            }
-            {   // + fc_1 bias of the last block -> net5
-                const float4 A = W[(k++) * 64 + lane];
-                net = mfma32(A.y, ax1, net);
-            }
-            {   // XO = relu(net5) and its sign mask
-                f32x16 t;
-                unsigned m = 0;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { t[r] = relu_ieee(net[r]); m |= (net[r] > 0.f ? 1u : 0u) << r; }
-                mnet[NBLK] = m;
-                store_rows(S + 21 * AS, g, hi, t, valid);
-            }
+            dec32_recompute(W, ctab, lane, hi, cf, ax0, ax1, ax2, mnet, mhid, net, tap);
             // ================= 2. epilogue backward: dO (<= 4 values, identical in both lane halves) ============
             const int id = a.head_id[h];
             float dO[4] = {0.f, 0.f, 0.f, 0.f};
@@ -215,7 +142,7 @@ __global__ __launch_bounds__(256, 1) void decoder_bwd_kernel(DecBwdArgs a) {
             }
             // ================= 3. swap to the transposed image ====================================================
             __syncthreads();
-            dma_image4<(int)(DECB_BYTES / FRAG)>(a.bwd_blob + a.bwd_off[h], smem, wave, lane);
+            lds_dma_frags<4, (int)(DECB_BYTES / FRAG)>(a.bwd_blob + a.bwd_off[h], smem, wave, lane);
             __builtin_amdgcn_s_waitcnt(0x0F70);
             __syncthreads();
             const float* wout = reinterpret_cast<const float*>(smem + (size_t)DECB_FRAGS * FRAG);   // [4][32]
@@ -227,7 +154,7 @@ __global__ __launch_bounds__(256, 1) void decoder_bwd_kernel(DecBwdArgs a) {
                 for (int o = 0; o < 4; ++o) {
                     float s = 0.f;
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) s = fmaf(wout[o * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi], relu_ieee(net[r]), s);
+                    for (int r = 0; r < 16; ++r) s = fmaf(wout[o * 32 + drow(r, hi)], relu_ieee(net[r]), s);
                     s += __shfl_xor(s, 32);
                     z[o] = s;
                 }
@@ -240,7 +167,7 @@ __global__ __launch_bounds__(256, 1) void decoder_bwd_kernel(DecBwdArgs a) {
 #pragma unroll
                 for (int o = 0; o < 4; ++o) { z[o] += fb[o]; nrm2 = fmaf(z[o], z[o], nrm2); }
                 const float inv = 1.0f / fmaxf(sqrtf(nrm2), 1e-12f);
-                const float rd = r4.x * dO[0] + r4.y * dO[1] + r4.z * dO[2] + r4.w * dO[3];
+                const float rd = dot4_rn(r4.x, dO[0], r4.y, dO[1], r4.z, dO[2], r4.w, dO[3]);
                 dO[0] = (dO[0] - r4.x * rd) * inv; dO[1] = (dO[1] - r4.y * rd) * inv;
                 dO[2] = (dO[2] - r4.z * rd) * inv; dO[3] = (dO[3] - r4.w * rd) * inv;
             }
@@ -250,52 +177,10 @@ __global__ __launch_bounds__(256, 1) void decoder_bwd_kernel(DecBwdArgs a) {
 #pragma unroll
                 for (int q = 1; q < 8; ++q) *reinterpret_cast<float4*>(dr + 4 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
             }
-            // DN[5] = (Wout^T dO) * (net5 > 0)
-            f32x16 G;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int f = (r & 3) + 8 * (r >> 2) + 4 * hi;
-                const float v = wout[f] * dO[0] + wout[32 + f] * dO[1] + wout[64 + f] * dO[2] + wout[96 + f] * dO[3];
-                G[r] = (mnet[NBLK] >> r & 1u) ? v : 0.f;
-            }
-            store_rows(S + 5 * AS, g, hi, G, valid);
-            // ================= 4. gradient chain (fragments: block b -> Wc^T 20b..20b+11, W0^T +12..15, W1^T +16..19) ====
-#pragma unroll
-            for (int blk = NBLK - 1; blk >= 0; --blk) {
-                const int kb = 20 * blk;
-                f32x16 dh;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) dh[r] = 0.f;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {                       // W1^T G
-                    const float4 A = W[(kb + 16 + q) * 64 + lane];
-                    dh = mfma32(A.x, G[4 * q + 0], dh); dh = mfma32(A.y, G[4 * q + 1], dh);
-                    dh = mfma32(A.z, G[4 * q + 2], dh); dh = mfma32(A.w, G[4 * q + 3], dh);
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) dh[r] = (mhid[blk] >> r & 1u) ? dh[r] : 0.f;
-                store_rows(S + (6 + blk) * AS, g, hi, dh, valid);
-                f32x16 dn;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) dn[r] = 0.f;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {                       // W0^T DH
-                    const float4 A = W[(kb + 12 + q) * 64 + lane];
-                    dn = mfma32(A.x, dh[4 * q + 0], dn); dn = mfma32(A.y, dh[4 * q + 1], dn);
-                    dn = mfma32(A.z, dh[4 * q + 2], dn); dn = mfma32(A.w, dh[4 * q + 3], dn);
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) G[r] += (mnet[blk] >> r & 1u) ? dn[r] : 0.f;     // DN[blk]
-                store_rows(S + blk * AS, g, hi, G, valid);
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl)                      // dc += Wc^T DN[blk]
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float4 A = W[(kb + 4 * pl + q) * 64 + lane];
-                        dc[pl] = mfma32(A.x, G[4 * q + 0], dc[pl]); dc[pl] = mfma32(A.y, G[4 * q + 1], dc[pl]);
-                        dc[pl] = mfma32(A.z, G[4 * q + 2], dc[pl]); dc[pl] = mfma32(A.w, G[4 * q + 3], dc[pl]);
-                    }
-            }
+            f32x16 G = dec32_dn5<true>(wout, dO, mnet[NBLK], hi);
+            tap(5, G);
+            // ================= 4. gradient chain ================================================================
+            dec32_grad_chain(W, lane, G, mnet, mhid, dc, tap);
         }
         // ---------------- scatter dc into the plane gradients (sample_plane_feature backward) ------------------
         // Every atomic instruction covers two (point, tap) pairs x 32 CONTIGUOUS channels (two 128-B runs) instead of
@@ -540,7 +425,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(LinArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float v = acc[r] + red[0][lane][r] + red[1][lane][r] + red[2][lane][r];
-            const int m = (r & 3) + 8 * (r >> 2) + 4 * hi, nn = nb * 32 + i;
+            const int m = drow(r, hi), nn = nb * 32 + i;
             if (m < pr.mvalid && nn < pr.nvalid) atomicAdd(pr.dW + (size_t)m * pr.sM + nn, v);
         }
         if (nb == 0 && pr.db && hi == 0 && i < pr.mvalid)

@@ -23,7 +23,7 @@
 // through an LDS transposition (few queries), as in the fp32 path (giga_decoder_bwd.hip).
 // tools/tr16_probe.hip pins the lane map of ds_read_b64_tr_b16 and the tile layout on the device (profiles/r05/tr16_probe.txt).
 #include "giga_args.h"
-#include "giga_dev.h"
+#include "giga_dec_common.h"
 #include "giga_dect.h"
 
 namespace giga {
@@ -88,14 +88,6 @@ struct DectArgs {
     long long P;
     float invN;
 };
-
-// 64 lanes x 16 B chunks of an image by LDS-DMA, the chunks dealt over the workgroup's waves
-template <int CHUNKS, int NW>
-__device__ __forceinline__ void dect_dma(const uint8_t* src, uint8_t* lds_dst, int wave, int lane) {
-    for (int c = wave; c < CHUNKS; c += NW)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)c * FRAG + lane * 16),
-                                         (__attribute__((address_space(3))) void*)(lds_dst + c * FRAG), 16, 0, 0);
-}
 
 __device__ __forceinline__ bf8 relu_bf8(const f32x16& d, int c) {      // bf16(relu(D registers 8c .. 8c+7)), round to nearest even
     bf8 x;
@@ -191,8 +183,8 @@ __global__ __launch_bounds__(NW * 64, 1) void dect_kernel(DectArgs a) {
     const long long tile_lo = tiles_total * bid / gridDim.x, tile_hi = tiles_total * (bid + 1) / gridDim.x;
     const int rounds = (int)((tile_hi - tile_lo + NW - 1) / NW);
 
-    dect_dma<(int)(DECT_FWD_BYTES / FRAG), NW>(a.img_fwd[h], zone, wave, lane);
-    if constexpr (BWD) dect_dma<(int)(DECT_BWD_BYTES / FRAG), NW>(a.img_bwd[h], imgb, wave, lane);
+    lds_dma_frags<NW, (int)(DECT_FWD_BYTES / FRAG)>(a.img_fwd[h], zone, wave, lane);
+    if constexpr (BWD) lds_dma_frags<NW, (int)(DECT_BWD_BYTES / FRAG)>(a.img_bwd[h], imgb, wave, lane);
 
     // per-lane LDS offsets, the same for every tile
     int wa[4];                                                           // chain layout -> tile pieces (tile_write)
@@ -273,13 +265,9 @@ __global__ __launch_bounds__(NW * 64, 1) void dect_kernel(DectArgs a) {
                     const int pt = (2 * half + u) * 8 + (lane >> 3);
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl) {
-                        const float4 v00 = v[u][pl][0], v01 = v[u][pl][1], v10 = v[u][pl][2], v11 = v[u][pl][3];
-                        const float w00 = wq[u][pl][0], w01 = wq[u][pl][1], w10 = wq[u][pl][2], w11 = wq[u][pl][3];
-                        bf4 o4;
-                        o4[0] = (__bf16)fmaf(v11.x, w11, fmaf(v10.x, w10, fmaf(v01.x, w01, v00.x * w00)));
-                        o4[1] = (__bf16)fmaf(v11.y, w11, fmaf(v10.y, w10, fmaf(v01.y, w01, v00.y * w00)));
-                        o4[2] = (__bf16)fmaf(v11.z, w11, fmaf(v10.z, w10, fmaf(v01.z, w01, v00.z * w00)));
-                        o4[3] = (__bf16)fmaf(v11.w, w11, fmaf(v10.w, w10, fmaf(v01.w, w01, v00.w * w00)));
+                        const float4 f = bilerp(v[u][pl][0], v[u][pl][1], v[u][pl][2], v[u][pl][3],
+                                                wq[u][pl][0], wq[u][pl][1], wq[u][pl][2], wq[u][pl][3]);
+                        const bf4 o4 = {(__bf16)f.x, (__bf16)f.y, (__bf16)f.z, (__bf16)f.w};
                         *reinterpret_cast<bf4*>(cw + pl * TILE_B + piece_addr(pt, q)) = o4;
                     }
                 }
@@ -405,7 +393,7 @@ __global__ __launch_bounds__(NW * 64, 1) void dect_kernel(DectArgs a) {
             f32x16 G;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int f = (r & 3) + 8 * (r >> 2) + 4 * hi;
+                const int f = drow(r, hi);
                 G[r] = wout[f] * dO[0] + wout[32 + f] * dO[1] + wout[64 + f] * dO[2] + wout[96 + f] * dO[3];
             }
             mask_by(G, 0, XO[0]); mask_by(G, 1, XO[1]);
@@ -566,7 +554,7 @@ __global__ __launch_bounds__(NW * 64, 1) void dect_kernel(DectArgs a) {
                 __syncthreads();         // the stage is free before the next round's forward image lands on it
             }
             DT(23);
-            if (round + 1 < rounds) dect_dma<(int)(DECT_FWD_BYTES / FRAG), NW>(a.img_fwd[h], zone, wave, lane);
+            if (round + 1 < rounds) lds_dma_frags<NW, (int)(DECT_FWD_BYTES / FRAG)>(a.img_fwd[h], zone, wave, lane);
         }
     }
     if constexpr (BWD) {
@@ -639,7 +627,7 @@ __global__ __launch_bounds__(256) void dect_reduce_kernel(DectReduceArgs a) {
     for (int e = 0; e < 4; ++e) {
         const int idx = quarter * 256 + lane * 4 + e;          // = r * 64 + lane' of the D layout
         const int r = idx >> 6, l2 = idx & 63;
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * (l2 >> 5), col = l2 & 31;      // dW[row = output feature][col = input feature]
+        const int row = drow(r, l2 >> 5), col = l2 & 31;      // dW[row = output feature][col = input feature]
         const float v = vals[e];
         if (tile == 30) {
             if (row < out_dim) G[o.out_w + row * 32 + col] = v;
