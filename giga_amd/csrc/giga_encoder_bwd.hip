@@ -12,6 +12,7 @@
 #include "../../include/giga_hip.h"
 #include "giga_conv16.h"
 #include "giga_wino.h"
+#include "giga_wgrad3.h"
 #include <atomic>
 #include <functional>
 #include <mutex>
@@ -263,925 +264,7 @@ static int launch_wgrad(WgradArgs a, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-// ------------------------------- 3x3 weight gradient, LDS-staged -------------------------------------------------
-// dW[co][ci][tap] += sum_p dY[p][co] * X[p + tap][ci] for one 3x3 layer.  Unit = (image, strip of RS rows): the
-// workgroup stages the haloed input strip (all input channels, zero outside the image) and the dY strip (all
-// output channels) in LDS ONCE; its 8 waves then take their operands from LDS (one ds_read_b32 per 64-cycle MFMA,
-// immediate tap offsets, two VALU per pixel pair -- fp32 MFMA shares the VALU).  A wave owns one 32x32 (co, ci)
-// block for ALL nine taps (nine 32x32 accumulators, the dY operand is read once per nine MFMAs) and one of KS
-// interleaved shares of the strip's pixel pairs; blocks beyond 8 per workgroup go to blockIdx.y.  Accumulators
-// live across the whole persistent strip loop; the next strip is prefetched into registers under the MFMAs.
-// Epilogue: the waves of a block add their tiles into an LDS image laid out like the parameter ([co][ci][tap],
-// ds_add_f32), which is then added to the gradient with fully coalesced atomics.
-struct Wgrad3Args {
-    const float* dY;                 // [img][H][W][COUT]   gradient of the layer's pre-activation
-    const float* in0; const float* in1;   // layer input (concat order), dense NHWC with C0 / C1 channels
-    float* dW;                       // [COUT][CIN][3][3], accumulated by wgrad3_reduce_kernel
-    float* db;                       // [COUT] bias gradient = column sums of dY, accumulated by wgrad3_reduce_kernel
-    float* partial;                  // per-workgroup partial sums (workspace): [by][bx][block][9][32][32], then [bx][COUT]
-    int nimg;
-};
-constexpr int WG3_MAX_PARTS = 256 * 8;       // (workgroup, block) partial images of 9x32x32 floats
-constexpr int WG3_BIAS_FLOATS = 256 * 128;   // per-workgroup bias partials behind them
-
-#ifdef GIGA_TRACE
-static __device__ long long g_wg3_trace[8 * 32];
-#define WG3_T(idx) do { if (blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && (idx) < 32) \
-        g_wg3_trace[wave * 32 + (idx)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define WG3_T(idx) do {} while (0)
-#endif
-
-template <int C0, int C1, int COUT, int H, int RS>
-__global__ __launch_bounds__(512) void conv3_wgrad_kernel(Wgrad3Args a) {
-    constexpr int W = H, CIN = C0 + C1;
-    constexpr int NBK = CIN / 32, NBLK = (COUT / 32) * NBK;
-    constexpr int BPG = NBLK < 8 ? NBLK : 8;          // blocks per workgroup
-    constexpr int KS = 8 / BPG;                       // waves sharing a block (K split)
-    constexpr int XS = CIN + (CIN % 64 == 0 ? 32 : 0);      // LDS pixel strides (floats): odd multiple of 32 so that
-    constexpr int YS = COUT + (COUT % 64 == 0 ? 32 : 0);    // the two pixels of a pair fall into different bank halves
-    constexpr int XW = W + 2, XR = RS + 2;
-    constexpr int NVX = XR * XW * (CIN / 4), NVY = RS * W * (COUT / 4), NV = NVX + NVY;
-    constexpr int NLD = (NV + 511) / 512;
-    constexpr int XBYTES = XR * XW * XS * 4;
-    constexpr int NPAIR = RS * W / 2;
-    static_assert(H % RS == 0 && W % 2 == 0, "strip geometry");
-    extern __shared__ __attribute__((aligned(16))) float wg_lds[];
-    float* Xs = wg_lds;
-    float* Ys = wg_lds + XR * XW * XS;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int i = lane & 31, k = lane >> 5;
-    const int blk = blockIdx.y * BPG + wave / KS, ks = wave % KS;
-    const int mb = blk / NBK, nb = blk % NBK;
-
-    // staging geometry of this thread's vectors (fixed for the whole kernel): LDS float offset and source coordinates
-    int st_lds[NLD], st_src[NLD];                     // src: X: row<<20 | col<<10 | channel ; dY: 1<<30 | pixel<<10 | channel
-#pragma unroll
-    for (int q = 0; q < NLD; ++q) {
-        const int v = tid + 512 * q;
-        if (v < NVX) {
-            const int pix = v / (CIN / 4), c = (v % (CIN / 4)) * 4;
-            st_lds[q] = pix * XS + c;
-            st_src[q] = ((pix / XW) << 20) | ((pix % XW) << 10) | c;
-        } else if (v < NV) {
-            const int u = v - NVX, pix = u / (COUT / 4), c = (u % (COUT / 4)) * 4;
-            st_lds[q] = XR * XW * XS + pix * YS + c;
-            st_src[q] = (1 << 30) | (pix << 10) | c;
-        } else {
-            st_lds[q] = -1; st_src[q] = 0;
-        }
-    }
-    constexpr int SPI = H / RS;                       // strips per image
-    const int nstrips = a.nimg * SPI;
-    float4 stg[NLD];
-    auto issue = [&](int st) {
-        const int img = st / SPI, y0 = (st % SPI) * RS;
-#pragma unroll
-        for (int q = 0; q < NLD; ++q) {
-            float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
-            const int sd = st_src[q], c = sd & 1023;
-            if (st_lds[q] >= 0) {
-                if (sd >> 30) {
-                    const int pix = (sd >> 10) & 0xFFFFF;
-                    val = *reinterpret_cast<const float4*>(a.dY + ((size_t)(img * H + y0) * W + pix) * COUT + c);
-                } else {
-                    const int gy = y0 - 1 + (sd >> 20), gx = ((sd >> 10) & 1023) - 1;
-                    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-                        const size_t px = (size_t)(img * H + gy) * W + gx;
-                        val = c < C0 ? *reinterpret_cast<const float4*>(a.in0 + px * C0 + c)
-                                     : *reinterpret_cast<const float4*>(a.in1 + px * C1 + (c - C0));
-                    }
-                }
-            }
-            stg[q] = val;
-        }
-    };
-
-    f32x16 acc[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    const int lane_a = k * YS + mb * 32 + i;          // dY operand: row = co, k = pixel of the pair
-    const int lane_b = k * XS + nb * 32 + i;          // X operand: column = ci
-
-    WG3_T(0);
-    int tc = 1;
-    float bsum = 0.f;
-    int st = blockIdx.x;
-    if (st < nstrips) issue(st);
-    for (; st < nstrips; st += gridDim.x) {
-        __syncthreads();                              // everyone is done reading the previous strip
-#pragma unroll
-        for (int q = 0; q < NLD; ++q)
-            if (st_lds[q] >= 0) *reinterpret_cast<float4*>(wg_lds + st_lds[q]) = stg[q];
-        __syncthreads();
-        WG3_T(tc); ++tc;
-        if (st + (int)gridDim.x < nstrips) issue(st + gridDim.x);      // flies under this strip's MFMAs
-        WG3_T(tc); ++tc;
-        // bias gradient: column sums of the staged dY strip (ten adds per thread per strip)
-        if (blockIdx.y == 0) {
-            const int bc = tid % COUT;
-            for (int px = tid / COUT; px < RS * W; px += 512 / COUT) bsum += Ys[px * YS + bc];
-        }
-        // this wave's pixel pairs ks, ks+KS, ...: the ten operands of pair j+1 are read from LDS before the nine
-        // MFMAs of pair j are issued (ping-pong registers), so the LDS round trip never stalls the MFMA pipe
-        constexpr int CNT = NPAIR / KS;
-        static_assert(NPAIR % KS == 0 && CNT % 2 == 0, "pair split");
-        auto ld = [&](int j, float& av, float (&bv)[9]) {
-            const int pi = ks + j * KS;
-            const int r = pi / (W / 2), x = 2 * (pi % (W / 2));
-            av = Ys[(r * W + x) * YS + lane_a];
-            const float* xb = Xs + (r * XW + x) * XS + lane_b;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) bv[t] = xb[((t / 3) * XW + (t % 3)) * XS];
-        };
-        float a0, b0[9], a1, b1[9];
-        ld(0, a0, b0);
-        for (int j = 0; j < CNT; j += 2) {
-            ld(j + 1, a1, b1);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int t = 0; t < 9; ++t) acc[t] = mfma32(a0, b0[t], acc[t]);
-            __builtin_amdgcn_sched_barrier(0);
-            if (j + 2 < CNT) ld(j + 2, a0, b0);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int t = 0; t < 9; ++t) acc[t] = mfma32(a1, b1[t], acc[t]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        WG3_T(tc); ++tc;
-    }
-    WG3_T(30);
-    // ---- epilogue: three rounds of three taps.  Every wave parks its three 32x32 tiles in its own LDS slot (register
-    // layout, 16-B vectors, conflict-free), then all 512 threads sum the KS slots of every block and store the result
-    // tap-major ([block][tap][co][ci], coalesced) into this workgroup's partial image; wgrad3_reduce_kernel sums the
-    // workgroups and transposes to the parameter layout.  (Device-scope float atomics from 256 workgroups onto one
-    // 36 KiB image, and LDS float atomics, each cost several times the MFMA loop.)
-    if (blockIdx.y == 0) {                                            // fold the 512/COUT pixel shares of every channel
-        __syncthreads();
-        wg_lds[tid] = bsum;
-        __syncthreads();
-        if (tid < COUT) {
-            float sb = 0.f;
-            for (int q = 0; q < 512 / COUT; ++q) sb += wg_lds[q * COUT + tid];
-            a.partial[(size_t)gridDim.y * gridDim.x * BPG * 9 * 1024 + (size_t)blockIdx.x * COUT + tid] = sb;
-        }
-    }
-    float4* slot = reinterpret_cast<float4*>(wg_lds);                 // [wave][tap of the round][r4][lane]
-    constexpr int RN = 9 * 1024;
-    float* part = a.partial + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * BPG) * RN;
-#pragma unroll
-    for (int g3 = 0; g3 < 3; ++g3) {
-        __syncthreads();
-#pragma unroll
-        for (int tl = 0; tl < 3; ++tl)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4)
-                slot[((wave * 3 + tl) * 4 + r4) * 64 + lane] =
-                    make_float4(acc[3 * g3 + tl][4 * r4], acc[3 * g3 + tl][4 * r4 + 1], acc[3 * g3 + tl][4 * r4 + 2],
-                                acc[3 * g3 + tl][4 * r4 + 3]);
-        __syncthreads();
-        for (int v = tid; v < BPG * 3 * 4 * 64; v += 512) {
-            const int ln = v & 63, r4 = (v >> 6) & 3, tl = (v >> 8) % 3, b = v / 768;
-            float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int q = 0; q < KS; ++q) {
-                const float4 x = slot[(((b * KS + q) * 3 + tl) * 4 + r4) * 64 + ln];
-                sum.x += x.x; sum.y += x.y; sum.z += x.z; sum.w += x.w;
-            }
-            const int n = ln & 31, m0 = 8 * r4 + 4 * (ln >> 5);       // D rows of registers 4*r4 .. 4*r4+3: m0 .. m0+3
-            float* dst = part + ((size_t)(b * 9 + 3 * g3 + tl) * 32 + m0) * 32 + n;
-            dst[0] = sum.x; dst[32] = sum.y; dst[64] = sum.z; dst[96] = sum.w;
-        }
-    }
-    WG3_T(31);
-}
-
-// dW[co][ci][tap] of block gb = sum over the nx workgroups of partial[by][bx][b][tap][co][ci]   (gb = by*BPG + b).
-// A workgroup takes 64 elements of a block; every element's sum over the nx partial images is cut into four interleaved quarter
-// sums (one per wave, up to eight loads in flight), folded through LDS; every dW element has exactly one writer.  (Round 2: one
-// thread per element walked all nx = 128-256 images -- a chain of 32-64 dependent round trips, 13-24 us per layer, 128 us of the
-// bf16 step -- or, for the small layers, NZ groups meeting in dW with atomics.)
-template <int CIN, int BPG>
-__global__ __launch_bounds__(256) void wgrad3_reduce_kernel(const float* __restrict__ partial, int nx, float* __restrict__ dW,
-                                                            float* __restrict__ db, int cout, int ny) {
-    constexpr int RN = 9 * 1024, NBK = CIN / 32;
-    __shared__ float sb[256];
-    if (blockIdx.x == RN / 64) {                                // one extra block: the bias gradient
-        if (blockIdx.y != 0) return;
-        const int c = threadIdx.x % cout, part = threadIdx.x / cout, np = 256 / cout;     // cout divides 256
-        const float* bsrc = partial + (size_t)ny * nx * BPG * RN + c;
-        float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-        int x = part;
-        for (; x + 3 * np < nx; x += 4 * np) {
-            v0 += bsrc[(size_t)x * cout]; v1 += bsrc[(size_t)(x + np) * cout];
-            v2 += bsrc[(size_t)(x + 2 * np) * cout]; v3 += bsrc[(size_t)(x + 3 * np) * cout];
-        }
-        for (; x < nx; x += np) v0 += bsrc[(size_t)x * cout];
-        sb[threadIdx.x] = (v0 + v1) + (v2 + v3);
-        __syncthreads();
-        if ((int)threadIdx.x < cout) {
-            float t = 0.f;
-            for (int q = 0; q < np; ++q) t += sb[q * cout + threadIdx.x];
-            db[threadIdx.x] += t;
-        }
-        return;
-    }
-    const int e = blockIdx.x * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
-    const int gb = blockIdx.y, by = gb / BPG, b = gb % BPG;
-    const float* src = partial + ((size_t)by * nx * BPG + b) * RN + e;
-    constexpr size_t ST = (size_t)BPG * RN;
-    float s[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s[k] = 0.f;
-    int x = q;
-    for (; x + 28 < nx; x += 32) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s[k] += src[(size_t)(x + 4 * k) * ST];
-    }
-    for (; x < nx; x += 4) s[0] += src[(size_t)x * ST];
-    sb[threadIdx.x] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
-    __syncthreads();
-    if (q == 0) {
-        const float v = (sb[threadIdx.x] + sb[64 + threadIdx.x]) + (sb[128 + threadIdx.x] + sb[192 + threadIdx.x]);
-        const int t = e >> 10, m = (e >> 5) & 31, n = e & 31;
-        const int gmb = gb / NBK, gnb = gb % NBK;
-        dW[((size_t)(gmb * 32 + m) * CIN + gnb * 32 + n) * 9 + t] += v;
-    }
-}
-
-// ONE reduce launch for the 3x3 layers of a backward pass (round 5): every layer's weight-gradient launch leaves its partial images in
-// its OWN region of the workspace and a descriptor here; this kernel runs the blocks of wgrad3_reduce_kernel for all of them (same
-// element -> thread map, same order of summation: bit-identical results) in one grid.  Ten launches of 145 x NBLK blocks -- 9-13 us
-// each, none of them filling the chip -- become one of ~6 800 blocks.
-struct Wg3RedLayer {
-    const float* partial; float* dW; float* db;
-    int nx, ny, bpg, cin, cout, first_block;      // first_block: prefix sum of (144 * nblk + 1) over the layers before this one
-};
-constexpr int WG3_RED_MAX = 10;
-struct Wg3RedArgs { Wg3RedLayer L[WG3_RED_MAX]; int nlayers; int nblocks; };
-
-__global__ __launch_bounds__(256) void wgrad3_reduce_all_kernel(Wg3RedArgs A) {
-    constexpr int RN = 9 * 1024;
-    __shared__ float sb[256];
-    const int bid = blockIdx.x;
-    const float* partial = A.L[0].partial; float* dW = A.L[0].dW; float* db = A.L[0].db;
-    int nx = A.L[0].nx, ny = A.L[0].ny, bpg = A.L[0].bpg, cin = A.L[0].cin, cout = A.L[0].cout, first = 0;
-#pragma unroll
-    for (int i = 1; i < WG3_RED_MAX; ++i)
-        if (i < A.nlayers && bid >= A.L[i].first_block) {
-            partial = A.L[i].partial; dW = A.L[i].dW; db = A.L[i].db;
-            nx = A.L[i].nx; ny = A.L[i].ny; bpg = A.L[i].bpg; cin = A.L[i].cin; cout = A.L[i].cout; first = A.L[i].first_block;
-        }
-    const int local = bid - first, nbk = cin >> 5, nblk = (cout >> 5) * nbk;
-    if (local == 144 * nblk) {                                  // the layer's bias gradient
-        const int c = threadIdx.x % cout, part = threadIdx.x / cout, np = 256 / cout;     // cout divides 256
-        const float* bsrc = partial + (size_t)ny * nx * bpg * RN + c;
-        float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-        int x = part;
-        for (; x + 3 * np < nx; x += 4 * np) {
-            v0 += bsrc[(size_t)x * cout]; v1 += bsrc[(size_t)(x + np) * cout];
-            v2 += bsrc[(size_t)(x + 2 * np) * cout]; v3 += bsrc[(size_t)(x + 3 * np) * cout];
-        }
-        for (; x < nx; x += np) v0 += bsrc[(size_t)x * cout];
-        sb[threadIdx.x] = (v0 + v1) + (v2 + v3);
-        __syncthreads();
-        if ((int)threadIdx.x < cout) {
-            float t = 0.f;
-            for (int q = 0; q < np; ++q) t += sb[q * cout + threadIdx.x];
-            db[threadIdx.x] += t;
-        }
-        return;
-    }
-    const int gb = local / 144, ex = local - gb * 144;
-    const int e = ex * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
-    const int by = gb / bpg, b = gb - by * bpg;
-    const float* src = partial + ((size_t)by * nx * bpg + b) * RN + e;
-    const size_t ST = (size_t)bpg * RN;
-    float sacc[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) sacc[k] = 0.f;
-    int x = q;
-    for (; x + 28 < nx; x += 32) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) sacc[k] += src[(size_t)(x + 4 * k) * ST];
-    }
-    for (; x < nx; x += 4) sacc[0] += src[(size_t)x * ST];
-    sb[threadIdx.x] = ((sacc[0] + sacc[1]) + (sacc[2] + sacc[3])) + ((sacc[4] + sacc[5]) + (sacc[6] + sacc[7]));
-    __syncthreads();
-    if (q == 0) {
-        const float v = (sb[threadIdx.x] + sb[64 + threadIdx.x]) + (sb[128 + threadIdx.x] + sb[192 + threadIdx.x]);
-        const int t = e >> 10, m = (e >> 5) & 31, n = e & 31;
-        const int gmb = gb / nbk, gnb = gb - gmb * nbk;
-        dW[((size_t)(gmb * 32 + m) * cin + gnb * 32 + n) * 9 + t] += v;
-    }
-}
-
-// what a layer's launcher does with its reduce: launch it (defer == nullptr) or describe it for wgrad3_reduce_all_kernel
-static void wg3_defer(Wg3RedArgs* R, const float* partial, int nx, int ny, int bpg, int cin, int cout, float* dW, float* db) {
-    Wg3RedLayer& L = R->L[R->nlayers++];
-    L.partial = partial; L.dW = dW; L.db = db; L.nx = nx; L.ny = ny; L.bpg = bpg; L.cin = cin; L.cout = cout;
-    L.first_block = R->nblocks;
-    R->nblocks += 144 * (cout / 32) * (cin / 32) + 1;
-}
-static int launch_wgrad3_reduce_all(const Wg3RedArgs& R, hipStream_t s) {
-    if (R.nlayers == 0) return 0;
-    GIGA_LAUNCH(wgrad3_reduce_all_kernel, dim3(R.nblocks), dim3(256), 0, s, R);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-template <int C0, int C1, int COUT, int H, int RS>
-static int launch_wgrad3(const Wgrad3Args& a, hipStream_t s, Wg3RedArgs* defer = nullptr) {
-    constexpr int CIN = C0 + C1, W = H;
-    constexpr int NBLK = (COUT / 32) * (CIN / 32), BPG = NBLK < 8 ? NBLK : 8, NY = NBLK / BPG;
-    constexpr int XS = CIN + (CIN % 64 == 0 ? 32 : 0), YS = COUT + (COUT % 64 == 0 ? 32 : 0);
-    constexpr size_t strip = ((size_t)(RS + 2) * (W + 2) * XS + (size_t)RS * W * YS) * 4;
-    constexpr size_t lds = strip > 8 * 3 * 4 * 64 * 16 ? strip : 8 * 3 * 4 * 64 * 16;      // strip or the epilogue slots (96 KiB)
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    const int nstrips = a.nimg * (H / RS);
-    int gx = 256 / NY;
-    if (gx > nstrips) gx = nstrips;
-    auto kern = conv3_wgrad_kernel<C0, C1, COUT, H, RS>;
-    giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)lds);
-    GIGA_LAUNCH(kern, dim3(gx, NY), dim3(512), lds, s, a);
-    if (defer) { wg3_defer(defer, a.partial, gx, NY, BPG, CIN, COUT, a.dW, a.db); return hipGetLastError() == hipSuccess ? 0 : -10; }
-    GIGA_LAUNCH((wgrad3_reduce_kernel<CIN, BPG>), dim3(9 * 1024 / 64 + 1, NBLK), dim3(256), 0, s, a.partial, gx,
-                       a.dW, a.db, COUT, NY);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-// ------------------------------- 3x3 weight gradient on bf16 MFMA (BASELINE c5) -----------------------------
-// dW[co][ci][tap] = sum_pixels dY[p][co] * X[p + tap][ci]   with bf16 operands, fp32 accumulation: v_mfma_f32_32x32x16_bf16,
-// D[co][ci] += A[co][k] * B[k][ci], k = 16 PIXELS per instruction (the fp32 kernel above: 2 pixels per 64-cycle instruction).
-// Same decomposition, partial images, epilogue and reduce kernel as conv3_wgrad_kernel; what changes is the operand side:
-//   * the contraction runs over pixels, so a lane needs 8 consecutive pixels of ONE channel: the strips are staged
-//     TRANSPOSED, channel-major bf16 -- Xt[ci][row][col], Yt[co][row][col].  A staging item is (4 channels, row, 8-pixel
-//     group): eight coalesced float4 loads (a pixel's channels are contiguous across lanes), converted and written as four
-//     16-byte rows.  Rounding to bf16 happens here, once per element.
-//   * a k-chunk = two 8-pixel groups (lane half hi takes group 2j + hi); groups tile the rows (40 = 5 groups; 20 and 10 are
-//     padded to 24 / 16 with zeros, which contribute nothing).
-//   * the three horizontal taps are ONE aligned 16-byte read plus the two neighbouring elements (two 4-byte reads), shifted
-//     into place with v_alignbyte_b32: per k-chunk 1 + 3 x 3 LDS reads and 24 VALU feed nine MFMAs (288 matrix cycles).
-//   X columns: data at col 8 + x; cols < 8 and >= 8 + 8G stay zero (the convolution's zero padding), zeroed once.
-typedef __bf16 wbf8 __attribute__((ext_vector_type(8)));
-// channel stride (bf16 elements) of the transposed strips: the smallest value >= n that is 8 mod 128, i.e. 16 bytes mod 256: the 32
-// lanes of an operand read (one channel each, 16 bytes) then fall into 16 different 16-byte bank groups per pass -- with the natural
-// stride (rows x pitch: 0 or 64 bytes mod 256 for every layer) they shared one to four (a third of the launch's cycles carried LDS
-// bank conflicts: 2-8.6 M per launch) -- and the staging stores of 16 channel quads hit four bank groups instead of one.
-constexpr int wg_cs(int n) { return (n - 8 + 127) / 128 * 128 + 8; }
-
-template <int C0, int C1, int COUT, int H, int RS>
-__global__ __launch_bounds__(512) void conv3_wgrad_bf16_kernel(Wgrad3Args a) {
-    constexpr int W = H, CIN = C0 + C1;
-    constexpr int NBK = CIN / 32, NBLK = (COUT / 32) * NBK;
-    constexpr int BPG = NBLK < 8 ? NBLK : 8;          // blocks per workgroup
-    constexpr int KS = 8 / BPG;                       // waves sharing a block (K split)
-    constexpr int G = (W + 7) / 8;                    // 8-pixel groups per row
-    constexpr int PY = 8 * G, PX = 8 * G + 16;        // row pitches (bf16 elements)
-    constexpr int XR = RS + 2;
-    constexpr int NVX = (CIN / 4) * XR * G, NVY = (COUT / 4) * RS * G, NV = NVX + NVY;
-    static_assert(NV <= 512, "one staging item per thread");
-    constexpr int XCS = wg_cs(XR * PX), YCS = wg_cs(RS * PY);        // channel strides
-    constexpr int XELEMS = CIN * XCS, YELEMS = COUT * YCS;
-    constexpr int NCH = RS * G / 2;                   // k-chunks (two groups each) per strip
-    static_assert((RS * G) % 2 == 0 && H % RS == 0, "strip geometry");
-    extern __shared__ __attribute__((aligned(16))) float wg_lds[];
-    __bf16* Xt = reinterpret_cast<__bf16*>(wg_lds);
-    __bf16* Yt = Xt + XELEMS;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = lane & 31, hi = lane >> 5;
-    const int blk = blockIdx.y * BPG + wave / KS, ks = wave % KS;
-    const int mb = blk / NBK, nb = blk % NBK;
-
-    // zero the whole X image once: the halo columns are never written again
-    for (int v = tid; v < XELEMS / 8; v += 512) reinterpret_cast<uint4*>(Xt)[v] = make_uint4(0, 0, 0, 0);
-
-    // this thread's staging item
-    const bool isx = tid < NVX, isy = !isx && tid < NV;
-    const int u = isx ? tid : tid - NVX;
-    const int cq = isx ? u % (CIN / 4) : u % (COUT / 4);
-    const int rest = isx ? u / (CIN / 4) : u / (COUT / 4);
-    const int sg = rest % G, sr = rest / G;           // group within the row, strip row
-    constexpr int SPI = H / RS;
-    const int nstrips = a.nimg * SPI;
-    // All eight loads of a staging item are issued UNCONDITIONALLY from clamped addresses and zeroed when they are stored
-    // (`ok`): behind `if`s every load sat in its own basic block, the register allocator overlapped their destinations and the
-    // compiler put s_waitcnt vmcnt(0) between them -- an item cost two to three dependent memory round trips instead of one
-    // (the strip loop ran at ~6 k clocks per strip, tools/gpu_wgrad_trace.py).
-    float4 stg[8];
-    unsigned ok = 0;                                  // bit e: element e of the staged item is inside the image
-    auto issue = [&](int st) {
-        const int img = st / SPI, y0 = (st % SPI) * RS;
-        const int gy = y0 - 1 + sr, gyc = gy < 0 ? 0 : gy >= H ? H - 1 : gy, c = 4 * cq;
-        // (threads without an item read like a dY item of row 0: always a valid address)
-        const float* rowp = !isx ? a.dY + ((size_t)(img * H + y0 + (isy ? sr : 0)) * W) * COUT + c
-                                 : c < C0 ? a.in0 + ((size_t)(img * H + gyc) * W) * C0 + c
-                                          : a.in1 + ((size_t)(img * H + gyc) * W) * C1 + (c - C0);
-        const int ps = !isx ? COUT : c < C0 ? C0 : C1;
-        const bool row_ok = isy || (isx && gy >= 0 && gy < H);
-        ok = 0;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int x = 8 * sg + e, xc = x < W ? x : W - 1;
-            stg[e] = *reinterpret_cast<const float4*>(rowp + (size_t)xc * ps);
-            ok |= (row_ok && x < W) ? 1u << e : 0u;
-        }
-    };
-
-    f32x16 acc[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    const __bf16* ya = Yt + (size_t)(mb * 32 + n) * YCS;              // this lane's dY channel row block
-    const __bf16* xb = Xt + (size_t)(nb * 32 + n) * XCS + 8;          // this lane's X channel, col of x = 0
-
-    float bsum[4] = {0.f, 0.f, 0.f, 0.f};
-    int st = blockIdx.x;
-    if (st < nstrips) issue(st);
-    for (; st < nstrips; st += gridDim.x) {
-        __syncthreads();                              // everyone is done reading the previous strip (and the zero fill)
-        const unsigned okc = ok;
-        if (isx || isy) {
-            __bf16* dst = isx ? Xt + (size_t)(4 * cq) * XCS + sr * PX + 8 + 8 * sg : Yt + (size_t)(4 * cq) * YCS + sr * PY + 8 * sg;
-            const int cstride = isx ? XCS : YCS;
-#pragma unroll
-            for (int ch = 0; ch < 4; ++ch) {
-                float v8[8] = {ch == 0 ? stg[0].x : ch == 1 ? stg[0].y : ch == 2 ? stg[0].z : stg[0].w,
-                                     ch == 0 ? stg[1].x : ch == 1 ? stg[1].y : ch == 2 ? stg[1].z : stg[1].w,
-                                     ch == 0 ? stg[2].x : ch == 1 ? stg[2].y : ch == 2 ? stg[2].z : stg[2].w,
-                                     ch == 0 ? stg[3].x : ch == 1 ? stg[3].y : ch == 2 ? stg[3].z : stg[3].w,
-                                     ch == 0 ? stg[4].x : ch == 1 ? stg[4].y : ch == 2 ? stg[4].z : stg[4].w,
-                                     ch == 0 ? stg[5].x : ch == 1 ? stg[5].y : ch == 2 ? stg[5].z : stg[5].w,
-                                     ch == 0 ? stg[6].x : ch == 1 ? stg[6].y : ch == 2 ? stg[6].z : stg[6].w,
-                                     ch == 0 ? stg[7].x : ch == 1 ? stg[7].y : ch == 2 ? stg[7].z : stg[7].w};
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v8[e] = (okc >> e & 1u) ? v8[e] : 0.f;
-                wbf8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (__bf16)v8[e];
-                *reinterpret_cast<wbf8*>(dst + (size_t)ch * cstride) = o;
-                if (isy && blockIdx.y == 0)           // bias gradient: column sums of dY, from the fp32 values
-                    bsum[ch] += ((v8[0] + v8[1]) + (v8[2] + v8[3])) + ((v8[4] + v8[5]) + (v8[6] + v8[7]));
-            }
-        }
-        __syncthreads();
-        if (st + (int)gridDim.x < nstrips) issue(st + gridDim.x);      // flies under this strip's MFMAs
-        for (int j = ks; j < NCH; j += KS) {
-            const int gi = 2 * j + hi, r = gi / G, xg = gi % G;
-            const wbf8 A = *reinterpret_cast<const wbf8*>(ya + r * PY + 8 * xg);
-#pragma unroll
-            for (int ty = 0; ty < 3; ++ty) {
-                const __bf16* row = xb + (r + ty) * PX + 8 * xg;                 // X row y + ty - 1, col of the group's x0
-                const uint4 mid = *reinterpret_cast<const uint4*>(row);
-                const unsigned wp = *reinterpret_cast<const unsigned*>(row - 2);  // elements x0-2, x0-1
-                const unsigned wn = *reinterpret_cast<const unsigned*>(row + 8);  // elements x0+8, x0+9
-                const uint4 left = {__builtin_amdgcn_alignbyte(mid.x, wp, 2), __builtin_amdgcn_alignbyte(mid.y, mid.x, 2),
-                                    __builtin_amdgcn_alignbyte(mid.z, mid.y, 2), __builtin_amdgcn_alignbyte(mid.w, mid.z, 2)};
-                const uint4 right = {__builtin_amdgcn_alignbyte(mid.y, mid.x, 2), __builtin_amdgcn_alignbyte(mid.z, mid.y, 2),
-                                     __builtin_amdgcn_alignbyte(mid.w, mid.z, 2), __builtin_amdgcn_alignbyte(wn, mid.w, 2)};
-                acc[3 * ty + 0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, __builtin_bit_cast(wbf8, left), acc[3 * ty + 0], 0, 0, 0);
-                acc[3 * ty + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, __builtin_bit_cast(wbf8, mid), acc[3 * ty + 1], 0, 0, 0);
-                acc[3 * ty + 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, __builtin_bit_cast(wbf8, right), acc[3 * ty + 2], 0, 0, 0);
-            }
-        }
-    }
-    // ---- epilogue: as conv3_wgrad_kernel (the D layout of the bf16 MFMA is the same 32x32 map) ----------------------
-    if (blockIdx.y == 0) {
-        __syncthreads();
-        // per-channel totals: threads of the dY items hold 4 channels each for their (row, group)
-        float* red = wg_lds;                                          // [COUT] after zeroing
-        for (int c = tid; c < COUT; c += 512) red[c] = 0.f;
-        __syncthreads();
-        if (isy) {
-#pragma unroll
-            for (int ch = 0; ch < 4; ++ch) atomicAdd(red + 4 * cq + ch, bsum[ch]);      // LDS, <= RS*G addends per channel
-        }
-        __syncthreads();
-        if (tid < COUT)
-            a.partial[(size_t)gridDim.y * gridDim.x * BPG * 9 * 1024 + (size_t)blockIdx.x * COUT + tid] = red[tid];
-    }
-    float4* slot = reinterpret_cast<float4*>(wg_lds);                 // [wave][tap of the round][r4][lane]
-    constexpr int RN = 9 * 1024;
-    float* part = a.partial + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * BPG) * RN;
-#pragma unroll
-    for (int g3 = 0; g3 < 3; ++g3) {
-        __syncthreads();
-#pragma unroll
-        for (int tl = 0; tl < 3; ++tl)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4)
-                slot[((wave * 3 + tl) * 4 + r4) * 64 + lane] =
-                    make_float4(acc[3 * g3 + tl][4 * r4], acc[3 * g3 + tl][4 * r4 + 1], acc[3 * g3 + tl][4 * r4 + 2],
-                                acc[3 * g3 + tl][4 * r4 + 3]);
-        __syncthreads();
-        for (int v = tid; v < BPG * 3 * 4 * 64; v += 512) {
-            const int ln = v & 63, r4 = (v >> 6) & 3, tl = (v >> 8) % 3, b = v / 768;
-            float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int q = 0; q < KS; ++q) {
-                const float4 x = slot[(((b * KS + q) * 3 + tl) * 4 + r4) * 64 + ln];
-                sum.x += x.x; sum.y += x.y; sum.z += x.z; sum.w += x.w;
-            }
-            const int nn = ln & 31, m0 = 8 * r4 + 4 * (ln >> 5);      // D rows of registers 4*r4 .. 4*r4+3: m0 .. m0+3
-            float* dst = part + ((size_t)(b * 9 + 3 * g3 + tl) * 32 + m0) * 32 + nn;
-            dst[0] = sum.x; dst[32] = sum.y; dst[64] = sum.z; dst[96] = sum.w;
-        }
-    }
-}
-
-// ---- the same kernel with the OUTPUT split over the workgroups as well (the layers with eight or sixteen 32x32 blocks) -------------
-// In conv3_wgrad_bf16_kernel a workgroup computes eight blocks for its share of the strips and leaves a partial image of 8 x 36 KiB:
-// with 256 workgroups that is 75 MB written and 75 MB read back by the reduce kernel PER LAYER (up0.conv1, down2.conv1, down2.conv2:
-// 450 MB of the step's traffic for 7 MB of gradients) against 20-40 MB of operands.  Here a workgroup owns BX blocks that share
-// their dY channels (one 32-channel block mb, the X blocks nb0 .. nb0 + BX - 1), the grid is (strips' share, all block groups), and
-// only the channels those blocks need are staged: 32 of dY and 32 BX of X.  Same strips, k-chunks, MFMAs and epilogue; 8 / BX
-// waves share a block (K split inside the workgroup).  Partial images: 256 workgroups x BX x 36 KiB = 19 MB at BX = 2.
-template <int C0, int C1, int COUT, int H, int RS, int BX>
-__global__ __launch_bounds__(512) void conv3_wgrad_bf16_ns_kernel(Wgrad3Args a) {
-    constexpr int W = H, CIN = C0 + C1;
-    constexpr int NBK = CIN / 32, NBLK = (COUT / 32) * NBK;
-    constexpr int BPG = BX;                           // blocks per workgroup: (mb, nb0 .. nb0 + BX - 1)
-    constexpr int KS = 8 / BPG;                       // waves sharing a block (K split)
-    constexpr int NGX = NBK / BX;                     // X block groups per dY block
-    static_assert(NBK % BX == 0 && 8 % BX == 0 && (C1 == 0 || C0 % (32 * BX) == 0), "block groups");
-    constexpr int CINW = 32 * BX, COUTW = 32;         // channels this workgroup stages
-    constexpr int G = (W + 7) / 8;                    // 8-pixel groups per row
-    constexpr int PY = 8 * G, PX = 8 * G + 16;        // row pitches (bf16 elements)
-    constexpr int XR = RS + 2;
-    constexpr int NVX = (CINW / 4) * XR * G, NVY = (COUTW / 4) * RS * G, NV = NVX + NVY;
-    static_assert(NV <= 512, "one staging item per thread");
-    constexpr int XCS = wg_cs(XR * PX), YCS = wg_cs(RS * PY);        // channel strides
-    constexpr int XELEMS = CINW * XCS, YELEMS = COUTW * YCS;
-    constexpr int NCH = RS * G / 2;                   // k-chunks (two groups each) per strip
-    static_assert((RS * G) % 2 == 0 && H % RS == 0, "strip geometry");
-    extern __shared__ __attribute__((aligned(16))) float wg_lds[];
-    __bf16* Xt = reinterpret_cast<__bf16*>(wg_lds);
-    __bf16* Yt = Xt + XELEMS;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = lane & 31, hi = lane >> 5;
-    const int mb = blockIdx.y / NGX, nb0 = (blockIdx.y % NGX) * BX;       // this workgroup's dY block and first X block
-    const int nbl = wave / KS, ks = wave % KS;                            // this wave's block (local X block index) and K share
-
-    // zero the whole X image once: the halo columns are never written again
-    for (int v = tid; v < XELEMS / 8; v += 512) reinterpret_cast<uint4*>(Xt)[v] = make_uint4(0, 0, 0, 0);
-
-    // this thread's staging item
-    const bool isx = tid < NVX, isy = !isx && tid < NV;
-    const int u = isx ? tid : tid - NVX;
-    const int cq = isx ? u % (CINW / 4) : u % (COUTW / 4);       // channel quad inside the staged channels
-    const int rest = isx ? u / (CINW / 4) : u / (COUTW / 4);
-    const int sg = rest % G, sr = rest / G;           // group within the row, strip row
-    constexpr int SPI = H / RS;
-    const int nstrips = a.nimg * SPI;
-    // All eight loads of a staging item are issued UNCONDITIONALLY from clamped addresses and zeroed when they are stored
-    // (`ok`): behind `if`s every load sat in its own basic block, the register allocator overlapped their destinations and the
-    // compiler put s_waitcnt vmcnt(0) between them -- an item cost two to three dependent memory round trips instead of one
-    // (the strip loop ran at ~6 k clocks per strip, tools/gpu_wgrad_trace.py).
-    float4 stg[8];
-    unsigned ok = 0;                                  // bit e: element e of the staged item is inside the image
-    auto issue = [&](int st) {
-        const int img = st / SPI, y0 = (st % SPI) * RS;
-        const int gy = y0 - 1 + sr, gyc = gy < 0 ? 0 : gy >= H ? H - 1 : gy;
-        const int c = 4 * cq + (isx ? 32 * nb0 : 32 * mb);          // channel in the tensor
-        // (threads without an item read like a dY item of row 0: always a valid address)
-        const float* rowp = !isx ? a.dY + ((size_t)(img * H + y0 + (isy ? sr : 0)) * W) * COUT + c
-                                 : c < C0 ? a.in0 + ((size_t)(img * H + gyc) * W) * C0 + c
-                                          : a.in1 + ((size_t)(img * H + gyc) * W) * C1 + (c - C0);
-        const int ps = !isx ? COUT : c < C0 ? C0 : C1;
-        const bool row_ok = isy || (isx && gy >= 0 && gy < H);
-        ok = 0;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int x = 8 * sg + e, xc = x < W ? x : W - 1;
-            stg[e] = *reinterpret_cast<const float4*>(rowp + (size_t)xc * ps);
-            ok |= (row_ok && x < W) ? 1u << e : 0u;
-        }
-    };
-
-    f32x16 acc[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    const __bf16* ya = Yt + (size_t)n * YCS;                           // this lane's dY channel (of block mb)
-    const __bf16* xb = Xt + (size_t)(nbl * 32 + n) * XCS + 8;          // this lane's X channel, col of x = 0
-
-    float bsum[4] = {0.f, 0.f, 0.f, 0.f};
-    int st = blockIdx.x;
-    if (st < nstrips) issue(st);
-    for (; st < nstrips; st += gridDim.x) {
-        __syncthreads();                              // everyone is done reading the previous strip (and the zero fill)
-        const unsigned okc = ok;
-        if (isx || isy) {
-            __bf16* dst = isx ? Xt + (size_t)(4 * cq) * XCS + sr * PX + 8 + 8 * sg : Yt + (size_t)(4 * cq) * YCS + sr * PY + 8 * sg;
-            const int cstride = isx ? XCS : YCS;
-#pragma unroll
-            for (int ch = 0; ch < 4; ++ch) {
-                float v8[8] = {ch == 0 ? stg[0].x : ch == 1 ? stg[0].y : ch == 2 ? stg[0].z : stg[0].w,
-                                     ch == 0 ? stg[1].x : ch == 1 ? stg[1].y : ch == 2 ? stg[1].z : stg[1].w,
-                                     ch == 0 ? stg[2].x : ch == 1 ? stg[2].y : ch == 2 ? stg[2].z : stg[2].w,
-                                     ch == 0 ? stg[3].x : ch == 1 ? stg[3].y : ch == 2 ? stg[3].z : stg[3].w,
-                                     ch == 0 ? stg[4].x : ch == 1 ? stg[4].y : ch == 2 ? stg[4].z : stg[4].w,
-                                     ch == 0 ? stg[5].x : ch == 1 ? stg[5].y : ch == 2 ? stg[5].z : stg[5].w,
-                                     ch == 0 ? stg[6].x : ch == 1 ? stg[6].y : ch == 2 ? stg[6].z : stg[6].w,
-                                     ch == 0 ? stg[7].x : ch == 1 ? stg[7].y : ch == 2 ? stg[7].z : stg[7].w};
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v8[e] = (okc >> e & 1u) ? v8[e] : 0.f;
-                wbf8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (__bf16)v8[e];
-                *reinterpret_cast<wbf8*>(dst + (size_t)ch * cstride) = o;
-                if (isy && nb0 == 0)                  // bias gradient: column sums of dY (this block's 32 channels), from the fp32 values
-                    bsum[ch] += ((v8[0] + v8[1]) + (v8[2] + v8[3])) + ((v8[4] + v8[5]) + (v8[6] + v8[7]));
-            }
-        }
-        __syncthreads();
-        if (st + (int)gridDim.x < nstrips) issue(st + gridDim.x);      // flies under this strip's MFMAs
-        for (int j = ks; j < NCH; j += KS) {
-            const int gi = 2 * j + hi, r = gi / G, xg = gi % G;
-            const wbf8 A = *reinterpret_cast<const wbf8*>(ya + r * PY + 8 * xg);
-#pragma unroll
-            for (int ty = 0; ty < 3; ++ty) {
-                const __bf16* row = xb + (r + ty) * PX + 8 * xg;                 // X row y + ty - 1, col of the group's x0
-                const uint4 mid = *reinterpret_cast<const uint4*>(row);
-                const unsigned wp = *reinterpret_cast<const unsigned*>(row - 2);  // elements x0-2, x0-1
-                const unsigned wn = *reinterpret_cast<const unsigned*>(row + 8);  // elements x0+8, x0+9
-                const uint4 left = {__builtin_amdgcn_alignbyte(mid.x, wp, 2), __builtin_amdgcn_alignbyte(mid.y, mid.x, 2),
-                                    __builtin_amdgcn_alignbyte(mid.z, mid.y, 2), __builtin_amdgcn_alignbyte(mid.w, mid.z, 2)};
-                const uint4 right = {__builtin_amdgcn_alignbyte(mid.y, mid.x, 2), __builtin_amdgcn_alignbyte(mid.z, mid.y, 2),
-                                     __builtin_amdgcn_alignbyte(mid.w, mid.z, 2), __builtin_amdgcn_alignbyte(wn, mid.w, 2)};
-                acc[3 * ty + 0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, __builtin_bit_cast(wbf8, left), acc[3 * ty + 0], 0, 0, 0);
-                acc[3 * ty + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, __builtin_bit_cast(wbf8, mid), acc[3 * ty + 1], 0, 0, 0);
-                acc[3 * ty + 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, __builtin_bit_cast(wbf8, right), acc[3 * ty + 2], 0, 0, 0);
-            }
-        }
-    }
-    // ---- epilogue: as conv3_wgrad_kernel (the D layout of the bf16 MFMA is the same 32x32 map) ----------------------
-    if (nb0 == 0) {
-        __syncthreads();
-        // per-channel totals: threads of the dY items hold 4 channels each for their (row, group)
-        float* red = wg_lds;                                          // [32] after zeroing
-        for (int c = tid; c < COUTW; c += 512) red[c] = 0.f;
-        __syncthreads();
-        if (isy) {
-#pragma unroll
-            for (int ch = 0; ch < 4; ++ch) atomicAdd(red + 4 * cq + ch, bsum[ch]);      // LDS, <= RS*G addends per channel
-        }
-        __syncthreads();
-        if (tid < COUTW)
-            a.partial[(size_t)gridDim.y * gridDim.x * BPG * 9 * 1024 + (size_t)blockIdx.x * COUT + 32 * mb + tid] = red[tid];
-    }
-    float4* slot = reinterpret_cast<float4*>(wg_lds);                 // [wave][tap of the round][r4][lane]
-    constexpr int RN = 9 * 1024;
-    float* part = a.partial + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * BPG) * RN;
-#pragma unroll
-    for (int g3 = 0; g3 < 3; ++g3) {
-        __syncthreads();
-#pragma unroll
-        for (int tl = 0; tl < 3; ++tl)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4)
-                slot[((wave * 3 + tl) * 4 + r4) * 64 + lane] =
-                    make_float4(acc[3 * g3 + tl][4 * r4], acc[3 * g3 + tl][4 * r4 + 1], acc[3 * g3 + tl][4 * r4 + 2],
-                                acc[3 * g3 + tl][4 * r4 + 3]);
-        __syncthreads();
-        for (int v = tid; v < BPG * 3 * 4 * 64; v += 512) {
-            const int ln = v & 63, r4 = (v >> 6) & 3, tl = (v >> 8) % 3, b = v / 768;
-            float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int q = 0; q < KS; ++q) {
-                const float4 x = slot[(((b * KS + q) * 3 + tl) * 4 + r4) * 64 + ln];
-                sum.x += x.x; sum.y += x.y; sum.z += x.z; sum.w += x.w;
-            }
-            const int nn = ln & 31, m0 = 8 * r4 + 4 * (ln >> 5);      // D rows of registers 4*r4 .. 4*r4+3: m0 .. m0+3
-            float* dst = part + ((size_t)(b * 9 + 3 * g3 + tl) * 32 + m0) * 32 + nn;
-            dst[0] = sum.x; dst[32] = sum.y; dst[64] = sum.z; dst[96] = sum.w;
-        }
-    }
-}
-
-// ---- the same weight gradient for layers with at most four 32x32 blocks: the NINE TAPS go to nine waves ----------------------
-// In conv3_wgrad_bf16_kernel a wave owns a block for all nine taps (144 accumulator registers) and the waves of a block split the
-// pixels.  For the layers with one to four blocks (32 -> 32 and 32 + 32 -> 32 at 40x40, 32 -> 64 and 64 -> 64 at 20x20) that leaves
-//   * no registers for a second strip of loads in flight: a strip is ~600 clocks of MFMAs against a ~6 k-clock memory round trip,
-//     one strip deep the loop runs at one strip per round trip (tools/gpu_wgrad_trace.py, profiles/r03/wgrad3_bf16_trace_layer0.txt);
-//   * an epilogue of three LDS rounds in which the 8 waves' tiles are summed (9.6 k of the launch's 44 k clocks).
-// Here wave t takes tap t of EVERY block and every k-chunk of the strip: 16 x NBLK accumulator registers, the same number of
-// MFMAs per wave, no cross-wave sum at all (a wave writes its tiles straight to the partial image), and two strips of loads in
-// flight (ping-pong staging registers).  Workgroup barriers inside the loop are s_barrier after lgkmcnt(0) only: __syncthreads()
-// also waits for vmcnt(0), i.e. for the prefetched loads.  Staging, partial-image layout and reduce kernel are unchanged.
-template <int C0, int C1, int COUT, int H, int RS>
-__global__ __launch_bounds__(576) void conv3_wgrad_bf16_taps_kernel(Wgrad3Args a) {
-    constexpr int W = H, CIN = C0 + C1;
-    constexpr int NBK = CIN / 32, NMB = COUT / 32, NBLK = NMB * NBK;
-    static_assert(NBLK <= 4, "one tap per wave: few blocks");
-    constexpr bool DEEP = NBLK == 1;                  // two strips of loads in flight; with 2-4 blocks (32-64 accumulator registers) the second
-                                                      // staging set no longer fits the 168 registers of a 9-wave workgroup (100-400 B of scratch)
-    constexpr int G = (W + 7) / 8;
-    constexpr int PY = 8 * G, PX = 8 * G + 16;
-    constexpr int XR = RS + 2;
-    constexpr int NVX = (CIN / 4) * XR * G, NVY = (COUT / 4) * RS * G, NV = NVX + NVY;
-    static_assert(NV <= 512, "one staging item per thread");
-    constexpr int XCS = wg_cs(XR * PX), YCS = wg_cs(RS * PY);        // channel strides (see wg_cs)
-    constexpr int XELEMS = CIN * XCS;
-    constexpr int NCH = RS * G / 2;
-    static_assert((RS * G) % 2 == 0 && H % RS == 0, "strip geometry");
-    extern __shared__ __attribute__((aligned(16))) float wg_lds[];
-    __bf16* Xt = reinterpret_cast<__bf16*>(wg_lds);
-    __bf16* Yt = Xt + XELEMS;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);          // = tap
-    const int n = lane & 31, hi = lane >> 5;
-    const int ty = wave / 3, tx = wave - 3 * ty;
-
-    for (int v = tid; v < XELEMS / 8; v += 576) reinterpret_cast<uint4*>(Xt)[v] = make_uint4(0, 0, 0, 0);
-
-    const bool isx = tid < NVX, isy = !isx && tid < NV;
-    const int u = isx ? tid : tid - NVX;
-    const int cq = isx ? u % (CIN / 4) : u % (COUT / 4);
-    const int rest = isx ? u / (CIN / 4) : u / (COUT / 4);
-    const int sg = rest % G, sr = rest / G;
-    constexpr int SPI = H / RS;
-    const int nstrips = a.nimg * SPI;
-    auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-    float4 stgA[8], stgB[8];
-    unsigned okA = 0, okB = 0;                        // bit e: element e of the staged item is inside the image
-    // (unconditional loads from clamped addresses, zeroed when stored: see conv3_wgrad_bf16_kernel)
-    auto issue = [&](int st, float4 (&stg)[8], unsigned& ok) {
-        const int img = st / SPI, y0 = (st % SPI) * RS;
-        const int gy = y0 - 1 + sr, gyc = gy < 0 ? 0 : gy >= H ? H - 1 : gy, c = 4 * cq;
-        // (threads without an item read like a dY item of row 0: always a valid address)
-        const float* rowp = !isx ? a.dY + ((size_t)(img * H + y0 + (isy ? sr : 0)) * W) * COUT + c
-                                 : c < C0 ? a.in0 + ((size_t)(img * H + gyc) * W) * C0 + c
-                                          : a.in1 + ((size_t)(img * H + gyc) * W) * C1 + (c - C0);
-        const int ps = !isx ? COUT : c < C0 ? C0 : C1;
-        const bool row_ok = isy || (isx && gy >= 0 && gy < H);
-        ok = 0;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int x = 8 * sg + e, xc = x < W ? x : W - 1;
-            stg[e] = *reinterpret_cast<const float4*>(rowp + (size_t)xc * ps);
-            ok |= (row_ok && x < W) ? 1u << e : 0u;
-        }
-    };
-
-    f32x16 acc[NBLK];
-#pragma unroll
-    for (int b = 0; b < NBLK; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-    float bsum[4] = {0.f, 0.f, 0.f, 0.f};
-    int st = blockIdx.x;
-    const int gstep = (int)gridDim.x;
-    if (st < nstrips) issue(st, stgA, okA);
-    if (DEEP && st + gstep < nstrips) issue(st + gstep, stgB, okB);
-    __syncthreads();                                  // the zero fill of the X image
-    auto strip = [&](float4 (&stg)[8], unsigned& ok, int st_) {
-        lds_barrier();                                // everyone is done reading the previous strip
-        const unsigned okc = ok;
-        if (isx || isy) {
-            __bf16* dst = isx ? Xt + (size_t)(4 * cq) * XCS + sr * PX + 8 + 8 * sg : Yt + (size_t)(4 * cq) * YCS + sr * PY + 8 * sg;
-            const int cstride = isx ? XCS : YCS;
-#pragma unroll
-            for (int ch = 0; ch < 4; ++ch) {
-                float v8[8] = {ch == 0 ? stg[0].x : ch == 1 ? stg[0].y : ch == 2 ? stg[0].z : stg[0].w,
-                                     ch == 0 ? stg[1].x : ch == 1 ? stg[1].y : ch == 2 ? stg[1].z : stg[1].w,
-                                     ch == 0 ? stg[2].x : ch == 1 ? stg[2].y : ch == 2 ? stg[2].z : stg[2].w,
-                                     ch == 0 ? stg[3].x : ch == 1 ? stg[3].y : ch == 2 ? stg[3].z : stg[3].w,
-                                     ch == 0 ? stg[4].x : ch == 1 ? stg[4].y : ch == 2 ? stg[4].z : stg[4].w,
-                                     ch == 0 ? stg[5].x : ch == 1 ? stg[5].y : ch == 2 ? stg[5].z : stg[5].w,
-                                     ch == 0 ? stg[6].x : ch == 1 ? stg[6].y : ch == 2 ? stg[6].z : stg[6].w,
-                                     ch == 0 ? stg[7].x : ch == 1 ? stg[7].y : ch == 2 ? stg[7].z : stg[7].w};
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v8[e] = (okc >> e & 1u) ? v8[e] : 0.f;
-                wbf8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (__bf16)v8[e];
-                *reinterpret_cast<wbf8*>(dst + (size_t)ch * cstride) = o;
-                if (isy)                              // bias gradient: column sums of dY, from the fp32 values
-                    bsum[ch] += ((v8[0] + v8[1]) + (v8[2] + v8[3])) + ((v8[4] + v8[5]) + (v8[6] + v8[7]));
-            }
-        }
-        if (st_ + (DEEP ? 2 : 1) * gstep < nstrips) issue(st_ + (DEEP ? 2 : 1) * gstep, stg, ok);   // into the registers just drained
-        lds_barrier();
-#pragma unroll 2
-        for (int j = 0; j < NCH; ++j) {
-            const int gi = 2 * j + hi, r = gi / G, xg = gi % G;
-            wbf8 A[NMB], B[NBK];
-#pragma unroll
-            for (int m = 0; m < NMB; ++m) A[m] = *reinterpret_cast<const wbf8*>(Yt + (size_t)(m * 32 + n) * YCS + r * PY + 8 * xg);
-#pragma unroll
-            for (int k = 0; k < NBK; ++k) {
-                const __bf16* row = Xt + (size_t)(k * 32 + n) * XCS + 8 + (r + ty) * PX + 8 * xg;   // X row y + ty - 1, col of the group's x0
-                const uint4 mid = *reinterpret_cast<const uint4*>(row);
-                uint4 sel = mid;
-                if (tx == 0) {
-                    const unsigned wp = *reinterpret_cast<const unsigned*>(row - 2);                  // elements x0-2, x0-1
-                    sel = uint4{__builtin_amdgcn_alignbyte(mid.x, wp, 2), __builtin_amdgcn_alignbyte(mid.y, mid.x, 2),
-                                __builtin_amdgcn_alignbyte(mid.z, mid.y, 2), __builtin_amdgcn_alignbyte(mid.w, mid.z, 2)};
-                } else if (tx == 2) {
-                    const unsigned wn = *reinterpret_cast<const unsigned*>(row + 8);                  // elements x0+8, x0+9
-                    sel = uint4{__builtin_amdgcn_alignbyte(mid.y, mid.x, 2), __builtin_amdgcn_alignbyte(mid.z, mid.y, 2),
-                                __builtin_amdgcn_alignbyte(mid.w, mid.z, 2), __builtin_amdgcn_alignbyte(wn, mid.w, 2)};
-                }
-                B[k] = __builtin_bit_cast(wbf8, sel);
-            }
-#pragma unroll
-            for (int m = 0; m < NMB; ++m)
-#pragma unroll
-                for (int k = 0; k < NBK; ++k)
-                    acc[m * NBK + k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[m], B[k], acc[m * NBK + k], 0, 0, 0);
-        }
-    };
-    if constexpr (DEEP) {
-        for (;;) {
-            if (st >= nstrips) break;
-            strip(stgA, okA, st); st += gstep;
-            if (st >= nstrips) break;
-            strip(stgB, okB, st); st += gstep;
-        }
-    } else {
-        for (; st < nstrips; st += gstep) strip(stgA, okA, st);
-    }
-    // ---- epilogue: every wave writes its tap's tiles (D layout: lane (n, hi), register r <-> row (r&3) + 8(r>>2) + 4hi) ------------
-    constexpr int RN = 9 * 1024;
-    float* part = a.partial + (size_t)blockIdx.x * NBLK * RN;
-#pragma unroll
-    for (int b = 0; b < NBLK; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            part[((size_t)(b * 9 + wave) * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi) * 32 + n] = acc[b][r];
-    // per-channel totals of dY: threads of the dY items hold 4 channels each for their (row, group)
-    __syncthreads();
-    float* red = wg_lds;
-    for (int c = tid; c < COUT; c += 576) red[c] = 0.f;
-    __syncthreads();
-    if (isy) {
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch) atomicAdd(red + 4 * cq + ch, bsum[ch]);      // LDS, <= RS*G addends per channel
-    }
-    __syncthreads();
-    if (tid < COUT) a.partial[(size_t)gridDim.x * NBLK * RN + (size_t)blockIdx.x * COUT + tid] = red[tid];
-}
-
-template <int C0, int C1, int COUT, int H, int RS>
-static int launch_wgrad3_bf16(const Wgrad3Args& a, hipStream_t s, Wg3RedArgs* defer = nullptr) {
-    constexpr int CIN = C0 + C1, W = H;
-    constexpr int NBLK = (COUT / 32) * (CIN / 32), BPG = NBLK < 8 ? NBLK : 8, NY = NBLK / BPG;
-    constexpr int G = (W + 7) / 8;
-    constexpr size_t strip = ((size_t)CIN * wg_cs((RS + 2) * (8 * G + 16)) + (size_t)COUT * wg_cs(RS * 8 * G)) * 2;
-    constexpr size_t lds = strip > 8 * 3 * 4 * 64 * 16 ? strip : 8 * 3 * 4 * 64 * 16;      // strip or the epilogue slots (96 KiB)
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    const int nstrips = a.nimg * (H / RS);
-    int gx = 256 / NY;
-    if (gx > nstrips) gx = nstrips;
-    if constexpr (NBLK <= 4) {                        // one tap per wave (conv3_wgrad_bf16_taps_kernel)
-        static const bool taps = [] { const char* e = getenv("GIGA_WGRAD_TAPS"); return !e || atoi(e) != 0; }();
-        if (taps) {
-            auto kern = conv3_wgrad_bf16_taps_kernel<C0, C1, COUT, H, RS>;
-            giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)strip);
-            GIGA_LAUNCH(kern, dim3(gx), dim3(576), strip, s, a);
-            if (defer) { wg3_defer(defer, a.partial, gx, NY, BPG, CIN, COUT, a.dW, a.db); return hipGetLastError() == hipSuccess ? 0 : -10; }
-            GIGA_LAUNCH((wgrad3_reduce_kernel<CIN, BPG>), dim3(9 * 1024 / 64 + 1, NBLK), dim3(256), 0, s, a.partial, gx,
-                               a.dW, a.db, COUT, NY);
-            return hipGetLastError() == hipSuccess ? 0 : -10;
-        }
-    }
-    if constexpr (NBLK > 4) {                         // the output split over the workgroups too (conv3_wgrad_bf16_ns_kernel)
-        static const bool nsplit = [] { const char* e = getenv("GIGA_WGRAD_NSPLIT"); return !e || atoi(e) != 0; }();
-        if (nsplit) {
-            constexpr int BX = 2, NYS = NBLK / BX;
-            constexpr size_t strip_ns = ((size_t)32 * BX * wg_cs((RS + 2) * (8 * G + 16)) + (size_t)32 * wg_cs(RS * 8 * G)) * 2;
-            constexpr size_t slots = (size_t)8 * 3 * 4 * 64 * 16;                          // the epilogue's LDS slots (96 KiB)
-            constexpr size_t lds_ns = strip_ns > slots ? strip_ns : slots;
-            int gxs = 256 / NYS;
-            if (gxs > nstrips) gxs = nstrips;
-            auto kns = conv3_wgrad_bf16_ns_kernel<C0, C1, COUT, H, RS, BX>;
-            giga::dyn_lds_once(reinterpret_cast<const void*>(kns), (int)lds_ns);
-            GIGA_LAUNCH(kns, dim3(gxs, NYS), dim3(512), lds_ns, s, a);
-            if (defer) { wg3_defer(defer, a.partial, gxs, NYS, BX, CIN, COUT, a.dW, a.db); return hipGetLastError() == hipSuccess ? 0 : -10; }
-            GIGA_LAUNCH((wgrad3_reduce_kernel<CIN, BX>), dim3(9 * 1024 / 64 + 1, NBLK), dim3(256), 0, s, a.partial, gxs,
-                               a.dW, a.db, COUT, NYS);
-            return hipGetLastError() == hipSuccess ? 0 : -10;
-        }
-    }
-    auto kern = conv3_wgrad_bf16_kernel<C0, C1, COUT, H, RS>;
-    giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)lds);
-    GIGA_LAUNCH(kern, dim3(gx, NY), dim3(512), lds, s, a);
-    if (defer) { wg3_defer(defer, a.partial, gx, NY, BPG, CIN, COUT, a.dW, a.db); return hipGetLastError() == hipSuccess ? 0 : -10; }
-    GIGA_LAUNCH((wgrad3_reduce_kernel<CIN, BPG>), dim3(9 * 1024 / 64 + 1, NBLK), dim3(256), 0, s, a.partial, gx,
-                       a.dW, a.db, COUT, NY);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
+// (the 3x3 layers: giga_wgrad3.h)
 
 // ------------------------------- conv_in backward ----------------------------------------------------------
 // Same decomposition as convin_project_kernel: workgroup = (x-part, iy-group x channel half, scene), the haloed TSDF
@@ -1424,7 +507,7 @@ BwdWs enc_bwd_workspace(int B) {
     w.gS2 = take(n * 100 * 128); w.gA2 = take(n * 100 * 128); w.gQ1 = take(n * 100 * 64);
     w.gS1 = take(n * 400 * 64);  w.gA1 = take(n * 400 * 64);  w.gQ0 = take(n * 400 * 32);
     w.gS0 = take(n * 1600 * 32); w.gA0 = take(n * 1600 * 32); w.gP0 = take(n * 1600 * 32);
-    w.WG = take((size_t)WG3_MAX_PARTS * 32 * 288 + WG3_BIAS_FLOATS);      // per-workgroup weight-gradient partials (conv3_wgrad_kernel)
+    w.WG = take((size_t)WG3_MAX_PARTS * 32 * 288 + WG3_BIAS_FLOATS);      // per-workgroup weight-gradient partials (conv_wgrad_kernel; giga_wgrad3.h with one reduce per layer)
     // one region per 3x3 layer for the single reduce launch at the end (wgrad3_reduce_all_kernel): 256 x min(blocks, 8) partial
     // images of 36 KiB + the bias partials; 368 MB in all, whatever the batch size
     for (int l = 0; l < 12; ++l) {
@@ -1469,15 +552,6 @@ static int encoder_backward_impl(const float* tsdf, const uint8_t* blob, const u
     // weight gradient of layer l: R = dPre (channels = cout), columns = layer input (in0 [, in1])
     auto wgrad3_now = [&](int l, const float* dpre, const float* in0, const float* in1, int H) {
         const ConvLayerDesc& d = kConv[l];
-        const int cin = d.cin0 + d.cin1, taps = d.kind == CONV3 ? 9 : 1;
-        WgradArgs a{};
-        a.R = dpre; a.csR = d.cout; a.coR = 0;
-        a.C0p = in0; a.C1p = in1; a.csC0 = d.cin0; a.csC1 = d.cin1; a.nC0 = d.cin0;
-        a.dW = grads + po.conv_w[l]; a.sM = cin * taps; a.sN = taps; a.sT = 1;
-        a.kind = d.kind; a.taps = taps; a.Mb = d.cout / 32; a.Nb = cin / 32;
-        a.nimg = nimg; a.H = H; a.W = H;
-        a.partial = G(g.WG);
-        a.db = grads + po.conv_b[l]; a.nbias = d.cout;          // bias gradient = column sums of dPre, folded into the same two launches
         if (d.kind == CONV3) {
             Wgrad3Args w3{dpre, in0, in1, grads + po.conv_w[l], grads + po.conv_b[l], one_reduce ? G(g.WG3[l]) : G(g.WG), nimg};
             Wg3RedArgs* defer = one_reduce ? &RED : nullptr;
@@ -1491,9 +565,18 @@ static int encoder_backward_impl(const float* tsdf, const uint8_t* blob, const u
                 case 4: rc |= WG3(64, 0, 128, 10, 2); break;
                 case 5: rc |= WG3(128, 0, 128, 10, 2); break;
 #undef WG3
-                default: rc |= launch_wgrad(a, ws);
+                default: rc |= -1;                                  // a 3x3 layer without an instantiation
             }
-        } else {
+        } else {                                                    // CONV1 (the 1x1 layer at the end)
+            const int cin = d.cin0 + d.cin1;
+            WgradArgs a{};
+            a.R = dpre; a.csR = d.cout; a.coR = 0;
+            a.C0p = in0; a.C1p = in1; a.csC0 = d.cin0; a.csC1 = d.cin1; a.nC0 = d.cin0;
+            a.dW = grads + po.conv_w[l]; a.sM = cin; a.sN = 1; a.sT = 1;
+            a.kind = d.kind; a.taps = 1; a.Mb = d.cout / 32; a.Nb = cin / 32;
+            a.nimg = nimg; a.H = H; a.W = H;
+            a.partial = G(g.WG);
+            a.db = grads + po.conv_b[l]; a.nbias = d.cout;          // bias gradient = column sums of dPre, folded into the same two launches
             rc |= launch_wgrad(a, ws);
         }
     };

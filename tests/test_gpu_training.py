@@ -2,6 +2,10 @@
 tensor from the HIP backward against torch autograd through the CPU oracle, and against the reference-
 generated golden G4 (losses + per-tensor gradient norms).  fp32; weight gradients are reduced with atomics,
 so the tolerance is relative (2e-3 of the tensor's max |grad|, plus 1e-6 absolute)."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -11,6 +15,7 @@ from giga_amd.training import giga_loss
 from oracle import giga_oracle as O
 
 pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def ref_style_loss(out, y):
@@ -554,18 +559,9 @@ def test_flat_adam_matches_torch_adam(wd):
     assert torch.allclose(sa["exp_avg_sq"], sb["exp_avg_sq"], rtol=1e-5, atol=1e-8)
 
 
-@pytest.mark.parametrize("B", [2, 32])
-def test_bf16_weight_gradient_kernels_with_rounded_operands(sd7, B):
-    """Every bf16 3x3 weight-gradient kernel that runs (csrc/giga_encoder_bwd.hip: the tap-per-wave conv3_wgrad_bf16_taps_kernel for
-    the layers with at most four 32x32 blocks, the output-split conv3_wgrad_bf16_ns_kernel for the wider ones) held to what it is
-    supposed to compute, layer by layer, on the operands the
-    GPU itself used:  dW[co][ci][ky][kx] = sum over images and pixels of bf16(dY[y, x, co]) * bf16(X[y + ky - 1, x + kx - 1, ci])
-    with fp32 accumulation, X zero outside the image (encoder/unet.py:14-23: padding 1) -- so a dropped tap at an image border, a
-    wrong strip boundary or a stale operand shows as a large relative error of ONE tap, which the 2 % whole-network bound of
-    test_bf16_training_step cannot see.  dY and X are read back from the workspaces the C ABI exposes
-    (giga_encoder_workspace_layout, giga_backward_workspace_layout); bias gradients are the column sums of the UNROUNDED dY.
-    Tolerance: 2e-5 of the tensor's range + the fp32 summation noise of ~1e5 products (1e-5 relative of the sum of |products|).
-    B = 2 runs the small-batch strip schedules, B = 32 the c5 shape."""
+def check_bf16_weight_gradients(sd7, B):
+    """Body of test_bf16_weight_gradient_kernels_with_rounded_operands (see there) for one batch size, on whichever bf16 3x3
+    weight-gradient kernels this process's environment selects."""
     import ctypes
 
     import torch.nn.functional as F
@@ -628,6 +624,42 @@ def test_bf16_weight_gradient_kernels_with_rounded_operands(sd7, B):
         wb = dy32.double().sum(dim=(0, 2, 3))
         assert float((gb - wb).abs().max()) <= 2e-5 * max(1.0, float(wb.abs().max())) + 1e-6 * float(dy32.double().abs().sum(dim=(0, 2, 3)).max()), key
     print("bf16 weight gradients with rounded operands: worst error / tolerance", worst)
+
+
+@pytest.mark.parametrize("B", [2, 32])
+def test_bf16_weight_gradient_kernels_with_rounded_operands(sd7, B):
+    """Every bf16 3x3 weight-gradient kernel that runs (csrc/giga_wgrad3.h: the tap-per-wave conv3_wgrad_bf16_taps_kernel for
+    the layers with at most four 32x32 blocks, the output-split conv3_wgrad_bf16_ns_kernel for the wider ones) held to what it is
+    supposed to compute, layer by layer, on the operands the
+    GPU itself used:  dW[co][ci][ky][kx] = sum over images and pixels of bf16(dY[y, x, co]) * bf16(X[y + ky - 1, x + kx - 1, ci])
+    with fp32 accumulation, X zero outside the image (encoder/unet.py:14-23: padding 1) -- so a dropped tap at an image border, a
+    wrong strip boundary or a stale operand shows as a large relative error of ONE tap, which the 2 % whole-network bound of
+    test_bf16_training_step cannot see.  dY and X are read back from the workspaces the C ABI exposes
+    (giga_encoder_workspace_layout, giga_backward_workspace_layout); bias gradients are the column sums of the UNROUNDED dY.
+    Tolerance: 2e-5 of the tensor's range + the fp32 summation noise of ~1e5 products (1e-5 relative of the sum of |products|).
+    B = 2 runs the small-batch strip schedules, B = 32 the c5 shape.
+    This run (default environment) reaches conv3_wgrad_bf16_taps_kernel and conv3_wgrad_bf16_ns_kernel and the single reduce
+    launch; the generic conv3_wgrad_bf16_kernel, which both replace, runs in test_bf16_weight_gradient_generic_kernel."""
+    check_bf16_weight_gradients(sd7, B)
+
+
+def test_bf16_weight_gradient_generic_kernel():
+    """The same check on conv3_wgrad_bf16_kernel for all ten layers: GIGA_WGRAD_TAPS=0 GIGA_WGRAD_NSPLIT=0 (both read once per
+    process, hence a child process).  B = 2: 6 images, every layer has fewer strips than workgroups (one strip per workgroup).
+    B = 11: 33 images -- 330 strips against 256 workgroups at 40x40 and for 64 + 64 -> 64, 165 against 128 for 128 -> 128 -- so
+    some workgroups walk two strips through the prefetch and others one: the ragged case of the persistent strip loop."""
+    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import test_gpu_training as T\n"
+            "from giga_amd import weights\n"
+            "sd7 = weights.make_state_dict(7)\n"
+            "for B in (2, 11):\n"
+            "    T.check_bf16_weight_gradients(sd7, B)\n"
+            "print('ok')\n") % (ROOT, os.path.join(ROOT, "tests"))
+    env = dict(os.environ, GIGA_WGRAD_TAPS="0", GIGA_WGRAD_NSPLIT="0")
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    print(r.stdout[-4000:])
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-3000:] + r.stderr[-3000:]
+    assert r.stdout.count("bf16 weight gradients with rounded operands") == 2
 
 
 def test_conv_in_relu_mask_of_the_training_forward(sd7):
