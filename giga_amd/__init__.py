@@ -3,6 +3,7 @@
     from giga_amd.networks import get_network, load_network     # vgn.networks drop-in (GIGA entries)
     from giga_amd.detection import query_lattice, predict       # vgn.detection_implicit counterpart
     from giga_amd import render_depth, acquire_tsdf, save_occ   # depth images and occupancy labels from meshes (giga_amd.render)
+    from giga_amd import ResidentTrainingSet, ResidentBatches   # training batches from a set in device memory (giga_amd.resident)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/giga_hip.h."""
 __version__ = "0.1.0"
@@ -10,10 +11,15 @@ __version__ = "0.1.0"
 # names of giga_amd.render, resolved on first use (importing the package stays free of torch)
 _RENDER_EXPORTS = ("scene_mesh", "Camera", "render_depth", "render_depth_batch", "acquire_tsdf", "acquire_tsdfs", "write_raw_scenes",
                    "sample_iou_points", "save_occ")
+# ... and of giga_amd.resident: the training set in device memory and its batch iterator
+_RESIDENT_EXPORTS = ("ResidentTrainingSet", "ResidentBatches")
 
 
 def __getattr__(name):
     if name in _RENDER_EXPORTS:
         from . import render
         return getattr(render, name)
+    if name in _RESIDENT_EXPORTS:
+        from . import resident
+        return getattr(resident, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

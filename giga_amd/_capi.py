@@ -157,8 +157,21 @@ _SIGNATURES = {
     "giga_depth_noise_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "giga_depth_noise": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_uint64,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_batch_draw": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 5),
+    "giga_batch_assemble": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 8),
 }
 EXPORTS = tuple(_SIGNATURES)
+BATCH_POINTS = {"float32": 0, "float16": 1}              # GIGA_BATCH_POINTS_F32 / _F16
+BATCH_MAX_ITEMS = 65535  # GIGA_BATCH_MAX_ITEMS
+
+
+class BatchSet(ctypes.Structure):
+    """struct GigaBatchSet of include/giga_hip.h."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("grids", "row_scene", "row_pos", "row_quat", "row_rotations", "row_width",
+                                                      "row_label", "scene_files", "file_points", "points", "occ",
+                                                      "scene_files_host", "file_points_host")] + \
+               [("n_points", ctypes.c_int64), ("n_scenes", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("n_files", ctypes.c_int32),
+                ("point_dtype", ctypes.c_int32), ("size", ctypes.c_double)]
 
 
 class GraspParams(ctypes.Structure):

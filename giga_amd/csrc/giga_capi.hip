@@ -69,6 +69,12 @@ int launch_depth_render(const float* vertices, const int* vertex_offsets, const 
 size_t depth_noise_workspace_bytes(int n);
 int launch_depth_noise(const float* in, float* out, int n, int W, int H, int model, const double* p, unsigned long long seed,
                        const unsigned long long* image_ids, uint8_t* ws, hipStream_t s);
+// giga_batch.hip
+int launch_batch_draw(const GigaBatchSet& set, const int32_t* ordinals, const int32_t* rows, int B, int M, int epoch,
+                      unsigned long long seed, int32_t* quarter, double* u, int32_t* file, int32_t* index, hipStream_t s);
+int launch_batch_assemble(const GigaBatchSet& set, const int32_t* rows, const int32_t* quarter, const double* u, const int32_t* file,
+                          const int32_t* index, int B, int M, int augment, float* x, float* pos, float* pos_occ, float* label,
+                          float* rotations, float* width, float* occ, hipStream_t s);
 // giga_mesh.hip
 size_t mesh_workspace_bytes(int B, int nx, int ny, int nz);
 int launch_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, uint8_t* ws, int* counts, hipStream_t s);
@@ -968,6 +974,63 @@ int giga_depth_noise(const float* depth_in, float* depth_out, int n_images, int 
     if (workspace_bytes < giga_depth_noise_workspace_bytes(n_images, width, height, model)) return -4;
     return launch_depth_noise(depth_in, depth_out, n_images, width, height, model, p, seed, image_ids,
                               static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+// ---- training batches from a resident set (giga_batch.hip) ----
+// everything about the set that can be checked on the host; `all`: giga_batch_assemble reads every array, giga_batch_draw the tables
+// behind the file sizes only
+static int batch_set_check(const GigaBatchSet* set, bool all) {
+    if (!set) return -1;
+    if (set->n_scenes < 0 || set->n_rows < 0 || set->n_files < 0 || set->n_points < 0) return -1;
+    if (!set->row_scene || !set->scene_files || !set->file_points) return -1;
+    if (all) {
+        if (!set->grids || !set->row_pos || !set->row_quat || !set->row_rotations || !set->row_width || !set->row_label ||
+            !set->points || !set->occ)
+            return -1;
+        if (set->point_dtype != GIGA_BATCH_POINTS_F32 && set->point_dtype != GIGA_BATCH_POINTS_F16) return -1;
+        if (!tsdf_finite(set->size) || !(set->size > 0.0)) return -1;
+        if (reinterpret_cast<uintptr_t>(set->grids) % 16 != 0) return -1;
+    }
+    if (set->scene_files_host) {
+        const int32_t* f = set->scene_files_host;
+        if (f[0] != 0 || f[set->n_scenes] != set->n_files) return -1;
+        for (int i = 0; i < set->n_scenes; ++i)
+            if (f[i + 1] < f[i]) return -1;
+    }
+    if (set->file_points_host) {
+        const int64_t* p = set->file_points_host;
+        if (p[0] != 0 || p[set->n_files] != set->n_points) return -1;
+        for (int i = 0; i < set->n_files; ++i)
+            if (p[i + 1] < p[i] || p[i + 1] - p[i] >= (1LL << 31)) return -1;
+    }
+    return 0;
+}
+
+static bool batch_shape_ok(int B, int M) {
+    return B >= 0 && M >= 0 && B <= GIGA_BATCH_MAX_ITEMS && (long long)B * M < (1LL << 31);
+}
+
+int giga_batch_draw(const GigaBatchSet* set, const int32_t* ordinals, const int32_t* rows, int B, int M, int epoch,
+                    unsigned long long seed, int32_t* quarter, double* u, int32_t* file, int32_t* index, void* stream) {
+    if (!batch_shape_ok(B, M) || epoch < 0) return -1;
+    if (const int rc = batch_set_check(set, false)) return rc;
+    if (B == 0) return 0;
+    if (!ordinals || !rows) return -1;
+    if (!quarter || !u || !file || (M > 0 && !index)) return -6;
+    return launch_batch_draw(*set, ordinals, rows, B, M, epoch, seed, quarter, u, file, index, static_cast<hipStream_t>(stream));
+}
+
+int giga_batch_assemble(const GigaBatchSet* set, const int32_t* rows, const int32_t* quarter, const double* u, const int32_t* file,
+                        const int32_t* index, int B, int M, int augment, float* x, float* pos, float* pos_occ, float* label,
+                        float* rotations, float* width, float* occ, void* stream) {
+    if (!batch_shape_ok(B, M)) return -1;
+    if (const int rc = batch_set_check(set, true)) return rc;
+    if (B == 0) return 0;
+    if (!rows || !file || (M > 0 && !index) || (augment && (!quarter || !u))) return -1;
+    if (!x || !pos || !label || !rotations || !width || (M > 0 && (!pos_occ || !occ))) return -6;
+    if (reinterpret_cast<uintptr_t>(x) % 16 != 0) return -1;
+    return launch_batch_assemble(*set, rows, quarter, u, file, index, B, M, augment, x, pos, pos_occ, label, rotations, width, occ,
+                                 static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

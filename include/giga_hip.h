@@ -425,6 +425,87 @@ int giga_depth_noise(const float* depth_in, float* depth_out, int n_images, int 
                      unsigned long long seed, const unsigned long long* image_ids, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ---- input side: training batches from a device-resident training set (the reference's DatasetVoxelOccFile.__getitem__ with its
+ * apply_transform, src/vgn/dataset_voxel.py:55-135, and the DataLoader's collate) -----
+ * GigaBatchSet describes the set; every array is the caller's and is only read.  Device arrays: grids [n_scenes][40][40][40]
+ * float32 (16-byte aligned); per grasp row r: row_scene int32, row_pos [3] float32 (METRIC position of the grasp table), row_quat
+ * [4] float32 (x, y, z, w as in the table), row_rotations [2][4] float32 (the two gripper rotations of the un-augmented item),
+ * row_width float32 (metric), row_label float32; scene_files [n_scenes + 1] int32: the files of scene s are scene_files[s] ..
+ * scene_files[s + 1] - 1, in the order the host reader lists them; file_points [n_files + 1] INT64: the points of file f are
+ * file_points[f] .. file_points[f + 1] - 1 (a set may hold more than 2^31 points; one file holds fewer); points [n_points][3] of
+ * point_dtype (GIGA_BATCH_POINTS_F32 / _F16), occ [n_points] uint8.  scene_files_host / file_points_host: HOST copies of the two
+ * offset arrays or NULL; where given they are checked (first entry 0, non-decreasing, last entry n_files / n_points) before the
+ * first HIP call -- pass them on the first call for a set, NULL afterwards.  size: the workspace edge length of setup.json.
+ *
+ * giga_batch_draw: the random draws of B items.  ordinals [B] int32 (device): an item's position in its epoch's order; rows [B]
+ * int32 (device): its grasp row.  Philox-4x32-10 (as giga_depth_noise) on the counter (block, ordinal, epoch, stream) with the key
+ * (seed & 0xffffffff, seed >> 32), so an item's draws depend on (seed, epoch, ordinal) and its scene's file sizes only: not on the
+ * batch size, the batch it falls in or the rank.  mulhi(a, b) = (a b) >> 32 on 64-bit integers.
+ *   stream 0, block 0, words x0..x3:  quarter [B] int32 = x0 >> 30;  u [B] FLOAT64 = 6 + 28 (x1 2^-32) in double;  file [B] int32 =
+ *     mulhi(x3, number of files of the row's scene): the index into the scene's file list.
+ *   stream 1: index [B][M] int32 into the drawn file of n points.
+ *     M > n   with replacement: word (m & 3) of block (m >> 2) gives index[m] = mulhi(word, n).
+ *     M <= n  M distinct indices index[m] = pi(m), pi a keyed bijection of [0, n): n = 1 gives 0; otherwise a balanced Feistel
+ *             network on b bits, b the smallest even number >= 2 with 2^b >= n, halves of h = b / 2 bits, v = m = (L << h) | R,
+ *             GIGA_BATCH_FEISTEL_ROUNDS rounds (L, R) <- (R, L ^ (fmix32(R ^ k_r) & (2^h - 1))) with k_r = x[r & 3] + r 0x9E3779B9
+ *             (mod 2^32), x the words of block 0, and fmix32 MurmurHash3's finaliser (h ^= h >> 16, h *= 0x85ebca6b, h ^= h >> 13,
+ *             h *= 0xc2b2ae35, h ^= h >> 16).  The network is applied again while v >= n (cycle walking: it is a bijection of
+ *             [0, 2^b), so the walk returns below n after at most 2^b - n + 1 < 3 n + 2 applications, the bound of the loop; each
+ *             application ends the walk with probability n / 2^b > 1/4).  Each m is evaluated on its own.
+ * giga_batch_assemble: the batch of B items from forced draws (quarter, u, file, index as above, device).  For item b with row r
+ * and scene s = row_scene[r]:
+ *   x [B][40][40][40] (16-byte aligned)  augment == 0: grids[s].  Otherwise z_off = u - double(row_pos[r][2]) and output voxel
+ *     (i, j, k) reads source (s_i, s_j, s_k): (s_i, s_j) = (i, j), (j, 40 - i), (40 - i, 40 - j), (40 - j, i) for quarter 0..3;
+ *     c = double(k) - z_off, s_k = floor(c + 0.5); the value is grids[s][s_i][s_j][s_k] where 0 <= s_i, s_j <= 39 and 0 <= c <= 39
+ *     and 0 elsewhere: scipy.ndimage.affine_transform(order=0, mode="constant") about the centre (20, 20, 20), with exact integers
+ *     in x and y (scipy's own in-range test of a source index of exactly 0 or 39 hangs on the rounding of its rotation matrix).
+ *   pos [B][3]  augment == 0: float32 arithmetic, row_pos / float(size) - 0.5.  Otherwise in double: d = (x - 20, y - 20) turned to
+ *     (dx, dy), (-dy, dx), (-dx, -dy), (dy, -dx) for quarter 0..3, plus 20; z' = z + z_off; then p' / size - 0.5, rounded once to
+ *     float32 (the reference transforms the metric position with these voxel-unit offsets; restated as it is).
+ *   rotations [B][2][4]  augment == 0: row_rotations.  Otherwise in double: o = row_quat / sqrt(((x^2 + y^2) + z^2) + w^2), then
+ *     rot[0] = q_aug (x) o = (c o.x - s o.y, c o.y + s o.x, c o.z + s o.w, c o.w - s o.z) with (s, c) = (sin, cos)(quarter pi / 4) the
+ *     doubles (0, 1), (0.7071067811865475, 0.7071067811865476), (1, 6.123233995736766e-17), (0.7071067811865476,
+ *     -0.7071067811865475); rot[1] = rot[0] (x) (0, 0, 1, 0) = (r.y, -r.x, r.w, -r.z); each rounded once to float32.
+ *   width [B] = row_width / float(size) in float32; label [B] = row_label.
+ *   pos_occ [B][M][3] = points[file_points[scene_files[s] + file] + index[m]] / size - 0.5 in the points' own type, then widened:
+ *     float32 points: (p / float(size)) - 0.5f.  float16 points: size rounded to float16, the quotient of the two as float32 rounded
+ *     to float16, minus 0.5 as float32 rounded to float16 (what numpy computes).  occ [B][M] = the byte as float.
+ * All double arithmetic is one IEEE rounding per operation (compiled without contraction); equal input gives equal bytes (no
+ * atomics).  A row, file or index outside its range (possible only with inconsistent input) yields zeros, never an access outside
+ * the set.  Both calls are asynchronous on `stream`, allocate nothing, and are one launch each.
+ * Every argument is checked before the first HIP call.  Errors: -1 null set, rows, ordinals or draws, a null array of the set,
+ * negative B, M, epoch or counts, B > GIGA_BATCH_MAX_ITEMS, unknown point_dtype, size not finite or not > 0, misaligned grids or x,
+ * host offsets that do not start at 0, decrease, or end elsewhere than n_files / n_points; -6 a null output (index, pos_occ and occ
+ * may be null when M = 0).  B = 0 returns 0. */
+#define GIGA_BATCH_RES 40
+#define GIGA_BATCH_POINTS_F32 0
+#define GIGA_BATCH_POINTS_F16 1
+#define GIGA_BATCH_FEISTEL_ROUNDS 8
+#define GIGA_BATCH_MAX_ITEMS 65535
+typedef struct GigaBatchSet {
+    const float* grids;
+    const int32_t* row_scene;
+    const float* row_pos;
+    const float* row_quat;
+    const float* row_rotations;
+    const float* row_width;
+    const float* row_label;
+    const int32_t* scene_files;
+    const int64_t* file_points;
+    const void* points;
+    const uint8_t* occ;
+    const int32_t* scene_files_host;
+    const int64_t* file_points_host;
+    int64_t n_points;
+    int32_t n_scenes, n_rows, n_files, point_dtype;
+    double size;
+} GigaBatchSet;
+int giga_batch_draw(const GigaBatchSet* set, const int32_t* ordinals, const int32_t* rows, int B, int M, int epoch,
+                    unsigned long long seed, int32_t* quarter, double* u, int32_t* file, int32_t* index, void* stream);
+int giga_batch_assemble(const GigaBatchSet* set, const int32_t* rows, const int32_t* quarter, const double* u, const int32_t* file,
+                        const int32_t* index, int B, int M, int augment, float* x, float* pos, float* pos_occ, float* label,
+                        float* rotations, float* width, float* occ, void* stream);
+
 /* ---- fused training loss (scripts/train_giga.py:154-195: `select` + `loss_fn`, literal call shape N = 1) -----
  * Inputs are the head outputs of the model's forward for one grasp query per scene -- qual [B] (post sigmoid), rot [B][4]
  * (unit), width [B], occ_logits [B][M] (raw; the sigmoid of `select` is part of this function) -- and the labels of
