@@ -4,6 +4,7 @@
     from giga_amd.detection import query_lattice, predict       # vgn.detection_implicit counterpart
     from giga_amd import render_depth, acquire_tsdf, save_occ   # depth images and occupancy labels from meshes (giga_amd.render)
     from giga_amd import ResidentTrainingSet, ResidentBatches   # training batches from a set in device memory (giga_amd.resident)
+    from giga_amd import Trainer, train_val_split               # the training loop of scripts/train_giga.py (giga_amd.trainer)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/giga_hip.h."""
 __version__ = "0.1.0"
@@ -13,6 +14,8 @@ _RENDER_EXPORTS = ("scene_mesh", "Camera", "render_depth", "render_depth_batch",
                    "sample_iou_points", "save_occ")
 # ... and of giga_amd.resident: the training set in device memory and its batch iterator
 _RESIDENT_EXPORTS = ("ResidentTrainingSet", "ResidentBatches")
+# ... and of giga_amd.trainer: the training loop, its device-side epoch metrics and the train / validation split
+_TRAINER_EXPORTS = ("Trainer", "TrainMetrics", "train_val_split")
 
 
 def __getattr__(name):
@@ -22,4 +25,7 @@ def __getattr__(name):
     if name in _RESIDENT_EXPORTS:
         from . import resident
         return getattr(resident, name)
+    if name in _TRAINER_EXPORTS:
+        from . import trainer
+        return getattr(trainer, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

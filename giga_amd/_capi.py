@@ -101,6 +101,7 @@ _SIGNATURES = {
                                             ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     "giga_train_loss": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                                ctypes.c_void_p]),
+    "giga_train_loss_metrics": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4),
     "giga_train_loss_backward": (ctypes.c_int, [ctypes.c_void_p] * 9 + [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5),
     "giga_adam_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                       ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
@@ -163,6 +164,7 @@ _SIGNATURES = {
 EXPORTS = tuple(_SIGNATURES)
 BATCH_POINTS = {"float32": 0, "float16": 1}              # GIGA_BATCH_POINTS_F32 / _F16
 BATCH_MAX_ITEMS = 65535  # GIGA_BATCH_MAX_ITEMS
+TRAIN_METRICS_BYTES = 128  # GIGA_TRAIN_METRICS_BYTES
 
 
 class BatchSet(ctypes.Structure):

@@ -45,6 +45,9 @@ int launch_dect_reduce(const DectPending& pend, float* grads, int head_present, 
 int launch_train_loss(const float* qual, const float* rot, const float* width, const float* occ, const float* label,
                       const float* rot_t, const float* width_t, const float* occ_t, int B, int M, float* losses,
                       float* scene_loss, hipStream_t s);
+int launch_train_loss_metrics(const float* qual, const float* rot, const float* width, const float* occ, const float* label,
+                              const float* rot_t, const float* width_t, const float* occ_t, int B, int M, float* losses,
+                              float* scene_loss, void* acc, hipStream_t s);
 int launch_train_loss_backward(const float* qual, const float* rot, const float* width, const float* occ,
                                const float* label, const float* rot_t, const float* width_t, const float* occ_t,
                                const float* gout, int B, int M, float* dqual, float* drot, float* dwidth, float* docc,
@@ -707,6 +710,18 @@ int giga_train_loss(const float* qual, const float* rot, const float* width, con
     if (M > 0 && (!occ_logits || !occ_target)) return -1;
     return launch_train_loss(qual, rot, width, occ_logits, label, rot_targets, width_target, occ_target, B, M, losses,
                              scene_losses, static_cast<hipStream_t>(stream));
+}
+
+int giga_train_loss_metrics(const float* qual, const float* rot, const float* width, const float* occ_logits, const float* label,
+                            const float* rot_targets, const float* width_target, const float* occ_target, int B, int M,
+                            float* losses, float* scene_losses, void* acc, void* stream) {
+    if (B < 0 || M < 0) return -1;
+    if (!acc || (reinterpret_cast<uintptr_t>(acc) & 7)) return -1;
+    if (B == 0) return 0;
+    if (!qual || !rot || !width || !label || !rot_targets || !width_target || !losses || !scene_losses) return -1;
+    if (M > 0 && (!occ_logits || !occ_target)) return -1;
+    return launch_train_loss_metrics(qual, rot, width, occ_logits, label, rot_targets, width_target, occ_target, B, M, losses,
+                                     scene_losses, acc, static_cast<hipStream_t>(stream));
 }
 
 int giga_train_loss_backward(const float* qual, const float* rot, const float* width, const float* occ_logits,

@@ -74,6 +74,66 @@ __global__ __launch_bounds__(64) void loss_mean_kernel(const float* __restrict__
     losses[k] = s / (float)B;
 }
 
+// The mean launch of a training loop (giga_train_loss_metrics): the same five means, and the epoch accumulator of
+// include/giga_hip.h updated from this batch -- uint64 words 0-6 (batches, examples, correct, tp, fp, fn, invalid), double
+// words 8-12 (running sums of the batch means); words 7 and 13-15 are not touched.  One workgroup of four waves.  Lanes 0-4 of
+// wave 0 compute the means exactly as loss_mean_kernel does (same loop, same fp32 sum); that serial loop is the launch's critical
+// path, so wave 0 does nothing else beside it: lane 0 loads the twelve accumulator words first (their latency passes under the
+// loop), and waves 1-3 classify the scenes meanwhile, b = lane, lane + 192, ... (a uniform trip count, so each ballot sees whole
+// waves): prediction qual > 0.5f (torch.round of a sigmoid output, half to even), valid when 0 <= qual <= 1 and label is exactly
+// 0 or 1.  Counts are popcounts of ballots per wave, summed over the three waves through LDS in wave order by lane 0, which alone
+// reads, updates and writes `acc`.  Integer counts and one double addition per sum: no atomics and nothing whose order could
+// vary, so the accumulator is a pure function of the calls.
+__global__ __launch_bounds__(256) void loss_mean_metrics_kernel(const float* __restrict__ scene_loss, const float* __restrict__ qual,
+                                                                const float* __restrict__ label, int B, float* losses,
+                                                                unsigned long long* acc) {
+    __shared__ unsigned cnt[3][6];                              // per counting wave: examples, correct, tp, fp, fn, invalid
+    __shared__ float mean[5];
+    const int tid = threadIdx.x;
+    // thread 0's view of `acc`: + 0 as a per-lane value (every lane is active here), so that its accesses are vector loads and
+    // stores, not reads through the scalar cache; no other thread uses it
+    unsigned long long* const words = acc + __builtin_amdgcn_mbcnt_lo(~0u, 0u);
+    unsigned long long old[7];
+    double old_sum[5];
+    if (tid == 0) {
+        for (int k = 0; k < 7; ++k) old[k] = words[k];
+        for (int k = 0; k < 5; ++k) old_sum[k] = reinterpret_cast<const double*>(words)[8 + k];
+    }
+    if (tid < 64) {
+        if (tid < 5) {
+            float s = 0.f;
+            for (int b = 0; b < B; ++b) s += scene_loss[5 * b + tid];
+            const float m = s / (float)B;
+            losses[tid] = m;
+            mean[tid] = m;
+        }
+    } else {
+        const int lane = tid - 64;
+        unsigned c[6] = {0, 0, 0, 0, 0, 0};
+        for (long long base = 0; base < B; base += 192) {       // (64-bit: base + 192 passes INT_MAX for the largest B)
+            const long long b = base + lane;
+            const bool in = b < B;
+            const float q = in ? qual[b] : 0.f, y = in ? label[b] : 0.f;
+            const bool valid = in && q >= 0.f && q <= 1.f && (y == 0.f || y == 1.f);
+            const bool pred = q > 0.5f, pos = y == 1.f;
+            c[0] += __popcll(__ballot(valid));
+            c[1] += __popcll(__ballot(valid && pred == pos));
+            c[2] += __popcll(__ballot(valid && pred && pos));
+            c[3] += __popcll(__ballot(valid && pred && !pos));
+            c[4] += __popcll(__ballot(valid && !pred && pos));
+            c[5] += __popcll(__ballot(in && !valid));
+        }
+        if ((lane & 63) == 0)
+            for (int k = 0; k < 6; ++k) cnt[lane >> 6][k] = c[k];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        words[0] = old[0] + 1ull;
+        for (int k = 0; k < 6; ++k) words[1 + k] = old[1 + k] + ((unsigned long long)cnt[0][k] + cnt[1][k] + cnt[2][k]);
+        for (int k = 0; k < 5; ++k) reinterpret_cast<double*>(words)[8 + k] = old_sum[k] + (double)mean[k];
+    }
+}
+
 // gradients of `loss` (times the upstream scalar *gout) with respect to the head outputs
 __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict__ qual, const float* __restrict__ rot,
                                                         const float* __restrict__ width, const float* __restrict__ occ,
@@ -114,6 +174,16 @@ int launch_train_loss(const float* qual, const float* rot, const float* width, c
     GIGA_LAUNCH(loss_scene_kernel, dim3(B), dim3(256), 0, s, qual, rot, width, occ, label, rot_t, width_t, occ_t, M,
                        scene_loss);
     GIGA_LAUNCH(loss_mean_kernel, dim3(1), dim3(64), 0, s, scene_loss, B, losses);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int launch_train_loss_metrics(const float* qual, const float* rot, const float* width, const float* occ, const float* label,
+                              const float* rot_t, const float* width_t, const float* occ_t, int B, int M, float* losses,
+                              float* scene_loss, void* acc, hipStream_t s) {
+    GIGA_LAUNCH(loss_scene_kernel, dim3(B), dim3(256), 0, s, qual, rot, width, occ, label, rot_t, width_t, occ_t, M,
+                       scene_loss);
+    GIGA_LAUNCH(loss_mean_metrics_kernel, dim3(1), dim3(256), 0, s, scene_loss, qual, label, B, losses,
+                       static_cast<unsigned long long*>(acc));
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 

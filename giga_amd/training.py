@@ -270,7 +270,7 @@ LOSS_KEYS = ("loss_qual", "loss_rot", "loss_width", "loss_occ", "loss_all")     
 
 class _GigaLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qual, rot, width, occ, label, rot_t, width_t, occ_t):
+    def forward(ctx, acc, qual, rot, width, occ, label, rot_t, width_t, occ_t):
         L = _capi.lib()
         B, M = occ.shape[0], occ.shape[1]
         dev = occ.device
@@ -278,8 +278,12 @@ class _GigaLoss(torch.autograd.Function):
         losses = torch.empty(5, device=dev)
         scene = torch.empty((B, 5), device=dev)
         with torch.cuda.device(dev):
-            _capi.check(L.giga_train_loss(*[_capi.ptr(t) for t in args], B, M, _capi.ptr(losses), _capi.ptr(scene),
-                                          _capi.stream_ptr(dev)), "giga_train_loss")
+            if acc is None:
+                _capi.check(L.giga_train_loss(*[_capi.ptr(t) for t in args], B, M, _capi.ptr(losses), _capi.ptr(scene),
+                                              _capi.stream_ptr(dev)), "giga_train_loss")
+            else:                                            # the same two launches; the mean launch also updates the epoch accumulator
+                _capi.check(L.giga_train_loss_metrics(*[_capi.ptr(t) for t in args], B, M, _capi.ptr(losses), _capi.ptr(scene),
+                                                      _capi.ptr(acc), _capi.stream_ptr(dev)), "giga_train_loss_metrics")
         ctx.save_for_backward(*args)
         ctx.shapes = (qual.shape, rot.shape, width.shape, occ.shape)
         parts = losses[:4]
@@ -299,15 +303,19 @@ class _GigaLoss(torch.autograd.Function):
             _capi.check(L.giga_train_loss_backward(*[_capi.ptr(t) for t in args], _capi.ptr(g), B, M, _capi.ptr(dq),
                                                    _capi.ptr(dr), _capi.ptr(dw), _capi.ptr(do), _capi.stream_ptr(dev)),
                         "giga_train_loss_backward")
-        return dq, dr, dw, do, None, None, None, None
+        return None, dq, dr, dw, do, None, None, None, None
 
 
-def giga_loss(out, y):
+def giga_loss(out, y, metrics=None):
     """Fused `loss_fn(select(out), y)` of scripts/train_giga.py:154-195 for the literal call shape.
 
     out: the model's 4-tuple for ONE grasp query per scene -- qual (B,1), rot (B,1,4), width (B,1), occupancy logits (B,M);
     y:   (label (B,), rotations (B,2,4), width (B,), occ (B,M)) as `prepare_batch` builds them (train_giga.py:141-151).
-    Returns (loss, loss_dict) with the reference's keys; `loss` is differentiable w.r.t. the four head outputs."""
+    Returns (loss, loss_dict) with the reference's keys; `loss` is differentiable w.r.t. the four head outputs.
+    metrics: a `giga_amd.trainer.TrainMetrics`; the loss launch then also adds this batch to its device accumulator (accuracy,
+    precision and recall counts of round(qual) against label, running sums of the five means: giga_train_loss_metrics), with the
+    same returned values and the same backward.  An empty batch leaves the accumulator alone.  For `giga_aff` (no occupancy head)
+    pass occupancy logits and targets of shape (B, 0)."""
     qual, rot, width, occ = out
     label, rot_t, width_t, occ_t = y
     _capi.require_device(qual, rot, width, occ, label, rot_t, width_t, occ_t)
@@ -322,7 +330,12 @@ def giga_loss(out, y):
     if B == 0:                                               # F.*_loss(...).mean() of an empty batch
         nan = occ.new_full((), float("nan")) + 0.0 * occ.sum()
         return nan, {k: nan.detach() for k in LOSS_KEYS}
-    loss, parts = _GigaLoss.apply(qual, rot, width, occ, label, rot_t, width_t, occ_t)
+    acc = None
+    if metrics is not None:
+        acc = metrics.acc
+        if _capi.device_of(acc) != occ.device or acc.dtype != torch.int64 or acc.numel() * 8 != _capi.TRAIN_METRICS_BYTES:
+            raise ValueError("giga_loss: `metrics` is a TrainMetrics on the device of the head outputs")
+    loss, parts = _GigaLoss.apply(acc, qual, rot, width, occ, label, rot_t, width_t, occ_t)
     d = {k: parts[i] for i, k in enumerate(LOSS_KEYS[:4])}
     d["loss_all"] = loss.detach()
     return loss, d

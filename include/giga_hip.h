@@ -524,6 +524,25 @@ int giga_train_loss_backward(const float* qual, const float* rot, const float* w
                              const float* occ_target, const float* grad_loss, int B, int M, float* dqual, float* drot,
                              float* dwidth, float* docc, void* stream);
 
+/* giga_train_loss with the metrics of a training epoch (scripts/train_giga.py:53-59: ignite's Accuracy, Precision, Recall and five
+ * Averages) accumulated by the mean launch itself: still two launches, and `losses` / `scene_losses` get the bytes giga_train_loss
+ * writes.  `acc`: GIGA_TRAIN_METRICS_BYTES of device memory owned by the caller, 8-byte aligned, sixteen 8-byte words:
+ *   words 0-6  uint64  batches, examples, correct, tp, fp, fn, invalid
+ *   word  7            reserved, left as found
+ *   words 8-12 double  running sums of the batch means, in the order of scene_losses' columns (qual, rot, width, occ, all)
+ *   words 13-15        reserved, left as found
+ * The prediction of a scene is torch.round(qual), i.e. qual > 0.5f (half to even: 0.5 itself rounds to 0).  A scene is valid when
+ * 0 <= qual <= 1 (so not NaN) and label is exactly 0 or 1; a valid scene adds to `examples` and to `correct` (pred == label), `tp`
+ * (pred 1, label 1), `fp` (pred 1, label 0), `fn` (pred 0, label 1); any other scene adds 1 to `invalid` only.  Each call adds 1 to
+ * `batches` and (double)losses[k] to sum k.  One workgroup, one lane updates `acc` with plain loads and stores: no atomics, so the
+ * accumulator after a sequence of calls on one stream is a pure function of the inputs in call order.  The caller zeroes `acc` at
+ * the start of an epoch.  Checks: those of giga_train_loss, and `acc` non-null and 8-byte aligned (-1); B == 0 returns 0 and leaves
+ * `acc` untouched. */
+#define GIGA_TRAIN_METRICS_BYTES 128
+int giga_train_loss_metrics(const float* qual, const float* rot, const float* width, const float* occ_logits, const float* label,
+                            const float* rot_targets, const float* width_target, const float* occ_target, int B, int M,
+                            float* losses, float* scene_losses, void* acc, void* stream);
+
 /* Adam over ONE flat fp32 buffer (the flattened parameters of the module, `net.flatten_parameters()`), in place: the update of
  * torch.optim.Adam (the reference's optimiser, scripts/train_giga.py:49; no amsgrad), formulas and order of torch/optim/adam.py:
  * m = lerp(m, g, 1 - beta1); v = beta2 v + (1 - beta2) g^2; p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps);
