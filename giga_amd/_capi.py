@@ -29,7 +29,8 @@ CONV16_UNET = 256        # GIGA_CONV16_UNET: ... on the conv16 kernels
 DIRECT_CONV = 1024       # GIGA_DIRECT_CONV: precision 0 keeps the direct 3x3 convolutions (default: Winograd F(2x2, 3x3), csrc/giga_wino.h)
 PATH_PERSISTENT, PATH_CONV32, PATH_FUSED_PAIRS, PATH_WINOGRAD = 1, 2, 4, 8          # giga_encoder_last_path()
 BWD_PATH_PERSISTENT, BWD_PATH_WINOGRAD, BWD_PATH_BF16 = 1, 2, 4                      # giga_backward_last_path()
-MESH_MAX_N = 256         # GIGA_MESH_MAX_N: samples per axis of a marching-cubes grid
+MESH_MAX_N = 513         # GIGA_MESH_MAX_N: samples per axis of a marching-cubes grid
+MISE_MAX_N = 513         # GIGA_MISE_MAX_N: samples per axis of a MISE value grid (resolution0 << depth) + 1
 TSDF_MAX_R = 512         # GIGA_TSDF_MAX_R: cells per axis of a fused volume
 RENDER_MAX_IMAGE = 4096  # GIGA_RENDER_MAX_IMAGE: width and height of a rendered depth image
 NOISE_MODEL = {"dex": 1, "trans": 2, "norm": 3}          # GIGA_NOISE_DEX / _TRANS / _NORM
@@ -144,6 +145,14 @@ _SIGNATURES = {
     "giga_mesh_emit": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
                                       ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
                                       ctypes.c_void_p, ctypes.c_void_p]),
+    "giga_mise_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "giga_mise_init": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_mise_count": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "giga_mise_emit": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
+                       + [ctypes.c_void_p] * 4),
+    "giga_mise_update": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_int] * 3
+                         + [ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_mise_to_dense": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     "giga_nn_query_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
     "giga_nn_query": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]),
     "giga_mesh_sample_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),

@@ -83,6 +83,15 @@ size_t mesh_workspace_bytes(int B, int nx, int ny, int nz);
 int launch_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, uint8_t* ws, int* counts, hipStream_t s);
 int launch_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso, double box, const uint8_t* ws, float* vertices,
                      size_t cap_v, int* triangles, size_t cap_t, int* shortfall, hipStream_t s);
+// giga_mise.hip
+size_t mise_workspace_bytes(int B, int res0, int depth);
+int launch_mise_init(int B, int res0, int depth, uint8_t* ws, hipStream_t s);
+int launch_mise_count(int B, int res0, int depth, uint8_t* ws, int* counts, hipStream_t s);
+int launch_mise_emit(int B, int res0, int depth, const uint8_t* ws, int* query, size_t cap, int* shortfall, const float* lin,
+                     float* points, hipStream_t s);
+int launch_mise_update(const float* values, const int* query, size_t cap, int B, int res0, int depth, double thr, uint8_t* ws,
+                       hipStream_t s);
+int launch_mise_to_dense(int B, int res0, int depth, const uint8_t* ws, float* grid, hipStream_t s);
 // giga_eval.hip
 size_t nn_workspace_bytes(int B, int n_src);
 int launch_nn_query(const float* src, const int* src_offsets, const float* tgt, const int* tgt_offsets, int B, float* dist,
@@ -750,6 +759,8 @@ int giga_adam_step(float* params, const float* grads, float* exp_avg, float* exp
 }
 
 // ---- marching cubes (giga_mesh.hip) ----
+// counts and triangle entries are int32: a scene has at most 3 vertices and 5 triangles per cell
+static_assert(5LL * (GIGA_MESH_MAX_N + 1) * (GIGA_MESH_MAX_N + 1) * (GIGA_MESH_MAX_N + 1) < (1LL << 31), "per-scene counts are int32");
 // 0 when the shape is supported, else the error code
 static int mesh_shape_check(int B, int nx, int ny, int nz) {
     if (B < 0 || nx < 2 || ny < 2 || nz < 2) return -1;
@@ -783,6 +794,70 @@ int giga_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso
     if (workspace_bytes < giga_mesh_workspace_bytes(B, nx, ny, nz)) return -4;
     return launch_mesh_emit(grids, B, nx, ny, nz, iso, box_size, static_cast<const uint8_t*>(workspace), vertices, cap_v, triangles,
                             cap_t, shortfall, static_cast<hipStream_t>(stream));
+}
+
+// ---- MISE (giga_mise.hip) ----
+// 0 when the tree shape is supported, else the error code
+static int mise_shape_check(int B, int res0, int depth) {
+    if (B < 0 || res0 < 1 || depth < 1 || depth > 30) return -1;
+    if (((long long)res0 << depth) + 1 > GIGA_MISE_MAX_N) return -1;
+    if (B > GIGA_MAX_SCENES) return -7;
+    const long long N = ((long long)res0 << depth) + 1;
+    if ((long long)B * N * N * N >= (1LL << 31)) return -1;                           // sample numbers are 32-bit
+    return 0;
+}
+
+size_t giga_mise_workspace_bytes(int B, int resolution0, int depth) {
+    if (B <= 0 || mise_shape_check(B, resolution0, depth) != 0) return 0;
+    return mise_workspace_bytes(B, resolution0, depth);
+}
+
+int giga_mise_init(int B, int resolution0, int depth, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
+    if (B == 0) return 0;
+    if (!workspace) return -1;
+    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
+    return launch_mise_init(B, resolution0, depth, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+int giga_mise_count(int B, int resolution0, int depth, void* workspace, size_t workspace_bytes, int32_t* counts, void* stream) {
+    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
+    if (B == 0) return 0;
+    if (!workspace || !counts) return -1;
+    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
+    return launch_mise_count(B, resolution0, depth, static_cast<uint8_t*>(workspace), counts, static_cast<hipStream_t>(stream));
+}
+
+int giga_mise_emit(int B, int resolution0, int depth, const void* workspace, size_t workspace_bytes, int32_t* query, size_t cap,
+                   int32_t* shortfall, const float* lin, float* points, void* stream) {
+    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
+    if (B == 0) return 0;
+    if (!workspace || (points && !lin)) return -1;
+    if (cap > 0 && !query) return -6;
+    if ((unsigned long long)B * cap >= (1ull << 31)) return -1;
+    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
+    return launch_mise_emit(B, resolution0, depth, static_cast<const uint8_t*>(workspace), query, cap, shortfall, lin, points,
+                            static_cast<hipStream_t>(stream));
+}
+
+int giga_mise_update(const float* values, const int32_t* query, size_t cap, int B, int resolution0, int depth, double threshold,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
+    if (!(threshold == threshold)) return -1;
+    if (B == 0) return 0;
+    if (!workspace || (cap > 0 && (!values || !query))) return -1;
+    if ((unsigned long long)B * cap >= (1ull << 31)) return -1;
+    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
+    return launch_mise_update(values, query, cap, B, resolution0, depth, threshold, static_cast<uint8_t*>(workspace),
+                              static_cast<hipStream_t>(stream));
+}
+
+int giga_mise_to_dense(int B, int resolution0, int depth, const void* workspace, size_t workspace_bytes, float* grid, void* stream) {
+    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
+    if (B == 0) return 0;
+    if (!workspace || !grid) return -1;
+    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
+    return launch_mise_to_dense(B, resolution0, depth, static_cast<const uint8_t*>(workspace), grid, static_cast<hipStream_t>(stream));
 }
 
 // ---- mesh evaluation (giga_eval.hip) ----

@@ -22,6 +22,7 @@
 // Integer work on a few bytes per cell: no MFMA, 4.3 KB of LDS for the case tables (read with a divergent index).
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "giga_scan.h"
 #define GIGA_MC_QUAL __device__ __attribute__((aligned(16)))
 #include "giga_mc_tables.h"
 #include <cmath>
@@ -121,17 +122,6 @@ __global__ __launch_bounds__(MESH_BLOCK) void mesh_classify_kernel(const float* 
     block_scan(flags, nt, wsum, pv, pt, totv, tott);
     if (cell < d.cells) words[(size_t)scene * d.cells + cell] = pv << 3 | flags;
     if (threadIdx.x == 0) blk[(size_t)scene * d.nblk + blockIdx.x] = make_uint2(totv, tott);
-}
-
-// inclusive scan across a wave by shuffles (fixed order)
-template <typename T>
-__device__ __forceinline__ T wave_incl(T x, unsigned lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T y = __shfl_up(x, o, 64);
-        if (lane >= (unsigned)o) x += y;
-    }
-    return x;
 }
 
 __global__ __launch_bounds__(SCAN_BLOCK) void mesh_scan_kernel(uint2* __restrict__ blk, unsigned nblk, int* __restrict__ counts) {

@@ -12,11 +12,15 @@ queries takes the lattice path (each plane sampled once per lattice coordinate p
 Mesh extraction (`generate_mesh`, `generate_from_latent`, `extract_mesh`, generation.py:68-148, 360-428) runs on the device
 too: marching cubes is csrc/giga_mesh.hip (the reference pads the grid on the host and calls libmcubes), the vertices stay
 on the device for `estimate_normals`, and the only device-to-host traffic before the final copy of the mesh is the B x 2
-vertex / triangle counts.  MISE (utils/libmise) is NOT built: it exists to save decoder evaluations on a CPU by refining
-only cells next to the surface, and the dense grid of its `to_dense()` shape -- resolution0 * 2**upsampling_steps + 1
-samples per axis, 129^3 by default -- is one decoder launch here.  The mesh equals the reference's wherever MISE evaluated
-every sample next to the surface; it can contain components smaller than a coarse cell, which MISE skips.  Mesh
-refinement (`refinement_step`), simplification (`simplify_nfaces`) and the crop mode (`vol_bound`) are not built."""
+vertex / triangle counts.  The value grid has the shape of MISE's `to_dense()` -- resolution0 * 2**upsampling_steps + 1 samples
+per axis, 129^3 by default -- and is filled in one of two ways.  By default (`mise=False`) every sample is decoded, in one launch;
+the mesh then equals the reference's wherever MISE evaluated every sample next to the surface, and it can contain components
+smaller than a coarse cell, which MISE skips.  With `mise=True` (and upsampling_steps > 0) the grid is the reference's: MISE
+(utils/libmise/mise.pyx) runs on the device (`giga_amd.mise`, csrc/giga_mise.hip), bit for bit libmise's bookkeeping -- decode the
+coarse lattice, subdivide only voxels that see both sides of the threshold, repeat, `to_dense()` -- with one decoder launch per
+round over all scenes and the B list lengths as the only device-to-host traffic of a round; it is also the route to the grids the
+dense one cannot afford (257^3, 513^3).  Mesh refinement (`refinement_step`), simplification (`simplify_nfaces`) and the crop mode
+(`vol_bound`) are not built."""
 import time
 
 import numpy as np
@@ -25,6 +29,7 @@ import torch
 from . import _capi
 from .convonet import _planes_to_nhwc, decoder_point_grad, register_lattice
 from .mesh import Mesh, marching_cubes
+from .mise import lin_table, mise_grid
 
 
 class Generator3D:
@@ -32,10 +37,11 @@ class Generator3D:
 
     def __init__(self, model, points_batch_size=100000, threshold=0.5, device=None, resolution0=16, upsampling_steps=3,
                  with_normals=False, padding=0.1, refinement_step=0, simplify_nfaces=None, sample=False, input_type=None,
-                 vol_info=None, vol_bound=None):
+                 vol_info=None, vol_bound=None, mise=False):
         """The reference's arguments by name (generation.py:42-49).  `refinement_step > 0` (second-order point gradients) and
         `simplify_nfaces` (quadric simplification) are not built and raise here; `vol_bound` (crop mode) raises when a mesh
-        is asked for.  `mesh_options` records the mesh arguments as a dict."""
+        is asked for.  `mesh_options` records the mesh arguments as a dict.  `mise=True` fills the value grid by MISE as the
+        reference does (module docstring); the default decodes every sample."""
         if refinement_step:
             raise NotImplementedError("mesh refinement (refinement_step > 0) is not built")
         if simplify_nfaces is not None:
@@ -54,6 +60,7 @@ class Generator3D:
         self.padding = padding
         self.simplify_nfaces = None
         self.mesh_options = dict(mesh_options)
+        self.mise = bool(mise)
         self._grids = {}
 
     def encode(self, inputs):
@@ -140,10 +147,23 @@ class Generator3D:
             self._grids[key] = register_lattice(g, lin) if n <= 64 else g
         return g
 
-    def value_grid(self, c):
-        """Occupancy logits of every scene of `c` on the grid of `_mesh_points(n, 1 + padding)`, n = `grid_resolution()`:
-        (B,n,n,n) on the device.  Up to 64 samples per axis take the lattice decoder, larger grids the generic decoder in one
-        launch over all scenes."""
+    def mise_lin(self):
+        """The per-axis coordinate table of the MISE lattice (generation.py:132-135), float32 [grid_resolution()] on the host."""
+        return lin_table(self.resolution0 << self.upsampling_steps, 1 + self.padding)
+
+    def value_grid(self, c, stats_dict=None):
+        """Occupancy logits of every scene of `c`, (B,n,n,n) on the device, n = `grid_resolution()`.  Default: every sample of the
+        grid of `_mesh_points(n, 1 + padding)`; up to 64 samples per axis take the lattice decoder, larger grids the generic
+        decoder in one launch over all scenes.  `mise=True` with upsampling_steps > 0: MISE's `to_dense()` grid, one generic-decoder
+        launch per round over the ragged query lists of all scenes (padded to the longest); `stats_dict` receives "mise rounds"
+        and "mise points"."""
+        if self.mise and self.upsampling_steps > 0:
+            key = ("mise", self.resolution0, self.upsampling_steps, float(self.padding))
+            lin = self._grids.get(key)
+            if lin is None:
+                lin = self._grids[key] = torch.from_numpy(self.mise_lin()).to(self.device)
+            return mise_grid(lambda q, pts: self.eval_points(pts, c), self.resolution0, self.upsampling_steps, self._iso(),
+                             batch=self._scenes(c), device=lin.device, lin=lin, stats=stats_dict)
         n = self.grid_resolution()
         p = self._mesh_points(n, 1 + self.padding)
         B = self._scenes(c)
@@ -203,12 +223,12 @@ class Generator3D:
                             stats_dict if stats_dict is not None else {})[0]
 
     def generate_from_latent(self, c=None, stats_dict=None, **kwargs):
-        """generation.py:102-148 with the dense grid in MISE's place (module docstring)."""
+        """generation.py:102-148; the value grid is dense by default and MISE's with `mise=True` (module docstring)."""
         if self._scenes(c) != 1:
             raise ValueError("generate_from_latent takes the planes of one scene; use generate_meshes for a batch")
         stats_dict = stats_dict if stats_dict is not None else {}
         t0 = time.time()
-        grid = self.value_grid(c)
+        grid = self.value_grid(c, stats_dict)
         stats_dict["time (eval points)"] = time.time() - t0
         return self.extract_mesh(grid[0], c, stats_dict=stats_dict)
 

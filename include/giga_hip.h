@@ -591,7 +591,8 @@ int giga_grasp_select(const float* tsdf, const float* qual, const float* rot, co
 
 /* ---- mesh extraction: marching cubes on B dense value grids (conv_onet/generation.py:360-393, extract_mesh with
  * vol_bound None; libmcubes.marching_cubes on the grid padded with -1e6) -----
- * grids [B][nx][ny][nz] float32 (occupancy logits), 2 <= n <= GIGA_MESH_MAX_N per axis.  The padding by one sample of -1e6
+ * grids [B][nx][ny][nz] float32 (occupancy logits), 2 <= n <= GIGA_MESH_MAX_N per axis (513 = 32 * 2^4 + 1, the largest MISE grid;
+ * cell numbers, per-scene vertex and triangle numbers are 32-bit, the positions in the packed outputs 64-bit).  The padding by one sample of -1e6
  * on every side is virtual.  A corner counts as set when value <= iso; every crossed edge of the padded grid gives ONE
  * vertex at (iso - f1) / (f2 - f1) along it (evaluated in double, stored as float32), already in model coordinates
  * box_size * (g / (n - 1) - 0.5) with g the fractional grid index in [-1, n].  Triangles are wound as the reference's (the
@@ -605,13 +606,49 @@ int giga_grasp_select(const float* tsdf, const float* qual, const float* rot, co
  *           (0, 0 when everything was written).
  * Errors: -1 null grid / workspace / counts, n < 2 or n > GIGA_MESH_MAX_N, NaN iso, B (nx+1)(ny+1)(nz+1) >= 2^31;
  * -4 workspace too small; -6 null output with a non-zero capacity; -7 B > GIGA_MAX_SCENES. */
-#define GIGA_MESH_MAX_N 256
+#define GIGA_MESH_MAX_N 513
 size_t giga_mesh_workspace_bytes(int B, int nx, int ny, int nz);
 int giga_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, void* workspace, size_t workspace_bytes,
                     int32_t* counts, void* stream);
 int giga_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso, double box_size, const void* workspace,
                    size_t workspace_bytes, float* vertices, size_t cap_v, int32_t* triangles, size_t cap_t, int32_t* shortfall,
                    void* stream);
+
+/* ---- MISE: the sparse value grid of conv_onet/generation.py:125-142 (utils/libmise/mise.pyx), B independent octrees (added within
+ * ABI 3) -----
+ * R = resolution0 << depth, N = R + 1 <= GIGA_MISE_MAX_N samples per axis, depth >= 1; sample (i, j, k) has the linear index
+ * (i N + j) N + k.  The workspace (giga_mise_workspace_bytes(B, resolution0, depth)) holds the whole state: a known / unknown mark
+ * and a value per sample, and the leaves of the octree (a voxel of level l has edge 1 << (depth - l)).  All calls are asynchronous
+ * on `stream` and allocate nothing; scene b of a batch gives the bytes of a call on b alone.
+ *   init     : the resolution0^3 voxels of level 0 are leaves, the (resolution0 + 1)^3 coarse lattice points unknown.
+ *   count    : counts [B] int32 (device) = number of unknown points of every scene (MISE.query()'s length).  The workspace keeps
+ *              the offsets and must reach emit and update unchanged.
+ *   emit     : query [B][cap] int32 = the unknown points of scene b as linear indices in ASCENDING order (count / scan / emit, no
+ *              atomic append: equal state gives equal bytes).  Nothing is written at or beyond cap; shortfall [B] int32 (device,
+ *              may be NULL) receives the number of indices of each scene that did not fit.  With `points` [B][cap][3] float32 not
+ *              NULL, entry i of scene b also receives (lin[x], lin[y], lin[z]) of its sample, `lin` [N] float32 (device) being the
+ *              caller's per-axis table; entries at and beyond the scene's count repeat its first point (sample 0 when it has
+ *              none), so that one decoder launch over [B][cap] reads valid points only.
+ *   update   : values [B][cap] float32 are the values of the list that emit wrote (the first min(count, cap) of each scene count):
+ *              those points become known.  Then every leaf of level < depth for which a known point p of its CLOSED cube
+ *              (loc <= p <= loc + edge on all three axes) has (double)v >= threshold and one has (double)v <= threshold --
+ *              judged on all known points, before any subdivision of this round -- becomes an inner node with 8 leaf children, and
+ *              those of the children's 27 lattice points that did not exist are created unknown (mise.pyx:87-128, 184-280).
+ *   to_dense : grid [B][N][N][N] float32: the value of every created point (0 for one that is still unknown); then a sample without
+ *              value takes that of i-1 along x, then those still without take j-1 along y, then k-1 along z (mise.pyx:130-164).
+ * The caller loops count -> (copy of the B counts: the only device-to-host traffic of a round) -> emit -> decoder -> update until
+ * every count is 0, even if a leaf created in the last round would be subdivided by the next: that is what the reference does.
+ * Errors: -1 resolution0 < 1, depth < 1, N > GIGA_MISE_MAX_N, B N^3 >= 2^31, B cap >= 2^31, NaN threshold, null workspace / counts /
+ * grid / values / lin with points; -4 workspace too small; -6 null query with cap > 0; -7 B > GIGA_MAX_SCENES.  B = 0 returns 0. */
+#define GIGA_MISE_MAX_N 513
+size_t giga_mise_workspace_bytes(int B, int resolution0, int depth);
+int giga_mise_init(int B, int resolution0, int depth, void* workspace, size_t workspace_bytes, void* stream);
+int giga_mise_count(int B, int resolution0, int depth, void* workspace, size_t workspace_bytes, int32_t* counts, void* stream);
+int giga_mise_emit(int B, int resolution0, int depth, const void* workspace, size_t workspace_bytes, int32_t* query, size_t cap,
+                   int32_t* shortfall, const float* lin, float* points, void* stream);
+int giga_mise_update(const float* values, const int32_t* query, size_t cap, int B, int resolution0, int depth, double threshold,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int giga_mise_to_dense(int B, int resolution0, int depth, const void* workspace, size_t workspace_bytes, float* grid, void* stream);
 
 /* ---- mesh evaluation on ragged batches (vgn/ConvONets/eval.py:28-232, utils/libmesh/inside_mesh.py) -----
  * B scenes packed back to back, the layout giga_mesh_emit produces: every `*_offsets` argument is a HOST array of B + 1 int32
