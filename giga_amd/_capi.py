@@ -33,6 +33,7 @@ MESH_MAX_N = 513         # GIGA_MESH_MAX_N: samples per axis of a marching-cubes
 MISE_MAX_N = 513         # GIGA_MISE_MAX_N: samples per axis of a MISE value grid (resolution0 << depth) + 1
 TSDF_MAX_R = 512         # GIGA_TSDF_MAX_R: cells per axis of a fused volume
 RENDER_MAX_IMAGE = 4096  # GIGA_RENDER_MAX_IMAGE: width and height of a rendered depth image
+REFINE_MAX_FACES = 0x0FFFFFFF   # GIGA_REFINE_MAX_FACES (and _VERTICES)
 NOISE_MODEL = {"dex": 1, "trans": 2, "norm": 3}          # GIGA_NOISE_DEX / _TRANS / _NORM
 MAX_SCENES = 3072        # GIGA_MAX_SCENES: scenes per encoder / training call (error -7 beyond)
 HEAD_BITS = {"decoder_qual": 1, "decoder_rot": 2, "decoder_width": 4, "decoder_tsdf": 8}
@@ -87,6 +88,12 @@ _SIGNATURES = {
                                      ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "giga_decoder_point_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
                                 + [ctypes.c_void_p] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "giga_decoder_point_hess": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "giga_refine_face_points": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int,
+                                               ctypes.c_void_p]),
+    "giga_refine_face_grad": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_void_p]),
+    "giga_refine_vertex_step": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "giga_host_register": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
     "giga_host_unregister": (ctypes.c_int, [ctypes.c_void_p]),
     "giga_tsdf_scatter_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),

@@ -455,6 +455,29 @@ def decoder_point_grad(nhwc32, p, blob, bwd_blob, head_mask, douts, want_outputs
     return dp
 
 
+def decoder_point_hess(nhwc32, p, blob, bwd_blob):
+    """Occupancy logit f, its gradient and its Hessian w.r.t. the query points, the planes constant (giga_decoder_point_hess,
+    one launch).  nhwc32: fp32 FINAL planes [3,B,40,40,32]; p (B,N,3).  Returns (logit (B,N), dp (B,N,3), hess (B,N,3)):
+    logit and dp are `decoder_point_grad(..., 8, ones, want_outputs=True)`'s bit for bit, hess = (H_xy, H_xz, H_yz) -- the
+    diagonal is zero almost everywhere (piecewise-linear heads on bilinear samples)."""
+    dev = _capi.device_of(nhwc32, p, blob, bwd_blob)
+    if nhwc32.dtype != torch.float32:
+        raise ValueError("the point Hessian reads fp32 planes")
+    B = nhwc32.shape[1]
+    if p.dim() != 3 or p.shape[-1] != 3 or p.shape[0] != B:
+        raise ValueError(f"expected (B,N,3) query points for {B} scenes, got {tuple(p.shape)}")
+    N = p.shape[1]
+    pp = p.detach().float().contiguous()
+    logit = torch.empty((B, N), device=dev)
+    dp, hess = torch.empty((B, N, 3), device=dev), torch.empty((B, N, 3), device=dev)
+    if B * N > 0:
+        with torch.cuda.device(dev):
+            _capi.check(_capi.lib().giga_decoder_point_hess(
+                _capi.ptr(nhwc32), _capi.ptr(pp), _capi.ptr(blob), _capi.ptr(bwd_blob), _capi.ptr(logit), _capi.ptr(dp),
+                _capi.ptr(hess), B, N, _capi.stream_ptr(dev)), "giga_decoder_point_hess")
+    return logit, dp, hess
+
+
 def _wants_point_grad(module, *points):
     """Autograd w.r.t. the query points: grad enabled, some point tensor requires grad, no parameter does."""
     if not torch.is_grad_enabled() or not any(q is not None and q.requires_grad for q in points):

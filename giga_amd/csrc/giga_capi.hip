@@ -33,6 +33,15 @@ int launch_plane_gather(const float* dcbuf, const float* p, float* gplanes, int 
 // giga_decoder_pgrad.hip
 int launch_decoder_point_grad(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob, int head_mask,
                               const float* const* douts, float* const* outs, float* dp, int B, int N, hipStream_t s);
+int launch_decoder_point_hess(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob, float* logit,
+                              float* dp, float* hess, int B, int N, hipStream_t s);
+// giga_refine.hip
+int launch_refine_face_points(const float* vertices, const int* faces, const float* eps_in, float* eps, float* points, int V, int F,
+                              unsigned long long seed, int step, hipStream_t s);
+int launch_refine_face_grad(const float* vertices, const int* faces, const float* eps, const float* logit, const float* dp,
+                            const float* hess, double threshold, float* floss, float* fgrad, int V, int F, hipStream_t s);
+int launch_refine_vertex_step(const float* fgrad, const int* corner_order, const int* vertex_offsets, float* vertices,
+                              float* square_avg, float* grad, int V, int F, hipStream_t s);
 // giga_decoder_train16.hip (bf16 decoder of the bf16 training step)
 int launch_dect_forward(const float* planes, const float* p, const uint8_t* blob, int head_mask, float* const* outs, int B, int N,
                         int post, hipStream_t s);
@@ -681,6 +690,53 @@ int giga_decoder_point_grad(const void* planes_nhwc, const float* p, const void*
         if ((head_mask >> h & 1) && !douts[h]) return -6;
     return launch_decoder_point_grad(static_cast<const float*>(planes_nhwc), p, static_cast<const uint8_t*>(packed),
                                      static_cast<const uint8_t*>(bwd_packed), head_mask, douts, outs, dp, B, N,
+                                     static_cast<hipStream_t>(stream));
+}
+
+int giga_decoder_point_hess(const void* planes_nhwc, const float* p, const void* packed, const void* bwd_packed, float* logit,
+                            float* dp, float* hess, int B, int N, void* stream) {
+    if (B <= 0 || N <= 0) return -1;
+    if (B > GIGA_MAX_SCENES) return -7;
+    if ((long long)B * N >= (1LL << 31)) return -1;         // split_scene's point index is exact below 2^31
+    if (!planes_nhwc || !p || !packed || !bwd_packed || !logit || !dp || !hess) return -1;
+    return launch_decoder_point_hess(static_cast<const float*>(planes_nhwc), p, static_cast<const uint8_t*>(packed),
+                                     static_cast<const uint8_t*>(bwd_packed), logit, dp, hess, B, N,
+                                     static_cast<hipStream_t>(stream));
+}
+
+// 3 F corner indices and 9 F gradient floats are indexed with int / 32-bit products of the face count
+static bool refine_sizes_ok(int n_vertices, int n_faces) {
+    return n_vertices >= 0 && n_faces >= 0 && n_vertices <= GIGA_REFINE_MAX_VERTICES && n_faces <= GIGA_REFINE_MAX_FACES;
+}
+
+int giga_refine_face_points(const float* vertices, const int* faces, const float* eps_in, float* eps, float* points,
+                            int n_vertices, int n_faces, unsigned long long seed, int step, void* stream) {
+    if (!refine_sizes_ok(n_vertices, n_faces) || step < 0) return -1;
+    if (n_faces == 0) return 0;
+    if (!vertices || !faces) return -1;
+    if (!eps || !points) return -6;
+    return launch_refine_face_points(vertices, faces, eps_in, eps, points, n_vertices, n_faces, seed, step,
+                                     static_cast<hipStream_t>(stream));
+}
+
+int giga_refine_face_grad(const float* vertices, const int* faces, const float* eps, const float* logit, const float* dp,
+                          const float* hess, double threshold, float* face_loss, float* face_grad, int n_vertices, int n_faces,
+                          void* stream) {
+    if (!refine_sizes_ok(n_vertices, n_faces) || !(threshold > 0.0 && threshold < 1.0)) return -1;
+    if (n_faces == 0) return 0;
+    if (!vertices || !faces || !eps || !logit || !dp || !hess) return -1;
+    if (!face_loss || !face_grad) return -6;
+    return launch_refine_face_grad(vertices, faces, eps, logit, dp, hess, threshold, face_loss, face_grad, n_vertices, n_faces,
+                                   static_cast<hipStream_t>(stream));
+}
+
+int giga_refine_vertex_step(const float* face_grad, const int* corner_order, const int* vertex_offsets, float* vertices,
+                            float* square_avg, float* grad, int n_vertices, int n_faces, void* stream) {
+    if (!refine_sizes_ok(n_vertices, n_faces)) return -1;
+    if (n_vertices == 0) return 0;
+    if (!vertex_offsets || !vertices || !square_avg || (n_faces > 0 && (!face_grad || !corner_order))) return -1;
+    if (!grad) return -6;
+    return launch_refine_vertex_step(face_grad, corner_order, vertex_offsets, vertices, square_avg, grad, n_vertices, n_faces,
                                      static_cast<hipStream_t>(stream));
 }
 

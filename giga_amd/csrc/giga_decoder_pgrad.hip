@@ -14,6 +14,12 @@
 //      d fx / d p = 39 / 1.00001, and zero for a coordinate that norm_coord clamps (common.py:255-260 writes the clamp in place).
 // Planes are the encoder's FINAL planes (after conv_final): the transposed fc_c images exist for those only, so GIGA_FOLD_FINAL
 // is not accepted; a caller holding folded planes re-encodes without the flag (giga_amd/convonet.py does).
+//
+// decoder_pgrad_kernel<true> (giga_decoder_point_hess, mesh refinement) adds the second derivative of the occupancy logit f.  The
+// heads are piecewise linear in (p, c) and c(p) is bilinear per plane, so almost everywhere the Hessian of f has a zero diagonal and
+// one entry per plane, d2 f / du dv = s_u s_v sum_ch dc[plane][ch] (f00 - f01 - f10 + f11)[ch], accumulated against the dc the tile
+// holds anyway.  That instantiation runs the occupancy head alone with upstream gradient 1 and writes the raw logit, dp and
+// (H_xy, H_xz, H_yz); logit and dp are <false>'s bit for bit.  <false> is the point gradient as it was before the template.
 #include "giga_dec_common.h"
 
 namespace giga {
@@ -31,10 +37,12 @@ struct PgradArgs {
     int nheads, B, N;
     long long P;
     int nbatch; float invN;
+    float* hess;                // HESS: [P][3] = (H_xy, H_xz, H_yz), written (last: the other offsets are the point gradient's)
 };
 
 constexpr int PG_NW = 4;        // waves per workgroup, one 32-point tile each (436 VGPRs: one wave per SIMD; 8 waves spill)
 
+template <bool HESS>
 __global__ __launch_bounds__(PG_NW * 64, 1) void decoder_pgrad_kernel(PgradArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & 63;
@@ -94,7 +102,9 @@ __global__ __launch_bounds__(PG_NW * 64, 1) void decoder_pgrad_kernel(PgradArgs 
                 dO[2] = (d4.z - r2 * rd) * inv; dO[3] = (d4.w - r3 * rd) * inv;
                 if (a.out[h] && valid && hi == 0) *reinterpret_cast<float4*>(a.out[h] + 4 * g) = make_float4(r0, r1, r2, r3);
             } else {
-                float d = a.dout[h][g], v = z[0];
+                float d = 1.0f, v = z[0];
+                if constexpr (HESS) asm volatile("" : "+v"(d));     // upstream gradient 1, opaque: the chain compiles as <false>'s
+                else d = a.dout[h][g];
                 if (id == 0) { v = 1.0f / (1.0f + expf(-z[0])); d *= v * (1.0f - v); }      // sigmoid'
                 dO[0] = d;
                 if (a.out[h] && valid && hi == 0) a.out[h][g] = v;
@@ -161,16 +171,47 @@ __global__ __launch_bounds__(PG_NW * 64, 1) void decoder_pgrad_kernel(PgradArgs 
         if (valid && hi == 0) {
             a.dp[3 * g + 0] = dx; a.dp[3 * g + 1] = dy; a.dp[3 * g + 2] = dz;
         }
+        if constexpr (HESS) {                                      // one cross term per plane; a clamped axis zeroes its entries
+            // The taps are read again (cache hits) through a pointer the compiler cannot see through, in a loop of their own:
+            // sharing the loop above changes which of its multiply-adds get fused, and dp must stay <false>'s bit for bit.
+            float guv[3];
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) {
+                const float u = pl == 2 ? ny : nx, v = pl == 1 ? ny : nz;
+                const Bilin bl = bilin_setup(u, v);
+                const float* base = a.planes + pl * plane_stride + (size_t)b * RES * RES * CD + 4 * hi;
+                asm volatile("" : "+v"(base));
+                float suv = 0.f;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float4 v00 = *reinterpret_cast<const float4*>(base + (size_t)bl.o00 * CD + 8 * q);
+                    const float4 v01 = *reinterpret_cast<const float4*>(base + (size_t)bl.o01 * CD + 8 * q);
+                    const float4 v10 = *reinterpret_cast<const float4*>(base + (size_t)bl.o10 * CD + 8 * q);
+                    const float4 v11 = *reinterpret_cast<const float4*>(base + (size_t)bl.o11 * CD + 8 * q);
+                    suv = fmaf(dc[pl][4 * q + 0], (v00.x - v01.x) - (v10.x - v11.x), suv);
+                    suv = fmaf(dc[pl][4 * q + 1], (v00.y - v01.y) - (v10.y - v11.y), suv);
+                    suv = fmaf(dc[pl][4 * q + 2], (v00.z - v01.z) - (v10.z - v11.z), suv);
+                    suv = fmaf(dc[pl][4 * q + 3], (v00.w - v01.w) - (v10.w - v11.w), suv);
+                }
+                guv[pl] = suv;
+            }
+            float hxy = mx * my * guv[1], hxz = mx * mz * guv[0], hyz = my * mz * guv[2];
+            hxy += __shfl_xor(hxy, 32); hxz += __shfl_xor(hxz, 32); hyz += __shfl_xor(hyz, 32);
+            if (valid && hi == 0) {
+                a.hess[3 * g + 0] = hxy; a.hess[3 * g + 1] = hxz; a.hess[3 * g + 2] = hyz;
+            }
+        }
     }
 }
 
-int launch_decoder_point_grad(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob, int head_mask,
-                              const float* const* douts, float* const* outs, float* dp, int B, int N, hipStream_t s) {
+template <bool HESS>
+static int launch_pgrad(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob, int head_mask,
+                        const float* const* douts, float* const* outs, float* dp, float* hess, int B, int N, hipStream_t s) {
     const long long P = (long long)B * N;
     const PackOff ko = pack_offsets();
     const BwdPackOff bo = bwd_pack_offsets();
     PgradArgs a{};
-    a.planes = planes; a.p = p; a.blob = blob; a.bwd_blob = bwd_blob; a.dp = dp;
+    a.planes = planes; a.p = p; a.blob = blob; a.bwd_blob = bwd_blob; a.dp = dp; a.hess = hess;
     a.B = B; a.N = N; a.P = P; a.invN = 1.0f / (float)N;
     for (int h = 0; h < NHEADS; ++h) {
         if (!(head_mask >> h & 1)) continue;
@@ -182,9 +223,22 @@ int launch_decoder_point_grad(const float* planes, const float* p, const uint8_t
     a.nbatch = (int)((tiles + PG_NW - 1) / PG_NW);
     const int grid = a.nbatch < 256 ? a.nbatch : 256;
     const size_t lds = DEC32_BYTES > DECB_BYTES ? DEC32_BYTES : DECB_BYTES;
-    giga::dyn_lds_once(reinterpret_cast<const void*>(decoder_pgrad_kernel), (int)lds);
-    GIGA_LAUNCH(decoder_pgrad_kernel, dim3(grid), dim3(PG_NW * 64), lds, s, a);
+    giga::dyn_lds_once(reinterpret_cast<const void*>(decoder_pgrad_kernel<HESS>), (int)lds);
+    GIGA_LAUNCH(decoder_pgrad_kernel<HESS>, dim3(grid), dim3(PG_NW * 64), lds, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int launch_decoder_point_grad(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob, int head_mask,
+                              const float* const* douts, float* const* outs, float* dp, int B, int N, hipStream_t s) {
+    return launch_pgrad<false>(planes, p, blob, bwd_blob, head_mask, douts, outs, dp, nullptr, B, N, s);
+}
+
+// occupancy head alone, upstream gradient 1: raw logit, dp and the three Hessian entries per point
+int launch_decoder_point_hess(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob, float* logit,
+                              float* dp, float* hess, int B, int N, hipStream_t s) {
+    const float* douts[NHEADS] = {nullptr, nullptr, nullptr, nullptr};
+    float* outs[NHEADS] = {nullptr, nullptr, nullptr, logit};
+    return launch_pgrad<true>(planes, p, blob, bwd_blob, 8, douts, outs, dp, hess, B, N, s);
 }
 
 }  // namespace giga

@@ -43,26 +43,6 @@ struct NoiseArgs {
     unsigned k0, k1;
 };
 
-struct NoisePair { double z0, z1; };
-
-// 53 bits of two words, strictly inside (0, 1): k 2^-53, and 2^-54 in place of 0
-__device__ __forceinline__ double noise_u53(unsigned hi, unsigned lo) {
-    const unsigned long long k = ((unsigned long long)(hi >> 5) << 26) | (unsigned long long)(lo >> 6);
-    return k ? (double)k * 0x1p-53 : 0x1p-54;
-}
-
-__device__ __forceinline__ NoisePair noise_pair(unsigned block, unsigned id_lo, unsigned id_hi, unsigned stream, unsigned k0, unsigned k1) {
-    const Philox r = philox4x32_10(block, id_lo, id_hi, stream, k0, k1);
-    const double u1 = noise_u53(r.x[0], r.x[1]), u2 = noise_u53(r.x[2], r.x[3]);
-    const double rad = sqrt(-2.0 * log(u1)), th = 6.283185307179586 * u2;
-    return NoisePair{rad * cos(th), rad * sin(th)};
-}
-
-__device__ __forceinline__ double noise_normal(unsigned e, unsigned id_lo, unsigned id_hi, unsigned stream, unsigned k0, unsigned k1) {
-    const NoisePair q = noise_pair(e >> 1, id_lo, id_hi, stream, k0, k1);
-    return (e & 1u) ? q.z1 : q.z0;
-}
-
 // the normals of elements e0 .. e0 + 3: two blocks, three when e0 is odd
 __device__ __forceinline__ void noise_normals4(unsigned e0, unsigned id_lo, unsigned id_hi, unsigned stream, unsigned k0, unsigned k1,
                                                double z[4]) {

@@ -1,5 +1,8 @@
-// Philox-4x32 with 10 rounds (Salmon et al., SC 2011): the counter-based generator of giga_mesh_sample (giga_eval.hip) and
-// giga_depth_noise (giga_noise.hip).  Pure integer arithmetic: a numpy restatement reproduces every word (tests/eval_emu.py).
+// Philox-4x32 with 10 rounds (Salmon et al., SC 2011): the counter-based generator of giga_mesh_sample (giga_eval.hip),
+// giga_depth_noise (giga_noise.hip) and giga_refine_face_points (giga_refine.hip).  Pure integer arithmetic: a numpy restatement
+// reproduces every word (tests/eval_emu.py).  The double-precision uniforms and Box-Muller normals built on a block (noise_*) are
+// the depth noise's, shared with the refinement's barycentric draws; each of their operations is one IEEE rounding (there is no
+// multiply-add pair to contract).
 #ifndef GIGA_PHILOX_H_
 #define GIGA_PHILOX_H_
 #include <hip/hip_runtime.h>
@@ -17,6 +20,26 @@ __device__ __forceinline__ Philox philox4x32_10(unsigned c0, unsigned c1, unsign
         k1 += 0xBB67AE85u;
     }
     return Philox{{c0, c1, c2, c3}};
+}
+
+struct NoisePair { double z0, z1; };
+
+// 53 bits of two words, strictly inside (0, 1): k 2^-53, and 2^-54 in place of 0
+__device__ __forceinline__ double noise_u53(unsigned hi, unsigned lo) {
+    const unsigned long long k = ((unsigned long long)(hi >> 5) << 26) | (unsigned long long)(lo >> 6);
+    return k ? (double)k * 0x1p-53 : 0x1p-54;
+}
+
+__device__ __forceinline__ NoisePair noise_pair(unsigned block, unsigned id_lo, unsigned id_hi, unsigned stream, unsigned k0, unsigned k1) {
+    const Philox r = philox4x32_10(block, id_lo, id_hi, stream, k0, k1);
+    const double u1 = noise_u53(r.x[0], r.x[1]), u2 = noise_u53(r.x[2], r.x[3]);
+    const double rad = sqrt(-2.0 * log(u1)), th = 6.283185307179586 * u2;
+    return NoisePair{rad * cos(th), rad * sin(th)};
+}
+
+__device__ __forceinline__ double noise_normal(unsigned e, unsigned id_lo, unsigned id_hi, unsigned stream, unsigned k0, unsigned k1) {
+    const NoisePair q = noise_pair(e >> 1, id_lo, id_hi, stream, k0, k1);
+    return (e & 1u) ? q.z1 : q.z0;
 }
 
 }  // namespace giga

@@ -19,8 +19,13 @@ smaller than a coarse cell, which MISE skips.  With `mise=True` (and upsampling_
 (utils/libmise/mise.pyx) runs on the device (`giga_amd.mise`, csrc/giga_mise.hip), bit for bit libmise's bookkeeping -- decode the
 coarse lattice, subdivide only voxels that see both sides of the threshold, repeat, `to_dense()` -- with one decoder launch per
 round over all scenes and the B list lengths as the only device-to-host traffic of a round; it is also the route to the grids the
-dense one cannot afford (257^3, 513^3).  Mesh refinement (`refinement_step`), simplification (`simplify_nfaces`) and the crop mode
-(`vol_bound`) are not built."""
+dense one cannot afford (257^3, 513^3).
+
+Mesh refinement (`refinement_step`, generation.py:457-519) runs on the device as well (`giga_amd.refine`, csrc/giga_refine.hip):
+per scene, `refinement_step` RMSprop steps of four launches each on the vertices marching cubes left on the device, before the
+final copy.  The second derivative of the occupancy logit that the reference asks of autograd through `F.grid_sample` (a double
+backward current torch builds do not implement) is three numbers per face point from the point-gradient kernel.  Simplification
+(`simplify_nfaces`) and the crop mode (`vol_bound`) are not built."""
 import time
 
 import numpy as np
@@ -30,6 +35,7 @@ from . import _capi
 from .convonet import _planes_to_nhwc, decoder_point_grad, register_lattice
 from .mesh import Mesh, marching_cubes
 from .mise import lin_table, mise_grid
+from .refine import MeshRefiner
 
 
 class Generator3D:
@@ -37,13 +43,18 @@ class Generator3D:
 
     def __init__(self, model, points_batch_size=100000, threshold=0.5, device=None, resolution0=16, upsampling_steps=3,
                  with_normals=False, padding=0.1, refinement_step=0, simplify_nfaces=None, sample=False, input_type=None,
-                 vol_info=None, vol_bound=None, mise=False):
-        """The reference's arguments by name (generation.py:42-49).  `refinement_step > 0` (second-order point gradients) and
-        `simplify_nfaces` (quadric simplification) are not built and raise here; `vol_bound` (crop mode) raises when a mesh
-        is asked for.  `mesh_options` records the mesh arguments as a dict.  `mise=True` fills the value grid by MISE as the
-        reference does (module docstring); the default decodes every sample."""
-        if refinement_step:
-            raise NotImplementedError("mesh refinement (refinement_step > 0) is not built")
+                 vol_info=None, vol_bound=None, mise=False, refine_seed=0):
+        """The reference's arguments by name (generation.py:42-49).  `refinement_step > 0` runs that many refinement steps on
+        every extracted mesh (`refine_mesh`); it has no CPU path and raises here for a device that is not a HIP device.
+        `refine_seed` keys the barycentric draws (the reference uses numpy's global generator).  `simplify_nfaces` (quadric
+        simplification) is not built and raises here; `vol_bound` (crop mode) raises when a mesh is asked for.  `mesh_options`
+        records the mesh arguments as a dict.  `mise=True` fills the value grid by MISE as the reference does (module
+        docstring); the default decodes every sample."""
+        device = device if device is not None else torch.device("cuda")
+        if refinement_step > 0 and torch.device(device).type != "cuda":
+            raise NotImplementedError("mesh refinement runs only on a HIP device")
+        if refinement_step < 0:                                # (as before: every non-zero value that is not served raises)
+            raise NotImplementedError("a negative refinement_step is not built")
         if simplify_nfaces is not None:
             raise NotImplementedError("mesh simplification (simplify_nfaces) is not built")
         mesh_options = dict(upsampling_steps=upsampling_steps, with_normals=with_normals, padding=padding,
@@ -52,8 +63,9 @@ class Generator3D:
         self.model = model
         self.points_batch_size = int(points_batch_size)
         self.threshold = threshold
-        self.refinement_step = 0
-        self.device = device if device is not None else torch.device("cuda")
+        self.refinement_step = int(refinement_step)
+        self.refine_seed = int(refine_seed)
+        self.device = device
         self.resolution0 = resolution0
         self.upsampling_steps = int(upsampling_steps)
         self.with_normals = bool(with_normals)
@@ -203,6 +215,18 @@ class Generator3D:
                     if nv:
                         normals[v1 - nv:v1] = self._normals_on_device(vertices[v1 - nv:v1], nhwc[:, b:b + 1].contiguous())
             stats_dict["time (normals)"] = time.time() - t0
+        if self.refinement_step > 0 and v_end[-1] > 0:
+            # generation.py:423-426: after the normals, which belong to the unrefined vertices and are lost with them (trimesh
+            # drops its cached vertex normals when `mesh.vertices` is assigned): a refined mesh carries none
+            t0 = time.time()
+            nhwc = _planes_to_nhwc(c, "fp32")
+            for b, (v1, nv) in enumerate(zip(v_end, counts[:, 0].tolist())):
+                nt = int(counts[b, 1])
+                if nv and nt:
+                    vertices[v1 - nv:v1] = self._refine_on_device(vertices[v1 - nv:v1], triangles[t_end[b] - nt:t_end[b]],
+                                                                  nhwc[:, b:b + 1])
+            normals = None
+            stats_dict["time (refine)"] = time.time() - t0
         vertices, faces = vertices.cpu().numpy(), triangles.cpu().numpy().astype(np.int64)
         normals = normals.cpu().numpy() if normals is not None else None
         out = []
@@ -221,6 +245,26 @@ class Generator3D:
             raise ValueError(f"expected an (nx,ny,nz) grid, got {tuple(occ_hat.shape)}")
         return self._meshes(occ_hat.unsqueeze(0) if torch.is_tensor(occ_hat) else occ_hat, c,
                             stats_dict if stats_dict is not None else {})[0]
+
+    def _refine_on_device(self, vertices, faces, nhwc):
+        """`refinement_step` steps on device-resident (V,3) vertices / (F,3) faces of one scene (fp32 NHWC planes); returns the
+        refined vertices, on the device."""
+        return MeshRefiner(self.model, nhwc, vertices, faces, threshold=self.threshold, seed=self.refine_seed) \
+            .run(self.refinement_step)
+
+    def refine_mesh(self, mesh, occ_hat=None, c=None):
+        """generation.py:457-519: `refinement_step` RMSprop steps on the vertices of `mesh` (a `Mesh`; c: the planes of its
+        scene), which is changed in place and returned; its vertex normals, which belonged to the old vertices, are dropped.
+        `occ_hat` is accepted for the reference's signature (it only asserts a cubic grid there).  The mesh path of
+        `extract_mesh` does not come through here: it refines before the mesh leaves the device."""
+        if self.refinement_step <= 0 or len(mesh.vertices) == 0 or len(mesh.faces) == 0:
+            return mesh
+        nhwc = _planes_to_nhwc(c, "fp32")
+        v = self._refine_on_device(torch.from_numpy(np.ascontiguousarray(mesh.vertices, dtype=np.float32)).to(nhwc.device),
+                                   torch.from_numpy(np.ascontiguousarray(mesh.faces)).to(nhwc.device), nhwc)
+        mesh.vertices = v.cpu().numpy()
+        mesh.vertex_normals = None
+        return mesh
 
     def generate_from_latent(self, c=None, stats_dict=None, **kwargs):
         """generation.py:102-148; the value grid is dense by default and MISE's with `mise=True` (module docstring)."""

@@ -277,6 +277,51 @@ int giga_decoder_point_grad(const void* planes_nhwc, const float* p, const void*
                             float* dp, float* out_qual, float* out_rot, float* out_width, float* out_tsdf,
                             int B, int N, int flags, void* stream);
 
+/* ---- occupancy logit, gradient and Hessian at query points (fp32; added within ABI 3) ------------------------------------
+ * giga_decoder_point_grad for the occupancy head alone with upstream gradient 1, plus the second derivative of the logit f with
+ * respect to p.  The decoder is piecewise linear in (p, c) and c(p) is a bilinear sample of three planes, so almost everywhere
+ * the Hessian of f has a zero diagonal and one entry per plane, d2f/du dv = s_u s_v sum_ch dc[ch] (f00 - f01 - f10 + f11)[ch] (dc:
+ * the gradient w.r.t. the sampled features, s = 39 / 1.00001, or 0 along an axis that common.py:255-260 clamps).
+ *   logit [B*N]: the raw occupancy output, bit for bit giga_decoder_point_grad's out_tsdf;  dp [B*N][3]: bit for bit its dp for
+ *   head_mask 8 and dtsdf = 1;  hess [B*N][3] = (H_xy, H_xz, H_yz).  All three are overwritten; planes and blobs as above.
+ * One launch (the HESS instantiation of the same kernel).  Errors before anything is enqueued: -1 (B <= 0, N <= 0, B*N >= 2^31, a
+ * NULL plane / point / blob pointer, logit, dp or hess), -7 (B > GIGA_MAX_SCENES). */
+int giga_decoder_point_hess(const void* planes_nhwc, const float* p, const void* packed, const void* bwd_packed, float* logit,
+                            float* dp, float* hess, int B, int N, void* stream);
+
+/* ---- mesh refinement: Generator3D.refine_mesh (conv_onet/generation.py:457-519) as closed-form per-face arithmetic ------------
+ * One refinement step of a triangle mesh (vertices [V][3] float32, faces [F][3] int32, both on the device) is
+ *   giga_refine_face_points -> giga_decoder_point_hess at the face points (B = 1, N = F) -> giga_refine_face_grad ->
+ *   giga_refine_vertex_step,
+ * and minimises mean_f (sigmoid(f(q_f)) - threshold)^2 + 0.01 mean_f |n_f - t_f|^2 over the vertices, q_f = sum_i eps_fi v_fi the
+ * face point, n_f = c / (|c| + 1e-10) with c = (v1 - v0) x (v2 - v1), t_f = -g / (|g| + 1e-10) with g = grad_q sigmoid(f(q_f)).
+ *
+ * giga_refine_face_points: eps [F][3] and points [F][3] are written.  eps_in [F][3] non-NULL: eps = eps_in.  NULL: eps is drawn,
+ *   Dirichlet(1/2, 1/2, 1/2) as z_i^2 / sum_j z_j^2 from the normals z_0, z_1 (Box-Muller pair of block 0) and z_2 (first normal of
+ *   block 1) of the Philox counter (block, face, step, 0), key = seed (blocks, uniforms and normals as in giga_depth_noise).
+ *   points = (v0 eps_0 + v1 eps_1) + v2 eps_2 in fp32.
+ * giga_refine_face_grad: logit [F], dp [F][3], hess [F][3] are giga_decoder_point_hess's outputs at `points`.  face_loss [F][2] =
+ *   ((sigma - threshold)^2, |n - t|^2) (the caller takes the means); face_grad [F][3][3] = d loss / d (corner i of face f), with
+ *   the 1/F of the means folded in.  Where |g| or |c| is exactly 0 the a a^T / |a| term of the normalisation's Jacobian is 0
+ *   (torch's subgradient of norm at the origin).  The arithmetic runs in double on the fp32 inputs.
+ * giga_refine_vertex_step: corner_order [3F] lists the corners (3 * face + i) sorted by their vertex, vertex_offsets [V+1] is the
+ *   CSR row table into it.  grad [V][3] = the sum of the vertex's corner gradients in list order (no atomics: bit reproducible),
+ *   then torch.optim.RMSprop's defaults in place: square_avg = 0.99 square_avg + 0.01 grad^2,
+ *   vertices -= 1e-4 grad / (sqrt(square_avg) + 1e-8).  A vertex without corners has grad 0 and does not move.
+ * A face with a corner index outside [0, V) gets NaN outputs and an entry of corner_order outside [0, 3F) is skipped: no index
+ * is followed out of its array.  Errors before anything is enqueued: -1 (negative counts, V > GIGA_REFINE_MAX_VERTICES,
+ * F > GIGA_REFINE_MAX_FACES, step < 0, threshold outside (0, 1), a NULL input), -6 (a NULL output).  F = 0 (face kernels) and
+ * V = 0 (vertex step) return 0 without a launch. */
+#define GIGA_REFINE_MAX_VERTICES 0x0FFFFFFF
+#define GIGA_REFINE_MAX_FACES 0x0FFFFFFF
+int giga_refine_face_points(const float* vertices, const int* faces, const float* eps_in, float* eps, float* points,
+                            int n_vertices, int n_faces, unsigned long long seed, int step, void* stream);
+int giga_refine_face_grad(const float* vertices, const int* faces, const float* eps, const float* logit, const float* dp,
+                          const float* hess, double threshold, float* face_loss, float* face_grad, int n_vertices, int n_faces,
+                          void* stream);
+int giga_refine_vertex_step(const float* face_grad, const int* corner_order, const int* vertex_offsets, float* vertices,
+                            float* square_avg, float* grad, int n_vertices, int n_faces, void* stream);
+
 /* ---- input side: page-locking of caller-owned host memory (hipHostRegister / hipHostUnregister), so that batches which
  * reader processes assemble in a shared-memory ring are DMA-ed to the device without a staging copy
  * (giga_amd/feed.py; replaces the pageable `.to(device)` of train_giga.py:141-151). */
