@@ -5,6 +5,7 @@
     from giga_amd import render_depth, acquire_tsdf, save_occ   # depth images and occupancy labels from meshes (giga_amd.render)
     from giga_amd import ResidentTrainingSet, ResidentBatches   # training batches from a set in device memory (giga_amd.resident)
     from giga_amd import Trainer, train_val_split               # the training loop of scripts/train_giga.py (giga_amd.trainer)
+    from giga_amd import affordance_visual, grasp2mesh          # the scene mesh coloured by grasp quality (giga_amd.visual)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/giga_hip.h."""
 __version__ = "0.1.0"
@@ -16,6 +17,8 @@ _RENDER_EXPORTS = ("scene_mesh", "Camera", "render_depth", "render_depth_batch",
 _RESIDENT_EXPORTS = ("ResidentTrainingSet", "ResidentBatches")
 # ... and of giga_amd.trainer: the training loop, its device-side epoch metrics and the train / validation split
 _TRAINER_EXPORTS = ("Trainer", "TrainMetrics", "train_val_split")
+# ... and of giga_amd.visual: the affordance colours of a scene mesh, the gripper glyph, the composed scene
+_VISUAL_EXPORTS = ("affordance_faces", "affordance_points", "affordance_visual", "grasp2mesh", "ColoredMesh", "Scene")
 
 
 def __getattr__(name):
@@ -28,4 +31,7 @@ def __getattr__(name):
     if name in _TRAINER_EXPORTS:
         from . import trainer
         return getattr(trainer, name)
+    if name in _VISUAL_EXPORTS:
+        from . import visual
+        return getattr(visual, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

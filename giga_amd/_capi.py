@@ -176,6 +176,12 @@ _SIGNATURES = {
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "giga_batch_draw": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 5),
     "giga_batch_assemble": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 8),
+    "giga_affordance_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "giga_affordance_points": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4
+                               + [ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_affordance_faces": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4
+                              + [ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_affordance_colormap": (None, [ctypes.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 BATCH_POINTS = {"float32": 0, "float16": 1}              # GIGA_BATCH_POINTS_F32 / _F16
@@ -198,6 +204,16 @@ class GraspParams(ctypes.Structure):
                 ("out_th", ctypes.c_float), ("low_th", ctypes.c_float), ("threshold", ctypes.c_float),
                 ("lim_x", ctypes.c_int), ("lim_y", ctypes.c_int), ("lim_z", ctypes.c_int),
                 ("max_filter_size", ctypes.c_int), ("force_detection", ctypes.c_int)]
+
+
+AFFORDANCE = {"max": 0, "softmax": 1, "mean": 2}       # GIGA_AFFORDANCE_MAX / _SOFTMAX / _MEAN
+AFFORDANCE_DENSE = 256   # GIGA_AFFORDANCE_DENSE: OR-ed into the aggregation, keeps the dense faces x points form
+
+
+class AffordanceParams(ctypes.Structure):
+    """struct GigaAffordanceParams of include/giga_hip.h."""
+    _fields_ = [(name, ctypes.c_double) for name in ("size", "th", "temp", "rad", "finger_depth", "finger_offset")] + \
+               [("move_center", ctypes.c_int32), ("aggregation", ctypes.c_int32)]
 
 
 class GigaHipError(RuntimeError):

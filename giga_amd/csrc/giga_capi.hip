@@ -113,6 +113,14 @@ size_t contains_workspace_bytes(int B, int n_tri, int n_pts);
 int launch_mesh_contains(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
                          const double* points, const int* point_offsets, int B, int resolution, uint8_t* inside, uint8_t* ws,
                          hipStream_t s);
+// giga_affordance.hip
+size_t affordance_workspace_bytes(int B, int R);
+void affordance_colormap(uint8_t* rgba);
+int launch_affordance_points(const float* qual, const float* rot, int B, int R, const GigaAffordanceParams* prm, double* points,
+                             int* counts, uint8_t* ws, hipStream_t s);
+int launch_affordance_faces(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
+                            const double* points, const int* counts, int B, int R, const GigaAffordanceParams* prm,
+                            double* affordance, uint8_t* rgba, uint8_t* ws, hipStream_t s);
 // giga_encoder.hip
 EncWs enc_workspace(int B, int precision);
 int launch_encoder(const float* tsdf, const uint8_t* blob, void* planes_nhwc, float* planes_nchw, int B,
@@ -1080,6 +1088,50 @@ int giga_depth_render(const float* vertices, const int32_t* vertex_offsets, cons
     if (workspace_bytes < giga_depth_render_workspace_bytes(B, n, vertex_offsets[B], triangle_offsets[B])) return -4;
     return launch_depth_render(vertices, vertex_offsets, triangles, triangle_offsets, view_offsets, extrinsics, intrinsics, B, W, H, near,
                                far, pixel_offset, depth, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+// ---- grasp affordance of a scene mesh (giga_affordance.hip) ----
+static int affordance_check(int B, int R, const GigaAffordanceParams* p) {
+    if (const int rc = ragged_batch_check(B)) return rc;
+    if (!p || R < 2 || R > GIGA_TSDF_MAX_R) return -1;
+    const int mode = p->aggregation & ~GIGA_AFFORDANCE_DENSE;
+    if (mode != GIGA_AFFORDANCE_MAX && mode != GIGA_AFFORDANCE_SOFTMAX && mode != GIGA_AFFORDANCE_MEAN) return -1;
+    if (!tsdf_finite(p->size) || !tsdf_finite(p->th) || !tsdf_finite(p->temp) || !tsdf_finite(p->rad) || !tsdf_finite(p->finger_depth) ||
+        !tsdf_finite(p->finger_offset))
+        return -1;
+    return 0;
+}
+
+size_t giga_affordance_workspace_bytes(int B, int R, int n_faces_total) {
+    if (B <= 0 || B > GIGA_MAX_SCENES || R < 2 || R > GIGA_TSDF_MAX_R || n_faces_total < 0) return 0;
+    return affordance_workspace_bytes(B, R);
+}
+
+int giga_affordance_points(const float* qual, const float* rot, int B, int R, const GigaAffordanceParams* params, double* points,
+                           int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = affordance_check(B, R, params)) return rc;
+    if (B == 0) return 0;
+    if (!qual || (params->move_center && !rot) || !points || !counts || !workspace) return -1;
+    if (workspace_bytes < giga_affordance_workspace_bytes(B, R, 0)) return -4;
+    return launch_affordance_points(qual, rot, B, R, params, points, counts, static_cast<uint8_t*>(workspace),
+                                    static_cast<hipStream_t>(stream));
+}
+
+int giga_affordance_faces(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                          const double* points, const int32_t* counts, int B, int R, const GigaAffordanceParams* params,
+                          double* affordance, uint8_t* rgba, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = affordance_check(B, R, params)) return rc;
+    if (B == 0) return 0;
+    if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B)) return -1;
+    if (triangle_offsets[B] == 0) return 0;
+    if ((vertex_offsets[B] > 0 && !vertices) || !triangles || !points || !counts || !affordance || !rgba || !workspace) return -1;
+    if (workspace_bytes < giga_affordance_workspace_bytes(B, R, triangle_offsets[B])) return -4;
+    return launch_affordance_faces(vertices, vertex_offsets, triangles, triangle_offsets, points, counts, B, R, params, affordance, rgba,
+                                   static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+void giga_affordance_colormap(uint8_t* rgba) {
+    if (rgba) affordance_colormap(rgba);
 }
 
 // ---- depth noise (giga_noise.hip) ----

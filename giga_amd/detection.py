@@ -160,13 +160,14 @@ def _grasp_collect(buf, force_detection):
 
 def grasp_select(tsdf, qual, rot, width, voxel_size=None, out_th=0.5, threshold=0.9, force_detection=False,
                  max_filter_size=4, gaussian_filter_sigma=1.0, min_width=0.033, max_width=0.233,
-                 limit=(0.02, 0.02, 0.055), return_volume=False):
+                 limit=(0.02, 0.02, 0.055), return_volume=False, _after_launch=None):
     """process + bound + select (detection_implicit.py:115-143, 87-97, 146-174) for B scenes on the device.
 
     tsdf (B,R,R,R) | (B,1,R,R,R), qual (B,R^3), rot (B,R^3,4), width (B,R^3): float32 device tensors (the
     network outputs of `predict_batch`).  Returns a list of B dicts with numpy arrays sorted by descending
     score: index (K,3) voxel indices, score (K,), rot (K,4) quaternions, width (K,), best_only flag; plus the
-    processed quality volume (B,R,R,R) (device tensor) when return_volume is set."""
+    processed quality volume (B,R,R,R) (device tensor) when return_volume is set.  _after_launch(qual_out (B,R,R,R), rot (B,R^3,4))
+    is called once, after the post-processing kernels are enqueued and before the survivors are copied to the host."""
     _capi.require_device(tsdf, qual, rot, width)
     B, R = qual.shape[0], tsdf.shape[-1]
     prm = _grasp_params(R, voxel_size, out_th, threshold, force_detection, max_filter_size, gaussian_filter_sigma,
@@ -175,6 +176,9 @@ def grasp_select(tsdf, qual, rot, width, voxel_size=None, out_th=0.5, threshold=
     for cap in (1024, R * R * R):                             # nearly always a few dozen survivors; plateaus need all
         buf = _GraspBuffers(B, R, cap, qual.device)
         _grasp_launch(tsdf, qual, rot, width, prm, buf)
+        if _after_launch is not None:
+            _after_launch(buf.qual_out.view(B, R, R, R), rot)
+            _after_launch = None                              # (a repeat with the full capacity writes the same volume)
         out = _grasp_collect(buf, force_detection)
         if out is not None:
             break
@@ -190,7 +194,12 @@ class VGNImplicit:
     giga_amd.perception.TSDFVolume, whose device grid is taken as it is) and
     returns (grasps, scores, toc) where each grasp is a dict {rotation (xyzw quat), translation (m), width (m)}
     -- the fields of vgn.grasp.Grasp/Transform, which live outside this package.  `plan_batch` is the batched,
-    tensor-in form."""
+    tensor-in form.
+
+    With visualize=True, `__call__(state, scene_mesh, aff_kwargs)` returns (grasps, scores, toc, composed_scene) as the reference
+    does (detection_implicit.py:57-58, 78-83): a `giga_amd.visual.Scene` holding the scene mesh coloured by the affordance of this
+    very call's quality volume and rotations ('scene') and the gripper glyphs of the returned grasps ('grasp_0', ...).  The
+    affordance kernels are enqueued between the post-processing and the copy of the survivors; the hipGraph path is not taken."""
 
     def __init__(self, model_path, model_type, best=False, force_detection=False, qual_th=0.9, out_th=0.5,
                  visualize=False, resolution=40, net=None, seed=None, use_graph=False, **kwargs):
@@ -207,16 +216,16 @@ class VGNImplicit:
         self._graphs = {}
         self._graph_weights = None
 
-    def plan_batch(self, tsdf, tsdf_process=None, voxel_size=None):
+    def plan_batch(self, tsdf, tsdf_process=None, voxel_size=None, _after_launch=None):
         """tsdf (B,R,R,R) device tensor -> per-scene candidate dicts (see grasp_select), lattice positions added."""
         sel = None
-        if self.use_graph and tsdf.shape[0] <= 4:              # launch-bound regime only: at larger batches the eager
+        if self.use_graph and not self.visualize and tsdf.shape[0] <= 4:   # launch-bound regime only: at larger batches the eager
             sel = self._graphed_plan(tsdf, tsdf_process, voxel_size)   # stream is GPU-bound and graph nodes do not pipeline
         if sel is None:
             qual, rot, width = predict_batch(tsdf, self.pos, self.net)
             sel = grasp_select(tsdf if tsdf_process is None else tsdf_process, qual, rot, width, voxel_size=voxel_size,
                                out_th=self.out_th, threshold=self.qual_th, force_detection=self.force_detection,
-                               max_filter_size=8 if self.visualize else 4)
+                               max_filter_size=8 if self.visualize else 4, _after_launch=_after_launch)
         lin = self._lin_host
         for s in sel:
             s["position"] = lin[s["index"]]                    # center_vol[i, j, k], detection_implicit.py:181
@@ -269,6 +278,8 @@ class VGNImplicit:
         return _grasp_collect(buf, self.force_detection)
 
     def __call__(self, state, scene_mesh=None, aff_kwargs={}):
+        if self.visualize and scene_mesh is None:
+            raise ValueError("visualize=True colours the scene mesh: pass scene_mesh")
         from .perception import TSDFVolume
         tsdf_process = state.tsdf_process if hasattr(state, "tsdf_process") else state.tsdf
         R = self.resolution
@@ -287,12 +298,26 @@ class VGNImplicit:
             t = torch.from_numpy(np.ascontiguousarray(tsdf_vol, np.float32).reshape(1, R, R, R)).to(self.device)
             tp = t if tsdf_process is tsdf_vol else torch.from_numpy(
                 np.ascontiguousarray(tsdf_process, np.float32).reshape(1, R, R, R)).to(self.device)
-        sel = self.plan_batch(t, tp, voxel_size)[0]
+        aff = []
+        if self.visualize:                                     # detection_implicit.py:57-58: between bound and select, inside toc
+            from . import visual
+
+            def colour(qual_out, rot):
+                aff.append(visual._Affordance(qual_out, rot, [scene_mesh], size=size, **aff_kwargs).launch())
+            sel = self.plan_batch(t, tp, voxel_size, _after_launch=colour)[0]
+            colored = visual._colored(scene_mesh, *aff[0].finish()[0])
+        else:
+            sel = self.plan_batch(t, tp, voxel_size)[0]
         toc = time.time() - tic
         k = len(sel["score"])
         p = np.arange(k) if self.best else self._rng.permutation(k)       # detection_implicit.py:65-68
         grasps = [{"rotation": sel["rot"][i], "translation": (sel["position"][i] + 0.5) * size,
                    "width": float(sel["width"][i]) * size} for i in p]
+        if self.visualize:                                     # detection_implicit.py:78-83
+            composed_scene = visual.Scene(colored)
+            for i, (g, s) in enumerate(zip(grasps, sel["score"][p])):
+                composed_scene.add_geometry(visual.grasp2mesh(g, s), node_name=f"grasp_{i}")
+            return grasps, sel["score"][p], toc, composed_scene
         return grasps, sel["score"][p], toc
 
     def plan_from_depth(self, depth_imgs, intrinsic, extrinsics, size=0.3, noise=None):

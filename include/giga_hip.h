@@ -741,6 +741,61 @@ int giga_mesh_contains(const float* vertices, const int32_t* vertex_offsets, con
                        const double* points, const int32_t* point_offsets, int B, int resolution, uint8_t* inside, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---- output side: grasp affordance of a scene mesh (src/vgn/utils/visual.py:22-98, affordance_visual; added within ABI 3) -----
+ * Colours every face of B scene meshes by the grasp quality predicted near it.  qual [B][R^3] float32 is the volume after process
+ * and bound (the qual_out of giga_grasp_select), rot [B][R^3][4] float32 the quaternions (xyzw), voxel (i, j, k) at i R^2 + j R + k.
+ * Two calls, both asynchronous on `stream`, without allocation and without atomics; equal input gives equal bytes, and a batch
+ * gives scene b the bytes of a call on scene b alone.
+ *
+ * giga_affordance_points: the voxels with qual > float(th) (a float32 comparison), in ascending voxel order, as points [B][R^3][4]
+ * double (x, y, z, q); counts[b] rows of scene b are written, the rest is left as it was.
+ *   position   (lin[i], lin[j], lin[k]) in double, lin = np.linspace(0, size, R): lin[t] = t (size / (R - 1)), lin[R - 1] = size.  (The
+ *              spacing is size / (R - 1), not the planner lattice's size / R: the reference's choice, kept.)
+ *   move_center != 0 adds the third column of the rotation matrix, computed in float32 with one rounding per operation:
+ *              zx = (2 r0) r2 + (2 r1) r3, zy = (2 r1) r2 - (2 r0) r3, zz = (1 - (2 r0) r0) - (2 r1) r1,
+ *              off = (z float(finger_depth)) float(finger_offset); off is widened to double and added to the position.
+ *   q          the float32 quality widened to double.
+ *
+ * giga_affordance_faces: the meshes are packed back to back in the ragged layout of giga_depth_render (vertices [.][3] float32,
+ * triangles [.][3] int32 counting from the scene's own first vertex, both on the device; vertex_offsets and triangle_offsets
+ * [B+1] int32 on the HOST, copied into the workspace before the call returns).  points and counts are what
+ * giga_affordance_points wrote (device).  Per face, in double, one rounding per operation:
+ *   centre     ((v0 + v1) + v2) / 3 from the float32 vertices;
+ *   dist       sqrt(((dx dx) + (dy dy)) + (dz dz)), d = centre - point, the root correctly rounded;
+ *   over the P = counts[b] points of the scene
+ *     GIGA_AFFORDANCE_MAX      a = max_p (dist <= rad ? q_p : 0)
+ *     GIGA_AFFORDANCE_SOFTMAX  w_p = dist <= rad ? exp(q_p temp) : 0,  a = (sum w_p q_p) / (sum w_p + 1e-5)
+ *     GIGA_AFFORDANCE_MEAN     w_p = exp(-dist temp),                   a = (sum w_p q_p) / (sum w_p)       (0 / 0 = NaN)
+ *              the sums taken in ascending point order;
+ *   affordance a = (min(max(a, th), 1) - th) / (1 - th), NaN staying NaN -> affordance [F] double;
+ *   colour     matplotlib's 'Reds' with its 256 entries at x = (a a) (a a): entry min(int(256 x), 255) as rint(255 c), alpha 255;
+ *              NaN gives (0, 0, 0, 0) -> rgba [F][4] uint8.  giga_affordance_colormap writes the table ([256][4], host memory).
+ * A scene without points (P = 0) gets affordance NaN and the colour (102, 102, 102, 255) on every face; a face with a vertex
+ * index outside its scene gets NaN and (0, 0, 0, 0).
+ * GIGA_AFFORDANCE_MAX walks a uniform cell grid over the points instead of all of them when that grid has at least 3 cells per
+ * axis and R^3 <= 2^20; the results are the same bytes.  GIGA_AFFORDANCE_DENSE, OR-ed into `aggregation`, keeps the dense form
+ * (what the tests compare the grid against).
+ * workspace: giga_affordance_workspace_bytes(B, R, n_faces_total) for both calls (0 for arguments the calls reject).
+ * Errors: -1 null params, B < 0, R < 2 or R > GIGA_TSDF_MAX_R, an unknown aggregation, a parameter that is not finite, offsets
+ * that are null, do not start at 0 or decrease, a null pointer to a non-empty array, null workspace; -4 workspace too small;
+ * -7 B > GIGA_MAX_SCENES.  B = 0 returns 0. */
+#define GIGA_AFFORDANCE_MAX 0
+#define GIGA_AFFORDANCE_SOFTMAX 1
+#define GIGA_AFFORDANCE_MEAN 2
+#define GIGA_AFFORDANCE_DENSE 256
+typedef struct GigaAffordanceParams {
+    double size, th, temp, rad, finger_depth, finger_offset;
+    int32_t move_center;
+    int32_t aggregation;
+} GigaAffordanceParams;
+size_t giga_affordance_workspace_bytes(int B, int R, int n_faces_total);
+int giga_affordance_points(const float* qual, const float* rot, int B, int R, const GigaAffordanceParams* params, double* points,
+                           int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int giga_affordance_faces(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                          const double* points, const int32_t* counts, int B, int R, const GigaAffordanceParams* params,
+                          double* affordance, uint8_t* rgba, void* workspace, size_t workspace_bytes, void* stream);
+void giga_affordance_colormap(uint8_t* rgba);
+
 /* Number of kernel launches the library has enqueued in this process so far (all streams): the difference around a call is
  * that call's launch count.  Diagnostic only. */
 unsigned long long giga_launch_count(void);

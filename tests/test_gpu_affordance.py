@@ -1,0 +1,294 @@
+"""GPU: giga_affordance_points / giga_affordance_faces and the planner's visualize path against the numpy restatement of
+tests/affordance_emu.py.
+
+What is asked.  The points are byte-equal to the restatement, and so are the 'max' affordance and its colours: both sides perform
+the same IEEE operations in the same order.  'mean' and 'softmax' are held to an absolute (P + 2) 2^-50 / (1 - th) of the
+float64 restatement, which is derived, not measured: each of the two sums of P positive terms is within (P - 1) 2^-53 relative in
+any order of summation, exp is given 3 ulp (HIP's documented bound for the double exp is 1 ulp), the quotient adds one rounding --
+together less than 2 (P + 2) 2^-53 relative on an aggregate that is at most 1 -- times 4 as margin, divided by the 1 - th of the
+normalisation.
+Exact 'max' needs no face / point pair within 1e-9 of rad (both sides round the same distance, but a pair ON the radius would make
+the test turn on the last bit of the square root), and exact colours of the other two aggregations need no face whose 256 a^4 is
+within 1e-6 of one of the table's edges 1 .. 255 (0 and 256 are no edges: a face without a point in range has a = 0 exactly on
+both sides).  Every case asserts both from the restatement with zero faces left out; the seeds were chosen on the CPU so that this
+holds."""
+import numpy as np
+import pytest
+import torch
+
+import affordance_emu as aemu
+import render_emu as remu
+from giga_amd import networks, synth, visual
+from giga_amd.detection import VGNImplicit, grasp_select, predict_batch
+
+pytestmark = pytest.mark.gpu
+
+F32 = np.float32
+AGGREGATIONS = ("max", "softmax", "mean")
+
+
+def dev():
+    return torch.device("cuda:0")
+
+
+def t(x):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(dev())
+
+
+def volumes(seed, R, lo=0.0, hi=1.0, rot_scale=1.0):
+    rng = np.random.default_rng(seed)
+    qual = (F32(lo) + F32(hi - lo) * rng.random((R, R, R), dtype=F32)).astype(F32)
+    rot = rng.standard_normal((R, R, R, 4)).astype(F32)
+    rot /= np.linalg.norm(rot, axis=-1, keepdims=True)
+    return qual, (rot * F32(rot_scale)).astype(F32)
+
+
+def sphere_and_plane(subdiv=2, c=(0.15, 0.15, 0.1), r=0.08):
+    return remu.merge(remu.icosphere(c, r, subdiv), remu.plane_mesh(0.05, (0.0, 0.3, 0.0, 0.3)))
+
+
+def bits(x):
+    return np.ascontiguousarray(x).view(np.uint64)
+
+
+def tolerance(P, th):
+    return (P + 2) * 2.0 ** -50 / (1.0 - th)
+
+
+def check(qual, rot, mesh, dense_too=False, **kw):
+    """one scene on the device against the restatement; returns (device affordance or None, device colours, P)"""
+    v, f = mesh
+    p = dict(aemu.DEFAULTS, **kw)
+    pts, want, want_rgba, near = aemu.affordance(qual, rot, v, f, **kw)
+    got_pts = visual.affordance_points(t(qual), t(rot), p["size"], p["th"], p["finger_depth"], p["finger_offset"], p["move_center"])
+    assert got_pts.dtype == torch.float64 and tuple(got_pts.shape) == pts.shape
+    assert np.array_equal(bits(got_pts.cpu().numpy()), bits(pts))
+    aff, rgba = visual.affordance_faces(t(qual), t(rot), (v, f), **kw)
+    assert rgba.dtype == torch.uint8 and tuple(rgba.shape) == (len(f), 4) and rgba.is_cuda
+    rgba = rgba.cpu().numpy()
+    if len(pts) == 0:
+        assert aff is None and want is None and np.array_equal(rgba, want_rgba)
+        return None, rgba, 0
+    assert aff.dtype == torch.float64 and tuple(aff.shape) == (len(f),) and aff.is_cuda
+    aff = aff.cpu().numpy()
+    if p["aggregation"] == "max":
+        print(f"max: P {len(pts)}, F {len(f)}, pairs within 1e-9 of rad: {near}, faces above 0: {(want > 0).sum()}")
+        assert near == 0
+        assert np.array_equal(bits(aff), bits(want))
+    else:
+        edge = int(aemu.knife_edge_colours(want).sum())
+        err = np.abs(aff - want)
+        err = np.where(np.isnan(aff) & np.isnan(want), 0.0, err)
+        print(f"{p['aggregation']}: P {len(pts)}, F {len(f)}, knife-edge colours {edge}, max |device - restatement| {np.nanmax(err):.3e}, "
+              f"bound {tolerance(len(pts), p['th']):.3e}")
+        assert edge == 0
+        assert np.array_equal(np.isnan(aff), np.isnan(want))
+        assert (err <= tolerance(len(pts), p["th"])).all()
+    assert np.array_equal(rgba, want_rgba)
+    if dense_too:                                        # the cell grid changes no bit
+        aff2, rgba2 = visual.affordance_faces(t(qual), t(rot), (v, f), dense=True, **kw)
+        assert np.array_equal(bits(aff2.cpu().numpy()), bits(aff)) and np.array_equal(rgba2.cpu().numpy(), rgba)
+    return aff, rgba, len(pts)
+
+
+# ---- 1: R = 8, the 320-face icosphere merged with a plane -----------------------------------------------------------------
+@pytest.mark.parametrize("move_center", [True, False])
+@pytest.mark.parametrize("rad", [0.02, 0.05, 1.0])             # cell grid (18 and 8 cells per axis) and, at 1.0, the dense form
+@pytest.mark.parametrize("aggregation", AGGREGATIONS)
+def test_small_scene(aggregation, rad, move_center):
+    qual, rot = volumes(3, 8)
+    aff, rgba, P = check(qual, rot, sphere_and_plane(), dense_too=aggregation == "max", aggregation=aggregation, rad=rad,
+                         move_center=move_center)
+    assert 200 < P < 320 and (aff > 0).any()
+    if rad < 1.0 and aggregation != "mean":
+        assert (aff == 0).any() and len(np.unique(rgba, axis=0)) > 3
+
+
+def test_quaternions_of_any_length_fall_into_the_outermost_cells():
+    qual, rot = volumes(3, 8, rot_scale=2.5)                  # |z| up to ~12: points far outside the grid's box
+    mesh = remu.merge(sphere_and_plane(), remu.icosphere((0.2, 0.5, -0.3), 0.3, 1))
+    aff, _, _ = check(qual, rot, mesh, dense_too=True, rad=0.05)
+    assert (aff > 0).any()
+
+
+# ---- 2: more than one LDS tile and more than one workgroup of points ------------------------------------------------------
+@pytest.mark.parametrize("aggregation", AGGREGATIONS)
+@pytest.mark.parametrize("F", [1, 1283])
+def test_every_voxel_a_point(F, aggregation):
+    qual, rot = volumes(5, 12, lo=0.55, hi=0.95)
+    v, f = remu.merge(sphere_and_plane(3), (np.array([[0.1, 0.1, 0.12], [0.12, 0.1, 0.12], [0.1, 0.13, 0.14]], F32), np.array([[0, 1, 2]])))
+    assert len(f) == 1283
+    mesh = (v, f) if F == 1283 else (v[-3:], np.array([[0, 1, 2]], np.int32))
+    aff, _, P = check(qual, rot, mesh, dense_too=aggregation == "max", aggregation=aggregation)
+    assert P == 1728 and (aff > 0).any()
+
+
+# ---- 3: the planner's own volume at R = 40 --------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def planner_volume():
+    tsdf, qual, rot, width = synth.post_volumes(3, 40)
+    _, vol = grasp_select(t(tsdf[None]), t(qual.reshape(1, -1)), t(rot.reshape(1, -1, 4)), t(width.reshape(1, -1)), out_th=0.1,
+                          threshold=0.8, return_volume=True)
+    return vol[0].cpu().numpy(), rot, remu.merge(remu.icosphere((0.15, 0.15, 0.12), 0.1, 4), remu.plane_mesh(0.05, (0.0, 0.3, 0.0, 0.3)))
+
+
+@pytest.mark.parametrize("aggregation", AGGREGATIONS)
+def test_planner_volume(planner_volume, aggregation):
+    vol, rot, mesh = planner_volume
+    assert len(mesh[1]) == 5122
+    aff, rgba, P = check(vol, rot, mesh, dense_too=aggregation == "max", aggregation=aggregation)
+    assert P > 400 and (aff > 0).any()
+    if aggregation != "mean":
+        assert (aff == 0).any()                          # faces without a point in range
+
+
+# ---- 4: no point, one point ----------------------------------------------------------------------------------------------
+def test_no_point_and_one_point():
+    qual, rot = volumes(7, 8, lo=0.0, hi=0.5)
+    assert (qual <= F32(0.5)).all()
+    mesh = sphere_and_plane()
+    aff, rgba, P = check(qual, rot, mesh)
+    assert aff is None and P == 0 and (rgba == np.array([102, 102, 102, 255], np.uint8)).all()
+    cm = visual.affordance_visual(t(qual), t(rot), mesh, 0.3, 8)
+    assert cm.affordance is None and (cm.face_colors == np.array([102, 102, 102, 255], np.uint8)).all() and cm.ranges == {"scene": (0, 322)}
+    qual[4, 4, 3] = 0.9
+    for aggregation in AGGREGATIONS:
+        aff, rgba, P = check(qual, rot, mesh, dense_too=aggregation == "max", aggregation=aggregation, rad=0.05)
+        assert P == 1 and (aff > 0).any()
+
+
+# ---- 5: a ragged batch ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("aggregation", ["max", "mean"])
+def test_ragged_batch_equals_single_scene_calls(aggregation):
+    vols = [volumes(11, 8), volumes(12, 8, hi=0.5), volumes(13, 8)]
+    meshes = [(np.zeros((0, 3), F32), np.zeros((0, 3), np.int32)),
+              remu.merge(remu.box_mesh((0.05, 0.05, 0.05), (0.1, 0.12, 0.1)), remu.box_mesh((0.2, 0.1, 0.05), (0.25, 0.2, 0.2)),
+                         remu.plane_mesh(0.05, (0.0, 0.3, 0.0, 0.3))),
+              remu.icosphere((0.15, 0.15, 0.1), 0.08, 2)]
+    assert [len(m[1]) for m in meshes] == [0, 26, 320]
+    qual, rot = t(np.stack([v[0] for v in vols])), t(np.stack([v[1] for v in vols]).reshape(3, -1, 4))
+    batch = visual.affordance_faces(qual, rot, meshes, aggregation=aggregation, rad=0.05)
+    pts = visual.affordance_points(qual, rot)
+    assert len(batch) == 3 and len(pts) == 3 and len(pts[1]) == 0 and batch[1][0] is None
+    for b in range(3):
+        aff, rgba = visual.affordance_faces(qual[b], rot[b].reshape(8, 8, 8, 4), meshes[b], aggregation=aggregation, rad=0.05)
+        assert (aff is None) == (batch[b][0] is None) == (b == 1)
+        if aff is not None:
+            assert tuple(aff.shape) == (len(meshes[b][1]),) and np.array_equal(bits(aff.cpu().numpy()), bits(batch[b][0].cpu().numpy()))
+        assert np.array_equal(rgba.cpu().numpy(), batch[b][1].cpu().numpy())
+        one = visual.affordance_points(qual[b], rot[b].reshape(8, 8, 8, 4))
+        assert np.array_equal(bits(one.cpu().numpy()), bits(pts[b].cpu().numpy()))
+        want = aemu.affordance(vols[b][0], vols[b][1], *meshes[b], aggregation=aggregation, rad=0.05)
+        assert np.array_equal(rgba.cpu().numpy(), want[2]) and np.array_equal(bits(one.cpu().numpy()), bits(want[0]))
+
+
+# ---- 6: the <= of the radius on exact numbers -----------------------------------------------------------------------------
+def degenerate(points):
+    """one face per point, all three vertices on it"""
+    v = np.repeat(np.asarray(points, F32), 3, 0)
+    assert np.array_equal(v.astype(np.float64), np.repeat(np.asarray(points, np.float64), 3, 0))       # exact in float32
+    return v, np.arange(len(v), dtype=np.int32).reshape(-1, 3)
+
+
+@pytest.mark.parametrize("dense", [False, True])
+def test_radius_is_inclusive(dense):
+    R, e = 8, 2.0 ** -20
+    qual = np.zeros((R, R, R), F32)
+    qual[2, 3, 4] = 0.75
+    rot = np.zeros((R, R, R, 4), F32)
+    mesh = degenerate([(2.25, 3, 4), (2.25 + e, 3, 4), (1.75, 3, 4), (1.75 - e, 3, 4), (2, 3.25, 4), (2, 3.25 + e, 4), (2, 3, 3.75),
+                       (2, 3, 3.75 - e), (2, 3, 4), (6, 6, 6)])
+    kw = dict(size=float(R - 1), rad=0.25, move_center=False)
+    pts = visual.affordance_points(t(qual), t(rot), size=kw["size"], move_center=False).cpu().numpy()
+    assert np.array_equal(pts, [[2.0, 3.0, 4.0, 0.75]])
+    aff, rgba = visual.affordance_faces(t(qual), t(rot), mesh, dense=dense, **kw)
+    assert np.array_equal(aff.cpu().numpy(), [0.5, 0, 0.5, 0, 0.5, 0, 0.5, 0, 0.5, 0])
+    want = aemu.affordance(qual, rot, *mesh, **kw)
+    assert np.array_equal(want[1], aff.cpu().numpy()) and np.array_equal(want[2], rgba.cpu().numpy())
+
+
+# ---- 7: 'mean' without any weight ----------------------------------------------------------------------------------------
+def test_mean_of_no_weight_is_nan_and_transparent_black():
+    R = 8
+    qual = np.zeros((R, R, R), F32)
+    qual[0, 0, 0], qual[0, 0, 1] = 0.75, 0.875
+    rot = np.zeros((R, R, R, 4), F32)
+    mesh = degenerate([(0.25, 0, 0), (0, 0, 0)])               # the first 0.2 and more from both points: exp(-2000) = 0
+    kw = dict(aggregation="mean", temp=1e4, move_center=False)
+    aff, rgba = visual.affordance_faces(t(qual), t(rot), mesh, **kw)
+    aff, rgba = aff.cpu().numpy(), rgba.cpu().numpy()
+    assert np.isnan(aff[0]) and np.array_equal(rgba[0], [0, 0, 0, 0])
+    assert aff[1] == 0.5 and rgba[1, 3] == 255                 # exp(0) = 1 beside exp(-428) = 0: the mean is 0.75
+    want = aemu.affordance(qual, rot, *mesh, **kw)
+    assert np.isnan(want[1][0]) and want[1][1] == 0.5 and np.array_equal(want[2], rgba)
+
+
+# ---- 8: th is compared in float32 and subtracted in double ---------------------------------------------------------------
+def test_threshold_compares_in_float32_and_clips_in_double():
+    R, th = 8, 0.6
+    above = np.nextafter(F32(th), F32(1))
+    qual = np.zeros((R, R, R), F32)
+    qual[1, 1, 1], qual[2, 2, 2], qual[5, 5, 5] = F32(th), above, 0.9
+    rot = np.zeros((R, R, R, 4), F32)
+    kw = dict(th=th, move_center=False)
+    lin = aemu.lin(0.3, R)
+    pts = visual.affordance_points(t(qual), t(rot), th=th, move_center=False).cpu().numpy()
+    assert np.array_equal(pts, [[lin[2]] * 3 + [float(above)], [lin[5]] * 3 + [float(F32(0.9))]])      # F32(0.6) itself is dropped
+    mesh = degenerate([[F32(lin[1])] * 3, [F32(lin[2])] * 3, [F32(lin[5])] * 3])
+    aff, rgba = visual.affordance_faces(t(qual), t(rot), mesh, **kw)
+    aff = aff.cpu().numpy()
+    want = aemu.affordance(qual, rot, *mesh, **kw)
+    assert np.array_equal(bits(aff), bits(want[1])) and np.array_equal(rgba.cpu().numpy(), want[2])
+    assert aff[0] == 0 and aff[1] == (float(above) - 0.6) / (1 - 0.6) and aff[1] > 0 and aff[2] == (float(F32(0.9)) - 0.6) / (1 - 0.6)
+    assert aff[1] != float((above - F32(th)) / (F32(1) - F32(th)))                       # (what a float32 clip would give)
+
+
+def test_face_with_an_index_outside_its_scene():
+    qual, rot = volumes(3, 8)
+    v, f = remu.icosphere((0.15, 0.15, 0.1), 0.08, 1)
+    bad = np.concatenate((f, [[0, 1, len(v)], [0, -1, 2]])).astype(np.int32)
+    aff, rgba = visual.affordance_faces(t(qual), t(rot), (v, bad), rad=0.05)
+    good, good_rgba = visual.affordance_faces(t(qual), t(rot), (v, f), rad=0.05)
+    aff, rgba = aff.cpu().numpy(), rgba.cpu().numpy()
+    assert np.array_equal(aff[:-2], good.cpu().numpy()) and np.array_equal(rgba[:-2], good_rgba.cpu().numpy())
+    assert np.isnan(aff[-2:]).all() and (rgba[-2:] == 0).all()
+
+
+# ---- 9: the planner ------------------------------------------------------------------------------------------------------
+def test_planner_returns_the_composed_scene(sd7, tmp_path):
+    net = networks.get_network("giga")
+    net.load_state_dict(sd7)
+    net = net.to(dev()).eval()
+    kw = dict(net=net, best=True, force_detection=True, qual_th=0.6, out_th=0.1)
+    planner = VGNImplicit(None, None, visualize=True, use_graph=True, **kw)
+    mesh = sphere_and_plane()
+
+    class State:
+        tsdf = synth.tsdf_batch(0, 1, realistic=True)
+    out = planner(State(), mesh, {"rad": 0.03})
+    assert len(out) == 4 and not planner._graphs                  # the hipGraph path is not taken
+    grasps, scores, toc, scene = out
+    tsdf = t(State.tsdf)
+    qual, rot, width = predict_batch(tsdf, planner.pos, net)
+    sel, vol = grasp_select(tsdf, qual, rot, width, voxel_size=0.3 / 40, out_th=0.1, threshold=0.6, force_detection=True, max_filter_size=8,
+                            return_volume=True)
+    assert len(grasps) == len(sel[0]["score"]) > 0 and np.array_equal(scores, sel[0]["score"])
+    assert np.array_equal(np.stack([g["rotation"] for g in grasps]), sel[0]["rot"])
+    lin = planner._lin_host
+    assert np.array_equal(np.stack([g["translation"] for g in grasps]), (lin[sel[0]["index"]] + 0.5) * 0.3)
+    aff, rgba = visual.affordance_faces(vol[0], rot, mesh, rad=0.03)
+    F = len(mesh[1])
+    assert aff is not None and isinstance(scene, visual.Scene) and len(scene.faces) == F + 512 * len(grasps)
+    assert scene.ranges["scene"] == (0, F) and scene.ranges[f"grasp_{len(grasps) - 1}"] == (len(scene.faces) - 512, len(scene.faces))
+    assert np.array_equal(scene.face_colors[:F], rgba.cpu().numpy()) and len(np.unique(scene.face_colors[:F], axis=0)) > 1
+    assert np.array_equal(bits(scene.affordance.cpu().numpy()), bits(aff.cpu().numpy()))
+    assert np.array_equal(scene.geometry("grasp_0")[0] - (len(mesh[0])), visual.grasp2mesh(grasps[0]).faces)
+    assert np.array_equal(scene.vertices[len(mesh[0]):len(mesh[0]) + 264], visual.grasp2mesh(grasps[0], scores[0]).vertices)
+    assert (scene.face_colors[F:] == np.array([0, 250, 0, 180], np.uint8)).all()
+    assert scene.export(tmp_path / "scene.ply").endswith("scene.ply")
+    want = aemu.affordance(vol[0].cpu().numpy(), rot[0].cpu().numpy(), *mesh, rad=0.03)
+    assert want[3] == 0 and np.array_equal(want[2], scene.face_colors[:F])
+    plain = VGNImplicit(None, None, **kw)(State())
+    assert len(plain) == 3 and len(VGNImplicit(None, None, **kw)(State(), mesh)) == 3
+    with pytest.raises(ValueError):
+        planner(State())
