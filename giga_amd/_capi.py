@@ -30,7 +30,8 @@ DIRECT_CONV = 1024       # GIGA_DIRECT_CONV: precision 0 keeps the direct 3x3 co
 PATH_PERSISTENT, PATH_CONV32, PATH_FUSED_PAIRS, PATH_WINOGRAD = 1, 2, 4, 8          # giga_encoder_last_path()
 BWD_PATH_PERSISTENT, BWD_PATH_WINOGRAD, BWD_PATH_BF16 = 1, 2, 4                      # giga_backward_last_path()
 MESH_MAX_N = 513         # GIGA_MESH_MAX_N: samples per axis of a marching-cubes grid
-MISE_MAX_N = 513         # GIGA_MISE_MAX_N: samples per axis of a MISE value grid (resolution0 << depth) + 1
+SIMPLIFY_MIN_REF_EXTRA = 64      # GIGA_SIMPLIFY_MIN_REF_EXTRA: smallest appended room of a mesh's reference lists
+MISE_MAX_N = 513        # GIGA_MISE_MAX_N: samples per axis of a MISE value grid (resolution0 << depth) + 1
 TSDF_MAX_R = 512         # GIGA_TSDF_MAX_R: cells per axis of a fused volume
 RENDER_MAX_IMAGE = 4096  # GIGA_RENDER_MAX_IMAGE: width and height of a rendered depth image
 REFINE_MAX_FACES = 0x0FFFFFFF   # GIGA_REFINE_MAX_FACES (and _VERTICES)
@@ -152,6 +153,9 @@ _SIGNATURES = {
     "giga_mesh_emit": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
                                       ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
                                       ctypes.c_void_p, ctypes.c_void_p]),
+    "giga_simplify_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "giga_mesh_simplify": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_double,
+                                          ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]),
     "giga_mise_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "giga_mise_init": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "giga_mise_count": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),

@@ -92,6 +92,12 @@ size_t mesh_workspace_bytes(int B, int nx, int ny, int nz);
 int launch_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, uint8_t* ws, int* counts, hipStream_t s);
 int launch_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso, double box, const uint8_t* ws, float* vertices,
                      size_t cap_v, int* triangles, size_t cap_t, int* shortfall, hipStream_t s);
+// giga_simplify.hip
+long long simplify_ref_capacity(int n_triangles_of_mesh, int ref_extra);
+size_t simplify_workspace_bytes(int B, long long n_vertices, long long n_triangles, long long ref_total);
+int launch_mesh_simplify(const void* vertices, int vertices_f64, const int* vertex_offsets, const int* triangles,
+                         const int* triangle_offsets, const int* targets, int B, double agressiveness, int ref_extra,
+                         double* out_vertices, int* out_triangles, int* out_counts, int* stats, uint8_t* ws, hipStream_t st);
 // giga_mise.hip
 size_t mise_workspace_bytes(int B, int res0, int depth);
 int launch_mise_init(int B, int res0, int depth, uint8_t* ws, hipStream_t s);
@@ -364,6 +370,8 @@ const char* giga_strerror(int code) {
         case -7: return "more than GIGA_MAX_SCENES scenes in one call";
         case -8: return "packed blob was not produced by this version of the library (repack the weights)";
         case -10: return "HIP launch failed";
+        case -11: return "a face index lies outside its mesh's vertex range";
+        case -12: return "mesh simplification: a pass exceeded its round bound, or the reference-list capacity is too small for one collapse";
         default: return "unknown error";
     }
 }
@@ -933,6 +941,44 @@ static bool ragged_ok(const int32_t* offs, int B) {
     return true;
 }
 static int ragged_batch_check(int B) { return B < 0 ? -1 : (B > GIGA_MAX_SCENES ? -7 : 0); }
+
+// ---- mesh simplification (giga_simplify.hip) ----
+// the reference-list entries of a batch of B meshes with n_triangles faces in all (every mesh: 3 F entries + the appended room)
+static long long simplify_ref_total(int B, long long n_triangles, int ref_extra) {
+    return ref_extra < 0 ? 6 * n_triangles + (long long)GIGA_SIMPLIFY_MIN_REF_EXTRA * B : 3 * n_triangles + (long long)ref_extra * B;
+}
+static int simplify_shape_check(int B, long long n_vertices, long long n_triangles, int ref_extra) {
+    if (B < 0 || n_vertices < 0 || n_triangles < 0) return -1;
+    if (ref_extra >= 0 && ref_extra < GIGA_SIMPLIFY_MIN_REF_EXTRA) return -1;
+    if (B > GIGA_MAX_SCENES) return -7;
+    if (n_vertices > GIGA_SIMPLIFY_MAX_FACES || n_triangles > GIGA_SIMPLIFY_MAX_FACES) return -1;
+    if (simplify_ref_total(B, n_triangles, ref_extra) >= (1LL << 31)) return -1;
+    return 0;
+}
+
+size_t giga_simplify_workspace_bytes(int B, int n_vertices, int n_triangles, int ref_extra) {
+    if (B <= 0 || simplify_shape_check(B, n_vertices, n_triangles, ref_extra) != 0) return 0;
+    return simplify_workspace_bytes(B, n_vertices, n_triangles, simplify_ref_total(B, n_triangles, ref_extra));
+}
+
+int giga_mesh_simplify(const void* vertices, int vertices_f64, const int32_t* vertex_offsets, const int32_t* triangles,
+                       const int32_t* triangle_offsets, const int32_t* targets, int B, double agressiveness, int ref_extra,
+                       double* out_vertices, int32_t* out_triangles, int32_t* out_counts, int32_t* stats, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    if (const int rc = ragged_batch_check(B)) return rc;
+    if (B == 0) return 0;
+    if (!(agressiveness == agressiveness) || (vertices_f64 != 0 && vertices_f64 != 1)) return -1;
+    if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B) || !targets) return -1;
+    if (const int rc = simplify_shape_check(B, vertex_offsets[B], triangle_offsets[B], ref_extra)) return rc;
+    for (int b = 0; b < B; ++b)
+        if (targets[b] < 0) return -1;
+    if ((vertex_offsets[B] > 0 && !vertices) || (triangle_offsets[B] > 0 && !triangles) || !workspace) return -1;
+    if (!out_counts || (vertex_offsets[B] > 0 && triangle_offsets[B] > 0 && (!out_vertices || !out_triangles))) return -6;
+    if (workspace_bytes < giga_simplify_workspace_bytes(B, vertex_offsets[B], triangle_offsets[B], ref_extra)) return -4;
+    return launch_mesh_simplify(vertices, vertices_f64, vertex_offsets, triangles, triangle_offsets, targets, B, agressiveness, ref_extra,
+                                out_vertices, out_triangles, out_counts, stats, static_cast<uint8_t*>(workspace),
+                                static_cast<hipStream_t>(stream));
+}
 
 size_t giga_nn_query_workspace_bytes(int B, int n_src) {
     if (B <= 0 || B > GIGA_MAX_SCENES || n_src < 0) return 0;

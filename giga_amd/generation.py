@@ -24,8 +24,14 @@ dense one cannot afford (257^3, 513^3).
 Mesh refinement (`refinement_step`, generation.py:457-519) runs on the device as well (`giga_amd.refine`, csrc/giga_refine.hip):
 per scene, `refinement_step` RMSprop steps of four launches each on the vertices marching cubes left on the device, before the
 final copy.  The second derivative of the occupancy logit that the reference asks of autograd through `F.grid_sample` (a double
-backward current torch builds do not implement) is three numbers per face point from the point-gradient kernel.  Simplification
-(`simplify_nfaces`) and the crop mode (`vol_bound`) are not built."""
+backward current torch builds do not implement) is three numbers per face point from the point-gradient kernel.
+
+Mesh simplification (`simplify_nfaces`, generation.py:417-420: `simplify_mesh(mesh, simplify_nfaces, 5.)`, the quadric edge collapse
+of utils/libsimplify/Simplify.h) runs on the device too (`giga_amd.mesh.simplify_mesh`, csrc/giga_simplify.hip): after the normals,
+all scenes in one call, the reference's mesh face for face and vertex for vertex in float64 (cast to float32 where the `Mesh` leaves
+the device).  A simplified mesh carries no vertex normals ("normals are lost here", generation.py:419).  `simplify_nfaces` together
+with `refinement_step > 0` in ONE generator is not built; the two-call route works: simplify with one generator, then
+`Generator3D(net, refinement_step=k).refine_mesh(mesh, c=c)`.  The crop mode (`vol_bound`) is not built."""
 import time
 
 import numpy as np
@@ -33,7 +39,7 @@ import torch
 
 from . import _capi
 from .convonet import _planes_to_nhwc, decoder_point_grad, register_lattice
-from .mesh import Mesh, marching_cubes
+from .mesh import Mesh, marching_cubes, simplify_mesh
 from .mise import lin_table, mise_grid
 from .refine import MeshRefiner
 
@@ -46,8 +52,11 @@ class Generator3D:
                  vol_info=None, vol_bound=None, mise=False, refine_seed=0):
         """The reference's arguments by name (generation.py:42-49).  `refinement_step > 0` runs that many refinement steps on
         every extracted mesh (`refine_mesh`); it has no CPU path and raises here for a device that is not a HIP device.
-        `refine_seed` keys the barycentric draws (the reference uses numpy's global generator).  `simplify_nfaces` (quadric
-        simplification) is not built and raises here; `vol_bound` (crop mode) raises when a mesh is asked for.  `mesh_options`
+        `refine_seed` keys the barycentric draws (the reference uses numpy's global generator).  `simplify_nfaces=N` simplifies
+        every extracted mesh to at most N faces (quadric edge collapse, agressiveness 5, module docstring); it has no CPU path
+        either and raises here for a device that is not a HIP device, and so does its combination with `refinement_step > 0`,
+        which is not built (simplify with one generator, then `Generator3D(net, refinement_step=k).refine_mesh(mesh, c=c)`).
+        `vol_bound` (crop mode) raises when a mesh is asked for.  `mesh_options`
         records the mesh arguments as a dict.  `mise=True` fills the value grid by MISE as the reference does (module
         docstring); the default decodes every sample."""
         device = device if device is not None else torch.device("cuda")
@@ -56,7 +65,13 @@ class Generator3D:
         if refinement_step < 0:                                # (as before: every non-zero value that is not served raises)
             raise NotImplementedError("a negative refinement_step is not built")
         if simplify_nfaces is not None:
-            raise NotImplementedError("mesh simplification (simplify_nfaces) is not built")
+            if torch.device(device).type != "cuda":
+                raise NotImplementedError("mesh simplification runs only on a HIP device")
+            if refinement_step > 0:
+                raise NotImplementedError("simplify_nfaces together with refinement_step > 0 is not built: simplify with one "
+                                          "generator, then Generator3D(net, refinement_step=k).refine_mesh(mesh, c=c)")
+            if int(simplify_nfaces) < 0:
+                raise ValueError("simplify_nfaces must not be negative")
         mesh_options = dict(upsampling_steps=upsampling_steps, with_normals=with_normals, padding=padding,
                             refinement_step=refinement_step, simplify_nfaces=simplify_nfaces, sample=sample,
                             input_type=input_type, vol_info=vol_info, vol_bound=vol_bound)
@@ -70,7 +85,7 @@ class Generator3D:
         self.upsampling_steps = int(upsampling_steps)
         self.with_normals = bool(with_normals)
         self.padding = padding
-        self.simplify_nfaces = None
+        self.simplify_nfaces = int(simplify_nfaces) if simplify_nfaces is not None else None
         self.mesh_options = dict(mesh_options)
         self.mise = bool(mise)
         self._grids = {}
@@ -215,6 +230,15 @@ class Generator3D:
                     if nv:
                         normals[v1 - nv:v1] = self._normals_on_device(vertices[v1 - nv:v1], nhwc[:, b:b + 1].contiguous())
             stats_dict["time (normals)"] = time.time() - t0
+        if self.simplify_nfaces is not None and t_end[-1] > 0:
+            # generation.py:417-420: after the normals, which belong to the vertices of the full mesh ("normals are lost here").
+            # All scenes in one call (they share their rounds); an empty mesh passes through as it is.
+            t0 = time.time()
+            vertices, triangles, counts = simplify_mesh(vertices, triangles, self.simplify_nfaces, 5., counts=counts)
+            counts = counts.cpu()
+            v_end, t_end = counts[:, 0].cumsum(0).tolist(), counts[:, 1].cumsum(0).tolist()
+            vertices, normals = vertices.float(), None
+            stats_dict["time (simplify)"] = time.time() - t0
         if self.refinement_step > 0 and v_end[-1] > 0:
             # generation.py:423-426: after the normals, which belong to the unrefined vertices and are lost with them (trimesh
             # drops its cached vertex normals when `mesh.vertices` is assigned): a refined mesh carries none

@@ -49,3 +49,58 @@ def marching_cubes(grids, iso, box_size=1.0):
                                      _capi.ptr(vertices), cap_v, _capi.ptr(triangles), cap_t, None,
                                      _capi.stream_ptr(dev)), "giga_mesh_emit")
     return vertices, triangles, counts
+
+
+def simplify_mesh(vertices, faces, f_target, agressiveness=7., counts=None, stats=None, ref_extra=None):
+    """The reference's `simplify_mesh(mesh, f_target, agressiveness)` (utils/libsimplify: the greedy quadric edge collapse of
+    Simplify.h) on device-resident meshes, face for face and vertex for vertex in float64 (csrc/giga_simplify.hip through
+    giga_mesh_simplify).  vertices (V,3) float32 or float64 and faces (F,3) integer tensors on the device; one mesh, or with
+    `counts` (B,2) = {#vertices, #faces} per mesh, B meshes back to back as `marching_cubes` returns them (a mesh's faces count
+    from its own first vertex).  f_target: an int, or one int per mesh.  Returns device tensors (vertices (V',3) float64, faces
+    (F',3) of the dtype given, counts (B,2) int64) in the same layout.  A mesh with no more than f_target faces comes back with
+    its unreferenced vertices dropped, an empty mesh comes back empty.  `stats` (a dict) receives "iterations", "rounds",
+    "repeated passes" and "list rebuilds", one int per mesh.  `ref_extra`: room of the per-vertex reference lists beyond 3 F
+    entries per mesh (default 3 F + 64; not below `_capi.SIMPLIFY_MIN_REF_EXTRA`), which changes how often the lists are rebuilt
+    and nothing else.  There is no CPU path: a host tensor raises GigaHipError.  The call reads the pending counts back between
+    rounds, so it returns with the result computed."""
+    if vertices.dim() != 2 or vertices.shape[-1] != 3 or faces.dim() != 2 or faces.shape[-1] != 3:
+        raise ValueError(f"expected (V,3) vertices and (F,3) faces, got {tuple(vertices.shape)} and {tuple(faces.shape)}")
+    dev = _capi.device_of(vertices, faces)
+    if counts is None:
+        counts_h = torch.tensor([[vertices.shape[0], faces.shape[0]]], dtype=torch.int64)
+    else:
+        counts_h = torch.as_tensor(counts).detach().cpu().to(torch.int64).reshape(-1, 2)
+    B = counts_h.shape[0]
+    if int(counts_h[:, 0].sum()) != vertices.shape[0] or int(counts_h[:, 1].sum()) != faces.shape[0] or bool((counts_h < 0).any()):
+        raise ValueError("counts do not add up to the vertices and faces given")
+    targets = torch.as_tensor(f_target, dtype=torch.int64).reshape(-1).cpu()
+    targets = targets.expand(B) if targets.numel() == 1 else targets
+    if targets.numel() != B:
+        raise ValueError(f"expected one f_target or one per mesh ({B}), got {targets.numel()}")
+    targets = targets.clamp(max=2 ** 31 - 1).to(torch.int32).contiguous()
+    v = vertices.detach().contiguous()
+    if v.dtype != torch.float64:
+        v = v.float()
+    f = faces.detach().to(torch.int32).contiguous()
+    zero = torch.zeros((1, 1), dtype=torch.int64)
+    voff = torch.cat((zero, counts_h[:, :1].cumsum(0))).to(torch.int32).reshape(-1).contiguous()
+    foff = torch.cat((zero, counts_h[:, 1:].cumsum(0))).to(torch.int32).reshape(-1).contiguous()
+    extra = -1 if ref_extra is None else int(ref_extra)
+    L = _capi.lib()
+    out_v = torch.empty((v.shape[0], 3), dtype=torch.float64, device=dev)
+    out_f = torch.empty((f.shape[0], 3), dtype=torch.int32, device=dev)
+    out_c = torch.zeros((max(B, 1), 2), dtype=torch.int32, device=dev)
+    st = torch.zeros((max(B, 1), 4), dtype=torch.int32)
+    need = L.giga_simplify_workspace_bytes(B, v.shape[0], f.shape[0], extra) if B else 0
+    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _capi.check(L.giga_mesh_simplify(_capi.ptr(v), int(v.dtype == torch.float64), _capi.ptr(voff), _capi.ptr(f), _capi.ptr(foff),
+                                         _capi.ptr(targets), B, float(agressiveness), extra, _capi.ptr(out_v), _capi.ptr(out_f),
+                                         _capi.ptr(out_c), _capi.ptr(st), _capi.ptr(ws), ws.numel() if need else 0,
+                                         _capi.stream_ptr(dev)), "giga_mesh_simplify")
+        out_counts = out_c[:B].to(torch.int64)
+        totals = out_counts.sum(0).tolist() if B else [0, 0]
+    if stats is not None:
+        for k, name in enumerate(("iterations", "rounds", "repeated passes", "list rebuilds")):
+            stats[name] = st[:B, k].tolist()
+    return out_v[:totals[0]], out_f[:totals[1]].to(faces.dtype), out_counts

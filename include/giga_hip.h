@@ -659,6 +659,35 @@ int giga_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso
                    size_t workspace_bytes, float* vertices, size_t cap_v, int32_t* triangles, size_t cap_t, int32_t* shortfall,
                    void* stream);
 
+/* ---- mesh simplification: the greedy quadric edge collapse of utils/libsimplify/Simplify.h, as conv_onet/generation.py:417-420
+ * calls it (simplify_mesh(mesh, simplify_nfaces, 5.)); added within ABI 3 -----
+ * B meshes packed back to back in the layout giga_mesh_emit produces: vertices [.][3] float32 (vertices_f64 = 0; widened exactly)
+ * or float64 (vertices_f64 = 1) and triangles [.][3] int32 (device), a mesh's triangles counting from its OWN first vertex;
+ * vertex_offsets, triangle_offsets [B+1] int32 and targets [B] int32 are HOST arrays.  Mesh b is simplified to at most targets[b]
+ * faces exactly as `Simplify::simplify_mesh(targets[b], agressiveness)` on value-initialised records does it -- float64 in the
+ * header's order of operations, no fused multiply-add; up to 100 iterations, a mesh that cannot reach its target ends above it;
+ * a mesh with no more faces than its target only loses its unreferenced vertices.  All meshes of a call share their rounds (a
+ * batch costs the rounds of its slowest mesh).  Outputs (device, caller-owned, at least as large as the inputs): out_vertices
+ * [.][3] float64 and out_triangles [.][3] int32, meshes back to back, faces counting from the mesh's own first vertex;
+ * out_counts [B][2] int32 = {#vertices, #triangles}.  stats (HOST, may be NULL) [B][4] int32 = {iterations, rounds, passes run
+ * again to meet the face budget exactly, rebuilds of the reference lists}.  ref_extra: entries of the per-vertex reference lists
+ * beyond the 3 F a mesh starts with, per mesh; < 0 = the default 3 F + GIGA_SIMPLIFY_MIN_REF_EXTRA; a smaller value (at least
+ * GIGA_SIMPLIFY_MIN_REF_EXTRA) only makes the lists be rebuilt more often, the result is the same.
+ * The call drives the rounds itself: it synchronises `stream` (the pending counts are read back every few rounds) and has
+ * returned its result when it returns.  No allocation: everything lives in the workspace.
+ * Errors: -1 negative B, offsets that do not start at 0 or decrease, a target < 0, NaN agressiveness, vertices_f64 not 0 / 1,
+ * 0 <= ref_extra < GIGA_SIMPLIFY_MIN_REF_EXTRA, more than GIGA_SIMPLIFY_MAX_FACES vertices or faces in the call, null inputs /
+ * targets / workspace; -4 workspace too small; -6 null output; -7 B > GIGA_MAX_SCENES; -11 a face index outside its mesh's
+ * vertex range (found by a check launch before anything else runs, nothing is written to the outputs); -12 a pass exceeded its
+ * bound of one round per candidate, or ref_extra is too small for a single collapse.  B = 0 returns 0. */
+#define GIGA_SIMPLIFY_MIN_REF_EXTRA 64
+#define GIGA_SIMPLIFY_MAX_FACES 0x0FFFFFFF
+size_t giga_simplify_workspace_bytes(int B, int n_vertices, int n_triangles, int ref_extra);
+int giga_mesh_simplify(const void* vertices, int vertices_f64, const int32_t* vertex_offsets, const int32_t* triangles,
+                       const int32_t* triangle_offsets, const int32_t* targets, int B, double agressiveness, int ref_extra,
+                       double* out_vertices, int32_t* out_triangles, int32_t* out_counts, int32_t* stats, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* ---- MISE: the sparse value grid of conv_onet/generation.py:125-142 (utils/libmise/mise.pyx), B independent octrees (added within
  * ABI 3) -----
  * R = resolution0 << depth, N = R + 1 <= GIGA_MISE_MAX_N samples per axis, depth >= 1; sample (i, j, k) has the linear index
