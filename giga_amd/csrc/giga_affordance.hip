@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
 #include "giga_scan.h"
+#include "giga_ws.h"
 #include "../../include/giga_hip.h"
 #include <cmath>
 #include <cstdint>
@@ -93,8 +94,7 @@ struct AffPointArgs {
     const float* qual;
     const float* rot;
     double* points;
-    int* counts;
-    unsigned* block_base;                         // [B][nblk]: counts after the first kernel, exclusive prefixes after the second
+    unsigned* block_base;                         // [B][nblk]: counts after the first kernel, exclusive prefixes after the scan
     double step, size;
     float th, depth, offset;
     int R, nblk, move_center;
@@ -108,23 +108,6 @@ __global__ __launch_bounds__(AFF_BLOCK) void affordance_count_kernel(AffPointArg
     unsigned total;
     block_excl<AFF_WAVES>(keep ? 1u : 0u, wsum, total);
     if (threadIdx.x == 0) g.block_base[(size_t)blockIdx.y * g.nblk + blockIdx.x] = total;
-}
-
-// one workgroup per scene turns its block counts into exclusive prefixes, in block order
-__global__ __launch_bounds__(AFF_BLOCK) void affordance_scan_kernel(AffPointArgs g) {
-    __shared__ unsigned wsum[AFF_WAVES];
-    unsigned* __restrict__ base = g.block_base + (size_t)blockIdx.x * g.nblk;
-    unsigned run = 0;
-    for (int b0 = 0; b0 < g.nblk; b0 += AFF_BLOCK) {
-        const int b = b0 + (int)threadIdx.x;
-        const unsigned n = b < g.nblk ? base[b] : 0u;
-        unsigned total;
-        const unsigned pre = block_excl<AFF_WAVES>(n, wsum, total);
-        if (b < g.nblk) base[b] = run + pre;
-        run += total;
-        __syncthreads();                          // wsum is written again by the next round
-    }
-    if (threadIdx.x == 0) g.counts[blockIdx.x] = (int)run;
 }
 
 __global__ __launch_bounds__(AFF_BLOCK) void affordance_emit_kernel(AffPointArgs g) {
@@ -371,24 +354,21 @@ __global__ __launch_bounds__(AFF_BLOCK) void affordance_faces_kernel(AffFaceArgs
 }
 
 // ------------------------------------------------------------------------------------------------------------------- host
-static size_t aff_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct AffWs { size_t reds, voffs, toffs, boffs, block_base, keys[2], order[2], start, total; };
 static AffWs aff_workspace(int B, int R) {
     const size_t V = (size_t)R * R * R, nblk = (V + AFF_BLOCK - 1) / AFF_BLOCK;
     const size_t sortV = (long long)V <= AFF_GRID_MAX_VOXELS ? V : 0;
+    WsLayout L;
     AffWs w;
-    w.reds = 0;
-    w.voffs = 1024;
-    w.toffs = w.voffs + aff_align((size_t)(B + 1) * sizeof(int));
-    w.boffs = w.toffs + aff_align((size_t)(B + 1) * sizeof(int));
-    w.block_base = w.boffs + aff_align((size_t)(B + 1) * sizeof(int));
-    size_t at = w.block_base + aff_align((size_t)B * nblk * sizeof(unsigned));
-    for (int i = 0; i < 2; ++i) { w.keys[i] = at; at += aff_align((size_t)B * sortV * sizeof(unsigned)); }
-    for (int i = 0; i < 2; ++i) { w.order[i] = at; at += aff_align((size_t)B * sortV * sizeof(unsigned)); }
-    w.start = at;
-    at += sortV ? aff_align((size_t)B * ((size_t)AFF_GRID_MAX * AFF_GRID_MAX * AFF_GRID_MAX + 1) * sizeof(unsigned)) : 0;
-    w.total = at;
+    w.reds = L.take<uchar4>(256);
+    w.voffs = L.take<int>((size_t)B + 1);
+    w.toffs = L.take<int>((size_t)B + 1);
+    w.boffs = L.take<int>((size_t)B + 1);
+    w.block_base = L.take<unsigned>((size_t)B * nblk);
+    for (int i = 0; i < 2; ++i) w.keys[i] = L.take<unsigned>((size_t)B * sortV);
+    for (int i = 0; i < 2; ++i) w.order[i] = L.take<unsigned>((size_t)B * sortV);
+    w.start = L.take<unsigned>(sortV ? (size_t)B * ((size_t)AFF_GRID_MAX * AFF_GRID_MAX * AFF_GRID_MAX + 1) : 0);
+    w.total = L.total;
     return w;
 }
 size_t affordance_workspace_bytes(int B, int R) { return aff_workspace(B, R).total; }
@@ -397,7 +377,7 @@ int launch_affordance_points(const float* qual, const float* rot, int B, int R, 
                              int* counts, uint8_t* ws, hipStream_t s) {
     const AffWs w = aff_workspace(B, R);
     AffPointArgs g;
-    g.qual = qual; g.rot = rot; g.points = points; g.counts = counts;
+    g.qual = qual; g.rot = rot; g.points = points;
     g.block_base = reinterpret_cast<unsigned*>(ws + w.block_base);
     g.step = prm->size / (double)(R - 1);
     g.size = prm->size;
@@ -406,7 +386,8 @@ int launch_affordance_points(const float* qual, const float* rot, int B, int R, 
     g.V = (unsigned)((size_t)R * R * R);
     g.nblk = (int)((g.V + AFF_BLOCK - 1) / AFF_BLOCK);
     GIGA_LAUNCH(affordance_count_kernel, dim3((unsigned)g.nblk, (unsigned)B), dim3(AFF_BLOCK), 0, s, g);
-    GIGA_LAUNCH(affordance_scan_kernel, dim3((unsigned)B), dim3(AFF_BLOCK), 0, s, g);
+    GIGA_LAUNCH(scene_offsets_kernel<unsigned>, dim3((unsigned)B), dim3(SCAN_BLOCK), 0, s, g.block_base, (unsigned)g.nblk, counts,
+                static_cast<int*>(nullptr));
     GIGA_LAUNCH(affordance_emit_kernel, dim3((unsigned)g.nblk, (unsigned)B), dim3(AFF_BLOCK), 0, s, g);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }

@@ -942,6 +942,27 @@ static bool ragged_ok(const int32_t* offs, int B) {
 }
 static int ragged_batch_check(int B) { return B < 0 ? -1 : (B > GIGA_MAX_SCENES ? -7 : 0); }
 
+// a ragged batch of B meshes: both offset arrays are well formed, and data that is not empty has a pointer
+static bool mesh_batch_check(const int32_t* vertex_offsets, const int32_t* triangle_offsets, int B, const void* vertices,
+                             const void* triangles) {
+    if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B)) return false;
+    return (vertex_offsets[B] == 0 || vertices) && (triangle_offsets[B] == 0 || triangles);
+}
+
+static bool finite_f64(double x) { return x - x == 0.0; }
+
+// n cameras (extrinsics [n][16], intrinsics [n][4] = fx, fy, cx, cy): every number finite, no focal length zero
+static bool camera_check(int n, const double* extrinsics, const double* intrinsics) {
+    if (n > 0 && (!extrinsics || !intrinsics)) return false;
+    for (size_t i = 0; i < (size_t)n * 16; ++i)
+        if (!finite_f64(extrinsics[i])) return false;
+    for (size_t i = 0; i < (size_t)n * 4; ++i)
+        if (!finite_f64(intrinsics[i])) return false;
+    for (int v = 0; v < n; ++v)
+        if (intrinsics[4 * (size_t)v] == 0.0 || intrinsics[4 * (size_t)v + 1] == 0.0) return false;
+    return true;
+}
+
 // ---- mesh simplification (giga_simplify.hip) ----
 // the reference-list entries of a batch of B meshes with n_triangles faces in all (every mesh: 3 F entries + the appended room)
 static long long simplify_ref_total(int B, long long n_triangles, int ref_extra) {
@@ -968,11 +989,11 @@ int giga_mesh_simplify(const void* vertices, int vertices_f64, const int32_t* ve
     if (const int rc = ragged_batch_check(B)) return rc;
     if (B == 0) return 0;
     if (!(agressiveness == agressiveness) || (vertices_f64 != 0 && vertices_f64 != 1)) return -1;
-    if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B) || !targets) return -1;
+    // (every check from here to the workspace pointer answers -1: simplify_shape_check has no other code once B is in range)
+    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !targets || !workspace) return -1;
     if (const int rc = simplify_shape_check(B, vertex_offsets[B], triangle_offsets[B], ref_extra)) return rc;
     for (int b = 0; b < B; ++b)
         if (targets[b] < 0) return -1;
-    if ((vertex_offsets[B] > 0 && !vertices) || (triangle_offsets[B] > 0 && !triangles) || !workspace) return -1;
     if (!out_counts || (vertex_offsets[B] > 0 && triangle_offsets[B] > 0 && (!out_vertices || !out_triangles))) return -6;
     if (workspace_bytes < giga_simplify_workspace_bytes(B, vertex_offsets[B], triangle_offsets[B], ref_extra)) return -4;
     return launch_mesh_simplify(vertices, vertices_f64, vertex_offsets, triangles, triangle_offsets, targets, B, agressiveness, ref_extra,
@@ -1009,8 +1030,7 @@ int giga_mesh_sample(const float* vertices, const int32_t* vertex_offsets, const
     if (const int rc = ragged_batch_check(B)) return rc;
     if (n < 0 || first_scene < 0 || (long long)B * n >= (1LL << 31)) return -1;
     if (B == 0) return 0;
-    if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B)) return -1;
-    if ((vertex_offsets[B] > 0 && !vertices) || (triangle_offsets[B] > 0 && !triangles) || !workspace) return -1;
+    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !workspace) return -1;
     if (!counts || (n > 0 && (!points || !face || !normals))) return -6;
     if (workspace_bytes < giga_mesh_sample_workspace_bytes(B, triangle_offsets[B])) return -4;
     return launch_mesh_sample(vertices, vertex_offsets, triangles, triangle_offsets, B, n, seed, first_scene, points, face, normals, counts,
@@ -1029,8 +1049,8 @@ int giga_mesh_contains(const float* vertices, const int32_t* vertex_offsets, con
     if (resolution < 2 || resolution > GIGA_CONTAINS_MAX_RESOLUTION) return -1;
     if (B == 0) return 0;
     if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B) || !ragged_ok(point_offsets, B)) return -1;
-    if (point_offsets[B] == 0) return 0;
-    if ((vertex_offsets[B] > 0 && !vertices) || (triangle_offsets[B] > 0 && !triangles) || !points || !workspace) return -1;
+    if (point_offsets[B] == 0) return 0;                    // (whatever the data pointers: only the offsets are looked at before)
+    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !points || !workspace) return -1;
     if (!inside) return -6;
     if (workspace_bytes < giga_mesh_contains_workspace_bytes(B, triangle_offsets[B], point_offsets[B])) return -4;
     return launch_mesh_contains(vertices, vertex_offsets, triangles, triangle_offsets, points, point_offsets, B, resolution, inside,
@@ -1039,8 +1059,6 @@ int giga_mesh_contains(const float* vertices, const int32_t* vertex_offsets, con
 
 
 // ---- depth fusion (giga_tsdf.hip) ----
-static bool tsdf_finite(double x) { return x - x == 0.0; }
-
 static int tsdf_volume_check(int B, int R) {
     if (B < 0 || R < 2 || R > GIGA_TSDF_MAX_R) return -1;
     if (B > GIGA_MAX_SCENES) return -7;
@@ -1057,22 +1075,14 @@ int giga_tsdf_integrate(const float* depth, const int32_t* view_offsets, const d
                         float* tsdf, float* weight, float* grid, void* workspace, size_t workspace_bytes, void* stream) {
     if (const int rc = tsdf_volume_check(B, R)) return rc;
     if (width < 1 || height < 1 || width > GIGA_TSDF_MAX_IMAGE || height > GIGA_TSDF_MAX_IMAGE) return -1;
-    if (!tsdf_finite(length) || !(length > 0.0) || !tsdf_finite(sdf_trunc) || !(sdf_trunc > 0.0) || !tsdf_finite(depth_scale) ||
+    if (!finite_f64(length) || !(length > 0.0) || !finite_f64(sdf_trunc) || !(sdf_trunc > 0.0) || !finite_f64(depth_scale) ||
         !(depth_scale > 0.0) || !(depth_trunc == depth_trunc))
         return -1;
     if (B == 0) return 0;
     if (!ragged_ok(view_offsets, B)) return -1;
     const int n = view_offsets[B];
     if ((long long)n * width * height >= (1LL << 40)) return -1;
-    if (n > 0) {
-        if (!extrinsics || !intrinsics || !depth) return -1;
-        for (size_t i = 0; i < (size_t)n * 16; ++i)
-            if (!tsdf_finite(extrinsics[i])) return -1;
-        for (size_t i = 0; i < (size_t)n * 4; ++i)
-            if (!tsdf_finite(intrinsics[i])) return -1;
-        for (int v = 0; v < n; ++v)
-            if (intrinsics[4 * (size_t)v] == 0.0 || intrinsics[4 * (size_t)v + 1] == 0.0) return -1;
-    }
+    if (!camera_check(n, extrinsics, intrinsics) || (n > 0 && !depth)) return -1;
     if (!tsdf || !weight || !workspace) return -1;
     if (workspace_bytes < giga_tsdf_integrate_workspace_bytes(B, n)) return -4;
     return launch_tsdf_integrate(depth, view_offsets, extrinsics, intrinsics, B, width, height, length, R, sdf_trunc, depth_scale,
@@ -1096,7 +1106,7 @@ int giga_tsdf_cloud_count(const float* tsdf, const float* weight, int B, int R, 
 int giga_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, double length, const void* workspace,
                          size_t workspace_bytes, float* points, size_t cap, int32_t* shortfall, void* stream) {
     if (const int rc = tsdf_volume_check(B, R)) return rc;
-    if (!tsdf_finite(length) || !(length > 0.0)) return -1;
+    if (!finite_f64(length) || !(length > 0.0)) return -1;
     if (B == 0) return 0;
     if (!tsdf || !weight || !workspace) return -1;
     if (cap > 0 && !points) return -6;
@@ -1116,20 +1126,13 @@ int giga_depth_render(const float* vertices, const int32_t* vertex_offsets, cons
                       double far, double pixel_offset, float* depth, void* workspace, size_t workspace_bytes, void* stream) {
     if (const int rc = ragged_batch_check(B)) return rc;
     if (W < 1 || H < 1 || W > GIGA_RENDER_MAX_IMAGE || H > GIGA_RENDER_MAX_IMAGE) return -1;
-    if (!tsdf_finite(near) || !tsdf_finite(far) || !(near > 0.0) || !(far > near) || !tsdf_finite(pixel_offset)) return -1;
+    if (!finite_f64(near) || !finite_f64(far) || !(near > 0.0) || !(far > near) || !finite_f64(pixel_offset)) return -1;
     if (B == 0) return 0;
-    if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B) || !ragged_ok(view_offsets, B)) return -1;
+    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !ragged_ok(view_offsets, B)) return -1;
     const int n = view_offsets[B];
     if ((long long)n * W * H >= (1LL << 31)) return -1;
-    if ((vertex_offsets[B] > 0 && !vertices) || (triangle_offsets[B] > 0 && !triangles)) return -1;
     if (n == 0) return 0;
-    if (!extrinsics || !intrinsics || !workspace) return -1;
-    for (size_t i = 0; i < (size_t)n * 16; ++i)
-        if (!tsdf_finite(extrinsics[i])) return -1;
-    for (size_t i = 0; i < (size_t)n * 4; ++i)
-        if (!tsdf_finite(intrinsics[i])) return -1;
-    for (int v = 0; v < n; ++v)
-        if (intrinsics[4 * (size_t)v] == 0.0 || intrinsics[4 * (size_t)v + 1] == 0.0) return -1;
+    if (!camera_check(n, extrinsics, intrinsics) || !workspace) return -1;
     if (!depth) return -6;
     if (workspace_bytes < giga_depth_render_workspace_bytes(B, n, vertex_offsets[B], triangle_offsets[B])) return -4;
     return launch_depth_render(vertices, vertex_offsets, triangles, triangle_offsets, view_offsets, extrinsics, intrinsics, B, W, H, near,
@@ -1142,8 +1145,8 @@ static int affordance_check(int B, int R, const GigaAffordanceParams* p) {
     if (!p || R < 2 || R > GIGA_TSDF_MAX_R) return -1;
     const int mode = p->aggregation & ~GIGA_AFFORDANCE_DENSE;
     if (mode != GIGA_AFFORDANCE_MAX && mode != GIGA_AFFORDANCE_SOFTMAX && mode != GIGA_AFFORDANCE_MEAN) return -1;
-    if (!tsdf_finite(p->size) || !tsdf_finite(p->th) || !tsdf_finite(p->temp) || !tsdf_finite(p->rad) || !tsdf_finite(p->finger_depth) ||
-        !tsdf_finite(p->finger_offset))
+    if (!finite_f64(p->size) || !finite_f64(p->th) || !finite_f64(p->temp) || !finite_f64(p->rad) || !finite_f64(p->finger_depth) ||
+        !finite_f64(p->finger_offset))
         return -1;
     return 0;
 }
@@ -1169,8 +1172,10 @@ int giga_affordance_faces(const float* vertices, const int32_t* vertex_offsets, 
     if (const int rc = affordance_check(B, R, params)) return rc;
     if (B == 0) return 0;
     if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B)) return -1;
-    if (triangle_offsets[B] == 0) return 0;
-    if ((vertex_offsets[B] > 0 && !vertices) || !triangles || !points || !counts || !affordance || !rgba || !workspace) return -1;
+    if (triangle_offsets[B] == 0) return 0;                 // (whatever the data pointers: only the offsets are looked at before)
+    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !points || !counts || !affordance || !rgba ||
+        !workspace)
+        return -1;
     if (workspace_bytes < giga_affordance_workspace_bytes(B, R, triangle_offsets[B])) return -4;
     return launch_affordance_faces(vertices, vertex_offsets, triangles, triangle_offsets, points, counts, B, R, params, affordance, rgba,
                                    static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
@@ -1181,7 +1186,7 @@ void giga_affordance_colormap(uint8_t* rgba) {
 }
 
 // ---- depth noise (giga_noise.hip) ----
-static bool noise_positive(double x) { return tsdf_finite(x) && x > 0.0; }
+static bool noise_positive(double x) { return finite_f64(x) && x > 0.0; }
 
 static bool noise_shape_ok(int n, int W, int H, int model) {
     if (n < 0 || W < 1 || H < 1 || W > GIGA_TSDF_MAX_IMAGE || H > GIGA_TSDF_MAX_IMAGE) return false;
@@ -1232,7 +1237,7 @@ static int batch_set_check(const GigaBatchSet* set, bool all) {
             !set->points || !set->occ)
             return -1;
         if (set->point_dtype != GIGA_BATCH_POINTS_F32 && set->point_dtype != GIGA_BATCH_POINTS_F16) return -1;
-        if (!tsdf_finite(set->size) || !(set->size > 0.0)) return -1;
+        if (!finite_f64(set->size) || !(set->size > 0.0)) return -1;
         if (reinterpret_cast<uintptr_t>(set->grids) % 16 != 0) return -1;
     }
     if (set->scene_files_host) {

@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
 #include "giga_philox.h"
+#include "giga_scan.h"
+#include "giga_ws.h"
 #include <cmath>
 #include <cstdint>
 
@@ -35,7 +37,6 @@ constexpr int EV_SCAN = 1024;
 constexpr unsigned long long NN_NONE = 0x7f800000ffffffffull;     // (+inf, -1)
 constexpr int EV_FILL_BLOCKS = 1024;  // split the inner set until a launch has about this many workgroups (256 CUs x 4)
 
-static size_t ev_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static int ev_div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // ---------------------------------------------------------------------------------------------------------- nearest neighbour
@@ -104,10 +105,11 @@ __global__ __launch_bounds__(EV_BLOCK) void nn_final_kernel(const unsigned long 
 
 struct NnWs { size_t offs, best, total; };
 static NnWs nn_workspace(int B, int n_src) {
+    WsLayout L;
     NnWs w;
-    w.offs = 0;
-    w.best = ev_align((size_t)2 * (B + 1) * sizeof(int));
-    w.total = w.best + ev_align((size_t)n_src * sizeof(unsigned long long));
+    w.offs = L.take<int>((size_t)2 * (B + 1));
+    w.best = L.take<unsigned long long>((size_t)n_src);
+    w.total = L.total;
     return w;
 }
 size_t nn_workspace_bytes(int B, int n_src) { return nn_workspace(B, n_src).total; }
@@ -186,16 +188,9 @@ __global__ __launch_bounds__(EV_BLOCK) void sample_area_kernel(const float* __re
     cum[f0 + f] = (t.ok && area > 0.0 && area < INFINITY) ? area : 0.0;    // (NaN compares false)
 }
 
-__device__ __forceinline__ double wave_incl_f64(double x, unsigned lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double y = __shfl_up(x, o, 64);
-        if (lane >= (unsigned)o) x += y;
-    }
-    return x;
-}
-
-// inclusive prefix sums of a scene's face areas, in place; the order of the additions depends on the face count alone
+// inclusive prefix sums of a scene's face areas, in place; the order of the additions depends on the face count alone:
+// ((carry + wsum[0]) + ... + wsum[wave - 1]) + the wave's inclusive sum, which tests/eval_emu.py restates.  That order is part of
+// the result, and it is not block_excl's (which starts from the in-wave prefix), so the loop over the waves is written out here.
 __global__ __launch_bounds__(EV_SCAN) void sample_scan_kernel(double* __restrict__ cum, const int* __restrict__ fo, int n,
                                                                double* __restrict__ totals, int* __restrict__ counts) {
     __shared__ double wsum[EV_SCAN / 64];
@@ -207,7 +202,7 @@ __global__ __launch_bounds__(EV_SCAN) void sample_scan_kernel(double* __restrict
     for (int base = 0; base < nf; base += EV_SCAN) {
         const int f = base + (int)threadIdx.x;
         const double own = f < nf ? cum[f0 + f] : 0.0;
-        const double inc = wave_incl_f64(own, lane);
+        const double inc = wave_incl(own, lane);
         if (lane == 63) wsum[wave] = inc;
         __syncthreads();
         double pre = carry, all = 0.0;
@@ -266,11 +261,12 @@ __global__ __launch_bounds__(EV_BLOCK) void sample_draw_kernel(const float* __re
 
 struct SampleWs { size_t offs, cum, totals, total; };
 static SampleWs sample_workspace(int B, int n_tri) {
+    WsLayout L;
     SampleWs w;
-    w.offs = 0;
-    w.cum = ev_align((size_t)2 * (B + 1) * sizeof(int));
-    w.totals = w.cum + ev_align((size_t)n_tri * sizeof(double));
-    w.total = w.totals + ev_align((size_t)B * sizeof(double));
+    w.offs = L.take<int>((size_t)2 * (B + 1));
+    w.cum = L.take<double>((size_t)n_tri);
+    w.totals = L.take<double>((size_t)B);
+    w.total = L.total;
     return w;
 }
 size_t sample_workspace_bytes(int B, int n_tri) { return sample_workspace(B, n_tri).total; }
@@ -471,13 +467,14 @@ __global__ __launch_bounds__(EV_BLOCK) void contains_final_kernel(const unsigned
 
 struct ContainsWs { size_t offs, xform, tri, cells, hits, total; };
 static ContainsWs contains_workspace(int B, int n_tri, int n_pts) {
+    WsLayout L;
     ContainsWs w;
-    w.offs = 0;
-    w.xform = ev_align((size_t)3 * (B + 1) * sizeof(int));
-    w.tri = w.xform + ev_align((size_t)B * 6 * sizeof(double));
-    w.cells = w.tri + ev_align((size_t)n_tri * 9 * sizeof(double));
-    w.hits = w.cells + ev_align((size_t)n_tri * sizeof(int4));
-    w.total = w.hits + ev_align((size_t)n_pts * sizeof(unsigned));
+    w.offs = L.take<int>((size_t)3 * (B + 1));
+    w.xform = L.take<double>((size_t)B * 6);
+    w.tri = L.take<double>((size_t)n_tri * 9);
+    w.cells = L.take<int4>((size_t)n_tri);
+    w.hits = L.take<unsigned>((size_t)n_pts);
+    w.total = L.total;
     return w;
 }
 size_t contains_workspace_bytes(int B, int n_tri, int n_pts) { return contains_workspace(B, n_tri, n_pts).total; }

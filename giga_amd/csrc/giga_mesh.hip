@@ -12,10 +12,10 @@
 // Passes (B scenes in each launch, gridDim.y = scene):
 //   classify  one thread per cell: case index from 8 samples, the 3 owned-edge flags, the triangle count from the table.
 //             Exclusive scan of both counts inside the workgroup: ballot + popcount inside a wave (the vertex count is
-//             three 1-bit flags, the triangle count three binary digits), LDS across the four waves.  Per cell one word
+//             three 1-bit flags, the triangle count three binary digits), LDS across the four waves (giga_scan.h).  Per cell one word
 //             (vertex prefix inside the workgroup << 3 | flags), per workgroup the two sums.
-//   scan      one workgroup per scene walks the workgroup sums in order (exclusive, in place) and writes the scene's
-//             totals to `counts`; one wave then turns the B totals into packed 64-bit bases.
+//   scan      giga_scan.h: one workgroup per scene walks the workgroup sums in order (exclusive, in place) and writes the
+//             scene's totals to `counts`; one wave then turns the B totals into 64-bit bases.
 //   emit      same cell mapping: owned crossed edges write their vertex at (scene base + workgroup offset + prefix); each
 //             triangle looks its three vertices up through the owning cells' words.
 // Every output position is a sum of counts in cell order: no atomics, two runs give the same bytes.
@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
 #include "giga_scan.h"
+#include "giga_ws.h"
 #define GIGA_MC_QUAL __device__ __attribute__((aligned(16)))
 #include "giga_mc_tables.h"
 #include <cmath>
@@ -32,7 +33,6 @@ namespace giga {
 
 constexpr int MESH_BLOCK = 256;
 constexpr int MESH_WAVES = MESH_BLOCK / 64;
-constexpr int SCAN_BLOCK = 1024;
 constexpr float MESH_PAD = -1e6f;
 static_assert(GIGA_MC_MAX_TRIS <= 7, "the triangle count is scanned as three binary digits");
 static_assert(sizeof(GIGA_MC_TRIS) == 4096, "one uint4 per thread fills the LDS copy");
@@ -82,33 +82,18 @@ __device__ __forceinline__ CellRead read_cell(const float* __restrict__ g, const
     return c;
 }
 
-// exclusive prefix of (number of set flags, ntri) over the workgroup's 256 cells, in cell order; totals in tot
-__device__ __forceinline__ void block_scan(unsigned flags, unsigned nt, unsigned (*wsum)[2], unsigned& pv, unsigned& pt,
-                                           unsigned& totv, unsigned& tott) {
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    const unsigned long long bx = __ballot(flags & 1), by = __ballot(flags & 2), bz = __ballot(flags & 4);
-    const unsigned long long t0 = __ballot(nt & 1), t1 = __ballot(nt & 2), t2 = __ballot(nt & 4);
-    pv = __popcll(bx & lt) + __popcll(by & lt) + __popcll(bz & lt);
-    pt = __popcll(t0 & lt) + 2 * __popcll(t1 & lt) + 4 * __popcll(t2 & lt);
-    if (lane == 0) {
-        wsum[wave][0] = __popcll(bx) + __popcll(by) + __popcll(bz);
-        wsum[wave][1] = __popcll(t0) + 2 * __popcll(t1) + 4 * __popcll(t2);
-    }
-    __syncthreads();
-    totv = tott = 0;
-#pragma unroll
-    for (unsigned w = 0; w < MESH_WAVES; ++w) {
-        if (w < wave) { pv += wsum[w][0]; pt += wsum[w][1]; }
-        totv += wsum[w][0];
-        tott += wsum[w][1];
-    }
+// exclusive prefix over the workgroup's cells, in cell order, of both counts of a cell: x = the number of set flags, y = ntri
+__device__ __forceinline__ uint2 cell_prefix(unsigned flags, unsigned nt, uint2* wsum, uint2& total) {
+    const unsigned lane = threadIdx.x & 63;
+    unsigned sv, st;
+    const unsigned pv = wave_excl_bits3<1, 1>(flags, lane, sv), pt = wave_excl_bits3<2, 4>(nt, lane, st);
+    return block_combine<MESH_WAVES>(make_uint2(pv, pt), make_uint2(sv, st), lane == 0, wsum, total);
 }
 
 __global__ __launch_bounds__(MESH_BLOCK) void mesh_classify_kernel(const float* __restrict__ grids, MeshDims d, float isof,
                                                                    unsigned* __restrict__ words, uint2* __restrict__ blk) {
     __shared__ unsigned char s_ntri[256];
-    __shared__ unsigned wsum[MESH_WAVES][2];
+    __shared__ uint2 wsum[MESH_WAVES];
     s_ntri[threadIdx.x] = GIGA_MC_NTRI[threadIdx.x];
     __syncthreads();
     const unsigned cell = blockIdx.x * MESH_BLOCK + threadIdx.x, scene = blockIdx.y;
@@ -118,56 +103,10 @@ __global__ __launch_bounds__(MESH_BLOCK) void mesh_classify_kernel(const float* 
         flags = c.flags;
         nt = s_ntri[c.cube];
     }
-    unsigned pv, pt, totv, tott;
-    block_scan(flags, nt, wsum, pv, pt, totv, tott);
-    if (cell < d.cells) words[(size_t)scene * d.cells + cell] = pv << 3 | flags;
-    if (threadIdx.x == 0) blk[(size_t)scene * d.nblk + blockIdx.x] = make_uint2(totv, tott);
-}
-
-__global__ __launch_bounds__(SCAN_BLOCK) void mesh_scan_kernel(uint2* __restrict__ blk, unsigned nblk, int* __restrict__ counts) {
-    __shared__ unsigned wsum[SCAN_BLOCK / 64][2];
-    __shared__ unsigned carry[2];
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint2* b = blk + (size_t)blockIdx.x * nblk;
-    if (threadIdx.x == 0) carry[0] = carry[1] = 0;
-    __syncthreads();
-    for (unsigned base = 0; base < nblk; base += SCAN_BLOCK) {
-        const unsigned idx = base + threadIdx.x;
-        const uint2 own = idx < nblk ? b[idx] : make_uint2(0, 0);
-        const unsigned iv = wave_incl(own.x, lane), it = wave_incl(own.y, lane);
-        if (lane == 63) { wsum[wave][0] = iv; wsum[wave][1] = it; }
-        __syncthreads();
-        unsigned pv = carry[0] + iv - own.x, pt = carry[1] + it - own.y, sv = 0, st = 0;
-#pragma unroll
-        for (unsigned w = 0; w < SCAN_BLOCK / 64; ++w) {
-            if (w < wave) { pv += wsum[w][0]; pt += wsum[w][1]; }
-            sv += wsum[w][0];
-            st += wsum[w][1];
-        }
-        if (idx < nblk) b[idx] = make_uint2(pv, pt);
-        __syncthreads();
-        if (threadIdx.x == 0) { carry[0] += sv; carry[1] += st; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        counts[2 * blockIdx.x] = (int)carry[0];
-        counts[2 * blockIdx.x + 1] = (int)carry[1];
-    }
-}
-
-// bases[b] = (vertices, triangles) of the scenes before b; bases[B] = the totals.  One wave.
-__global__ __launch_bounds__(64) void mesh_bases_kernel(const int* __restrict__ counts, int B, unsigned long long* __restrict__ bases) {
-    const unsigned lane = threadIdx.x;
-    unsigned long long cv = 0, ct = 0;
-    for (int base = 0; base < B; base += 64) {
-        const int b = base + (int)lane;
-        const unsigned long long v = b < B ? (unsigned)counts[2 * b] : 0u, t = b < B ? (unsigned)counts[2 * b + 1] : 0u;
-        const unsigned long long iv = wave_incl(v, lane), it = wave_incl(t, lane);
-        if (b < B) { bases[2 * b] = cv + iv - v; bases[2 * b + 1] = ct + it - t; }
-        cv += __shfl(iv, 63, 64);
-        ct += __shfl(it, 63, 64);
-    }
-    if (lane == 0) { bases[2 * B] = cv; bases[2 * B + 1] = ct; }
+    uint2 total;
+    const uint2 pre = cell_prefix(flags, nt, wsum, total);
+    if (cell < d.cells) words[(size_t)scene * d.cells + cell] = pre.x << 3 | flags;
+    if (threadIdx.x == 0) blk[(size_t)scene * d.nblk + blockIdx.x] = total;
 }
 
 // position along an edge in the padded grid, as the reference computes it: (x2 - x1) (iso - f1) / (f2 - f1) + x1, the midpoint
@@ -193,15 +132,14 @@ __global__ __launch_bounds__(MESH_BLOCK) void mesh_emit_kernel(const float* __re
                                                                int* __restrict__ shortfall) {
     __shared__ __attribute__((aligned(16))) unsigned char s_tris[256][16];
     __shared__ unsigned char s_ntri[256];
-    __shared__ unsigned wsum[MESH_WAVES][2];
+    __shared__ uint2 wsum[MESH_WAVES];
     reinterpret_cast<uint4*>(&s_tris[0][0])[threadIdx.x] = reinterpret_cast<const uint4*>(&GIGA_MC_TRIS[0][0])[threadIdx.x];
     s_ntri[threadIdx.x] = GIGA_MC_NTRI[threadIdx.x];
     __syncthreads();
     const unsigned cell = blockIdx.x * MESH_BLOCK + threadIdx.x, scene = blockIdx.y;
     if (shortfall && blockIdx.x == 0 && scene == 0 && threadIdx.x == 0) {
-        const unsigned long long tv = bases[2 * B], tt = bases[2 * B + 1], big = 0x7fffffffull;
-        shortfall[0] = (int)(tv > cap_v ? (tv - cap_v < big ? tv - cap_v : big) : 0);
-        shortfall[1] = (int)(tt > cap_t ? (tt - cap_t < big ? tt - cap_t : big) : 0);
+        shortfall[0] = scan_shortfall(bases[2 * B], cap_v);
+        shortfall[1] = scan_shortfall(bases[2 * B + 1], cap_t);
     }
     CellRead c;
     c.cube = 0;
@@ -212,8 +150,9 @@ __global__ __launch_bounds__(MESH_BLOCK) void mesh_emit_kernel(const float* __re
         c = read_cell(grids + (size_t)scene * d.nx * d.ny * d.nz, d, cell, isof);
         nt = s_ntri[c.cube];
     }
-    unsigned pv, pt, totv, tott;
-    block_scan(c.flags, nt, wsum, pv, pt, totv, tott);
+    uint2 total;
+    const uint2 pre = cell_prefix(c.flags, nt, wsum, total);
+    const unsigned pv = pre.x, pt = pre.y;
     if (!live || (c.flags == 0 && nt == 0)) return;
     const unsigned* w = words + (size_t)scene * d.cells;
     const uint2* bo = blk + (size_t)scene * d.nblk;
@@ -278,16 +217,15 @@ MeshDims mesh_dims(int nx, int ny, int nz) {
     return d;
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct MeshWs { size_t words, blk, bases, total; };
 MeshWs mesh_workspace(int B, int nx, int ny, int nz) {
     const MeshDims d = mesh_dims(nx, ny, nz);
+    WsLayout L;
     MeshWs w;
-    w.words = 0;
-    w.blk = align256((size_t)B * d.cells * sizeof(unsigned));
-    w.bases = w.blk + align256((size_t)B * d.nblk * sizeof(uint2));
-    w.total = w.bases + align256((size_t)(B + 1) * 2 * sizeof(unsigned long long));
+    w.words = L.take<unsigned>((size_t)B * d.cells);
+    w.blk = L.take<uint2>((size_t)B * d.nblk);
+    w.bases = L.take<unsigned long long>((size_t)(B + 1) * 2);
+    w.total = L.total;
     return w;
 }
 
@@ -307,8 +245,9 @@ int launch_mesh_count(const float* grids, int B, int nx, int ny, int nz, double 
     uint2* blk = reinterpret_cast<uint2*>(ws + w.blk);
     unsigned long long* bases = reinterpret_cast<unsigned long long*>(ws + w.bases);
     GIGA_LAUNCH(mesh_classify_kernel, dim3(d.nblk, B), dim3(MESH_BLOCK), 0, s, grids, d, iso_floor(iso), words, blk);
-    GIGA_LAUNCH(mesh_scan_kernel, dim3(B), dim3(SCAN_BLOCK), 0, s, blk, d.nblk, counts);
-    GIGA_LAUNCH(mesh_bases_kernel, dim3(1), dim3(64), 0, s, counts, B, bases);
+    GIGA_LAUNCH(scene_offsets_kernel<unsigned long long>, dim3(B), dim3(SCAN_BLOCK), 0, s, reinterpret_cast<unsigned long long*>(blk),
+                d.nblk, counts, static_cast<int*>(nullptr));
+    GIGA_LAUNCH(scene_bases_kernel<2>, dim3(1), dim3(64), 0, s, counts, B, bases);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 

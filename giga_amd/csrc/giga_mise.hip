@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
 #include "giga_scan.h"
+#include "giga_ws.h"
 #include <cmath>
 #include <cstdint>
 
@@ -33,7 +34,6 @@ namespace giga {
 
 constexpr int MISE_BLOCK = 256;
 constexpr int MISE_WAVES = MISE_BLOCK / 64;
-constexpr int MISE_SCAN_BLOCK = 1024;
 constexpr unsigned MISE_UNKNOWN = 1, MISE_KNOWN = 2;
 constexpr unsigned MISE_LEAF = 1, MISE_POS = 2, MISE_NEG = 4, MISE_INNER = 8, MISE_FRESH = 16;
 constexpr int MISE_MAX_DEPTH = 9;                           // (1 << depth) < GIGA_MISE_MAX_N = 513
@@ -68,20 +68,19 @@ MiseDims mise_dims(int res0, int depth) {
     return d;
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // counts | blk | dirty | state | tree | values : all but the values are cleared by one fill at init
 struct MiseWs { size_t counts, blk, dirty, state, tree, values, total; };
 MiseWs mise_workspace(int B, int res0, int depth) {
     const MiseDims d = mise_dims(res0, depth);
+    WsLayout L;
     MiseWs w;
-    w.counts = 0;
-    w.blk = align256((size_t)B * sizeof(int));
-    w.dirty = w.blk + align256((size_t)B * d.nblk * sizeof(unsigned));
-    w.state = w.dirty + align256((size_t)B * d.nblk);
-    w.tree = w.state + align256((size_t)B * d.words * 4);
-    w.values = w.tree + align256((size_t)B * d.tree);
-    w.total = w.values + align256((size_t)B * d.n3 * sizeof(float));
+    w.counts = L.take<int>((size_t)B);
+    w.blk = L.take<unsigned>((size_t)B * d.nblk);
+    w.dirty = L.take<unsigned char>((size_t)B * d.nblk);
+    w.state = L.take<unsigned>((size_t)B * d.words);
+    w.tree = L.take<unsigned char>((size_t)B * d.tree);
+    w.values = L.take<float>((size_t)B * d.n3);
+    w.total = L.total;
     return w;
 }
 size_t mise_workspace_bytes(int B, int res0, int depth) { return mise_workspace(B, res0, depth).total; }
@@ -119,34 +118,10 @@ __global__ __launch_bounds__(MISE_BLOCK) void mise_count_kernel(const unsigned* 
         return;
     }
     unsigned total;
-    block_excl<MISE_WAVES>(__popc(unknown_mask(state, d, scene, t)), wsum, total);
+    block_excl<MISE_WAVES>((unsigned)__popc(unknown_mask(state, d, scene, t)), wsum, total);
     if (threadIdx.x == 0) {
         blk[run] = total;
         if (!total) dirty[run] = 0;
-    }
-}
-
-// one workgroup per scene: exclusive scan of the workgroup sums in place, the scene's total to both copies of the counts
-__global__ __launch_bounds__(MISE_SCAN_BLOCK) void mise_scan_kernel(unsigned* __restrict__ blk, unsigned nblk, int* __restrict__ ws_counts,
-                                                                    int* __restrict__ counts) {
-    __shared__ unsigned wsum[MISE_SCAN_BLOCK / 64];
-    __shared__ unsigned carry;
-    unsigned* b = blk + (size_t)blockIdx.x * nblk;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (unsigned base = 0; base < nblk; base += MISE_SCAN_BLOCK) {
-        const unsigned idx = base + threadIdx.x;
-        const unsigned own = idx < nblk ? b[idx] : 0u;
-        unsigned total;
-        const unsigned pre = carry + block_excl<MISE_SCAN_BLOCK / 64>(own, wsum, total);
-        if (idx < nblk) b[idx] = pre;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        ws_counts[blockIdx.x] = (int)carry;
-        counts[blockIdx.x] = (int)carry;
     }
 }
 
@@ -156,14 +131,11 @@ __global__ __launch_bounds__(MISE_BLOCK) void mise_emit_kernel(const unsigned* _
                                                                unsigned long long cap, int* __restrict__ shortfall) {
     __shared__ unsigned wsum[MISE_WAVES];
     const unsigned t = blockIdx.x * MISE_BLOCK + threadIdx.x, scene = blockIdx.y;
-    if (shortfall && blockIdx.x == 0 && threadIdx.x == 0) {
-        const unsigned long long n = (unsigned)ws_counts[scene];
-        shortfall[scene] = (int)(n > cap ? n - cap : 0);
-    }
+    if (shortfall && blockIdx.x == 0 && threadIdx.x == 0) shortfall[scene] = scan_shortfall((unsigned)ws_counts[scene], cap);
     if (!dirty[(size_t)scene * d.nblk + blockIdx.x]) return;
     const unsigned m = unknown_mask(state, d, scene, t);
     unsigned total;
-    unsigned long long at = block_excl<MISE_WAVES>(__popc(m), wsum, total);
+    unsigned long long at = block_excl<MISE_WAVES>((unsigned)__popc(m), wsum, total);
     if (!m) return;
     at += blk[(size_t)scene * d.nblk + blockIdx.x];
     int* q = query + (size_t)scene * cap;
@@ -387,7 +359,8 @@ int launch_mise_count(int B, int res0, int depth, uint8_t* ws, int* counts, hipS
     unsigned* blk = reinterpret_cast<unsigned*>(ws + w.blk);
     GIGA_LAUNCH(mise_count_kernel, dim3(d.nblk, B), dim3(MISE_BLOCK), 0, s, reinterpret_cast<const unsigned*>(ws + w.state), d, blk,
                 ws + w.dirty);
-    GIGA_LAUNCH(mise_scan_kernel, dim3(B), dim3(MISE_SCAN_BLOCK), 0, s, blk, d.nblk, reinterpret_cast<int*>(ws + w.counts), counts);
+    // the scene's total goes to the workspace copy too: emit, points and mark read it there
+    GIGA_LAUNCH(scene_offsets_kernel<unsigned>, dim3(B), dim3(SCAN_BLOCK), 0, s, blk, d.nblk, reinterpret_cast<int*>(ws + w.counts), counts);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
 #include "giga_philox.h"
+#include "giga_ws.h"
 #include <cmath>
 #include <cstdint>
 
@@ -186,8 +187,7 @@ __global__ __launch_bounds__(NOISE_BLOCK) void depth_noise_kernel(NoiseArgs a) {
     }
 }
 
-static size_t noise_align(size_t x) { return (x + 255) & ~(size_t)255; }
-size_t depth_noise_workspace_bytes(int n) { return noise_align((size_t)(n > 0 ? n : 1) * sizeof(unsigned long long)); }
+size_t depth_noise_workspace_bytes(int n) { return ws_align((size_t)(n > 0 ? n : 1) * sizeof(unsigned long long)); }
 
 int launch_depth_noise(const float* in, float* out, int n, int W, int H, int model, const double* p, unsigned long long seed,
                        const unsigned long long* image_ids, uint8_t* ws, hipStream_t s) {

@@ -19,6 +19,7 @@
 //   test of its pixel against each entry; all lanes read the same entry, so the LDS read is a broadcast.
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "giga_ws.h"
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -163,17 +164,16 @@ __global__ __launch_bounds__(RENDER_BLOCK) void depth_render_kernel(RenderArgs g
     if (tid == 0 && tested) atomicAdd(g.tested, tested);
 }
 
-static size_t render_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct RenderWs { size_t tested, voffs, toffs, view_scene, cams, total; };
 static RenderWs render_workspace(int B, int n_views) {
+    WsLayout L;
     RenderWs w;
-    w.tested = 0;
-    w.voffs = 256;
-    w.toffs = w.voffs + render_align((size_t)(B + 1) * sizeof(int));
-    w.view_scene = w.toffs + render_align((size_t)(B + 1) * sizeof(int));
-    w.cams = w.view_scene + render_align((size_t)n_views * sizeof(int));
-    w.total = w.cams + render_align((size_t)n_views * RENDER_CAM * sizeof(double));
+    w.tested = L.take<unsigned long long>(1);
+    w.voffs = L.take<int>((size_t)B + 1);
+    w.toffs = L.take<int>((size_t)B + 1);
+    w.view_scene = L.take<int>((size_t)n_views);
+    w.cams = L.take<double>((size_t)n_views * RENDER_CAM);
+    w.total = L.total;
     return w;
 }
 size_t depth_render_workspace_bytes(int B, int n_views) { return render_workspace(B, n_views).total; }

@@ -41,6 +41,7 @@
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
 #include "giga_scan.h"
+#include "giga_ws.h"
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -238,21 +239,14 @@ __global__ void __launch_bounds__(SIMP_SCAN_BLOCK) simp_scan_kernel(SimpDev s, i
     const SimpMesh me = s.mesh[b];
     if (!all && !me.active) return;
     const int n = mode == 1 ? me.nt : me.nv, off = mode == 1 ? me.toff : me.voff;
-    unsigned run = 0;
-    for (int c = 0; c < n; c += SIMP_SCAN_BLOCK) {
-        const int i = c + (int)threadIdx.x;
-        unsigned x = 0;
-        if (i < n) x = mode == 0 ? (unsigned)s.tcount[off + i] : mode == 1 ? (s.tdel[off + i] ? 0u : 1u) : (unsigned)s.vflag[off + i];
-        unsigned total;
-        const unsigned pre = run + block_excl<SIMP_SCAN_BLOCK / 64>(x, wsum, total);
-        if (i < n) {
+    const unsigned run = block_scan_rounds<SIMP_SCAN_BLOCK / 64>(
+        (unsigned)(n > 0 ? n : 0), wsum,
+        [&](unsigned i) { return mode == 0 ? (unsigned)s.tcount[off + i] : mode == 1 ? (s.tdel[off + i] ? 0u : 1u) : (unsigned)s.vflag[off + i]; },
+        [&](unsigned i, unsigned pre) {
             if (mode == 0) { s.tstart[off + i] = me.roff + (int)pre; s.vcur[off + i] = 0; }
             else if (mode == 1) s.tdst[off + i] = (int)pre;
             else s.vnew[off + i] = (int)pre;
-        }
-        run += total;
-        __syncthreads();
-    }
+        });
     if (threadIdx.x == 0) {
         if (mode == 0) s.rused[b] = (int)run;
         else s.tot[(mode == 1 ? 0 : s.B) + b] = (int)run;
@@ -528,22 +522,14 @@ __global__ void simp_emit_faces_kernel(SimpDev s, int* out) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-static size_t simp_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 long long simplify_ref_capacity(int n_triangles_of_mesh, int ref_extra) {
     return 3LL * n_triangles_of_mesh + (ref_extra < 0 ? 3LL * n_triangles_of_mesh + SIMP_MIN_REF_EXTRA : ref_extra);
 }
 
 namespace {
-struct SimpLayout {
-    size_t total = 0;
-    template <typename T>
-    size_t take(size_t n) { const size_t at = total; total += simp_align(n * sizeof(T)); return at; }
-};
-
 // carves the workspace; with base == nullptr only the size is computed.  `snap` receives the copies taken before a pass.
 size_t simp_carve(uint8_t* base, int B, size_t Vt, size_t Tt, size_t R, SimpDev* d, SimpDev* snap) {
-    SimpLayout L;
+    WsLayout L;
     SimpDev dev{}, sn{};
     auto f64 = [&](size_t n) { return reinterpret_cast<double*>(base + L.take<double>(n)); };
     auto i32 = [&](size_t n) { return reinterpret_cast<int*>(base + L.take<int>(n)); };

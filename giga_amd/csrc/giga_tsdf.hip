@@ -9,6 +9,8 @@
 // Indices outside [0, R) are ignored on the device (numpy would raise; the Python wrapper checks host-side inputs).
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "giga_scan.h"
+#include "giga_ws.h"
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -75,12 +77,11 @@ int launch_tsdf_scatter(const int* index, const float* value, const int* offsets
 //   cloud      zero crossings between a voxel and its +x, +y, +z neighbour (extract_point_cloud without normals): count
 //              (ballot + popcount inside a wave, LDS across the four waves, per-workgroup sums), scan (one workgroup per scene,
 //              then one wave over the scenes), emit at (scene base + workgroup offset + prefix).  Order: cell order, then axis
-//              0, 1, 2; no atomics decide it (the scheme of giga_mesh.hip).
+//              0, 1, 2; no atomics decide it (giga_scan.h, the scheme of giga_mesh.hip).
 #pragma clang fp contract(off)
 
 constexpr int TSDF_BLOCK = 256;
 constexpr int TSDF_WAVES = TSDF_BLOCK / 64;
-constexpr int TSDF_SCAN = 1024;
 constexpr int TSDF_CAM = 20;                  // doubles per view in the workspace: extrinsic [16] row-major, fx, fy, cx, cy
 
 struct TsdfVol {
@@ -131,14 +132,13 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_integrate_kernel(const float*
     if (grid) grid[at] = (w != 0.f && (double)t >= -0.98 && (double)t < 0.98) ? (float)(((double)t + 1.0) * 0.5) : 0.f;
 }
 
-static size_t tsdf_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct IntegrateWs { size_t offs, cams, total; };
 static IntegrateWs integrate_workspace(int B, int n_views) {
+    WsLayout L;
     IntegrateWs w;
-    w.offs = 0;
-    w.cams = tsdf_align((size_t)(B + 1) * sizeof(int));
-    w.total = w.cams + tsdf_align((size_t)n_views * TSDF_CAM * sizeof(double));
+    w.offs = L.take<int>((size_t)B + 1);
+    w.cams = L.take<double>((size_t)n_views * TSDF_CAM);
+    w.total = L.total;
     return w;
 }
 size_t tsdf_integrate_workspace_bytes(int B, int n_views) { return integrate_workspace(B, n_views).total; }
@@ -202,20 +202,11 @@ __device__ __forceinline__ CloudRead cloud_read(const float* __restrict__ tsdf, 
 }
 
 // exclusive prefix of the number of set flags over the workgroup's cells, in cell order; the workgroup's total in tot
-__device__ __forceinline__ unsigned cloud_block_scan(unsigned flags, unsigned* wsum, unsigned& tot) {
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    const unsigned long long bx = __ballot(flags & 1), by = __ballot(flags & 2), bz = __ballot(flags & 4);
-    unsigned pre = __popcll(bx & lt) + __popcll(by & lt) + __popcll(bz & lt);
-    if (lane == 0) wsum[wave] = __popcll(bx) + __popcll(by) + __popcll(bz);
-    __syncthreads();
-    tot = 0;
-#pragma unroll
-    for (unsigned w = 0; w < TSDF_WAVES; ++w) {
-        if (w < wave) pre += wsum[w];
-        tot += wsum[w];
-    }
-    return pre;
+__device__ __forceinline__ unsigned cloud_prefix(unsigned flags, unsigned* wsum, unsigned& tot) {
+    const unsigned lane = threadIdx.x & 63;
+    unsigned sum;
+    const unsigned pre = wave_excl_bits3<1, 1>(flags, lane, sum);
+    return block_combine<TSDF_WAVES>(pre, sum, lane == 0, wsum, tot);
 }
 
 __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_cloud_count_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight,
@@ -226,59 +217,8 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_cloud_count_kernel(const floa
     const size_t base = (size_t)scene * cells;
     const unsigned flags = cell < cells ? cloud_read(tsdf + base, weight + base, R, cell).flags : 0u;
     unsigned tot;
-    cloud_block_scan(flags, wsum, tot);
+    cloud_prefix(flags, wsum, tot);
     if (threadIdx.x == 0) blk[(size_t)scene * nblk + blockIdx.x] = tot;
-}
-
-__device__ __forceinline__ unsigned long long tsdf_wave_incl(unsigned long long x, unsigned lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long y = __shfl_up(x, o, 64);
-        if (lane >= (unsigned)o) x += y;
-    }
-    return x;
-}
-
-// workgroup sums of one scene -> exclusive offsets (in place), the scene's total to counts
-__global__ __launch_bounds__(TSDF_SCAN) void tsdf_cloud_scan_kernel(unsigned* __restrict__ blk, unsigned nblk, int* __restrict__ counts) {
-    __shared__ unsigned wsum[TSDF_SCAN / 64];
-    __shared__ unsigned carry;
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned* b = blk + (size_t)blockIdx.x * nblk;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (unsigned base = 0; base < nblk; base += TSDF_SCAN) {
-        const unsigned idx = base + threadIdx.x;
-        const unsigned own = idx < nblk ? b[idx] : 0u;
-        const unsigned inc = (unsigned)tsdf_wave_incl(own, lane);
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        unsigned pre = carry + inc - own, all = 0;
-#pragma unroll
-        for (unsigned w = 0; w < TSDF_SCAN / 64; ++w) {
-            if (w < wave) pre += wsum[w];
-            all += wsum[w];
-        }
-        if (idx < nblk) b[idx] = pre;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) counts[blockIdx.x] = (int)carry;
-}
-
-// bases[b] = points of the scenes before b; bases[B] = the total.  One wave.
-__global__ __launch_bounds__(64) void tsdf_cloud_bases_kernel(const int* __restrict__ counts, int B, unsigned long long* __restrict__ bases) {
-    const unsigned lane = threadIdx.x;
-    unsigned long long carry = 0;
-    for (int base = 0; base < B; base += 64) {
-        const int b = base + (int)lane;
-        const unsigned long long n = b < B ? (unsigned)counts[b] : 0u;
-        const unsigned long long inc = tsdf_wave_incl(n, lane);
-        if (b < B) bases[b] = carry + inc - n;
-        carry += __shfl(inc, 63, 64);
-    }
-    if (lane == 0) bases[B] = carry;
 }
 
 __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_cloud_emit_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight,
@@ -289,16 +229,13 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_cloud_emit_kernel(const float
                                                                      int* __restrict__ shortfall) {
     __shared__ unsigned wsum[TSDF_WAVES];
     const unsigned cell = blockIdx.x * TSDF_BLOCK + threadIdx.x, scene = blockIdx.y;
-    if (shortfall && blockIdx.x == 0 && scene == 0 && threadIdx.x == 0) {
-        const unsigned long long tot = bases[B], big = 0x7fffffffull;
-        shortfall[0] = (int)(tot > cap ? (tot - cap < big ? tot - cap : big) : 0);
-    }
+    if (shortfall && blockIdx.x == 0 && scene == 0 && threadIdx.x == 0) shortfall[0] = scan_shortfall(bases[B], cap);
     const size_t base = (size_t)scene * cells;
     CloudRead c;
     c.flags = 0;
     if (cell < cells) c = cloud_read(tsdf + base, weight + base, R, cell);
     unsigned tot;
-    const unsigned pre = cloud_block_scan(c.flags, wsum, tot);
+    const unsigned pre = cloud_prefix(c.flags, wsum, tot);
     if (!c.flags) return;
     unsigned long long at = bases[scene] + blk[(size_t)scene * nblk + blockIdx.x] + pre;
     const double p0[3] = {((double)c.x + 0.5) * voxel, ((double)c.y + 0.5) * voxel, ((double)c.z + 0.5) * voxel};
@@ -319,12 +256,13 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_cloud_emit_kernel(const float
 
 struct CloudWs { size_t blk, bases, total; unsigned cells, nblk; };
 static CloudWs cloud_workspace(int B, int R) {
+    WsLayout L;
     CloudWs w;
     w.cells = (unsigned)R * R * R;
     w.nblk = (w.cells + TSDF_BLOCK - 1) / TSDF_BLOCK;
-    w.blk = 0;
-    w.bases = tsdf_align((size_t)B * w.nblk * sizeof(unsigned));
-    w.total = w.bases + tsdf_align((size_t)(B + 1) * sizeof(unsigned long long));
+    w.blk = L.take<unsigned>((size_t)B * w.nblk);
+    w.bases = L.take<unsigned long long>((size_t)B + 1);
+    w.total = L.total;
     return w;
 }
 size_t tsdf_cloud_workspace_bytes(int B, int R) { return cloud_workspace(B, R).total; }
@@ -334,8 +272,8 @@ int launch_tsdf_cloud_count(const float* tsdf, const float* weight, int B, int R
     unsigned* blk = reinterpret_cast<unsigned*>(ws + w.blk);
     unsigned long long* bases = reinterpret_cast<unsigned long long*>(ws + w.bases);
     GIGA_LAUNCH(tsdf_cloud_count_kernel, dim3(w.nblk, B), dim3(TSDF_BLOCK), 0, s, tsdf, weight, (unsigned)R, w.cells, w.nblk, blk);
-    GIGA_LAUNCH(tsdf_cloud_scan_kernel, dim3(B), dim3(TSDF_SCAN), 0, s, blk, w.nblk, counts);
-    GIGA_LAUNCH(tsdf_cloud_bases_kernel, dim3(1), dim3(64), 0, s, counts, B, bases);
+    GIGA_LAUNCH(scene_offsets_kernel<unsigned>, dim3(B), dim3(SCAN_BLOCK), 0, s, blk, w.nblk, counts, static_cast<int*>(nullptr));
+    GIGA_LAUNCH(scene_bases_kernel<1>, dim3(1), dim3(64), 0, s, counts, B, bases);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 

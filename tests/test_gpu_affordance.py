@@ -123,6 +123,17 @@ def test_every_voxel_a_point(F, aggregation):
     assert P == 1728 and (aff > 0).any()
 
 
+def test_every_voxel_a_point_with_more_block_sums_than_one_scan_round_of_256():
+    """R = 41: 270 blocks of 256 voxels, every one full (the planner's volume below has 250 of them)."""
+    R = 41
+    assert -(-R ** 3 // 256) == 270
+    qual, rot = volumes(41, R, lo=0.55, hi=0.95)
+    want = aemu.points(qual, rot)
+    assert want.shape == (R ** 3, 4)
+    got = visual.affordance_points(t(qual), t(rot))
+    assert got.dtype == torch.float64 and np.array_equal(bits(got.cpu().numpy()), bits(want))
+
+
 # ---- 3: the planner's own volume at R = 40 --------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def planner_volume():

@@ -116,6 +116,49 @@ def test_non_cubic_and_cpu_inputs():
     assert mesh_emu.closed_and_oriented(len(v), f) and len(v) == len(mesh_emu.crossed_edges(grid, 0.1))
 
 
+def _ball_at_the_far_face(shape, radius=9.0):
+    """radius - distance, in samples, from the middle of the x = nx - 1 face: a half ball that the padding closes with a cap.
+    Its crossed edges lie in the last x-slabs of cells, the cap's in the very last one, so the workgroups with the highest numbers
+    have counts, and every workgroup before them holds a share of the ball."""
+    i, j, k = np.meshgrid(*[np.arange(n, dtype=np.float64) for n in shape], indexing="ij")
+    c = (shape[0] - 1, (shape[1] - 1) / 2 + 0.25, (shape[2] - 1) / 2 - 0.25)
+    return (radius - np.sqrt((i - c[0]) ** 2 + (j - c[1]) ** 2 + (k - c[2]) ** 2)).astype(np.float32)
+
+
+@pytest.mark.parametrize("shape, nblk", [((63, 63, 63), 1024), ((63, 63, 64), 1040)], ids=["one-full-round", "second-round"])
+def test_scene_offsets_over_a_thousand_workgroup_sums(shape, nblk):
+    """The scan of a scene's workgroup sums runs in rounds of 1024: exactly one full round, and 16 sums into a second one."""
+    cells = (shape[0] + 1) * (shape[1] + 1) * (shape[2] + 1)
+    assert -(-cells // 256) == nblk
+    grid = _ball_at_the_far_face(shape)
+    ev, ef = mesh_emu.marching_cubes(grid, 0.125, 1.0)
+    last = mesh_emu.edges_in_kernel_order(grid, 0.125)[-1]
+    assert last[:2] == (0, shape[0]) and 500 < len(ev) < 5000        # the last vertex: an x edge into the padding, last slab of cells
+    v, f = _run(grid, 0.125, 1.0)
+    assert np.array_equal(f, ef) and v.tobytes() == ev.tobytes()
+    assert mesh_emu.closed_and_oriented(len(v), f)
+
+
+def test_bases_over_more_than_a_wave_of_scenes():
+    """65 scenes of 3x3x3 samples, every fourth one empty: the bases of the scenes are taken 64 at a time, scene 64 in a second
+    round."""
+    rng = np.random.default_rng(65)
+    grids = rng.standard_normal((65, 3, 3, 3)).astype(np.float32)
+    grids[1::4] = -5.0
+    v, t, counts = marching_cubes(torch.from_numpy(grids).to(DEV), 0.1, 1.2)
+    torch.cuda.synchronize()
+    v, t, counts = v.cpu().numpy(), t.cpu().numpy(), counts.cpu().numpy()
+    assert counts.shape == (65, 2) and (counts[1::4] == 0).all() and (counts[63:] > 0).all()      # scene 64 is not empty
+    v0 = t0 = 0
+    for b in range(65):
+        ev, ef = mesh_emu.marching_cubes(grids[b], 0.1, 1.2)
+        nv, nt = int(counts[b, 0]), int(counts[b, 1])
+        assert (nv, nt) == (len(ev), len(ef)), b
+        assert v[v0:v0 + nv].tobytes() == ev.tobytes() and t[t0:t0 + nt].tobytes() == ef.tobytes(), b
+        v0, t0 = v0 + nv, t0 + nt
+    assert (v0, t0) == (len(v), len(t))
+
+
 def _along_axis(vertices, edges, n, box):
     """{edge: position of its vertex along the edge's axis, in grid steps}; `edges` names the vertices' edges in order."""
     assert len(vertices) == len(edges)

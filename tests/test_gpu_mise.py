@@ -63,6 +63,24 @@ def test_rounds_and_dense_grid_equal_libmise(g19, name):
     assert all(a[0].tobytes() == b[0].tobytes() for a, b in zip(rounds, rounds2)) and dense.tobytes() == dense2.tobytes()
 
 
+def test_more_than_1024_workgroups_per_scene_against_the_emulator():
+    """resolution0 13, depth 3: 105^3 samples are 1131 runs of 1024 (the fixture's largest lattice, 33^3, has 36), so the scan of a
+    scene's workgroup sums takes a second round of 1024.  13 is the smallest resolution0 that gets there at the generator's default
+    depth.  A small ball about the last lattice plane along x: the queries of every round reach into the runs past the 1024th."""
+    res0, depth = 13, 3
+    N = (res0 << depth) + 1
+    assert -(-(-(-N ** 3 // 4)) // 256) == 1131
+    i, j, k = np.meshgrid(*[np.arange(N, dtype=np.float64)] * 3, indexing="ij")
+    field = (9.5 - np.sqrt((i - 100) ** 2 + (j - 52.3) ** 2 + (k - 51.8) ** 2)).astype(np.float32)
+    want_rounds, want_dense = mise_emu.run(field, res0, depth, 0.0)
+    assert len(want_rounds) == depth + 1 and all(r[-1] >= 1024 * 1024 for r in want_rounds)
+    rounds, dense = _run(field[None], res0, depth, 0.0)
+    assert [len(r[0]) for r in rounds] == [len(r) for r in want_rounds]
+    for k, (got, want) in enumerate(zip(rounds, want_rounds)):
+        assert np.array_equal(got[0], want), k
+    assert dense[0].tobytes() == want_dense.tobytes()
+
+
 def test_three_scenes_with_different_round_counts_equal_single_runs(g19):
     names = ["sphere43", "slab43", "ball43"]                         # 4, 5 and 1 rounds on the same 33^3 lattice, threshold 0
     cases = [fixture_case(g19, n) for n in names]

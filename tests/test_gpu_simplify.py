@@ -58,6 +58,23 @@ def test_kernels_match_the_reference_byte_for_byte(g20, name):
     assert stats["list rebuilds"] == [0]
 
 
+def test_more_than_1024_vertices_against_the_emulator(golden):
+    """No mesh of g20 has more than 1024 vertices (its largest, mc33, has 700; torus and mc33 have more than 1024 faces).  Mesh A of
+    g16_mesh.npz, the smallest of tests/golden/ that has them (2084 vertices, 4168 faces), takes the per-mesh scans over the
+    vertices into a third round of 1024; the float64 emulator of tests/simplify_emu.py is the reference."""
+    import mesh_emu
+    import simplify_emu
+    g16 = golden("g16_mesh.npz")
+    v, f = mesh_emu.marching_cubes(g16["A_grid"], float(g16["A_iso"]), float(g16["A_box_size"]))
+    assert (len(v), len(f)) == (2084, 4168) and np.array_equal(mesh_emu.sort_rows(v), g16["A_vertices"])
+    ev, ef = simplify_emu.simplify(v, f, 2000, 5.0)
+    assert len(ef) == 2000 and len(ev) > 900
+    ov, of, counts = simplify_mesh(torch.from_numpy(v).to(DEV), torch.from_numpy(f).to(DEV), 2000, 5.0)
+    assert counts.tolist() == [[len(ev), len(ef)]]
+    assert of.cpu().numpy().tobytes() == np.asarray(ef, np.int32).tobytes()
+    assert ov.cpu().numpy().tobytes() == np.asarray(ev, np.float64).tobytes()
+
+
 def test_float64_input_gives_the_same_bytes(g20):
     v, f, target, aggr = _inputs(g20, "ico2_32")
     ov, of, _ = simplify_mesh(v.double(), f.long(), target, aggr)

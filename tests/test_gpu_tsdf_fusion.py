@@ -161,6 +161,42 @@ def test_cloud_capacity_shortfall_is_reported_and_respected():
     assert part.shape == (100, 3) and torch.equal(part, full[:100]) and np.array_equal(offs, offs2)
 
 
+def synthetic_volume(R, seed):
+    """(tsdf, weight) without any integration: the signed distance, in units of 8 voxels, to a ball about the middle of the
+    x = R - 1 face, so that the cells with the highest numbers hold crossings too; one voxel in eight unobserved."""
+    rng = np.random.default_rng(seed)
+    i, j, k = np.meshgrid(*[np.arange(R, dtype=np.float64)] * 3, indexing="ij")
+    d = np.sqrt((i - (R - 1)) ** 2 + (j - R / 2 + 0.3) ** 2 + (k - R / 2 - 0.2) ** 2) - 0.3 * R
+    return np.clip(d / 8, -1, 1).astype(F32), (rng.random((R, R, R)) >= 0.125).astype(F32)
+
+
+@pytest.mark.parametrize("R, nblk", [(64, 1024), (65, 1073)], ids=["one-full-round", "second-round"])
+def test_cloud_of_a_synthetic_volume_with_a_thousand_workgroup_sums(R, nblk):
+    """The scan of a scene's workgroup sums runs in rounds of 1024: exactly one full round, and 49 sums into a second one."""
+    assert -(-R ** 3 // 256) == nblk
+    t, w = synthetic_volume(R, R)
+    want = emu.cloud(t, w, SIZE)
+    far = want[:, 0] > (R - 3) * (SIZE / R)                   # points of the last three x-planes: the last 49 workgroups and more
+    assert 1000 < len(want) < 20000 and far.sum() > 50 and far[-1]
+    points, offs = perception.cloud_batch(torch.from_numpy(t[None]).to(dev()), torch.from_numpy(w[None]).to(dev()), SIZE)
+    assert offs.tolist() == [0, len(want)]
+    same_bytes(points, want, f"synthetic R={R} cloud")
+
+
+def test_cloud_bases_over_more_than_a_wave_of_scenes():
+    """65 scenes at R = 4, every fourth one unobserved: the bases of the scenes are taken 64 at a time, scene 64 in a second
+    round."""
+    rng = np.random.default_rng(4)
+    t = (rng.random((65, 4, 4, 4)) * 2 - 1).astype(F32)
+    w = (rng.random((65, 4, 4, 4)) >= 0.125).astype(F32)
+    w[1::4] = 0
+    want = [emu.cloud(t[b], w[b], SIZE) for b in range(65)]
+    assert all(len(c) == 0 for c in want[1::4]) and len(want[63]) > 0 and len(want[64]) > 0
+    points, offs = perception.cloud_batch(torch.from_numpy(t).to(dev()), torch.from_numpy(w).to(dev()), SIZE)
+    assert np.array_equal(np.diff(offs), [len(c) for c in want])
+    same_bytes(points, np.concatenate(want), "65 scenes cloud")
+
+
 def test_dense_grids_reproduces_the_new_export():
     K = emu.SMALL_INTRINSIC
     scenes = [views(60 + b, K, 2 + b, 6) for b in range(3)]
