@@ -6,6 +6,7 @@
     from giga_amd import ResidentTrainingSet, ResidentBatches   # training batches from a set in device memory (giga_amd.resident)
     from giga_amd import Trainer, train_val_split               # the training loop of scripts/train_giga.py (giga_amd.trainer)
     from giga_amd import affordance_visual, grasp2mesh          # the scene mesh coloured by grasp quality (giga_amd.visual)
+    from giga_amd import GeometryEvaluator, VoxelOccGeoROIDataset   # scene IoU, chamfer, grasp-ROI occupancy (giga_amd.geometry)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/giga_hip.h."""
 __version__ = "0.1.0"
@@ -19,6 +20,9 @@ _RESIDENT_EXPORTS = ("ResidentTrainingSet", "ResidentBatches")
 _TRAINER_EXPORTS = ("Trainer", "TrainMetrics", "train_val_split")
 # ... and of giga_amd.visual: the affordance colours of a scene mesh, the gripper glyph, the composed scene
 _VISUAL_EXPORTS = ("affordance_faces", "affordance_points", "affordance_visual", "grasp2mesh", "ColoredMesh", "Scene")
+# ... and of giga_amd.geometry: the scoring of predicted geometry (scene IoU, chamfer, grasp-ROI occupancy) and its data sets
+_GEOMETRY_EXPORTS = ("GeometryEvaluator", "VoxelOccGeoDataset", "VoxelOccGeoROIDataset", "occ_confusion", "occ_scores",
+                     "roi_point_counts", "load_obj", "default_mesh_loader", "read_mesh_pose_list")
 
 
 def __getattr__(name):
@@ -34,4 +38,7 @@ def __getattr__(name):
     if name in _VISUAL_EXPORTS:
         from . import visual
         return getattr(visual, name)
+    if name in _GEOMETRY_EXPORTS:
+        from . import geometry
+        return getattr(geometry, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

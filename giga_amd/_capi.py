@@ -172,6 +172,12 @@ _SIGNATURES = {
     "giga_mesh_contains_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "giga_mesh_contains": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                                   ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_roi_points_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "giga_roi_points": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_uint64] + [ctypes.c_double] * 3
+                        + [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_occ_confusion_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "giga_occ_confusion": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "giga_depth_render_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "giga_depth_render": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 3 + [ctypes.c_double] * 3 + [ctypes.c_void_p] * 2
                           + [ctypes.c_size_t, ctypes.c_void_p]),

@@ -770,6 +770,42 @@ int giga_mesh_contains(const float* vertices, const int32_t* vertex_offsets, con
                        const double* points, const int32_t* point_offsets, int B, int resolution, uint8_t* inside, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---- geometry scoring (scripts/eval_geometry_voxel.py, src/vgn/dataset_voxel_occ.py:109-128; added within ABI 3) -----
+ * Caller-owned buffers, no allocation, asynchronous on `stream`, every argument checked before the first HIP call, no
+ * floating-point atomics: equal input gives equal bytes.  Errors: -1 negative count, null input or workspace, offsets that do not
+ * start at 0 or decrease, a number that is not finite, size 0, a negative scene or first index, a NaN threshold, both or neither of
+ * logits / pred; -4 workspace too small; -6 null output; -7 B > GIGA_MAX_SCENES.
+ *
+ * giga_roi_points: the query points of DatasetVoxelOccGeoROI.__getitem__ for a ragged batch of scenes.  All grasp arrays are HOST
+ * arrays (copied into the workspace before the call returns): grasps [G][13] float64 = the rotation matrix R row-major (9), the
+ * box origin pos = xyz + R (0,0,1) finger_depth (3) and the width; point_offsets [G + 1] int32, the prefix of the per-grasp point
+ * counts over the whole call (a grasp with count 0 emits nothing); grasp_scene [G] the index of the grasp's scene in the data set;
+ * grasp_first [G] the index inside its scene of the grasp's first point.  Point j of a scene (j counts through the scene's grasps)
+ * draws two Philox-4x32-10 blocks with counters (j, scene, 0, 0x524F49) and (j, scene, 1, 0x524F49) and key (seed & 0xffffffff,
+ * seed >> 32); u0, u1 = words (0,1), (2,3) of the first block and u2 = words (0,1) of the second, each 53 bits in (0, 1)
+ * (((hi >> 5) << 26 | lo >> 6) 2^-53, 2^-54 in place of 0).  So a point depends on (seed, scene, j) alone, not on the batch, the
+ * launch or the chunking.  In float64, one rounding per operation, no fused multiply-add:
+ *     x = (u0 - 1) e,  y = (u1 - 0.5) width,  z = (u2 - 1) e,  e = finger_depth * roi_scale
+ *     world [n][3] float64 = ((R[.][0] x + R[.][1] y) + R[.][2] z) + pos          (what the containment test sees)
+ *     normalised [n][3] float32 = float32(world / size - 0.5), rounded once
+ * n = point_offsets[G].  workspace: giga_roi_points_workspace_bytes(G).
+ *
+ * giga_occ_confusion: counts [B][4] uint64 (device) = [tp, fp, fn, tn] of every scene of a ragged batch (offsets: HOST, B + 1
+ * int32); an empty scene leaves zeros.  target [n] uint8: occupied where not 0.  The prediction is EITHER pred [n] uint8 (occupied
+ * where not 0; logits null) OR logits [n] float32 (pred null) with
+ *     predicted = (double)logit > logit_threshold,      logit_threshold = log(th / (1 - th)) computed by the caller in float64.
+ * A NaN logit predicts false.  This is the library's own definition of "sigmoid(logit) > th": the reference evaluates
+ * torch.sigmoid in float32 and compares with th, which decides differently only for logits within float32 rounding of the
+ * boundary (sigmoid(logit) rounds onto or across th there).  Integer atomics: the counts do not depend on the order of the
+ * additions.  workspace: giga_occ_confusion_workspace_bytes(B). */
+size_t giga_roi_points_workspace_bytes(int n_grasps);
+int giga_roi_points(const double* grasps, const int32_t* point_offsets, const int32_t* grasp_scene, const int32_t* grasp_first,
+                    int n_grasps, uint64_t seed, double finger_depth, double roi_scale, double size, double* world,
+                    float* normalised, void* workspace, size_t workspace_bytes, void* stream);
+size_t giga_occ_confusion_workspace_bytes(int B);
+int giga_occ_confusion(const float* logits, const uint8_t* pred, double logit_threshold, const uint8_t* target,
+                       const int32_t* offsets, int B, uint64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- output side: grasp affordance of a scene mesh (src/vgn/utils/visual.py:22-98, affordance_visual; added within ABI 3) -----
  * Colours every face of B scene meshes by the grasp quality predicted near it.  qual [B][R^3] float32 is the volume after process
  * and bound (the qual_out of giga_grasp_select), rot [B][R^3][4] float32 the quaternions (xyzw), voxel (i, j, k) at i R^2 + j R + k.
