@@ -5,6 +5,7 @@
     from giga_amd import render_depth, acquire_tsdf, save_occ   # depth images and occupancy labels from meshes (giga_amd.render)
     from giga_amd import ResidentTrainingSet, ResidentBatches   # training batches from a set in device memory (giga_amd.resident)
     from giga_amd import Trainer, train_val_split               # the training loop of scripts/train_giga.py (giga_amd.trainer)
+    from giga_amd import GeoTrainer, geo_loss                   # ... and of scripts/train_giga_geo.py: the occupancy-only giga_geo
     from giga_amd import affordance_visual, grasp2mesh          # the scene mesh coloured by grasp quality (giga_amd.visual)
     from giga_amd import GeometryEvaluator, VoxelOccGeoROIDataset   # scene IoU, chamfer, grasp-ROI occupancy (giga_amd.geometry)
 
@@ -17,7 +18,7 @@ _RENDER_EXPORTS = ("scene_mesh", "Camera", "render_depth", "render_depth_batch",
 # ... and of giga_amd.resident: the training set in device memory and its batch iterator
 _RESIDENT_EXPORTS = ("ResidentTrainingSet", "ResidentBatches")
 # ... and of giga_amd.trainer: the training loop, its device-side epoch metrics and the train / validation split
-_TRAINER_EXPORTS = ("Trainer", "TrainMetrics", "train_val_split")
+_TRAINER_EXPORTS = ("Trainer", "TrainMetrics", "train_val_split", "GeoTrainer", "geo_loss")
 # ... and of giga_amd.visual: the affordance colours of a scene mesh, the gripper glyph, the composed scene
 _VISUAL_EXPORTS = ("affordance_faces", "affordance_points", "affordance_visual", "grasp2mesh", "ColoredMesh", "Scene")
 # ... and of giga_amd.geometry: the scoring of predicted geometry (scene IoU, chamfer, grasp-ROI occupancy) and its data sets

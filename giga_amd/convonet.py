@@ -13,10 +13,10 @@ the reference (paths relative to /root/reference/src/vgn):
 The torch.nn layers below only OWN parameters (so `load_state_dict` of a reference checkpoint works
 unchanged and initialisation matches the reference); all arithmetic runs in the hand-written HIP
 kernels of libgiga_hip.so through `giga_amd._capi`.  Inputs must live on a HIP device: there is no
-CPU path (use the reference for that).  `ConvolutionalOccupancyNetwork.forward` is differentiable
-w.r.t. the parameters (fp32 HIP backward, giga_amd/training.py); the piecewise entry points
-(`encode_inputs`, `decode`, `LocalDecoder.forward`, ...) are inference-only and raise under autograd while parameters require
-grad.  With frozen parameters, `forward`, `decode`, `decode_occ` and `infer_geo` are differentiable w.r.t. the query points
+CPU path (use the reference for that).  `ConvolutionalOccupancyNetwork.forward` and
+`ConvolutionalOccupancyNetworkGeometry.forward` are differentiable w.r.t. the parameters (HIP backward, giga_amd/training.py); the
+piecewise entry points (`encode_inputs`, `decode`, `LocalDecoder.forward`, ...) are inference-only and raise under autograd while
+parameters require grad.  With frozen parameters, `forward`, `decode`, `decode_occ` and `infer_geo` are differentiable w.r.t. the query points
 (giga_decoder_point_grad; `grad_refine` uses it directly).
 """
 import os
@@ -611,62 +611,9 @@ class _ParamListCache:
         return super().train(mode)
 
 
-class ConvolutionalOccupancyNetwork(_ParamListCache, nn.Module):
-    """models/__init__.py:15-164: encoder + decoder_qual/rot/width (+ decoder_tsdf)."""
-
-    def __init__(self, decoders, encoder=None, device=None, detach_tsdf=False):
-        super().__init__()
-        self.decoder_qual = decoders[0].to(device)
-        self.decoder_rot = decoders[1].to(device)
-        self.decoder_width = decoders[2].to(device)
-        if len(decoders) == 4:
-            self.decoder_tsdf = decoders[3].to(device)
-        self.encoder = encoder.to(device) if encoder is not None else None
-        self._device = device
-        self.detach_tsdf = detach_tsdf
-        self.precision = _DEFAULT_PRECISION
-        self._packed = _PackedWeights()
-
-    # -- weights ----------------------------------------------------------------------------------
-    def set_precision(self, precision):
-        """'fp32' (exact fp32 MFMA, default), 'fp16' (f16 operands, fp32 accumulate: 2-5e-3 on raw logits), 'fp16x3'
-        (f16 MFMA on split hi/lo operands in encoder and decoders: fp32-grade results, <= 1e-5, at ~5x the fp32-MFMA rate) or
-        'fp16x3+fp16' (the f16x3 encoder under the plain-f16 LATTICE decoder: the throughput decoder without plain f16's encoder error;
-        other query sets take the f16x3 decoder);
-        'bf16' = the training step's forward arithmetic (bf16 U-Net convolutions, everything else fp32), ~1e-2."""
-        if precision not in _capi.PRECISION:
-            raise ValueError(precision)
-        self.precision = precision
-        for m in self.modules():
-            if isinstance(m, (LocalDecoder, LocalVoxelEncoder)):
-                m.precision = precision
-        return self
-
-    def set_persistent_unet(self, enabled=True):
-        """How the U-Net layers are launched (include/giga_hip.h, GIGA_PERSIST_UNET / GIGA_LAYERWISE_UNET): False = the default
-        (one persistent launch for the whole U-Net -- every batch size in the f16-class modes, from 8 scenes up in fp32 -- with
-        the same results as per-layer launches: bit for bit in the f16-class modes, to fp32 rounding in fp32); True = the
-        persistent launch also for small fp32 batches; "layers" = one launch per layer.  hipGraph capture is fine in every form.
-        At most four persistent launches are in flight per device: the library gives a fifth concurrent call (other streams) one
-        launch per layer on its own; other processes sharing the device and concurrent replays of captured graphs are not seen."""
-        self.encoder.persistent_unet = "layers" if enabled == "layers" else bool(enabled)
-        return self
-
-    def set_unet_kernel(self, kernel="auto"):
-        """Which convolution kernels run the f16-class U-Net ('fp16', 'fp16x3'; include/giga_hip.h, GIGA_CONV32_UNET / GIGA_CONV16_UNET):
-        "auto" (the library's default: conv32 -- 32x32x16 MFMA register tiles over LDS-resident row bands, same-resolution layer pairs
-        fused -- up to 16 scenes, conv16 beyond), "conv32" or "conv16" (16x16x32,
-        wave-private patches; the only kernels of 'fp32' / 'bf16').  A forced kernel makes a scene's result independent of the batch
-        size it runs in (bit for bit); "auto" does not across the 16-scene threshold.
-        'fp32' only: "direct" keeps the direct 3x3 convolutions (GIGA_DIRECT_CONV) where "auto" runs them as Winograd F(2x2, 3x3) on the
-        fp32 MFMA (csrc/giga_wino.h; planes within a few 1e-6 relative of the direct form)."""
-        if kernel not in ("auto", "conv16", "conv32", "direct"):
-            raise ValueError(kernel)
-        self.encoder.unet_kernel = kernel
-        return self
-
-    def _head_present(self):
-        return 7 | (8 if hasattr(self, "decoder_tsdf") else 0)
+class _Trainable(_ParamListCache):
+    """What the two models share beyond the parameter list: the packed blobs of the current weights (aware of training steps) and
+    the differentiable forward's switches and state (giga_amd/training.py).  A model names its heads with `_head_present()`."""
 
     def packed_blob(self, device):
         if self.__dict__.pop("_stale_after_training", False):
@@ -680,49 +627,6 @@ class ConvolutionalOccupancyNetwork(_ParamListCache, nn.Module):
         """Backward blob of the current weights (the point gradients need it next to `packed_blob`)."""
         self.packed_blob(device)                             # (drops both caches after a training step)
         return self._packed.get_bwd(self._ordered_params(), self._head_present(), device)
-
-    def _final_planes32(self, inputs):
-        """fp32 final planes (no conv_final folding) of `inputs`: what a point gradient differentiates through."""
-        nhwc, _ = self.encoder.encode_nhwc(inputs, blob=self.packed_blob(inputs.device), precision="fp32")
-        return nhwc
-
-    # -- reference API ------------------------------------------------------------------------------
-    def forward(self, inputs, p, p_tsdf=None, sample=True, _probe=None, **kwargs):
-        """models/__init__.py:42-67.  inputs (B,40,40,40); p (B,N,3); p_tsdf (B,M,3) ->
-        qual (B,N) [sigmoid], rot (B,N,4) [unit], width (B,N) [, tsdf (B,M) raw logits].
-        (`_probe`: bench.py's HIP-event bracket around one encoder kernel; not part of the API.)"""
-        _capi.require_device(inputs, p, p_tsdf)
-        fp = self.__dict__.get("_flat_param")
-        if torch.is_grad_enabled() and (fp.requires_grad if fp is not None else any(q.requires_grad for q in self._ordered_params())):
-            return self._forward_train(inputs, p, p_tsdf)
-        blob = self.packed_blob(inputs.device)
-        # encoder and decoders are called back to back here, so conv_final is folded into the heads' fc_c weights and
-        # never launched (GIGA_FOLD_FINAL); encode_inputs / decode keep exchanging the final planes, as the reference does
-        nhwc, _ = self.encoder.encode_nhwc(inputs, blob=blob, precision=self.precision, probe=_probe, fold_final=True)
-
-        def grasp():
-            g = decode_heads(nhwc, p, blob, 7, self.precision, post=True, folded=True)
-            return g["decoder_qual"], g["decoder_rot"], g["decoder_width"]
-
-        def occ():
-            return (decode_heads(nhwc, p_tsdf, blob, 8, self.precision, post=False, folded=True)["decoder_tsdf"],)
-
-        if not _wants_point_grad(self, p, p_tsdf):
-            return grasp() + (occ() if p_tsdf is not None else ())
-        # differentiable w.r.t. the points: same values; the backward re-encodes the final fp32 planes once (the folded planes
-        # above have no transposed fc_c images) and runs one point-gradient launch per point set
-        src = _LazyPlanes(lambda: (self._final_planes32(inputs), blob, self.packed_bwd_blob(inputs.device)))
-        out = _PointGrad.apply(p, grasp, src, _HEAD_SLOTS[:3]) if p.requires_grad else grasp()
-        if p_tsdf is not None:
-            out = out + (_PointGrad.apply(p_tsdf, occ, src, _HEAD_SLOTS[3:]) if p_tsdf.requires_grad else occ())
-        return out
-
-    def _param_list(self):
-        params = []
-        for h in HEAD_NAMES:
-            if hasattr(self, h):
-                params += _head_param_list(getattr(self, h))
-        return params + _encoder_param_list(self.encoder)
 
     def flatten_parameters(self):
         """Optional fast path for training loops: every parameter becomes a VIEW of one flat fp32 tensor in state-dict order,
@@ -782,7 +686,7 @@ class ConvolutionalOccupancyNetwork(_ParamListCache, nn.Module):
         from .training import GigaFunction, _TrainState
         st = getattr(self, "_train_state", None)
         if st is None or st.blob.device != inputs.device:
-            st = self._train_state = _TrainState(self._head_present(), inputs.device, detach_occ=self.detach_tsdf)
+            st = self._train_state = _TrainState(self._head_present(), inputs.device, detach_occ=getattr(self, "detach_tsdf", False))
             st.data_parallel, st.group = getattr(self, "_dp", (False, None))
             st.bf16 = getattr(self, "_train_bf16", False)
             st.bf16_dec = getattr(self, "_train_bf16_dec", False)
@@ -791,6 +695,113 @@ class ConvolutionalOccupancyNetwork(_ParamListCache, nn.Module):
         if fp is not None:
             return GigaFunction.apply(st, inputs, p, p_tsdf, fp)
         return GigaFunction.apply(st, inputs, p, p_tsdf, *self._ordered_params())
+
+    def _trains(self):
+        """autograd is on and the parameters (the flat one, once flattened) require grad: the call takes the training path"""
+        if not torch.is_grad_enabled():
+            return False
+        fp = self.__dict__.get("_flat_param")
+        return fp.requires_grad if fp is not None else any(q.requires_grad for q in self._ordered_params())
+
+
+class ConvolutionalOccupancyNetwork(_Trainable, nn.Module):
+    """models/__init__.py:15-164: encoder + decoder_qual/rot/width (+ decoder_tsdf)."""
+
+    def __init__(self, decoders, encoder=None, device=None, detach_tsdf=False):
+        super().__init__()
+        self.decoder_qual = decoders[0].to(device)
+        self.decoder_rot = decoders[1].to(device)
+        self.decoder_width = decoders[2].to(device)
+        if len(decoders) == 4:
+            self.decoder_tsdf = decoders[3].to(device)
+        self.encoder = encoder.to(device) if encoder is not None else None
+        self._device = device
+        self.detach_tsdf = detach_tsdf
+        self.precision = _DEFAULT_PRECISION
+        self._packed = _PackedWeights()
+
+    # -- weights ----------------------------------------------------------------------------------
+    def set_precision(self, precision):
+        """'fp32' (exact fp32 MFMA, default), 'fp16' (f16 operands, fp32 accumulate: 2-5e-3 on raw logits), 'fp16x3'
+        (f16 MFMA on split hi/lo operands in encoder and decoders: fp32-grade results, <= 1e-5, at ~5x the fp32-MFMA rate) or
+        'fp16x3+fp16' (the f16x3 encoder under the plain-f16 LATTICE decoder: the throughput decoder without plain f16's encoder error;
+        other query sets take the f16x3 decoder);
+        'bf16' = the training step's forward arithmetic (bf16 U-Net convolutions, everything else fp32), ~1e-2."""
+        if precision not in _capi.PRECISION:
+            raise ValueError(precision)
+        self.precision = precision
+        for m in self.modules():
+            if isinstance(m, (LocalDecoder, LocalVoxelEncoder)):
+                m.precision = precision
+        return self
+
+    def set_persistent_unet(self, enabled=True):
+        """How the U-Net layers are launched (include/giga_hip.h, GIGA_PERSIST_UNET / GIGA_LAYERWISE_UNET): False = the default
+        (one persistent launch for the whole U-Net -- every batch size in the f16-class modes, from 8 scenes up in fp32 -- with
+        the same results as per-layer launches: bit for bit in the f16-class modes, to fp32 rounding in fp32); True = the
+        persistent launch also for small fp32 batches; "layers" = one launch per layer.  hipGraph capture is fine in every form.
+        At most four persistent launches are in flight per device: the library gives a fifth concurrent call (other streams) one
+        launch per layer on its own; other processes sharing the device and concurrent replays of captured graphs are not seen."""
+        self.encoder.persistent_unet = "layers" if enabled == "layers" else bool(enabled)
+        return self
+
+    def set_unet_kernel(self, kernel="auto"):
+        """Which convolution kernels run the f16-class U-Net ('fp16', 'fp16x3'; include/giga_hip.h, GIGA_CONV32_UNET / GIGA_CONV16_UNET):
+        "auto" (the library's default: conv32 -- 32x32x16 MFMA register tiles over LDS-resident row bands, same-resolution layer pairs
+        fused -- up to 16 scenes, conv16 beyond), "conv32" or "conv16" (16x16x32,
+        wave-private patches; the only kernels of 'fp32' / 'bf16').  A forced kernel makes a scene's result independent of the batch
+        size it runs in (bit for bit); "auto" does not across the 16-scene threshold.
+        'fp32' only: "direct" keeps the direct 3x3 convolutions (GIGA_DIRECT_CONV) where "auto" runs them as Winograd F(2x2, 3x3) on the
+        fp32 MFMA (csrc/giga_wino.h; planes within a few 1e-6 relative of the direct form)."""
+        if kernel not in ("auto", "conv16", "conv32", "direct"):
+            raise ValueError(kernel)
+        self.encoder.unet_kernel = kernel
+        return self
+
+    def _head_present(self):
+        return 7 | (8 if hasattr(self, "decoder_tsdf") else 0)
+
+    def _final_planes32(self, inputs):
+        """fp32 final planes (no conv_final folding) of `inputs`: what a point gradient differentiates through."""
+        nhwc, _ = self.encoder.encode_nhwc(inputs, blob=self.packed_blob(inputs.device), precision="fp32")
+        return nhwc
+
+    # -- reference API ------------------------------------------------------------------------------
+    def forward(self, inputs, p, p_tsdf=None, sample=True, _probe=None, **kwargs):
+        """models/__init__.py:42-67.  inputs (B,40,40,40); p (B,N,3); p_tsdf (B,M,3) ->
+        qual (B,N) [sigmoid], rot (B,N,4) [unit], width (B,N) [, tsdf (B,M) raw logits].
+        (`_probe`: bench.py's HIP-event bracket around one encoder kernel; not part of the API.)"""
+        _capi.require_device(inputs, p, p_tsdf)
+        if self._trains():
+            return self._forward_train(inputs, p, p_tsdf)
+        blob = self.packed_blob(inputs.device)
+        # encoder and decoders are called back to back here, so conv_final is folded into the heads' fc_c weights and
+        # never launched (GIGA_FOLD_FINAL); encode_inputs / decode keep exchanging the final planes, as the reference does
+        nhwc, _ = self.encoder.encode_nhwc(inputs, blob=blob, precision=self.precision, probe=_probe, fold_final=True)
+
+        def grasp():
+            g = decode_heads(nhwc, p, blob, 7, self.precision, post=True, folded=True)
+            return g["decoder_qual"], g["decoder_rot"], g["decoder_width"]
+
+        def occ():
+            return (decode_heads(nhwc, p_tsdf, blob, 8, self.precision, post=False, folded=True)["decoder_tsdf"],)
+
+        if not _wants_point_grad(self, p, p_tsdf):
+            return grasp() + (occ() if p_tsdf is not None else ())
+        # differentiable w.r.t. the points: same values; the backward re-encodes the final fp32 planes once (the folded planes
+        # above have no transposed fc_c images) and runs one point-gradient launch per point set
+        src = _LazyPlanes(lambda: (self._final_planes32(inputs), blob, self.packed_bwd_blob(inputs.device)))
+        out = _PointGrad.apply(p, grasp, src, _HEAD_SLOTS[:3]) if p.requires_grad else grasp()
+        if p_tsdf is not None:
+            out = out + (_PointGrad.apply(p_tsdf, occ, src, _HEAD_SLOTS[3:]) if p_tsdf.requires_grad else occ())
+        return out
+
+    def _param_list(self):
+        params = []
+        for h in HEAD_NAMES:
+            if hasattr(self, h):
+                params += _head_param_list(getattr(self, h))
+        return params + _encoder_param_list(self.encoder)
 
     def infer_geo(self, inputs, p_tsdf, **kwargs):
         """models/__init__.py:69-72."""
@@ -876,7 +887,7 @@ class ConvolutionalOccupancyNetwork(_ParamListCache, nn.Module):
         return qual, pos_tmp, rot, width
 
 
-class ConvolutionalOccupancyNetworkGeometry(_ParamListCache, nn.Module):
+class ConvolutionalOccupancyNetworkGeometry(_Trainable, nn.Module):
     """models/__init__.py:166-226 (occupancy head only; `giga_geo`)."""
 
     def __init__(self, decoder, encoder=None, device=None):
@@ -898,15 +909,20 @@ class ConvolutionalOccupancyNetworkGeometry(_ParamListCache, nn.Module):
     def _param_list(self):
         return _head_param_list(self.decoder_tsdf) + _encoder_param_list(self.encoder)
 
-    def packed_blob(self, device):
-        return self._packed.get(self._ordered_params(), 8, device)
-
-    def packed_bwd_blob(self, device):
-        return self._packed.get_bwd(self._ordered_params(), 8, device)
+    def _head_present(self):
+        return 8
 
     def forward(self, inputs, p, p_tsdf, sample=True, **kwargs):
-        _check_no_grad(self)
+        """models/__init__.py:186-199.  inputs (B,40,40,40); p is ignored (may be None); p_tsdf (B,M,3) -> raw occupancy logits
+        (B,M).  With autograd on and trainable parameters the call is differentiable w.r.t. the parameters (the training path of
+        giga_amd/training.py on the occupancy head alone, `set_train_precision`'s arithmetic); otherwise it is the inference path
+        in `set_precision`'s arithmetic."""
         _capi.require_device(inputs, p_tsdf)
+        if self._trains():
+            if p_tsdf.dim() != 3 or p_tsdf.shape[1] == 0:
+                raise ValueError(f"the training forward of giga_geo takes (B,M,3) occupancy queries with M > 0, got {tuple(p_tsdf.shape)}")
+            no_grasp = torch.empty((p_tsdf.shape[0], 0, 3), device=p_tsdf.device)     # no grasp head: no grasp query
+            return self._forward_train(inputs, no_grasp, p_tsdf)[0]
         blob = self.packed_blob(inputs.device)
         nhwc, _ = self.encoder.encode_nhwc(inputs, blob=blob, precision=self.precision)
 

@@ -61,6 +61,9 @@ int launch_train_loss_backward(const float* qual, const float* rot, const float*
                                const float* label, const float* rot_t, const float* width_t, const float* occ_t,
                                const float* gout, int B, int M, float* dqual, float* drot, float* dwidth, float* docc,
                                hipStream_t s);
+int launch_train_occ_loss(const float* occ, const float* occ_t, int B, int M, float* loss, float* scene_loss, unsigned* scene_counts,
+                          void* acc, hipStream_t s);
+int launch_train_occ_loss_backward(const float* occ, const float* occ_t, const float* gout, int B, int M, float* docc, hipStream_t s);
 // giga_tsdf.hip
 int launch_tsdf_scatter(const int* index, const float* value, const int* offsets, int B, int R, int n, float* grid,
                         int* winner, hipStream_t s);
@@ -823,6 +826,34 @@ int giga_train_loss_backward(const float* qual, const float* rot, const float* w
     if (M > 0 && (!occ_logits || !occ_target || !docc)) return -1;
     return launch_train_loss_backward(qual, rot, width, occ_logits, label, rot_targets, width_target, occ_target, grad_loss,
                                       B, M, dqual, drot, dwidth, docc, static_cast<hipStream_t>(stream));
+}
+
+int giga_train_occ_loss(const float* occ_logits, const float* occ_target, int B, int M, float* loss, float* scene_losses,
+                        void* stream) {
+    if (B < 0 || M < 0) return -1;
+    if (B == 0) return 0;
+    if (M == 0) return -1;                                  // the loss of a scene is a mean over its points
+    if (!occ_logits || !occ_target || !loss || !scene_losses) return -1;
+    return launch_train_occ_loss(occ_logits, occ_target, B, M, loss, scene_losses, nullptr, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int giga_train_occ_loss_metrics(const float* occ_logits, const float* occ_target, int B, int M, float* loss, float* scene_losses,
+                                uint32_t* scene_counts, void* acc, void* stream) {
+    if (B < 0 || M < 0) return -1;
+    if (!acc || (reinterpret_cast<uintptr_t>(acc) & 7)) return -1;
+    if (B == 0) return 0;
+    if (M == 0) return -1;
+    if (!occ_logits || !occ_target || !loss || !scene_losses || !scene_counts) return -1;
+    return launch_train_occ_loss(occ_logits, occ_target, B, M, loss, scene_losses, scene_counts, acc, static_cast<hipStream_t>(stream));
+}
+
+int giga_train_occ_loss_backward(const float* occ_logits, const float* occ_target, const float* grad_loss, int B, int M, float* docc,
+                                 void* stream) {
+    if (B < 0 || M < 0) return -1;
+    if (B == 0) return 0;
+    if (M == 0) return -1;
+    if (!occ_logits || !occ_target || !grad_loss || !docc) return -1;
+    return launch_train_occ_loss_backward(occ_logits, occ_target, grad_loss, B, M, docc, static_cast<hipStream_t>(stream));
 }
 
 int giga_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,

@@ -198,6 +198,129 @@ int launch_train_loss_backward(const float* qual, const float* rot, const float*
 
 
 // ---------------------------------------------------------------------------------------------------------------------
+// The occupancy-only objective of giga_geo (scripts/train_giga_geo.py:152-165: loss = mean_B mean_M BCE(sigmoid(z), t)) and its
+// epoch metrics (:52-57: ignite's binary Accuracy / Precision / Recall over EVERY occupancy point of the epoch).  The arithmetic
+// is the occupancy term's of the kernels above, restated: the same p, the same bce_term, the same per-thread order (i = tid,
+// tid + 256, ...), the same wave and LDS tree, the same serial sum over the scenes -- `loss` equals losses[3] of giga_train_loss
+// and `docc` equals its docc, bit for bit (tests/test_gpu_geo_trainer.py).  HBM-bound: one read of each input per launch.
+//
+// One workgroup per scene.  The loop's trip count is uniform (ceil(M / 256) rounds for every thread; a thread past M adds nothing),
+// so each ballot sees whole waves; a point's prediction is p > 0.5f on the p the loss uses (torch.round(sigmoid(z)): half to even,
+// p == 0.5 rounds to 0), and it is valid when p is not NaN and the target is exactly 0 or 1.  With `scene_counts` (the metrics
+// form) thread 0 writes the scene's six counts -- examples, correct, tp, fp, fn, invalid -- as 32-bit words [b][6].
+__global__ __launch_bounds__(256) void occ_scene_kernel(const float* __restrict__ occ, const float* __restrict__ occ_t, int M,
+                                                        float* __restrict__ scene_loss, unsigned* __restrict__ scene_counts) {
+    __shared__ float part[4];
+    __shared__ unsigned cnt[4][6];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* z_row = occ + (size_t)b * M;
+    const float* t_row = occ_t + (size_t)b * M;
+    float s = 0.f;
+    unsigned c[6] = {0, 0, 0, 0, 0, 0};
+    for (long long base = 0; base < M; base += 256) {           // (64-bit: base + 256 passes INT_MAX for the largest M)
+        const long long i = base + tid;
+        const bool in = i < M;
+        const float z = in ? z_row[i] : 0.f, t = in ? t_row[i] : 0.f;
+        const float p = 1.0f / (1.0f + expf(-z));
+        if (in) s += bce_term(p, t);
+        const bool valid = in && p == p && (t == 0.f || t == 1.f);
+        const bool pred = p > 0.5f, pos = t == 1.f;
+        c[0] += __popcll(__ballot(valid));
+        c[1] += __popcll(__ballot(valid && pred == pos));
+        c[2] += __popcll(__ballot(valid && pred && pos));
+        c[3] += __popcll(__ballot(valid && pred && !pos));
+        c[4] += __popcll(__ballot(valid && !pred && pos));
+        c[5] += __popcll(__ballot(in && !valid));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((tid & 63) == 0) {
+        part[tid >> 6] = s;
+        for (int k = 0; k < 6; ++k) cnt[tid >> 6][k] = c[k];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        scene_loss[b] = ((part[0] + part[1]) + (part[2] + part[3])) / (float)M;
+        if (scene_counts)
+            for (int k = 0; k < 6; ++k) scene_counts[6 * (size_t)b + k] = (cnt[0][k] + cnt[1][k]) + (cnt[2][k] + cnt[3][k]);
+    }
+}
+
+// loss [1] = mean over the scenes, summed in scene order by one lane
+__global__ __launch_bounds__(64) void occ_mean_kernel(const float* __restrict__ scene_loss, int B, float* __restrict__ loss) {
+    if (threadIdx.x != 0) return;
+    float s = 0.f;
+    for (int b = 0; b < B; ++b) s += scene_loss[b];
+    loss[0] = s / (float)B;
+}
+
+// The mean launch of the giga_geo loop (giga_train_occ_loss_metrics), in the manner of loss_mean_metrics_kernel: lane 0 of wave 0
+// loads the accumulator words it will update and then runs the serial fp32 sum exactly as occ_mean_kernel does; lanes 0-5 of wave 1
+// meanwhile sum the per-scene counts over the scenes as 64-bit integers, one count each.  Lane 0 alone reads, updates and writes
+// `acc`: words 0-6 (batches + 1; examples, correct, tp, fp, fn, invalid in points) and the doubles 8 + 3 and 8 + 4 (both
+// += (double)loss: the occupancy mean is the whole objective here); words 7, 8-10 and 13-15 are not touched.  No atomics.
+__global__ __launch_bounds__(128) void occ_mean_metrics_kernel(const float* __restrict__ scene_loss,
+                                                               const unsigned* __restrict__ scene_counts, int B, float* loss,
+                                                               unsigned long long* acc) {
+    __shared__ unsigned long long total[6];
+    const int tid = threadIdx.x;
+    // thread 0's view of `acc`, + 0 as a per-lane value: vector loads and stores (see loss_mean_metrics_kernel)
+    unsigned long long* const words = acc + __builtin_amdgcn_mbcnt_lo(~0u, 0u);
+    unsigned long long old[7];
+    double old_sum[2];
+    float m = 0.f;
+    if (tid == 0) {
+        for (int k = 0; k < 7; ++k) old[k] = words[k];
+        for (int k = 0; k < 2; ++k) old_sum[k] = reinterpret_cast<const double*>(words)[8 + 3 + k];
+        float s = 0.f;
+        for (int b = 0; b < B; ++b) s += scene_loss[b];
+        m = s / (float)B;
+        loss[0] = m;
+    } else if (tid >= 64 && tid < 64 + 6) {
+        const int k = tid - 64;
+        unsigned long long n = 0;
+        for (int b = 0; b < B; ++b) n += scene_counts[6 * (size_t)b + k];
+        total[k] = n;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        words[0] = old[0] + 1ull;
+        for (int k = 0; k < 6; ++k) words[1 + k] = old[1 + k] + total[k];
+        for (int k = 0; k < 2; ++k) reinterpret_cast<double*>(words)[8 + 3 + k] = old_sum[k] + (double)m;
+    }
+}
+
+// docc = (g / B / M) * BCE'(p) * sigmoid'(z), the occupancy line of loss_grad_kernel
+__global__ __launch_bounds__(256) void occ_grad_kernel(const float* __restrict__ occ, const float* __restrict__ occ_t,
+                                                       const float* __restrict__ gout, int B, int M, float* __restrict__ docc) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float g = gout[0] / (float)B;
+    const float gm = g / (float)M;
+    for (int i = tid; i < M; i += 256) {
+        const float z = occ[(size_t)b * M + i];
+        const float p = 1.0f / (1.0f + expf(-z));
+        docc[(size_t)b * M + i] = gm * bce_grad(p, occ_t[(size_t)b * M + i]) * ((1.0f - p) * p);
+    }
+}
+
+int launch_train_occ_loss(const float* occ, const float* occ_t, int B, int M, float* loss, float* scene_loss, unsigned* scene_counts,
+                          void* acc, hipStream_t s) {
+    GIGA_LAUNCH(occ_scene_kernel, dim3(B), dim3(256), 0, s, occ, occ_t, M, scene_loss, acc ? scene_counts : nullptr);
+    if (acc)
+        GIGA_LAUNCH(occ_mean_metrics_kernel, dim3(1), dim3(128), 0, s, scene_loss, scene_counts, B, loss,
+                           static_cast<unsigned long long*>(acc));
+    else
+        GIGA_LAUNCH(occ_mean_kernel, dim3(1), dim3(64), 0, s, scene_loss, B, loss);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int launch_train_occ_loss_backward(const float* occ, const float* occ_t, const float* gout, int B, int M, float* docc, hipStream_t s) {
+    GIGA_LAUNCH(occ_grad_kernel, dim3(B), dim3(256), 0, s, occ, occ_t, gout, B, M, docc);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Adam over ONE flat fp32 parameter buffer (the module's flattened parameters, 581 863 elements): torch.optim.Adam's update
 // (scripts/train_giga.py:49 builds `torch.optim.Adam(net.parameters(), lr)`; no amsgrad, not maximize) in one launch that
 // uses the whole chip.  torch's fused multi-tensor kernel gives one tensor one workgroup per 65 536 elements: nine workgroups

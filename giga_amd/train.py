@@ -13,9 +13,10 @@ from datetime import datetime
 from pathlib import Path
 
 
-def build_parser():
-    parser = argparse.ArgumentParser(prog="python -m giga_amd.train", description=__doc__.split("\n\n")[0])
-    parser.add_argument("--net", default="giga")
+def build_parser(prog="python -m giga_amd.train", description=None, net="giga", nets=None):
+    """the flags; `net` is the default of `--net` and `nets`, when given, its choices (`python -m giga_amd.train_geo` shares them)"""
+    parser = argparse.ArgumentParser(prog=prog, description=description or __doc__.split("\n\n")[0])
+    parser.add_argument("--net", default=net, choices=nets)
     parser.add_argument("--dataset", type=Path, required=True)
     parser.add_argument("--dataset_raw", type=Path, required=True)
     parser.add_argument("--logdir", type=Path, default="data/runs")
@@ -44,16 +45,18 @@ def run_directory(args, now=None):
     return Path(args.logdir) / description
 
 
-def parse_args(argv=None):
-    parser = build_parser()
+def parse_args(argv=None, parser=None):
+    parser = parser or build_parser()
     args = parser.parse_args(argv)
     if args.resume and args.savedir == "":                   # (without it the directory's name carries the time of THIS start)
         parser.error("--resume continues the run in --savedir: name that directory")
     return args
 
 
-def main(argv=None):
-    args = parse_args(argv)
+def main(argv=None, parser=None, trainer_class=None):
+    """parse, read the set, build the network and run the epochs; `parser` and `trainer_class` (default: this module's flags and
+    `Trainer`) are what `python -m giga_amd.train_geo` replaces"""
+    args = parse_args(argv, parser)
     import torch
     import torch.distributed as dist
 
@@ -80,8 +83,8 @@ def main(argv=None):
         dist.broadcast_object_list(logdir, src=0)
     # --silence hides the reference's progress bar and nothing else; there is no bar here, so the flag changes nothing.  The ranks'
     # networks differ at this point (torch's initialisation): the Trainer broadcasts rank 0's
-    trainer = Trainer(net, train, val, lr=args.lr, net_name=args.net, logdir=logdir[0], precision=args.precision,
-                      group=group, resume=args.resume)
+    trainer = (trainer_class or Trainer)(net, train, val, lr=args.lr, net_name=args.net, logdir=logdir[0], precision=args.precision,
+                                         group=group, resume=args.resume)
     trainer.run(args.epochs)
     if group is not None:
         dist.destroy_process_group()

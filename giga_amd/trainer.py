@@ -13,7 +13,11 @@ small device-to-host copy.
 
 The files in `logdir` are the reference's: `vgn_<net>_<iteration>.pt` after every epoch and `best_vgn_<net>_val_acc=<acc>.pt` for
 the best validation accuracy, both plain state dicts that `load_network` reads; beside them `trainer_state.pt` (what `resume=True`
-needs) and `metrics.jsonl` (one line per epoch).  Device tensors only; no CPU fallback."""
+needs) and `metrics.jsonl` (one line per epoch).  Device tensors only; no CPU fallback.
+
+`GeoTrainer` is the same loop for the occupancy-only `giga_geo` (the reference's scripts/train_giga_geo.py):
+`geo_loss` in place of `giga_loss`, the metrics `loss`, `occ_accuracy`, `occ_precision`, `occ_recall` counted over every occupancy
+point by the loss launch (`giga_train_occ_loss_metrics`) into the same 128 bytes, `python -m giga_amd.train_geo`."""
 import glob
 import itertools
 import json
@@ -24,13 +28,14 @@ import torch
 
 from . import _capi
 from .optim import FlatAdam
-from .training import LOSS_KEYS, allreduce_mean_, giga_loss
+from .training import LOSS_KEYS, allreduce_mean_, geo_loss, giga_loss
 
 WORDS = _capi.TRAIN_METRICS_BYTES // 8                      # sixteen 8-byte words (include/giga_hip.h)
 COUNT_NAMES = ("batches", "examples", "correct", "tp", "fp", "fn", "invalid")       # words 0-6, uint64
 SUM_WORD = 8                                                 # words 8-12, double: running sums of the batch means, LOSS_KEYS' order
 METRIC_KEYS = ("accuracy", "precision", "recall", "loss_all", "loss_qual", "loss_rot", "loss_width", "loss_occ")    # train_giga.py:53-59
 NETS = ("giga", "giga_detach", "giga_aff")
+GEO_METRIC_KEYS = ("loss", "occ_accuracy", "occ_precision", "occ_recall")          # train_giga_geo.py:52-57
 
 
 def finalize_metrics(words):
@@ -54,6 +59,29 @@ def finalize_metrics(words):
     for k, s in zip(LOSS_KEYS, sums):
         out[k] = f(s) / f(c["batches"])
     return {k: float(out[k]) for k in METRIC_KEYS}
+
+
+def finalize_geo_metrics(words):
+    """The epoch metrics of the reference's train_giga_geo.py:52-57 (an Average of the loss and ignite's binary Accuracy, Precision
+    and Recall over every occupancy point of the epoch) from the sixteen accumulator words as `geo_loss(..., metrics=m)` fills them,
+    in float64 -> dict with GEO_METRIC_KEYS.  The counts are points, not scenes; the loss is the sum in word 8 + 3 (the occupancy
+    mean, which is the whole objective) over the batches.  ValueError for an accumulator that saw no batch, and for one that counted
+    points whose probability is NaN or whose target is not 0 or 1 (ignite raises there too)."""
+    raw = np.ascontiguousarray(np.asarray(words)).reshape(-1)
+    if raw.size != WORDS or raw.dtype.itemsize != 8:
+        raise ValueError(f"the accumulator is {WORDS} 8-byte words")
+    c = dict(zip(COUNT_NAMES, (int(v) for v in raw.view(np.uint64)[:len(COUNT_NAMES)])))
+    if c["batches"] == 0:
+        raise ValueError("the metrics of an epoch need at least one batch")
+    if c["invalid"] > 0:
+        raise ValueError(f"{c['invalid']} points with a NaN probability or a target other than 0 and 1: binary metrics are not "
+                         "defined for them")
+    f = np.float64
+    out = {"loss": f(raw.view(np.float64)[SUM_WORD + LOSS_KEYS.index("loss_occ")]) / f(c["batches"]),
+           "occ_accuracy": f(c["correct"]) / f(c["examples"]),
+           "occ_precision": f(c["tp"]) / (f(c["tp"] + c["fp"]) + f(1e-20)),
+           "occ_recall": f(c["tp"]) / (f(c["tp"] + c["fn"]) + f(1e-20))}
+    return {k: float(out[k]) for k in GEO_METRIC_KEYS}
 
 
 def all_reduce_words_(acc, group=None):
@@ -208,13 +236,20 @@ class Trainer:
     enters every collective; all ranks skip a validation pass that has no batch on one of them.  `quiet=True` drops the
     `Train …` / `Val …` lines (the reference's `--silence` hides its progress bar, which does not exist here)."""
 
+    finalize = staticmethod(finalize_metrics)                # the accumulator words of an epoch -> its metrics
+    score_key = "accuracy"                                   # the validation metric that names the "best" file (train_giga.py:93-95)
+
+    @staticmethod
+    def _check_net(net_name):
+        if net_name == "giga_geo":
+            raise NotImplementedError("giga_geo has no quality head, hence none of these epoch metrics; GeoTrainer runs it")
+        if net_name not in NETS:
+            raise ValueError(f"net_name is one of {NETS}")
+
     def __init__(self, net, train_batches, val_batches=None, lr=2e-4, net_name="giga", logdir=None, precision=None, group=None,
                  resume=False, on_step=None, quiet=False):
         net_name = str(net_name).lower()
-        if net_name == "giga_geo":
-            raise NotImplementedError("giga_geo has no quality head, hence none of the epoch metrics; the trainer does not run it")
-        if net_name not in NETS:
-            raise ValueError(f"net_name is one of {NETS}")
+        self._check_net(net_name)
         self.net, self.net_name, self.train_batches, self.val_batches = net, net_name, train_batches, val_batches
         self.group, self.on_step, self.quiet, self.phase = group, on_step, bool(quiet), None
         if precision is not None:
@@ -285,7 +320,7 @@ class Trainer:
             self.train_step(batch)
         self.phase = None
         self.epoch += 1
-        return self.metrics.all_reduce(self.group).compute()
+        return self.finalize(self.metrics.all_reduce(self.group).words())
 
     def validate(self):
         """`create_evaluator` (train_giga.py:221-235) over `val_batches` -> the metrics, or None without a validation batch"""
@@ -306,7 +341,7 @@ class Trainer:
             self.net.train()
         if n == 0 and self.val_steps is None:                # (drop_last=True on a small validation set; one rank, no collective)
             return None
-        return self.val_metrics.all_reduce(self.group).compute()
+        return self.finalize(self.val_metrics.all_reduce(self.group).words())
 
     def state(self):
         """what `resume=True` needs beside the network's own file"""
@@ -334,9 +369,37 @@ class Trainer:
                 # pair of two iterations, which resume=True refuses
                 sd = self.net.state_dict()
                 if val is not None:
-                    self.ckpt.save_best(sd, val["accuracy"])
+                    self.ckpt.save_best(sd, val[self.score_key])
                 self.ckpt.save_epoch(sd, self.iteration)
                 self.ckpt.save_state(self.state())
                 with open(os.path.join(self.logdir, "metrics.jsonl"), "a") as f:
                     f.write(json.dumps(record) + "\n")
         return records
+
+
+class GeoTrainer(Trainer):
+    """`create_trainer` + `create_evaluator` + the handlers of the reference's scripts/train_giga_geo.py:59-118 for the
+    occupancy-only model `giga_geo`, on `Trainer`'s machinery: the same `(x, pos, pos_occ, y)` batches (the script trains on the
+    grasp rows of `DatasetVoxelOccFile` and ignores their grasp fields: `pos` and `y[:3]` are not read), `FlatAdam`, `group`,
+    `resume`, checkpoints, `metrics.jsonl` and `quiet`.  A step is `net(x, None, p_tsdf=pos_occ)`, `geo_loss` and its backward; the
+    epoch metrics are GEO_METRIC_KEYS, counted over every occupancy point by the loss launch (`finalize_geo_metrics`); the files are
+    `vgn_giga_geo_<iteration>.pt` and `best_vgn_giga_geo_val_acc=<occ_accuracy>.pt` (train_giga_geo.py:91-93).
+    `on_step(trainer, batch, out, loss_dict)` gets `out = (None, None, None, logits)`, the shape of the script's `select`, and
+    `loss_dict = {"loss": ...}`."""
+
+    finalize = staticmethod(finalize_geo_metrics)
+    score_key = "occ_accuracy"
+
+    @staticmethod
+    def _check_net(net_name):
+        if net_name != "giga_geo":
+            raise ValueError(f"GeoTrainer runs giga_geo; Trainer runs {NETS}")
+
+    def __init__(self, net, train_batches, val_batches=None, lr=2e-4, net_name="giga_geo", **kwargs):
+        super().__init__(net, train_batches, val_batches, lr=lr, net_name=net_name, **kwargs)
+
+    def _forward(self, batch, metrics):
+        x, _, pos_occ, y = batch
+        logits = self.net(x, None, p_tsdf=pos_occ)
+        loss, loss_dict = geo_loss(logits, y[3], metrics=metrics)
+        return (None, None, None, logits), loss, loss_dict

@@ -16,7 +16,8 @@ reference loop works unchanged with ITS OWN helpers (`select`, `loss_fn` of trai
     y_pred = select(net(x, pos, p_tsdf=pos_occ)); loss, _ = loss_fn(y_pred, y); loss.backward(); optimizer.step()
 
 and `giga_loss(net(x, pos, p_tsdf=pos_occ), y)` is the fused replacement of `loss_fn(select(...), y)`: three HIP launches
-instead of ~40 ATen kernels (csrc/giga_loss.hip).
+instead of ~40 ATen kernels (csrc/giga_loss.hip).  The occupancy-only `giga_geo` trains the same way through its own forward,
+`net(x, None, p_tsdf=pos_occ)`, and `geo_loss(logits, occ)`, the fused `loss_fn(select(...), y)` of scripts/train_giga_geo.py.
 
 Every step the fp32 weight images (forward fragments and the transposed/flipped backward fragments) are rebuilt ON THE
 DEVICE from the current parameters with a gather map (giga_repack_device); the activations of the forward stay in an
@@ -339,3 +340,70 @@ def giga_loss(out, y, metrics=None):
     d = {k: parts[i] for i, k in enumerate(LOSS_KEYS[:4])}
     d["loss_all"] = loss.detach()
     return loss, d
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the occupancy-only objective of giga_geo: loss_fn(select(out), y) of scripts/train_giga_geo.py:152-165
+# ---------------------------------------------------------------------------------------------------------
+class _GeoLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, acc, occ, occ_t):
+        L = _capi.lib()
+        B, M = occ.shape
+        dev = occ.device
+        occ, occ_t = occ.contiguous().float(), occ_t.contiguous().float()
+        loss = torch.empty(1, device=dev)
+        scene = torch.empty(B, device=dev)
+        with torch.cuda.device(dev):
+            if acc is None:
+                _capi.check(L.giga_train_occ_loss(_capi.ptr(occ), _capi.ptr(occ_t), B, M, _capi.ptr(loss), _capi.ptr(scene),
+                                                  _capi.stream_ptr(dev)), "giga_train_occ_loss")
+            else:                                            # the same two launches; they also count the batch's points into `acc`
+                counts = torch.empty((B, 6), dtype=torch.int32, device=dev)
+                _capi.check(L.giga_train_occ_loss_metrics(_capi.ptr(occ), _capi.ptr(occ_t), B, M, _capi.ptr(loss), _capi.ptr(scene),
+                                                          _capi.ptr(counts), _capi.ptr(acc), _capi.stream_ptr(dev)),
+                            "giga_train_occ_loss_metrics")
+        ctx.save_for_backward(occ, occ_t)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, gloss):
+        L = _capi.lib()
+        occ, occ_t = ctx.saved_tensors
+        B, M = occ.shape
+        dev = occ.device
+        g = gloss.contiguous().float().reshape(1)
+        docc = torch.empty_like(occ)
+        with torch.cuda.device(dev):
+            _capi.check(L.giga_train_occ_loss_backward(_capi.ptr(occ), _capi.ptr(occ_t), _capi.ptr(g), B, M, _capi.ptr(docc),
+                                                       _capi.stream_ptr(dev)), "giga_train_occ_loss_backward")
+        return None, docc, None
+
+
+def geo_loss(occ_logits, occ_target, metrics=None):
+    """Fused `loss_fn(select(out), y)` of scripts/train_giga_geo.py:152-165: BCE(sigmoid(occ_logits), occ_target).mean(-1).mean().
+
+    occ_logits: the (B, M) raw occupancy logits `giga_geo` returns; occ_target: (B, M).  Returns (loss, {"loss": loss.detach()}), the
+    reference's `loss_dict`; `loss` is differentiable w.r.t. the logits.  The arithmetic is the occupancy term's of `giga_loss`, bit
+    for bit.  metrics: a `giga_amd.trainer.TrainMetrics`; the loss launch then also adds this batch to its device accumulator --
+    accuracy, precision and recall counts of round(sigmoid(logit)) against the target over all B * M points, and the running sum of
+    the loss (giga_train_occ_loss_metrics) -- with the same returned values and the same backward.  An empty batch gives NaN and
+    leaves the accumulator alone; a batch without points (M == 0) has no loss and is refused."""
+    _capi.device_of(occ_logits, occ_target)                  # (one HIP device; GigaHipError otherwise)
+    if occ_logits.dim() != 2:
+        raise ValueError(f"expected occupancy logits of shape (B, M), got {tuple(occ_logits.shape)}")
+    B, M = occ_logits.shape
+    if tuple(occ_target.shape) != (B, M):                    # (the kernels index the targets by this shape)
+        raise ValueError(f"geo_loss: target `occ` has shape {tuple(occ_target.shape)}, expected {(B, M)}")
+    if B == 0:                                              # F.binary_cross_entropy(...).mean(-1).mean() of an empty batch
+        nan = occ_logits.new_full((), float("nan")) + 0.0 * occ_logits.sum()
+        return nan, {"loss": nan.detach()}
+    if M == 0:
+        raise ValueError("geo_loss: the loss of a scene is a mean over its occupancy points; got M = 0")
+    acc = None
+    if metrics is not None:
+        acc = metrics.acc
+        if _capi.device_of(acc) != occ_logits.device or acc.dtype != torch.int64 or acc.numel() * 8 != _capi.TRAIN_METRICS_BYTES:
+            raise ValueError("geo_loss: `metrics` is a TrainMetrics on the device of the logits")
+    loss = _GeoLoss.apply(acc, occ_logits, occ_target)
+    return loss, {"loss": loss.detach()}

@@ -588,6 +588,34 @@ int giga_train_loss_metrics(const float* qual, const float* rot, const float* wi
                             const float* rot_targets, const float* width_target, const float* occ_target, int B, int M,
                             float* losses, float* scene_losses, void* acc, void* stream);
 
+/* ---- the occupancy-only objective of the model giga_geo, scripts/train_giga_geo.py:152-165, and its epoch metrics (:52-57) -----
+ * occ_logits [B][M] (raw; the sigmoid of `select` is part of these functions), occ_target [B][M].
+ *   giga_train_occ_loss          : scene_losses [B] = mean_M BCE(sigmoid(z), t); loss [1] = their mean over the scenes.  The
+ *                                  arithmetic is the occupancy term's of giga_train_loss: for the same logits and targets `loss`
+ *                                  equals its losses[3] bit for bit.
+ *   giga_train_occ_loss_backward : docc [B][M] = d loss / d occ_logits scaled by the device scalar *grad_loss; equals the docc of
+ *                                  giga_train_loss_backward bit for bit.
+ *   giga_train_occ_loss_metrics  : giga_train_occ_loss (the same bytes in `loss` and `scene_losses`, still two launches) that also
+ *                                  adds the batch to the epoch accumulator `acc` (GIGA_TRAIN_METRICS_BYTES, 8-byte aligned, the
+ *                                  layout above) -- counted in occupancy POINTS, B * M per call, as ignite's binary metrics over
+ *                                  (round(sigmoid(z)), t) count them:
+ *     word  0            batches, + 1
+ *     words 1-6          examples, correct, tp, fp, fn, invalid, in points
+ *     words 8 + 3, 8 + 4 double, both += (double)loss (the occupancy mean and the whole objective)
+ *     words 7, 8-10, 13-15  left as found
+ *   A point's prediction is p > 0.5f on the p = 1 / (1 + expf(-z)) the loss uses (half to even: p == 0.5 rounds to 0).  A point is
+ *   valid when p is not NaN and t is exactly 0 or 1; any other point adds 1 to `invalid` only.  `scene_counts`: scratch of the
+ *   caller, B * 6 32-bit words (per scene: examples, correct, tp, fp, fn, invalid).  One lane updates `acc` with plain loads and
+ *   stores: no atomics, so the accumulator after a sequence of calls on one stream is a pure function of the inputs in call order.
+ * Checks: B < 0 or M < 0, a null pointer, `acc` null or not 8-byte aligned: -1.  B == 0 returns 0 and leaves everything untouched;
+ * M == 0 with B > 0 is -1 (an empty mean). */
+int giga_train_occ_loss(const float* occ_logits, const float* occ_target, int B, int M, float* loss, float* scene_losses,
+                        void* stream);
+int giga_train_occ_loss_metrics(const float* occ_logits, const float* occ_target, int B, int M, float* loss, float* scene_losses,
+                                uint32_t* scene_counts, void* acc, void* stream);
+int giga_train_occ_loss_backward(const float* occ_logits, const float* occ_target, const float* grad_loss, int B, int M, float* docc,
+                                 void* stream);
+
 /* Adam over ONE flat fp32 buffer (the flattened parameters of the module, `net.flatten_parameters()`), in place: the update of
  * torch.optim.Adam (the reference's optimiser, scripts/train_giga.py:49; no amsgrad), formulas and order of torch/optim/adam.py:
  * m = lerp(m, g, 1 - beta1); v = beta2 v + (1 - beta2) g^2; p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps);
