@@ -3,9 +3,14 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "../../include/giga_hip.h"
 #include "giga_layout.h"
 
 namespace giga {
+
+// every per-call flag OR-ed into `precision` of giga_encoder_forward* (include/giga_hip.h); what is left is the precision 0..3
+constexpr int GIGA_ENCODER_FLAGS = GIGA_FOLD_FINAL | GIGA_PERSIST_UNET | GIGA_LAYERWISE_UNET | GIGA_CONV32_UNET | GIGA_CONV16_UNET |
+                                   GIGA_CONVIN_MASK | GIGA_DIRECT_CONV;
 
 struct DecArgs {
     const void* planes;      // [3][B][40][40][32]  (plane, scene, H, W, C)  half or float

@@ -412,14 +412,14 @@ int giga_repack_device(const float* params_dev, const int32_t* map_dev, void* pa
 }
 
 size_t giga_encoder_workspace_bytes(int B, int precision) {
-    precision &= ~(GIGA_FOLD_FINAL | GIGA_PERSIST_UNET | GIGA_LAYERWISE_UNET | GIGA_CONV32_UNET | GIGA_CONV16_UNET | GIGA_CONVIN_MASK | GIGA_DIRECT_CONV);
+    precision &= ~GIGA_ENCODER_FLAGS;
     if (B <= 0) return 0;
     return enc_workspace(B, precision).total;
 }
 
 int giga_encoder_workspace_layout(int B, int precision, size_t* offsets) {
     if (B <= 0 || !offsets) return -1;
-    precision &= ~(GIGA_FOLD_FINAL | GIGA_PERSIST_UNET | GIGA_LAYERWISE_UNET | GIGA_CONV32_UNET | GIGA_CONV16_UNET | GIGA_CONVIN_MASK | GIGA_DIRECT_CONV);
+    precision &= ~GIGA_ENCODER_FLAGS;
     if (precision < 0 || precision > 3) return -5;
     const EncWs w = enc_workspace(B, precision);
     const size_t v[17] = {w.P0, w.A0, w.S0, w.Q0, w.A1, w.S1, w.Q1, w.A2, w.S2, w.U0, w.A3, w.A4, w.U1, w.A5, w.A6,
@@ -435,7 +435,7 @@ int giga_encoder_forward_probe(const float* tsdf, const void* packed, void* plan
     if (B > GIGA_MAX_SCENES) return -7;
     const bool fold = (precision & GIGA_FOLD_FINAL) != 0;     // stop before conv_final (folded decoder images)
     const int persist = precision & (GIGA_PERSIST_UNET | GIGA_LAYERWISE_UNET | GIGA_CONV32_UNET | GIGA_CONV16_UNET | GIGA_CONVIN_MASK | GIGA_DIRECT_CONV);   // U-Net launch form and kernels (see the header)
-    precision &= ~(GIGA_FOLD_FINAL | GIGA_PERSIST_UNET | GIGA_LAYERWISE_UNET | GIGA_CONV32_UNET | GIGA_CONV16_UNET | GIGA_CONVIN_MASK | GIGA_DIRECT_CONV);
+    precision &= ~GIGA_ENCODER_FLAGS;
     if (precision < 0 || precision > 3) return -5;
     // only the fp32 and bf16 encoders store conv_in's ReLU mask: a precision 1 / 2 forward that claims to would leave giga_backward
     // (GIGA_CONVIN_MASK_BWD) reading workspace bytes nobody wrote

@@ -534,33 +534,22 @@ __device__ __forceinline__ ConvArgs c32_image_range(ConvArgs a, int img0, int n)
     return a;
 }
 
-// group q of nq: a contiguous, balanced share of the images (the persistent kernel's rule)
-__device__ __forceinline__ void c32_group_images(int q, int nq, int nimg, int& img0, int& per) {
-    img0 = (q * nimg + nq - 1) / nq;
-    per = ((q + 1) * nimg + nq - 1) / nq - img0;
-}
-
 // one layer as its own launch: nq groups x 8 workgroups (stage probes, A/B runs; the product path is the persistent kernel)
 template <class G, bool RELU>
 __global__ __launch_bounds__(C32_NW * 64) void conv32_kernel(ConvArgs a, int nq) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int q = (int)blockIdx.x / C32_GROUP, member = (int)blockIdx.x % C32_GROUP;
     int img0, per;
-    c32_group_images(q, nq, a.nimg, img0, per);
+    mega_group_images(q, nq, a.nimg, img0, per);
     if (per == 0) return;
     const ConvArgs ar = c32_image_range<G>(a, img0, per);
     c32_fill<G>(ar, smem, member);
     c32_run<G, RELU>(ar, smem, member);
 }
 
-inline int c32_groups(int nimg) {                     // groups of a launch: 8 per slot, up to 4 slots per XCD (as unet_mega_kernel)
-    const int slots = (nimg + 7) / 8 < 4 ? (nimg + 7) / 8 : 4;
-    return 8 * slots;
-}
-
 template <class G, bool RELU>
 inline int launch_conv32(const ConvArgs& a, hipStream_t s) {
-    const int nq = c32_groups(a.nimg);
+    const int nq = mega_groups(a.nimg);
     auto kern = conv32_kernel<G, RELU>;
     giga::dyn_lds_once(reinterpret_cast<const void*>(kern), C32_LDS_TOTAL);
     GIGA_LAUNCH(kern, dim3(nq * C32_GROUP), dim3(C32_NW * 64), C32_LDS_TOTAL, s, a, nq);

@@ -268,33 +268,38 @@ struct C32Pair {
     static GIGA_HD int mid_off(int orow, int x, int v) { return (orow * GB::P + x + 1) * GB::PS + v * GB::ILB; }
 };
 
-// The U-Net on conv32.  X(layer, KIND, C0, C1, COUT, H, W, POOLIN, SPW, SGM f16 / bf16, SGM f16x3, KP f16x3): layer order of
-// giga_layout.h::kConv.  SPW = slices of a wave's register tile; SGM = slice groups among the members of a group, chosen so that
+// The U-Net on conv32.  Rows (X, layer, POOLIN, SPW, SGM f16 / bf16, SGM f16x3, KP f16x3): the tuning columns of layer l, whose shape
+// (kind, channels, H, W) is giga_layout.h::kConv[l] (the row adapter below hands it to X).
+// SPW = slices of a wave's register tile; SGM = slice groups among the members of a group, chosen so that
 // a member's weights (SPM slices x taps x CIN / 16 KiB; twice that in the split mode) leave room for the image in 159 KiB; the
 // two 128-input-channel layers of the split mode (144 KiB for ONE slice) walk their channels in two parts.
 // Layers 2 and 4 read the un-pooled skip tensors and pool them while staging (and write the pooled tensors Q0 / Q1, which the
 // workspace layout of the C ABI exposes).
-#define GIGA_UNET32_LAYERS(X)                            \
-    X(0, CONV3, 32, 0, 32, 40, 40, false, 1, 1, 1, 1)    \
-    X(1, CONV3, 32, 0, 32, 40, 40, false, 1, 1, 1, 1)    \
-    X(2, CONV3, 32, 0, 64, 20, 20, true, 2, 1, 1, 1)     \
-    X(3, CONV3, 64, 0, 64, 20, 20, false, 2, 1, 2, 1)    \
-    X(4, CONV3, 64, 0, 128, 10, 10, true, 2, 2, 4, 1)    \
-    X(5, CONV3, 128, 0, 128, 10, 10, false, 1, 4, 4, 2)  \
-    X(6, UPCONV, 128, 0, 64, 10, 10, false, 2, 1, 2, 1)  \
-    X(7, CONV3, 64, 64, 64, 20, 20, false, 1, 2, 2, 2)   \
-    X(8, CONV3, 64, 0, 64, 20, 20, false, 2, 1, 2, 1)    \
-    X(9, UPCONV, 64, 0, 32, 20, 20, false, 2, 1, 1, 1)   \
-    X(10, CONV3, 32, 32, 32, 40, 40, false, 1, 1, 1, 1)  \
-    X(11, CONV3, 32, 0, 32, 40, 40, false, 1, 1, 1, 1)   \
-    X(12, CONV1, 32, 0, 32, 40, 40, false, 1, 1, 1, 1)
+#define GIGA_UNET32_LAYERS(X)                 \
+    GIGA_UNET32_ROW(X, 0, false, 1, 1, 1, 1)  \
+    GIGA_UNET32_ROW(X, 1, false, 1, 1, 1, 1)  \
+    GIGA_UNET32_ROW(X, 2, true, 2, 1, 1, 1)   \
+    GIGA_UNET32_ROW(X, 3, false, 2, 1, 2, 1)  \
+    GIGA_UNET32_ROW(X, 4, true, 2, 2, 4, 1)   \
+    GIGA_UNET32_ROW(X, 5, false, 1, 4, 4, 2)  \
+    GIGA_UNET32_ROW(X, 6, false, 2, 1, 2, 1)  \
+    GIGA_UNET32_ROW(X, 7, false, 1, 2, 2, 2)  \
+    GIGA_UNET32_ROW(X, 8, false, 2, 1, 2, 1)  \
+    GIGA_UNET32_ROW(X, 9, false, 2, 1, 1, 1)  \
+    GIGA_UNET32_ROW(X, 10, false, 1, 1, 1, 1) \
+    GIGA_UNET32_ROW(X, 11, false, 1, 1, 1, 1) \
+    GIGA_UNET32_ROW(X, 12, false, 1, 1, 1, 1)
+// row adapter: X(l, KIND, C0, C1, COUT, H, W, POOLIN, SPW, SGN, SGS, KPS) gets the shape columns from kConv[l]
+#define GIGA_UNET32_ROW(X, l, POOLIN, SPW, SGN, SGS, KPS) \
+    X(l, kConv[l].kind, kConv[l].cin0, kConv[l].cin1, kConv[l].cout, kConv[l].H, kConv[l].W, POOLIN, SPW, SGN, SGS, KPS)
 template <int MODE, int L> struct U32Layer;
 #define X(l, KIND, C0, C1, COUT, H, W, POOLIN, SPW, SGN, SGS, KPS)                                                \
     template <int MODE> struct U32Layer<MODE, l> {                                                                \
         using G = C32<MODE, KIND, C0, C1, COUT, H, W, POOLIN, SPW, (MODE == C32_SPLIT ? SGS : SGN),               \
                       (MODE == C32_SPLIT ? KPS : 1)>;                                                             \
         static constexpr bool RELU = KIND == CONV3;                                                               \
-    };
+    };                                                                                                            \
+    static_assert(POOLIN == (l > 0 && kConv[l > 0 ? l - 1 : 0].pool), "POOLIN rows = the layers whose producer has `pool` set (2 and 4)");
 GIGA_UNET32_LAYERS(X)
 #undef X
 

@@ -428,11 +428,15 @@ EncWs enc_workspace(int B, int precision) {
     EncWs w{};
     size_t at = 0;
     auto take = [&](size_t elems, size_t esz) { size_t o = at; at += align_up(elems * esz, 256); return o; };
-    w.P0 = take(n * 1600 * 32, es); w.A0 = take(n * 1600 * 32, es); w.S0 = take(n * 1600 * 32, es);
-    w.Q0 = take(n * 400 * 32, es);  w.A1 = take(n * 400 * 64, es);  w.S1 = take(n * 400 * 64, es);
-    w.Q1 = take(n * 100 * 64, es);  w.A2 = take(n * 100 * 128, es); w.S2 = take(n * 100 * 128, es);
-    w.U0 = take(n * 400 * 64, es);  w.A3 = take(n * 400 * 64, es);  w.A4 = take(n * 400 * 64, es);
-    w.U1 = take(n * 1600 * 32, es); w.A5 = take(n * 1600 * 32, es); w.A6 = take(n * 1600 * 32, es);
+    auto in = [&](int l) { return take(n * conv_in_elems(l), es); };        // layer l's input, output, pooled output (kConv)
+    auto out = [&](int l) { return take(n * conv_out_elems(l), es); };
+    auto pool = [&](int l) { return take(n * conv_pool_elems(l), es); };
+    w.P0 = in(0);   w.A0 = out(0);  w.S0 = out(1);
+    w.Q0 = pool(1); w.A1 = out(2);  w.S1 = out(3);
+    w.Q1 = pool(3); w.A2 = out(4);  w.S2 = out(5);
+    w.U0 = out(6);  w.A3 = out(7);  w.A4 = out(8);
+    w.U1 = out(9);  w.A5 = out(10); w.A6 = out(11);
+    // conv_in's partials and its mask are not U-Net tensors: their sizes are conv_in's (40^2 pixels x 32 channels per scene, not per image)
     w.YZ = take((size_t)(4 + enc_nxp(B)) * B * 1600 * 32, 4);   // 4 xz partials (iy-groups) + NXP yz partials (x-parts)
     w.XZ = w.YZ;
     w.SYNC = take(MEGA_SYNC_WORDS * 4, 4); // barrier counters of the persistent U-Net kernel (8 per-XCD + 32 per-group, 128 B apart)
@@ -446,31 +450,31 @@ EncWs enc_workspace(int B, int precision) {
 // Persistent U-Net kernel: all 12 (13) layers of UNet.forward (encoder/unet.py:225-239) in ONE launch.
 //   At 32 scenes a U-Net layer is 10-55 us of which ~7 us is per-launch floor (dispatch gap, the weight fill into LDS, the
 //   first patch round trip, the tail) -- 13 launches, i.e. ~90 us of a 200-420 us encoder that no per-layer tuning removes.
-//   EXPERIMENT, NOT THE PRODUCT PATH: measured 573 vs 423 us (fp32, 32 scenes) -- see the profile note.  The idea:
-//   one workgroup per CU stays resident and walks the layers; between two layers there is a device-wide barrier (an
-//   agent-scope release -> atomic counter -> acquire, so that the other XCDs' L2 see the layer's output), and the NEXT
-//   layer's weight group is already streaming into LDS (LDS-DMA) while the workgroup waits at that barrier.
-//   The layer bodies are the conv16 stages (giga_conv16.h), unchanged: same arithmetic, same results as per-layer launches.
-//   Co-residency of the 256 workgroups is what the barrier needs; the spin is bounded (no hang if another kernel holds CUs:
-//   the flag word behind the counter is set and the host falls back to per-layer launches).
+//   This is the DEFAULT form of the U-Net (every batch size in the f16-class modes, from 8 scenes up in fp32 / bf16; see
+//   encoder_run): workgroups stay resident and walk the layers, grouped by eight inside one XCD; between two layers there is
+//   a barrier among the eight workgroups of a group only, and the NEXT layer's weight group is already streaming into LDS
+//   (LDS-DMA) while the workgroup waits at that barrier.
+//   The layer bodies are the conv16 stages (giga_conv16.h) and, in exact fp32, the Winograd stages (giga_wino.h), unchanged:
+//   same arithmetic, same results as per-layer launches.  The barrier needs the eight workgroups of a group co-resident, not
+//   the whole launch; its spin is bounded by wall clock and traps (fails the launch loudly) instead of hanging the device.
 // ====================================================================================================
-// X(layer, KIND, C0, C1, COUT, H, W, NB, POOL, NB16): NB = 16-channel output blocks per unit for 4-byte operands (fp32, split:
+// Rows (X, layer, NB, NB16): the tuning columns of layer l, whose shape (kind, channels, H, W, pool) is giga_layout.h::kConv[l].
+// NB = 16-channel output blocks per unit for 4-byte operands (fp32, split:
 // the resident weights of NB blocks must fit LDS next to the patches); NB16 = the same for native f16 activations, whose
 // weights are half the size -- more blocks per unit = more MFMAs per A-operand read (the f16 layers are LDS-read-bound)
-#define GIGA_UNET_LAYERS(X)                              \
-    X(0, CONV3, 32, 0, 32, 40, 40, 2, false, 2)          \
-    X(1, CONV3, 32, 0, 32, 40, 40, 2, true, 2)           \
-    X(2, CONV3, 32, 0, 64, 20, 20, 1, false, 4)          \
-    X(3, CONV3, 64, 0, 64, 20, 20, 1, true, 4)           \
-    X(4, CONV3, 64, 0, 128, 10, 10, 1, false, 4)         \
-    X(5, CONV3, 128, 0, 128, 10, 10, 1, false, 2)        \
-    X(6, UPCONV, 128, 0, 64, 10, 10, 2, false, 2)        \
-    X(7, CONV3, 64, 64, 64, 20, 20, 1, false, 2)         \
-    X(8, CONV3, 64, 0, 64, 20, 20, 1, false, 4)          \
-    X(9, UPCONV, 64, 0, 32, 20, 20, 2, false, 2)         \
-    X(10, CONV3, 32, 32, 32, 40, 40, 2, false, 2)        \
-    X(11, CONV3, 32, 0, 32, 40, 40, 2, false, 2)         \
-    X(12, CONV1, 32, 0, 32, 40, 40, 2, false, 2)
+#define GIGA_UNET_LAYERS(X) \
+    GIGA_UNET_ROW(X, 0, 2, 2) GIGA_UNET_ROW(X, 1, 2, 2) GIGA_UNET_ROW(X, 2, 1, 4) GIGA_UNET_ROW(X, 3, 1, 4) GIGA_UNET_ROW(X, 4, 1, 4) GIGA_UNET_ROW(X, 5, 1, 2) GIGA_UNET_ROW(X, 6, 2, 2) \
+    GIGA_UNET_ROW(X, 7, 1, 2) GIGA_UNET_ROW(X, 8, 1, 4) GIGA_UNET_ROW(X, 9, 2, 2) GIGA_UNET_ROW(X, 10, 2, 2) GIGA_UNET_ROW(X, 11, 2, 2) GIGA_UNET_ROW(X, 12, 2, 2)
+// row adapter: X(l, KIND, C0, C1, COUT, H, W, NB, POOL, NB16) gets the shape columns from kConv[l]
+#define GIGA_UNET_ROW(X, l, NB, NB16) \
+    X(l, kConv[l].kind, kConv[l].cin0, kConv[l].cin1, kConv[l].cout, kConv[l].H, kConv[l].W, NB, kConv[l].pool, NB16)
+// the range guards of launch_wino (giga_wino.h) hold for every 3x3 layer at the largest call the C ABI admits, with dense strides:
+// the persistent kernel calls wino_run directly (encoder_run passes cs = 0), so launch_wino's run-time check never sees it
+#define X(l, KIND, C0, C1, COUT, H, W, NB, POOL, NB16) \
+    static_assert(KIND != CONV3 || wino_range_ok(C0, C1, COUT, H, W, 3 * GIGA_MAX_SCENES, 0, 0), \
+                  "wino_run's 32-bit offsets / 2 GiB sentinel at 3 * GIGA_MAX_SCENES images");
+GIGA_UNET_LAYERS(X)
+#undef X
 
 // ----------------------------------------------------------------------------------------------------
 // The U-Net as ONE persistent launch, synchronised per GROUP of 8 workgroups inside one XCD.
@@ -498,8 +502,6 @@ struct MegaArgs {
     int nlayers;               // 12 (conv_final folded into the decoder) or 13
     unsigned wino_mask;        // bit l: layer l (a 3x3 layer of the exact-fp32 path) runs as Winograd F(2x2, 3x3) (giga_wino.h)
 };
-constexpr int MEGA_GROUP = 8;                     // workgroups per group
-constexpr int MEGA_SLOTS = 4;                     // group slots per XCD at most: 8 x 4 x 8 = 256 workgroups, one per CU
 constexpr int MEGA_GROUP_MAX_IMG = 32;            // default form of the f16-class modes up to 32 images (one image per group)
 constexpr int MEGA_NW = CONV_NW;                  // waves per workgroup of the persistent kernel
 // A barrier wait is bounded by WALL CLOCK (s_memrealtime, 100 MHz): 20 s.  A group's partners can be late for honest reasons -- a long
@@ -522,14 +524,15 @@ constexpr size_t mega_lds_bytes() {
 #ifdef GIGA_TRACE
 static __device__ long long g_mega_trace[8][32];          // [workgroup 0..7][2 * layer: arrival, release]
 #endif
-__device__ __forceinline__ void xcd_barrier(unsigned* counter, unsigned target, int idx, int trace_row) {
-#ifdef GIGA_TRACE
-    if (threadIdx.x == 0 && trace_row >= 0 && trace_row < 8 && idx < 16) g_mega_trace[trace_row][2 * idx] = __builtin_amdgcn_s_memtime();
-#endif
-    // (ONE poller per workgroup.  Letting every wave poll for itself -- so that each requests its next patch the moment it sees the
-    //  release -- measured no gain for groups of 8 workgroups and made a barrier among 32 workgroups slower: 384 pollers on one L2 line.)
+// The barrier of a group in two halves: arrive (after the workgroup's stores are acknowledged), then -- after the caller has put its next
+// weight fill in flight -- wait.  What sits between the two does not delay the other members of the group.
+__device__ __forceinline__ void xcd_arrive(unsigned* counter) {
+    if (threadIdx.x == 0) __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);     // performed in this XCD's L2
+}
+// (ONE poller per workgroup.  Letting every wave poll for itself -- so that each requests its next patch the moment it sees the
+//  release -- measured no gain for groups of 8 workgroups and made a barrier among 32 workgroups slower: 384 pollers on one L2 line.)
+__device__ __forceinline__ void xcd_wait(unsigned* counter, unsigned target) {
     if (threadIdx.x == 0) {
-        __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);     // performed in this XCD's L2
         unsigned spins = 0;
         unsigned long long t0 = 0;                             // (the clock is read every 1024 polls only: the read itself is slow)
         while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {   // an L2 read
@@ -542,30 +545,17 @@ __device__ __forceinline__ void xcd_barrier(unsigned* counter, unsigned target, 
         }
     }
     __syncthreads();
+}
+// both halves at once (diagnostic builds stamp the arrival and the release of workgroup `trace_row` of the group that holds image 0)
+__device__ __forceinline__ void xcd_barrier(unsigned* counter, unsigned target, int idx, int trace_row) {
+#ifdef GIGA_TRACE
+    if (threadIdx.x == 0 && trace_row >= 0 && trace_row < 8 && idx < 16) g_mega_trace[trace_row][2 * idx] = __builtin_amdgcn_s_memtime();
+#endif
+    xcd_arrive(counter);
+    xcd_wait(counter, target);
 #ifdef GIGA_TRACE
     if (threadIdx.x == 0 && trace_row >= 0 && trace_row < 8 && idx < 16) g_mega_trace[trace_row][2 * idx + 1] = __builtin_amdgcn_s_memtime();
 #endif
-}
-
-// the same barrier in two halves: arrive (after the workgroup's stores are acknowledged), then -- after the caller has put its next
-// weight fill in flight -- wait.  What sits between the two does not delay the other members of the group.
-__device__ __forceinline__ void xcd_arrive(unsigned* counter) {
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);     // performed in this XCD's L2
-}
-__device__ __forceinline__ void xcd_wait(unsigned* counter, unsigned target) {
-    if (threadIdx.x == 0) {
-        unsigned spins = 0;
-        unsigned long long t0 = 0;
-        while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {   // an L2 read
-            __builtin_amdgcn_s_sleep(1);
-            if ((++spins & 1023u) == 0) {
-                const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-                if (t0 == 0) t0 = now;
-                else if (now - t0 > MEGA_SPIN_TICKS) __builtin_trap();               // fail loudly, never hang the device
-            }
-        }
-    }
-    __syncthreads();
 }
 
 // the image range [img0, img0 + n) of one layer's operands
@@ -585,41 +575,50 @@ __device__ __forceinline__ ConvArgs conv_image_range(ConvArgs a, int img0, int n
     return a;
 }
 
+// A workgroup finds its place by TICKET, not by blockIdx: it reads the XCD it runs on from the hardware (XCC_ID) and draws a
+// number from that XCD's ticket counter; ticket t is member t % 8 of group slot t / 8 on that XCD.
+//   * The barriers are XCD-local (workgroup-scope atomics, no agent-scope release / acquire), i.e. only correct if the
+//     workgroups that share a counter share an L2 -- true by construction here, whatever order the dispatcher uses.  (Rounds
+//     2-3a assumed "workgroup i runs on XCD i % 8" and checked it; the dispatcher's round-robin pointer carries over from the
+//     previous launch, so even that map is rotated after a grid that is not a multiple of 8.)  What is still assumed is that
+//     every XCD receives gridDim / 8 workgroups: a group that never fills traps after a few seconds instead of returning stale data.
+//   * The members of a group are the first eight workgroups of the launch that became RESIDENT on their XCD, so a launch has
+//     at most one unfilled group per XCD, and filled groups depend on nobody: several of these launches in flight at once
+//     (other streams, other processes) cannot hold each other's CUs in a cycle -- which is what made the blockIdx-based form
+//     an opt-in with a one-stream contract.
+// Defines xcd, ticket, q, img0, per (the group's images), block (the place inside the group) and counter (the group's arrival counter),
+// and returns from the kernel -- before any barrier -- when the workgroup has no images.  (A macro: as an inlined function, by reference
+// or by value, the same lines made the compiler read s_place in two pieces or select instead of branch, and the register allocation of
+// every instantiation of both kernels moved with it; profiles/refactor/unet_table_check.txt.)
+#define MEGA_PLACE(m)                                                                                                          \
+    __shared__ unsigned s_place[2];                                                                                            \
+    if (threadIdx.x == 0) {                                                                                                    \
+        const unsigned xcc = (unsigned)(__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 7);     /* HW_REG_XCC_ID[3:0] */ \
+        s_place[0] = xcc;                                                                                                      \
+        s_place[1] = __hip_atomic_fetch_add((m).sync + xcc * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   /* performed in this XCD's L2 */ \
+    }                                                                                                                          \
+    __syncthreads();                                                                                                           \
+    const int xcd = (int)s_place[0], ticket = (int)s_place[1];                                                                 \
+    const int nq = (int)gridDim.x >> 3, slot = ticket / MEGA_GROUP, q = slot * 8 + xcd, nimg = (m).layer[0].nimg;   /* nq = 8 * slots = #groups */ \
+    if (slot >= nq >> 3) return;                                            /* (an XCD that was handed more than its share) */ \
+    int img0, per;                                                                                                             \
+    mega_group_images(q, nq, nimg, img0, per);                                                                                 \
+    if (per == 0) return;                                                                                                      \
+    const int block = ticket - slot * MEGA_GROUP;                                                                              \
+    unsigned* counter = (m).sync + (8 + q) * 32;
+
 // WINO (exact fp32 only): the instantiation whose 3x3 layers may run as Winograd stages (giga_wino.h).  It launches WINO_NW = 8 waves
 // per workgroup -- those stages hold 64 accumulators + a transformed half-chunk + a prefetched chunk per lane, ~230 registers, which
 // three waves per SIMD (168) cannot -- and its direct stages (ConvTranspose, 1x1, unselected 3x3 layers) walk their units with 8 waves.
 template <typename T, int MATH, bool WINO = false>
 __global__ __launch_bounds__((WINO ? WINO_NW : MEGA_NW) * 64) void unet_mega_kernel(MegaArgs m) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    // A workgroup finds its place by TICKET, not by blockIdx: it reads the XCD it runs on from the hardware (XCC_ID) and draws a
-    // number from that XCD's ticket counter; ticket t is member t % 8 of group slot t / 8 on that XCD.
-    //   * The barriers are XCD-local (workgroup-scope atomics, no agent-scope release / acquire), i.e. only correct if the
-    //     workgroups that share a counter share an L2 -- true by construction here, whatever order the dispatcher uses.  (Rounds
-    //     2-3a assumed "workgroup i runs on XCD i % 8" and checked it; the dispatcher's round-robin pointer carries over from the
-    //     previous launch, so even that map is rotated after a grid that is not a multiple of 8.)  What is still assumed is that
-    //     every XCD receives gridDim / 8 workgroups: a group that never fills traps after a few seconds instead of returning stale data.
-    //   * The members of a group are the first eight workgroups of the launch that became RESIDENT on their XCD, so a launch has
-    //     at most one unfilled group per XCD, and filled groups depend on nobody: several of these launches in flight at once
-    //     (other streams, other processes) cannot hold each other's CUs in a cycle -- which is what made the blockIdx-based form
-    //     an opt-in with a one-stream contract.
-    __shared__ unsigned s_place[2];
-    if (threadIdx.x == 0) {
-        const unsigned xcc = (unsigned)(__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 7);     // HW_REG_XCC_ID[3:0]
-        s_place[0] = xcc;
-        s_place[1] = __hip_atomic_fetch_add(m.sync + xcc * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // performed in this XCD's L2
-    }
-    __syncthreads();
-    const int xcd = (int)s_place[0], ticket = (int)s_place[1];
-    const int nq = (int)gridDim.x >> 3, slot = ticket / MEGA_GROUP, q = slot * 8 + xcd, nimg = m.layer[0].nimg;   // nq = 8 * slots = #groups
-    if (slot >= nq >> 3) return;                                            // (an XCD that was handed more than its share)
-    const int img0 = (q * nimg + nq - 1) / nq, per = ((q + 1) * nimg + nq - 1) / nq - img0;   // group q of nq: a contiguous, balanced share of the images (group 0 is never empty)
-    if (per == 0) return;                                                   // (before any barrier)
-    const int block = ticket - slot * MEGA_GROUP, nblocks = MEGA_GROUP;     // this workgroup's place inside its group
-    unsigned* counter = m.sync + (8 + q) * 32;
+    MEGA_PLACE(m)
+    const int nblocks = MEGA_GROUP;
     unsigned epoch = 0;
     // a 3x3 layer whose bit is set in m.wino_mask runs as Winograd F(2x2, 3x3) (WINO instantiation only: exact fp32), in CIN / 64 K-passes
     auto is_wino = [&](auto kind_tag, int l) { return WINO && decltype(kind_tag)::value == CONV3 && (m.wino_mask >> l & 1u); };
-#define X(l, KIND, C0, C1, COUT, H, W, NB, POOL, NB16)                                                                     \
+#define RUN(l, KIND, C0, C1, COUT, H, W, NB, POOL, NB16)                                                                   \
     if (l < m.nlayers) {                                                                                                   \
         const ConvArgs a = conv_image_range<T, KIND, C0, C1, COUT, H, W>(m.layer[l], img0, per);                           \
         bool direct = true;                                                                                                \
@@ -662,33 +661,11 @@ __global__ __launch_bounds__((WINO ? WINO_NW : MEGA_NW) * 64) void unet_mega_ker
         if (direct) conv16_fill<T, KIND, C0, C1, COUT, (sizeof(T) == 2 ? NB16 : NB), MATH>(m.layer[l], smem, block, nblocks);       \
         xcd_barrier(counter, ++epoch * (unsigned)nblocks, l, img0 == 0 ? block : -1);                                                                 \
     }
-    X(0, CONV3, 32, 0, 32, 40, 40, 2, false, 2)
-    NEXT(1, CONV3, 32, 0, 32, 40, 40, 2, true, 2)
-    X(1, CONV3, 32, 0, 32, 40, 40, 2, true, 2)
-    NEXT(2, CONV3, 32, 0, 64, 20, 20, 1, false, 4)
-    X(2, CONV3, 32, 0, 64, 20, 20, 1, false, 4)
-    NEXT(3, CONV3, 64, 0, 64, 20, 20, 1, true, 4)
-    X(3, CONV3, 64, 0, 64, 20, 20, 1, true, 4)
-    NEXT(4, CONV3, 64, 0, 128, 10, 10, 1, false, 4)
-    X(4, CONV3, 64, 0, 128, 10, 10, 1, false, 4)
-    NEXT(5, CONV3, 128, 0, 128, 10, 10, 1, false, 2)
-    X(5, CONV3, 128, 0, 128, 10, 10, 1, false, 2)
-    NEXT(6, UPCONV, 128, 0, 64, 10, 10, 2, false, 2)
-    X(6, UPCONV, 128, 0, 64, 10, 10, 2, false, 2)
-    NEXT(7, CONV3, 64, 64, 64, 20, 20, 1, false, 2)
-    X(7, CONV3, 64, 64, 64, 20, 20, 1, false, 2)
-    NEXT(8, CONV3, 64, 0, 64, 20, 20, 1, false, 4)
-    X(8, CONV3, 64, 0, 64, 20, 20, 1, false, 4)
-    NEXT(9, UPCONV, 64, 0, 32, 20, 20, 2, false, 2)
-    X(9, UPCONV, 64, 0, 32, 20, 20, 2, false, 2)
-    NEXT(10, CONV3, 32, 32, 32, 40, 40, 2, false, 2)
-    X(10, CONV3, 32, 32, 32, 40, 40, 2, false, 2)
-    NEXT(11, CONV3, 32, 0, 32, 40, 40, 2, false, 2)
-    X(11, CONV3, 32, 0, 32, 40, 40, 2, false, 2)
-    NEXT(12, CONV1, 32, 0, 32, 40, 40, 2, false, 2)
-    X(12, CONV1, 32, 0, 32, 40, 40, 2, false, 2)
-#undef NEXT
+#define X(l, ...) if constexpr (l > 0) { NEXT(l, __VA_ARGS__) } RUN(l, __VA_ARGS__)
+    GIGA_UNET_LAYERS(X)
 #undef X
+#undef NEXT
+#undef RUN
 }
 
 // ----------------------------------------------------------------------------------------------------
@@ -700,22 +677,7 @@ __global__ __launch_bounds__((WINO ? WINO_NW : MEGA_NW) * 64) void unet_mega_ker
 template <int MODE, bool FUSE>
 __global__ __launch_bounds__(C32_NW * 64) void unet32_mega_kernel(MegaArgs m) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    // placement by ticket: see unet_mega_kernel
-    __shared__ unsigned s_place[2];
-    if (threadIdx.x == 0) {
-        const unsigned xcc = (unsigned)(__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 7);     // HW_REG_XCC_ID[3:0]
-        s_place[0] = xcc;
-        s_place[1] = __hip_atomic_fetch_add(m.sync + xcc * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    __syncthreads();
-    const int xcd = (int)s_place[0], ticket = (int)s_place[1];
-    const int nq = (int)gridDim.x >> 3, slot = ticket / MEGA_GROUP, q = slot * 8 + xcd, nimg = m.layer[0].nimg;
-    if (slot >= nq >> 3) return;
-    int img0, per;
-    c32_group_images(q, nq, nimg, img0, per);
-    if (per == 0) return;                                                   // (before any barrier)
-    const int block = ticket - slot * MEGA_GROUP;                           // this workgroup's place inside its group
-    unsigned* counter = m.sync + (8 + q) * 32;
+    MEGA_PLACE(m)
     unsigned epoch = 0;
     // FIRST(l): request the weights of layer l, no barrier.  NEXT(l): arrive at the group barrier, request layer l's weights
     // (LDS-DMA: they land while the barrier is waited for), then wait.  RUN(l): stage / MFMA / store; then every wave's stores
@@ -988,13 +950,13 @@ static int encoder_run(const float* tsdf, const uint8_t* blob, void* planes_nhwc
                 for (int l = 0; l < NCONV; ++l) m.layer[l] = M[l];
                 m.sync = reinterpret_cast<unsigned*>(b + w.SYNC);
                 m.nlayers = nlayers;
-                const unsigned grid = (unsigned)c32_groups(nimg) * MEGA_GROUP;
+                const unsigned grid = (unsigned)mega_groups(nimg) * MEGA_GROUP;
                 // fused same-resolution pairs (C32Pair) while a member's rows fit ONE sub-band of the pair (up to two images per
                 // group: the halo rows a member recomputes are 2 of ~12; beyond that the pair needs smaller sub-bands than the
                 // single layers and measured slower, profiles/r04/conv32_fused_pairs.txt).  Bit-identical either way;
                 // GIGA_C32_FUSE=0 / 1 forces one form (A/B runs).
                 static const int env_fuse = [] { const char* e = getenv("GIGA_C32_FUSE"); return e ? atoi(e) : -1; }();
-                const int groups = c32_groups(nimg);
+                const int groups = mega_groups(nimg);
                 const bool fuse = env_fuse >= 0 ? env_fuse != 0 : (nimg + groups - 1) / groups <= 2;
                 stage_no = 15;
                 pre();
@@ -1026,8 +988,7 @@ static int encoder_run(const float* tsdf, const uint8_t* blob, void* planes_nhwc
         m.sync = reinterpret_cast<unsigned*>(b + w.SYNC);
         m.nlayers = nlayers;
         m.wino_mask = wino_mask;
-        const int slots = (nimg + 7) / 8 < MEGA_SLOTS ? (nimg + 7) / 8 : MEGA_SLOTS;
-        const unsigned grid = 8u * (unsigned)slots * MEGA_GROUP;
+        const unsigned grid = (unsigned)mega_groups(nimg) * MEGA_GROUP;
         stage_no = 15;                                        // probe stage 15 = the whole U-Net
         auto go = [&](auto kern, const size_t lds, const int nw) {
             giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)lds);
@@ -1074,7 +1035,7 @@ int launch_encoder(const float* tsdf, const uint8_t* blob, void* planes_nhwc, fl
     Probe pr{ev0 && ev1 ? probe_stage : -1, static_cast<hipEvent_t>(ev0), static_cast<hipEvent_t>(ev1)};
     const bool fold = (precision & GIGA_FOLD_FINAL) != 0;
     const int persist = (precision & GIGA_LAYERWISE_UNET) ? -1 : (precision & GIGA_PERSIST_UNET) ? 1 : 0;   // -1 per-layer launches, 0 auto, 1 persistent
-    const int prec = precision & ~(GIGA_FOLD_FINAL | GIGA_PERSIST_UNET | GIGA_LAYERWISE_UNET | GIGA_CONV32_UNET | GIGA_CONV16_UNET | GIGA_CONVIN_MASK | GIGA_DIRECT_CONV);
+    const int prec = precision & ~GIGA_ENCODER_FLAGS;
     const int c32 = (precision & GIGA_CONV32_UNET) ? 1 : (precision & GIGA_CONV16_UNET) ? -1 : 0;      // 1 conv32, -1 conv16, 0 default
     const bool km = (precision & GIGA_CONVIN_MASK) != 0;      // training forward (precisions 0 and 3): keep conv_in's ReLU mask for the backward
     // Winograd F(2x2, 3x3) for the 3x3 layers of precision 0 (giga_wino.h): on unless the call says GIGA_DIRECT_CONV (a blob rebuilt on

@@ -502,11 +502,13 @@ BwdWs enc_bwd_workspace(int B) {
     BwdWs w{};
     size_t at = 0;
     auto take = [&](size_t elems) { size_t o = at; at += align_up(elems * 4, 256); return o; };
-    w.gA6 = take(n * 1600 * 32); w.gA5 = take(n * 1600 * 32); w.gC1 = take(n * 1600 * 64);
-    w.gA4 = take(n * 400 * 64);  w.gA3 = take(n * 400 * 64);  w.gC0 = take(n * 400 * 128);
-    w.gS2 = take(n * 100 * 128); w.gA2 = take(n * 100 * 128); w.gQ1 = take(n * 100 * 64);
-    w.gS1 = take(n * 400 * 64);  w.gA1 = take(n * 400 * 64);  w.gQ0 = take(n * 400 * 32);
-    w.gS0 = take(n * 1600 * 32); w.gA0 = take(n * 1600 * 32); w.gP0 = take(n * 1600 * 32);
+    auto gin = [&](int l) { return take(n * conv_in_elems(l)); };           // gradient of layer l's (concatenated) input / of its output
+    auto gout = [&](int l) { return take(n * conv_out_elems(l)); };
+    w.gA6 = gin(12); w.gA5 = gin(11); w.gC1 = gin(10);
+    w.gA4 = gin(9);  w.gA3 = gin(8);  w.gC0 = gin(7);
+    w.gS2 = gin(6);  w.gA2 = gin(5);  w.gQ1 = gin(4);
+    w.gS1 = gout(3); w.gA1 = gin(3);  w.gQ0 = gin(2);
+    w.gS0 = gout(1); w.gA0 = gin(1);  w.gP0 = gin(0);
     w.WG = take((size_t)WG3_MAX_PARTS * 32 * 288 + WG3_BIAS_FLOATS);      // per-workgroup weight-gradient partials (conv_wgrad_kernel; giga_wgrad3.h with one reduce per layer)
     // one region per 3x3 layer for the single reduce launch at the end (wgrad3_reduce_all_kernel): 256 x min(blocks, 8) partial
     // images of 36 KiB + the bias partials; 368 MB in all, whatever the batch size
@@ -527,6 +529,10 @@ int enc_nxp(int B);
 // MATH: arithmetic of the thirteen data-gradient convolutions (MATH_NATIVE fp32 MFMA, or MATH_BF16: bf16 operands from the
 // backward blob's bf16 images, fp32 accumulate and fp32 gradients in memory); everything else is fp32.
 template <int V> using IC = std::integral_constant<int, V>;
+// The two numbers of a layer's backward that are not its shape (giga_layout.h::kConv[l]): NB of its data gradient (16-channel output
+// blocks per unit, giga_conv16.h) and the rows per strip of its 3x3 weight gradient (giga_wgrad3.h; 0: not a 3x3 layer)
+struct BwdTune { int nb, rows; };
+constexpr BwdTune kBwdTune[NCONV] = {{2, 4}, {2, 4}, {2, 4}, {1, 4}, {1, 2}, {1, 2}, {1, 0}, {1, 2}, {1, 4}, {2, 0}, {2, 2}, {2, 4}, {2, 0}};
 template <int MATH>
 static int encoder_backward_impl(const float* tsdf, const uint8_t* blob, const uint8_t* bwd_blob, const uint8_t* fws,
                                  float* gplanes /* [3B][40][40][32], in: dLoss/dPlanes (read only: L12's input and its weight gradient's dY) */, uint8_t* gws,
@@ -550,23 +556,14 @@ static int encoder_backward_impl(const float* tsdf, const uint8_t* blob, const u
     const hipStream_t ws = side.stream();
     auto fork = [&]() { rc |= side.fork(); };
     // weight gradient of layer l: R = dPre (channels = cout), columns = layer input (in0 [, in1])
-    auto wgrad3_now = [&](int l, const float* dpre, const float* in0, const float* in1, int H) {
-        const ConvLayerDesc& d = kConv[l];
-        if (d.kind == CONV3) {
+    auto wgrad3_now = [&](auto lc, const float* dpre, const float* in0, const float* in1) {
+        constexpr int l = decltype(lc)::value;
+        constexpr ConvLayerDesc d = kConv[l];
+        if constexpr (d.kind == CONV3) {
             Wgrad3Args w3{dpre, in0, in1, grads + po.conv_w[l], grads + po.conv_b[l], one_reduce ? G(g.WG3[l]) : G(g.WG), nimg};
             Wg3RedArgs* defer = one_reduce ? &RED : nullptr;
-#define WG3(...) (MATH == MATH_BF16 ? launch_wgrad3_bf16<__VA_ARGS__>(w3, ws, defer) : launch_wgrad3<__VA_ARGS__>(w3, ws, defer))
-            switch (l) {   // <C0, C1, COUT, H, rows per strip>
-                case 0: case 1: case 11: rc |= WG3(32, 0, 32, 40, 4); break;
-                case 10: rc |= WG3(32, 32, 32, 40, 2); break;
-                case 2: rc |= WG3(32, 0, 64, 20, 4); break;
-                case 3: case 8: rc |= WG3(64, 0, 64, 20, 4); break;
-                case 7: rc |= WG3(64, 64, 64, 20, 2); break;
-                case 4: rc |= WG3(64, 0, 128, 10, 2); break;
-                case 5: rc |= WG3(128, 0, 128, 10, 2); break;
-#undef WG3
-                default: rc |= -1;                                  // a 3x3 layer without an instantiation
-            }
+            rc |= MATH == MATH_BF16 ? launch_wgrad3_bf16<d.cin0, d.cin1, d.cout, d.H, kBwdTune[l].rows>(w3, ws, defer)
+                                    : launch_wgrad3<d.cin0, d.cin1, d.cout, d.H, kBwdTune[l].rows>(w3, ws, defer);
         } else {                                                    // CONV1 (the 1x1 layer at the end)
             const int cin = d.cin0 + d.cin1;
             WgradArgs a{};
@@ -574,21 +571,21 @@ static int encoder_backward_impl(const float* tsdf, const uint8_t* blob, const u
             a.C0p = in0; a.C1p = in1; a.csC0 = d.cin0; a.csC1 = d.cin1; a.nC0 = d.cin0;
             a.dW = grads + po.conv_w[l]; a.sM = cin; a.sN = 1; a.sT = 1;
             a.kind = d.kind; a.taps = 1; a.Mb = d.cout / 32; a.Nb = cin / 32;
-            a.nimg = nimg; a.H = H; a.W = H;
+            a.nimg = nimg; a.H = d.H; a.W = d.W;
             a.partial = G(g.WG);
             a.db = grads + po.conv_b[l]; a.nbias = d.cout;          // bias gradient = column sums of dPre, folded into the same two launches
             rc |= launch_wgrad(a, ws);
         }
     };
     // ConvTranspose2d(cin, cout, 2, 2): dW[ci][co][d] = sum In[p][ci] * dU[up(p,d)][co]; dU = channels [0,cout) of dcat
-    auto wgrad_up_now = [&](int l, const float* in, const float* dcat, int cs_cat, int H) {
+    auto wgrad_up_now = [&](int l, const float* in, const float* dcat, int cs_cat) {
         const ConvLayerDesc& d = kConv[l];
         WgradArgs a{};
         a.R = in; a.csR = d.cin0; a.coR = 0;
         a.C0p = dcat; a.C1p = dcat; a.csC0 = cs_cat; a.csC1 = cs_cat; a.nC0 = d.cout;
         a.dW = grads + po.conv_w[l]; a.sM = d.cout * 4; a.sN = 4; a.sT = 1;
         a.kind = UPCONV; a.taps = 4; a.Mb = d.cin0 / 32; a.Nb = d.cout / 32;
-        a.nimg = nimg; a.H = H; a.W = H;
+        a.nimg = nimg; a.H = d.H; a.W = d.W;
         a.partial = G(g.WG);
         a.db = grads + po.conv_b[l]; a.nbias = d.cout;          // bias gradient = column sums of dU over all four taps
         rc |= launch_wgrad(a, ws);
@@ -608,11 +605,11 @@ static int encoder_backward_impl(const float* tsdf, const uint8_t* blob, const u
         pending[npending++] = std::move(f);
         if (npending >= fork_every) flush();
     };
-    auto wgrad3 = [&](int l, const float* dpre, const float* in0, const float* in1, int H) {
-        defer([=, &wgrad3_now]() { wgrad3_now(l, dpre, in0, in1, H); });
+    auto wgrad3 = [&](auto lc, const float* dpre, const float* in0, const float* in1) {
+        defer([=, &wgrad3_now]() { wgrad3_now(lc, dpre, in0, in1); });
     };
-    auto wgrad_up = [&](int l, const float* in, const float* dcat, int cs_cat, int H) {
-        defer([=, &wgrad_up_now]() { wgrad_up_now(l, in, dcat, cs_cat, H); });
+    auto wgrad_up = [&](int l, const float* in, const float* dcat, int cs_cat) {
+        defer([=, &wgrad_up_now]() { wgrad_up_now(l, in, dcat, cs_cat); });
     };
     // data gradient of layer l; relu_of: the forward activation the gradient flows into next (ReLU output of the layer
     // below): its backward mask is applied in the convolution's epilogue instead of by a separate pass over the tensor
@@ -644,64 +641,65 @@ static int encoder_backward_impl(const float* tsdf, const uint8_t* blob, const u
         dgrad_args(2, G(g.gA1), 0, G(g.gQ0)),                  // L2 down1.conv1: Q0 -> A1
         dgrad_args(1, G(g.gS0), 0, G(g.gA0), F(f.A0)),         // L1 down0.conv2: A0 -> S0
         dgrad_args(0, G(g.gA0), 0, G(g.gP0))};                 // L0 down0.conv1: P0 -> A0
-    // stage k of the chain is the data gradient of U-Net layer 12 - k
-    static constexpr int LAYER_OF_STAGE[13] = {12, 11, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1, 0};
     // fp32 step: the data gradients of the 3x3 layers are stride-1 3x3 convolutions too (flipped taps, channels swapped) and run as
     // Winograd F(2x2, 3x3) on the images giga_derive_winograd leaves behind the backward blob's other regions (giga_wino.h; the ReLU
     // mask of the layer below in the epilogue as before).  GIGA_WINOGRAD_BWD=0: the direct conv16 kernels.
     static const int env_wino_bwd = [] { const char* e = getenv("GIGA_WINOGRAD_BWD"); return e ? atoi(e) : 1; }();
     constexpr bool CAN_WINO_BWD = MATH == MATH_NATIVE;
     const bool wino_bwd = CAN_WINO_BWD && env_wino_bwd != 0;
-    auto dgrad3 = [&](auto c0, auto cout, auto hw, auto nb, int k, int layer) {
-        constexpr int C0 = decltype(c0)::value, COUT = decltype(cout)::value, HW = decltype(hw)::value, NB = decltype(nb)::value;
-        if constexpr (CAN_WINO_BWD) {
+    // the data gradient of layer L is stage 12 - L of the chain: a convolution of the layer's kind (ConvTranspose: DOWN) with the channels swapped
+    auto dgrad = [&](auto lc) {
+        constexpr int L = decltype(lc)::value, KIND = kConv[L].kind, C0 = kConv[L].cout, COUT = kConv[L].cin0 + kConv[L].cin1;
+        constexpr int H = kConv[L].H, W = kConv[L].W, NB = kBwdTune[L].nb;
+        const ConvArgs& st = stage[NCONV - 1 - L];
+        if constexpr (CAN_WINO_BWD && KIND == CONV3) {
             if (wino_bwd) {
-                ConvArgs a = stage[k];
-                a.w = bwd_blob + bo.wino[layer];
-                return launch_wino<C0, 0, COUT, HW, HW, false, false>(a, s);
+                ConvArgs a = st;
+                a.w = bwd_blob + bo.wino[L];
+                return launch_wino<C0, 0, COUT, H, W, false, false>(a, s);
             }
         }
-        return launch_conv<float, CONV3, C0, 0, COUT, HW, HW, NB, false, false, MATH>(stage[k], s);
+        return launch_conv<float, KIND == UPCONV ? DOWN : KIND, C0, 0, COUT, H, W, NB, false, false, MATH>(st, s);
     };
     g_last_bwd_path.store((wino_bwd ? GIGA_BWD_PATH_WINOGRAD : 0) | (MATH == MATH_BF16 ? GIGA_BWD_PATH_BF16 : 0), std::memory_order_relaxed);
     // one launch per stage, the weight gradient of a layer right behind the launch that produced its dPre (it is still in the
     // Infinity Cache then)
-    wgrad3(12, gplanes, F(f.A6), nullptr, 40);
-    rc |= launch_conv<float, CONV1, 32, 0, 32, 40, 40, 2, false, false, MATH>(stage[0], s);
-    wgrad3(11, G(g.gA6), F(f.A5), nullptr, 40);
-    rc |= dgrad3(IC<32>{}, IC<32>{}, IC<40>{}, IC<2>{}, 1, LAYER_OF_STAGE[1]);
-    wgrad3(10, G(g.gA5), F(f.U1), F(f.S0), 40);
-    rc |= dgrad3(IC<32>{}, IC<64>{}, IC<40>{}, IC<2>{}, 2, LAYER_OF_STAGE[2]);
-    wgrad_up(9, F(f.A4), G(g.gC1), 64, 20);
-    rc |= launch_conv<float, DOWN, 32, 0, 64, 20, 20, 2, false, false, MATH>(stage[3], s);
-    wgrad3(8, G(g.gA4), F(f.A3), nullptr, 20);
-    rc |= dgrad3(IC<64>{}, IC<64>{}, IC<20>{}, IC<1>{}, 4, LAYER_OF_STAGE[4]);
-    wgrad3(7, G(g.gA3), F(f.U0), F(f.S1), 20);
-    rc |= dgrad3(IC<64>{}, IC<128>{}, IC<20>{}, IC<1>{}, 5, LAYER_OF_STAGE[5]);
-    wgrad_up(6, F(f.S2), G(g.gC0), 128, 10);
-    rc |= launch_conv<float, DOWN, 64, 0, 128, 10, 10, 1, false, false, MATH>(stage[6], s);
-    wgrad3(5, G(g.gS2), F(f.A2), nullptr, 10);
-    rc |= dgrad3(IC<128>{}, IC<128>{}, IC<10>{}, IC<1>{}, 7, LAYER_OF_STAGE[7]);
-    wgrad3(4, G(g.gA2), F(f.Q1), nullptr, 10);
-    rc |= dgrad3(IC<128>{}, IC<64>{}, IC<10>{}, IC<1>{}, 8, LAYER_OF_STAGE[8]);
+    wgrad3(IC<12>{}, gplanes, F(f.A6), nullptr);
+    rc |= dgrad(IC<12>{});
+    wgrad3(IC<11>{}, G(g.gA6), F(f.A5), nullptr);
+    rc |= dgrad(IC<11>{});
+    wgrad3(IC<10>{}, G(g.gA5), F(f.U1), F(f.S0));
+    rc |= dgrad(IC<10>{});
+    wgrad_up(9, F(f.A4), G(g.gC1), 64);
+    rc |= dgrad(IC<9>{});
+    wgrad3(IC<8>{}, G(g.gA4), F(f.A3), nullptr);
+    rc |= dgrad(IC<8>{});
+    wgrad3(IC<7>{}, G(g.gA3), F(f.U0), F(f.S1));
+    rc |= dgrad(IC<7>{});
+    wgrad_up(6, F(f.S2), G(g.gC0), 128);
+    rc |= dgrad(IC<6>{});
+    wgrad3(IC<5>{}, G(g.gS2), F(f.A2), nullptr);
+    rc |= dgrad(IC<5>{});
+    wgrad3(IC<4>{}, G(g.gA2), F(f.Q1), nullptr);
+    rc |= dgrad(IC<4>{});
     {
         const size_t tot = n20 * 64 / 4;
         GIGA_LAUNCH(pool_bwd_add_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, G(g.gS1),
                            G(g.gC0), 128, 64, G(g.gQ1), F(f.S1), F(f.Q1), nimg, 20, 20, 64);
     }
-    wgrad3(3, G(g.gS1), F(f.A1), nullptr, 20);
-    rc |= dgrad3(IC<64>{}, IC<64>{}, IC<20>{}, IC<1>{}, 9, LAYER_OF_STAGE[9]);
-    wgrad3(2, G(g.gA1), F(f.Q0), nullptr, 20);
-    rc |= dgrad3(IC<64>{}, IC<32>{}, IC<20>{}, IC<2>{}, 10, LAYER_OF_STAGE[10]);
+    wgrad3(IC<3>{}, G(g.gS1), F(f.A1), nullptr);
+    rc |= dgrad(IC<3>{});
+    wgrad3(IC<2>{}, G(g.gA1), F(f.Q0), nullptr);
+    rc |= dgrad(IC<2>{});
     {
         const size_t tot = n40 * 32 / 4;
         GIGA_LAUNCH(pool_bwd_add_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, G(g.gS0),
                            G(g.gC1), 64, 32, G(g.gQ0), F(f.S0), F(f.Q0), nimg, 40, 40, 32);
     }
-    wgrad3(1, G(g.gS0), F(f.A0), nullptr, 40);
-    rc |= dgrad3(IC<32>{}, IC<32>{}, IC<40>{}, IC<2>{}, 11, LAYER_OF_STAGE[11]);
-    wgrad3(0, G(g.gA0), F(f.P0), nullptr, 40);
-    rc |= dgrad3(IC<32>{}, IC<32>{}, IC<40>{}, IC<2>{}, 12, LAYER_OF_STAGE[12]);
+    wgrad3(IC<1>{}, G(g.gS0), F(f.A0), nullptr);
+    rc |= dgrad(IC<1>{});
+    wgrad3(IC<0>{}, G(g.gA0), F(f.P0), nullptr);
+    rc |= dgrad(IC<0>{});
     flush();
     rc |= launch_wgrad3_reduce_all(RED, ws);
     // conv_in + projection

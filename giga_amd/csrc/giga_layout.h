@@ -51,6 +51,10 @@ constexpr ConvLayerDesc kConv[NCONV] = {
 };
 // order of the conv layers inside the state dict (down0.c1,c2, down1.., down2.., up0.upconv,c1,c2, up1.., final)
 // is identical to kConv order.
+// elements of ONE image of layer l (the workspace carves): its concatenated input, its output, its pooled output
+constexpr size_t conv_in_elems(int l) { return (size_t)kConv[l].H * kConv[l].W * (kConv[l].cin0 + kConv[l].cin1); }
+constexpr size_t conv_out_elems(int l) { return (size_t)kConv[l].H * kConv[l].W * (kConv[l].kind == UPCONV ? 4 : 1) * kConv[l].cout; }
+constexpr size_t conv_pool_elems(int l) { return (size_t)(kConv[l].H / 2) * (kConv[l].W / 2) * kConv[l].cout; }
 
 struct ParamOff {
     HeadParamOff head[NHEADS];

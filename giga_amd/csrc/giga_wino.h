@@ -479,6 +479,14 @@ inline int launch_up(const ConvArgs& a, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
+// what wino_run's addressing needs of a call (cs = 0: dense C0 / C1): one pixel stride for both sources, sources under 2 GiB (the
+// buffer loads' out-of-range sentinel), 24-bit pixel indices and 32-bit byte offsets
+constexpr bool wino_range_ok(int C0, int C1, int COUT, int H, int W, int nimg, int cs0, int cs1) {
+    const size_t in_pix = (size_t)nimg * H * W, b0 = (size_t)(cs0 ? cs0 : C0) * 4, b1 = (size_t)(cs1 ? cs1 : C1) * 4;
+    return (C1 == 0 || b0 == b1) && in_pix * b0 < (1ull << 31) && in_pix < (1u << 24) && (C1 == 0 || in_pix * b1 < (1ull << 32)) &&
+           in_pix * COUT * 4 < (1ull << 32);
+}
+
 template <int C0, int C1, int COUT, int H, int W, bool POOL, bool RELU = true>
 inline int launch_wino(const ConvArgs& a, hipStream_t s) {
     using G = WinoBlock<H, W>;
@@ -486,11 +494,7 @@ inline int launch_wino(const ConvArgs& a, hipStream_t s) {
     constexpr size_t lds = wino_lds_bytes<C0, C1, H, W>();
     static_assert(lds <= 160 * 1024 && NWV >= 4, "LDS budget");
     static_assert(256 % NGRP == 0, "weight groups must divide the CU count");
-    const size_t in_pix = (size_t)a.nimg * H * W;
-    if (C1 > 0 && (a.cs0 ? a.cs0 : C0) != (a.cs1 ? a.cs1 : C1)) return -7;              // one pixel stride for both sources (wino_run)
-    if (in_pix * (size_t)((a.cs0 ? a.cs0 : C0) * 4) >= (1ull << 31)) return -7;           // the buffer loads' out-of-range sentinel is 2 GiB
-    if (in_pix >= (1u << 24) || in_pix * (size_t)((a.cs0 ? a.cs0 : C0) * 4) >= (1ull << 32) ||
-        (C1 > 0 && in_pix * (size_t)((a.cs1 ? a.cs1 : C1) * 4) >= (1ull << 32)) || in_pix * COUT * 4 >= (1ull << 32)) return -7;
+    if (!wino_range_ok(C0, C1, COUT, H, W, a.nimg, a.cs0, a.cs1)) return -7;
     const int units = a.nimg * G::TXB * G::TYB;
     int wgs = (units + NWV - 1) / NWV;
     if (wgs > 256 / NGRP) wgs = 256 / NGRP;
