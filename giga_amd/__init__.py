@@ -8,6 +8,7 @@
     from giga_amd import GeoTrainer, geo_loss                   # ... and of scripts/train_giga_geo.py: the occupancy-only giga_geo
     from giga_amd import affordance_visual, grasp2mesh          # the scene mesh coloured by grasp quality (giga_amd.visual)
     from giga_amd import GeometryEvaluator, VoxelOccGeoROIDataset   # scene IoU, chamfer, grasp-ROI occupancy (giga_amd.geometry)
+    from giga_amd import mesh_collide, generate_packed_scenes, write_geo_dataset   # packed scenes from object meshes (giga_amd.scenes)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/giga_hip.h."""
 __version__ = "0.1.0"
@@ -24,6 +25,9 @@ _VISUAL_EXPORTS = ("affordance_faces", "affordance_points", "affordance_visual",
 # ... and of giga_amd.geometry: the scoring of predicted geometry (scene IoU, chamfer, grasp-ROI occupancy) and its data sets
 _GEOMETRY_EXPORTS = ("GeometryEvaluator", "VoxelOccGeoDataset", "VoxelOccGeoROIDataset", "occ_confusion", "occ_scores",
                      "roi_point_counts", "load_obj", "default_mesh_loader", "read_mesh_pose_list")
+# ... of giga_amd.collision (do two meshes intersect?) and of giga_amd.scenes (packed scenes and the geometry data set they make)
+_COLLISION_EXPORTS = ("mesh_collide", "mesh_bounds_batch")
+_SCENES_EXPORTS = ("ObjectSet", "packed_candidates", "resolve_packed", "generate_packed_scenes", "table_mesh", "write_geo_dataset")
 
 
 def __getattr__(name):
@@ -42,4 +46,10 @@ def __getattr__(name):
     if name in _GEOMETRY_EXPORTS:
         from . import geometry
         return getattr(geometry, name)
+    if name in _COLLISION_EXPORTS:
+        from . import collision
+        return getattr(collision, name)
+    if name in _SCENES_EXPORTS:
+        from . import scenes
+        return getattr(scenes, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -175,6 +175,9 @@ _SIGNATURES = {
     "giga_mesh_contains_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "giga_mesh_contains": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                                   ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_mesh_collide_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
+    "giga_mesh_collide": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                                 ctypes.c_size_t, ctypes.c_void_p]),
     "giga_roi_points_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "giga_roi_points": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_uint64] + [ctypes.c_double] * 3
                         + [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]),

@@ -122,6 +122,10 @@ size_t contains_workspace_bytes(int B, int n_tri, int n_pts);
 int launch_mesh_contains(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
                          const double* points, const int* point_offsets, int B, int resolution, uint8_t* inside, uint8_t* ws,
                          hipStream_t s);
+// giga_collide.hip
+size_t collide_workspace_bytes(int M, int P);
+int launch_mesh_collide(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets, int M,
+                        const int* pairs, int P, uint8_t* hit, uint8_t* ws, hipStream_t s);
 // giga_geometry.hip
 size_t roi_workspace_bytes(int G);
 int launch_roi_points(const double* grasps, const int* offsets, const int* scene, const int* first, int G, unsigned long long seed,
@@ -1093,6 +1097,28 @@ int giga_mesh_contains(const float* vertices, const int32_t* vertex_offsets, con
     if (workspace_bytes < giga_mesh_contains_workspace_bytes(B, triangle_offsets[B], point_offsets[B])) return -4;
     return launch_mesh_contains(vertices, vertex_offsets, triangles, triangle_offsets, points, point_offsets, B, resolution, inside,
                                 static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+// ---- mesh against mesh (giga_collide.hip) ----
+size_t giga_mesh_collide_workspace_bytes(int M, int P) {
+    if (M <= 0 || M > GIGA_MAX_SCENES || P < 0) return 0;
+    return collide_workspace_bytes(M, P);
+}
+
+int giga_mesh_collide(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                      int M, const int32_t* pairs, int P, uint8_t* hit, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = ragged_batch_check(M)) return rc;
+    if (P < 0) return -1;
+    if (M == 0 || P == 0) return 0;
+    if (!mesh_batch_check(vertex_offsets, triangle_offsets, M, vertices, triangles) || !pairs || !workspace) return -1;
+    for (size_t i = 0; i < (size_t)P; ++i) {
+        const int32_t a = pairs[2 * i], b = pairs[2 * i + 1];
+        if (a < 0 || a >= M || b < 0 || b >= M || a == b) return -1;
+    }
+    if (!hit) return -6;
+    if (workspace_bytes < giga_mesh_collide_workspace_bytes(M, P)) return -4;
+    return launch_mesh_collide(vertices, vertex_offsets, triangles, triangle_offsets, M, pairs, P, hit, static_cast<uint8_t*>(workspace),
+                               static_cast<hipStream_t>(stream));
 }
 
 // ---- geometry scoring (giga_geometry.hip) ----

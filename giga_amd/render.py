@@ -170,10 +170,12 @@ def pose_list(extrinsic):
     return np.r_[Rotation.from_matrix(m[:3, :3]).as_quat(), m[:3, 3]]
 
 
-def write_raw_scenes(raw_root, scene_ids, meshes, n, N=None, size=0.3, batch=32, device=None):
+def write_raw_scenes(raw_root, scene_ids, meshes, n, N=None, size=0.3, batch=32, device=None, extrinsics_dtype=np.float32):
     """The raw files scripts/generate_data_parallel.py leaves for construct_dataset: <raw_root>/setup.json (size and intrinsic;
     other keys of an existing file are kept) and <raw_root>/scenes/<id>.npz with depth_imgs (n, H, W) float32 and extrinsics
-    (n, 7) float32 [qx, qy, qz, qw, x, y, z] (io.write_sensor_data), rendered from the top-view circle, `batch` scenes per launch."""
+    (n, 7) float32 [qx, qy, qz, qw, x, y, z] (io.write_sensor_data), rendered from the top-view circle, `batch` scenes per launch.
+    extrinsics_dtype=np.float64 stores the poses unrounded: the images were rendered from the float64 cameras, and a float32 pose
+    moves the camera `construct_dataset` fuses them with by up to 2e-8, which shows in the last bits of the fused grid."""
     if len(scene_ids) != len(meshes):
         raise ValueError("one scene id per mesh")
     if int(batch) < 1:
@@ -189,7 +191,7 @@ def write_raw_scenes(raw_root, scene_ids, meshes, n, N=None, size=0.3, batch=32,
     with (raw_root / "setup.json").open("w") as f:
         json.dump(setup, f)
     extrinsics = acquire_extrinsics(n, N, size)
-    poses = np.stack([pose_list(e) for e in extrinsics]).astype(np.float32) if n else np.zeros((0, 7), np.float32)
+    poses = np.stack([pose_list(e) for e in extrinsics]).astype(extrinsics_dtype) if n else np.zeros((0, 7), extrinsics_dtype)
     for at in range(0, len(meshes), int(batch)):
         chunk = meshes[at:at + int(batch)]
         depth, offs = render_depth_batch(chunk, intrinsic, [extrinsics] * len(chunk), SIM_NEAR, SIM_FAR, 0.0, device)

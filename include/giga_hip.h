@@ -798,6 +798,39 @@ int giga_mesh_contains(const float* vertices, const int32_t* vertex_offsets, con
                        const double* points, const int32_t* point_offsets, int B, int resolution, uint8_t* inside, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---- mesh against mesh: do two bodies' surfaces intersect? (src/vgn/simulation.py:118-143 needs it; added within ABI 3) -----
+ * M bodies packed back to back in the ragged layout of the mesh-evaluation entries above: vertices [.][3] float32 in world space
+ * and triangles [.][3] int32 counting from the body's OWN first vertex, both on the device; vertex_offsets and triangle_offsets
+ * are HOST arrays of M + 1 int32, read (and copied into the workspace) before the call returns.  pairs is a HOST array
+ * [P][2] int32 of body indices, copied into the workspace before the call returns.  hit [P] uint8 (device) is the output.
+ * Caller-owned buffers, no allocation, asynchronous on `stream`; every argument is checked before the first HIP call.
+ * workspace: giga_mesh_collide_workspace_bytes(M, P) (0 for arguments the call rejects).
+ * Errors: -1 negative count, null input or workspace, offsets that do not start at 0 or decrease, a pair index outside
+ * 0 .. M-1, a pair with a == b; -4 workspace too small; -6 null hit with P > 0; -7 M > GIGA_MAX_SCENES.  M = 0 or P = 0 returns 0.
+ *
+ * All arithmetic is in double with one IEEE rounding per operation and no contraction.
+ *   Orientation.  orient(a, b, c, d) uses u = b - a, v = c - a, w = d - a.  These differences are exact, because the vertices
+ *     are float32.  Its value is (u.x*(v.y*w.z - v.z*w.y) - u.y*(v.x*w.z - v.z*w.x)) + u.z*(v.x*w.y - v.y*w.x), in exactly this
+ *     order.
+ *   Segment against triangle.  Segment (p, q) hits triangle (a, b, c) under these rules, with sp = orient(a,b,c,p) and
+ *     sq = orient(a,b,c,q): it misses when sp and sq are both > 0 or both < 0; it misses when both are exactly 0 (a segment in
+ *     the triangle's plane: coplanar contact is not detected); it misses when either is NaN; otherwise it hits iff
+ *     orient(p,q,a,b), orient(p,q,b,c) and orient(p,q,c,a) are all >= 0 or all <= 0.  Zero counts as touching, which is
+ *     giga_depth_render's watertight rule.
+ *   Triangle against triangle.  Triangles A and B intersect iff one of A's edges (v0,v1), (v1,v2), (v2,v0) hits B, or one of B's
+ *     edges hits A.  A triangle with an index outside its body or a non-finite vertex intersects nothing.
+ *   Pair.  hit[p] = 1 iff some triangle of body a intersects some triangle of body b, else 0.  The rule is symmetric, so
+ *     hit(a,b) == hit(b,a).  There are no floating-point atomics.  Equal input gives equal bytes.  A pair's byte does not depend on
+ *     the other pairs of the call or on their order.  Surface intersection only: a body that lies wholly inside another is not
+ *     detected (giga_mesh_contains on one of its vertices answers that).
+ * Culling, part of the definition: a body's box is the float32 box over the vertices of its triangles that can intersect
+ * anything (exact: min and max do not round).  A pair whose boxes are disjoint (or one of whose bodies has no such triangle) is
+ * 0, and only triangles whose own box meets the intersection of the two bodies' boxes (closed intervals) are tested against each
+ * other.  Triangles that are left out cannot meet the other body's surface; the determinants of such a pair are never taken. */
+size_t giga_mesh_collide_workspace_bytes(int M, int P);
+int giga_mesh_collide(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                      int M, const int32_t* pairs, int P, uint8_t* hit, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- geometry scoring (scripts/eval_geometry_voxel.py, src/vgn/dataset_voxel_occ.py:109-128; added within ABI 3) -----
  * Caller-owned buffers, no allocation, asynchronous on `stream`, every argument checked before the first HIP call, no
  * floating-point atomics: equal input gives equal bytes.  Errors: -1 negative count, null input or workspace, offsets that do not
