@@ -8,6 +8,7 @@ is the one PyTorch already loaded -- device pointers and streams are then shared
 import ctypes
 import os
 
+import numpy as np
 import torch  # noqa: F401  (must precede CDLL: shares torch's libamdhip64)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -284,6 +285,48 @@ def device_of(*tensors):
 
 def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def host_ptr(a):
+    """pointer to the first element of a (contiguous) numpy array; the caller keeps the array alive (cheaper than data_as)"""
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+def hip_device(*xs, device=None, what="giga_amd runs only on a HIP device"):
+    """The HIP device a call works on: `device` when given, else the one the tensors among `xs` live on, else the current one
+    (what is no tensor is ignored).  GigaHipError if that is no HIP device, if a tensor lives elsewhere or on the CPU, or if
+    there is no HIP device at all."""
+    tensors = [x for x in xs if torch.is_tensor(x)]
+    dev = torch.device(device) if device is not None else device_of(*tensors)
+    if dev is None:
+        if not torch.cuda.is_available():
+            raise GigaHipError(what + "; there is no CPU fallback. Use the reference implementation for CPU execution.")
+        return torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise GigaHipError(what + "; there is no CPU fallback")
+    if device is not None and tensors:
+        device_of(*tensors, torch.empty(0, device=dev))
+    return dev
+
+
+def workspace(stem, dev, *sizes):
+    """uint8 tensor on `dev` of `<stem>_workspace_bytes(*sizes)` bytes (at least 256, so that an empty batch has a pointer too)"""
+    n = getattr(lib(), stem + "_workspace_bytes")(*sizes)
+    return torch.empty(max(n, 256), dtype=torch.uint8, device=dev)
+
+
+def call(name, dev, *args):
+    """Library function `name` on `dev`, on torch's current stream of that device (the stream is the function's last argument and
+    is appended here).  A tensor goes in as its data pointer, None as NULL, a numpy array as its host pointer, a ctypes structure
+    by reference, everything else as it is.  Raises GigaHipError with the function's name unless the call returns 0."""
+    def convert(a):
+        if torch.is_tensor(a):
+            return ctypes.c_void_p(a.data_ptr())
+        if isinstance(a, np.ndarray):
+            return host_ptr(a)
+        return ctypes.byref(a) if isinstance(a, ctypes.Structure) else a
+    with torch.cuda.device(dev):
+        check(getattr(lib(), name)(*[convert(a) for a in args], stream_ptr(dev)), name)
 
 
 def require_device(*tensors):

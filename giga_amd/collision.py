@@ -9,8 +9,8 @@ either body.  Coplanar contact (two faces lying in one plane) is not detected, b
 import numpy as np
 import torch
 
-from . import _capi
-from .eval import _device, _hptr, _mesh_devices, _mesh_parts, _pack_meshes, mesh_contains_batch
+from . import _capi, ragged
+from .eval import mesh_contains_batch
 
 
 def mesh_bounds_batch(meshes):
@@ -19,7 +19,7 @@ def mesh_bounds_batch(meshes):
     out = np.empty((len(meshes), 2, 3), np.float32)
     out[:, 0], out[:, 1] = np.inf, -np.inf
     for m, mesh in enumerate(meshes):
-        v = _mesh_parts(mesh)[0]
+        v = ragged.mesh_parts(mesh)[0]
         if torch.is_tensor(v):
             v = v.detach().reshape(-1, 3).float()
             if len(v):
@@ -48,11 +48,7 @@ def mesh_collide(meshes, pairs, containment=True, device=None):
     containment=True ORs in two point-in-mesh queries per pair -- the first vertex that body a's faces use against body b, and the
     reverse, all pairs in one `mesh_contains_batch` call (one scene per body that is asked about) -- so that a solid wholly inside
     another solid counts as a collision, while an object standing inside a hollow open mesh does not."""
-    tensors = [t for t in _mesh_devices(meshes) if torch.is_tensor(t)]
-    dev = torch.device(device) if device is not None else _device(*tensors)
-    if dev.type != "cuda":
-        raise _capi.GigaHipError("mesh collision runs on a HIP device; there is no CPU fallback")
-    _capi.device_of(*tensors, torch.empty(0, device=dev))
+    dev = _capi.hip_device(*ragged.mesh_arrays(meshes), device=device, what="mesh collision runs on a HIP device")
     pairs = np.ascontiguousarray(np.asarray(pairs, np.int64).reshape(-1, 2))
     M, P = len(meshes), len(pairs)
     if P and (M == 0 or pairs.min() < 0 or pairs.max() >= M or (pairs[:, 0] == pairs[:, 1]).any()):
@@ -60,13 +56,9 @@ def mesh_collide(meshes, pairs, containment=True, device=None):
     hit = torch.zeros(P, dtype=torch.uint8, device=dev)
     if P == 0:
         return hit.to(torch.bool)
-    v, vo, f, fo = _pack_meshes(meshes, dev)
-    pairs32 = np.ascontiguousarray(pairs, np.int32)
-    L = _capi.lib()
-    ws = torch.empty(max(L.giga_mesh_collide_workspace_bytes(M, P), 256), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check(L.giga_mesh_collide(_capi.ptr(v), _hptr(vo), _capi.ptr(f), _hptr(fo), M, _hptr(pairs32), P, _capi.ptr(hit),
-                                        _capi.ptr(ws), ws.numel(), _capi.stream_ptr(dev)), "giga_mesh_collide")
+    v, vo, f, fo = ragged.pack_meshes(meshes, dev)
+    ws = _capi.workspace("giga_mesh_collide", dev, M, P)
+    _capi.call("giga_mesh_collide", dev, v, vo, f, fo, M, np.ascontiguousarray(pairs, np.int32), P, hit, ws, ws.numel())
     hit = hit.to(torch.bool)
     if not containment:
         return hit

@@ -25,6 +25,7 @@
 //   no square root.  'mean' takes the correctly rounded root.
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "giga_check.h"
 #include "giga_scan.h"
 #include "giga_ws.h"
 #include "../../include/giga_hip.h"
@@ -82,7 +83,7 @@ static const uint8_t AFF_REDS[256][3] = {
     {132,7,17}, {130,7,17}, {128,6,16}, {126,6,16}, {124,5,16}, {122,5,16}, {121,4,15}, {119,4,15},
     {117,3,15}, {115,3,15}, {113,2,14}, {111,2,14}, {109,1,14}, {107,1,14}, {105,0,13}, {103,0,13}};
 
-void affordance_colormap(uint8_t* rgba) {
+static void affordance_colormap(uint8_t* rgba) {
     for (int i = 0; i < 256; ++i) {
         for (int c = 0; c < 3; ++c) rgba[4 * i + c] = AFF_REDS[i][c];
         rgba[4 * i + 3] = 255;
@@ -371,10 +372,9 @@ static AffWs aff_workspace(int B, int R) {
     w.total = L.total;
     return w;
 }
-size_t affordance_workspace_bytes(int B, int R) { return aff_workspace(B, R).total; }
 
-int launch_affordance_points(const float* qual, const float* rot, int B, int R, const GigaAffordanceParams* prm, double* points,
-                             int* counts, uint8_t* ws, hipStream_t s) {
+static int launch_affordance_points(const float* qual, const float* rot, int B, int R, const GigaAffordanceParams* prm, double* points,
+                                    int* counts, uint8_t* ws, hipStream_t s) {
     const AffWs w = aff_workspace(B, R);
     AffPointArgs g;
     g.qual = qual; g.rot = rot; g.points = points;
@@ -422,9 +422,9 @@ static AffGrid aff_grid(int R, const GigaAffordanceParams* prm) {
     return gr;
 }
 
-int launch_affordance_faces(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
-                            const double* points, const int* counts, int B, int R, const GigaAffordanceParams* prm,
-                            double* affordance, uint8_t* rgba, uint8_t* ws, hipStream_t s) {
+static int launch_affordance_faces(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
+                                   const double* points, const int* counts, int B, int R, const GigaAffordanceParams* prm,
+                                   double* affordance, uint8_t* rgba, uint8_t* ws, hipStream_t s) {
     const AffWs w = aff_workspace(B, R);
     // one staging buffer, one copy (pageable host memory: the copy has left it when the call returns)
     std::vector<int> host(w.block_base / sizeof(int), 0);
@@ -481,3 +481,54 @@ int launch_affordance_faces(const float* vertices, const int* vertex_offsets, co
 }
 
 }  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+static int affordance_check(int B, int R, const GigaAffordanceParams* p) {
+    if (const int rc = ragged_batch_check(B)) return rc;
+    if (!p || R < 2 || R > GIGA_TSDF_MAX_R) return -1;
+    const int mode = p->aggregation & ~GIGA_AFFORDANCE_DENSE;
+    if (mode != GIGA_AFFORDANCE_MAX && mode != GIGA_AFFORDANCE_SOFTMAX && mode != GIGA_AFFORDANCE_MEAN) return -1;
+    if (!finite_f64(p->size) || !finite_f64(p->th) || !finite_f64(p->temp) || !finite_f64(p->rad) || !finite_f64(p->finger_depth) ||
+        !finite_f64(p->finger_offset))
+        return -1;
+    return 0;
+}
+
+size_t giga_affordance_workspace_bytes(int B, int R, int n_faces_total) {
+    if (B <= 0 || B > GIGA_MAX_SCENES || R < 2 || R > GIGA_TSDF_MAX_R || n_faces_total < 0) return 0;
+    return aff_workspace(B, R).total;
+}
+
+int giga_affordance_points(const float* qual, const float* rot, int B, int R, const GigaAffordanceParams* params, double* points,
+                           int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = affordance_check(B, R, params)) return rc;
+    if (B == 0) return 0;
+    if (!qual || (params->move_center && !rot) || !points || !counts || !workspace) return -1;
+    if (workspace_bytes < giga_affordance_workspace_bytes(B, R, 0)) return -4;
+    return launch_affordance_points(qual, rot, B, R, params, points, counts, static_cast<uint8_t*>(workspace),
+                                    static_cast<hipStream_t>(stream));
+}
+
+int giga_affordance_faces(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                          const double* points, const int32_t* counts, int B, int R, const GigaAffordanceParams* params,
+                          double* affordance, uint8_t* rgba, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = affordance_check(B, R, params)) return rc;
+    if (B == 0) return 0;
+    if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B)) return -1;
+    if (triangle_offsets[B] == 0) return 0;                 // (whatever the data pointers: only the offsets are looked at before)
+    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !points || !counts || !affordance || !rgba ||
+        !workspace)
+        return -1;
+    if (workspace_bytes < giga_affordance_workspace_bytes(B, R, triangle_offsets[B])) return -4;
+    return launch_affordance_faces(vertices, vertex_offsets, triangles, triangle_offsets, points, counts, B, R, params, affordance, rgba,
+                                   static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+void giga_affordance_colormap(uint8_t* rgba) {
+    if (rgba) affordance_colormap(rgba);
+}
+
+}  // extern "C"

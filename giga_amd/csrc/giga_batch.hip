@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include "giga_launch.h"
+#include "giga_check.h"
 #include "giga_philox.h"
 #include <cmath>
 #include <cstdint>
@@ -246,22 +247,14 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_assemble_kernel(BatchAsmArg
 }
 
 // `size` rounded once to float16 (round to nearest even, as numpy's conversion of a Python float), returned as a float
-float batch_size_as_half(double size) {
+static float batch_size_as_half(double size) {
     const _Float16 h = (_Float16)size;
     return (float)h;
 }
 
-int launch_batch_draw(const GigaBatchSet& set, const int32_t* ordinals, const int32_t* rows, int B, int M, int epoch,
-                      unsigned long long seed, int32_t* quarter, double* u, int32_t* file, int32_t* index, hipStream_t s) {
-    const int per = M > 0 ? (M + BATCH_BLOCK - 1) / BATCH_BLOCK : 1;
-    GIGA_LAUNCH(batch_draw_kernel, dim3((unsigned)per, (unsigned)B), dim3(BATCH_BLOCK), 0, s, set, ordinals, rows, M, (unsigned)epoch,
-                (unsigned)seed, (unsigned)(seed >> 32), quarter, u, file, index);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-int launch_batch_assemble(const GigaBatchSet& set, const int32_t* rows, const int32_t* quarter, const double* u, const int32_t* file,
-                          const int32_t* index, int B, int M, int augment, float* x, float* pos, float* pos_occ, float* label,
-                          float* rotations, float* width, float* occ, hipStream_t s) {
+static int launch_batch_assemble(const GigaBatchSet& set, const int32_t* rows, const int32_t* quarter, const double* u, const int32_t* file,
+                                 const int32_t* index, int B, int M, int augment, float* x, float* pos, float* pos_occ, float* label,
+                                 float* rotations, float* width, float* occ, hipStream_t s) {
     BatchAsmArgs a{};
     a.s = set;
     a.rows = rows; a.quarter = quarter; a.u = u; a.file = file; a.index = index;
@@ -277,3 +270,68 @@ int launch_batch_assemble(const GigaBatchSet& set, const int32_t* rows, const in
 }
 
 }  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+// everything about the set that can be checked on the host; `all`: giga_batch_assemble reads every array, giga_batch_draw the tables
+// behind the file sizes only
+static int batch_set_check(const GigaBatchSet* set, bool all) {
+    if (!set) return -1;
+    if (set->n_scenes < 0 || set->n_rows < 0 || set->n_files < 0 || set->n_points < 0) return -1;
+    if (!set->row_scene || !set->scene_files || !set->file_points) return -1;
+    if (all) {
+        if (!set->grids || !set->row_pos || !set->row_quat || !set->row_rotations || !set->row_width || !set->row_label ||
+            !set->points || !set->occ)
+            return -1;
+        if (set->point_dtype != GIGA_BATCH_POINTS_F32 && set->point_dtype != GIGA_BATCH_POINTS_F16) return -1;
+        if (!finite_f64(set->size) || !(set->size > 0.0)) return -1;
+        if (reinterpret_cast<uintptr_t>(set->grids) % 16 != 0) return -1;
+    }
+    if (set->scene_files_host) {
+        const int32_t* f = set->scene_files_host;
+        if (f[0] != 0 || f[set->n_scenes] != set->n_files) return -1;
+        for (int i = 0; i < set->n_scenes; ++i)
+            if (f[i + 1] < f[i]) return -1;
+    }
+    if (set->file_points_host) {
+        const int64_t* p = set->file_points_host;
+        if (p[0] != 0 || p[set->n_files] != set->n_points) return -1;
+        for (int i = 0; i < set->n_files; ++i)
+            if (p[i + 1] < p[i] || p[i + 1] - p[i] >= (1LL << 31)) return -1;
+    }
+    return 0;
+}
+
+static bool batch_shape_ok(int B, int M) {
+    return B >= 0 && M >= 0 && B <= GIGA_BATCH_MAX_ITEMS && (long long)B * M < (1LL << 31);
+}
+
+int giga_batch_draw(const GigaBatchSet* set, const int32_t* ordinals, const int32_t* rows, int B, int M, int epoch,
+                    unsigned long long seed, int32_t* quarter, double* u, int32_t* file, int32_t* index, void* stream) {
+    if (!batch_shape_ok(B, M) || epoch < 0) return -1;
+    if (const int rc = batch_set_check(set, false)) return rc;
+    if (B == 0) return 0;
+    if (!ordinals || !rows) return -1;
+    if (!quarter || !u || !file || (M > 0 && !index)) return -6;
+    const int per = M > 0 ? (M + BATCH_BLOCK - 1) / BATCH_BLOCK : 1;
+    GIGA_LAUNCH(batch_draw_kernel, dim3((unsigned)per, (unsigned)B), dim3(BATCH_BLOCK), 0, static_cast<hipStream_t>(stream), *set,
+                ordinals, rows, M, (unsigned)epoch, (unsigned)seed, (unsigned)(seed >> 32), quarter, u, file, index);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int giga_batch_assemble(const GigaBatchSet* set, const int32_t* rows, const int32_t* quarter, const double* u, const int32_t* file,
+                        const int32_t* index, int B, int M, int augment, float* x, float* pos, float* pos_occ, float* label,
+                        float* rotations, float* width, float* occ, void* stream) {
+    if (!batch_shape_ok(B, M)) return -1;
+    if (const int rc = batch_set_check(set, true)) return rc;
+    if (B == 0) return 0;
+    if (!rows || !file || (M > 0 && !index) || (augment && (!quarter || !u))) return -1;
+    if (!x || !pos || !label || !rotations || !width || (M > 0 && (!pos_occ || !occ))) return -6;
+    if (reinterpret_cast<uintptr_t>(x) % 16 != 0) return -1;
+    return launch_batch_assemble(*set, rows, quarter, u, file, index, B, M, augment, x, pos, pos_occ, label, rotations, width, occ,
+                                 static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -1,4 +1,8 @@
-// extern "C" entry points of libgiga_hip.so (declared in include/giga_hip.h).
+// The extern "C" entry points of libgiga_hip.so (declared in include/giga_hip.h) that span kernel files or belong to none: version and
+// giga_strerror, packing / repacking / deriving the weight images (with their kernels), the encoder, planes and decoder forward calls
+// with their probes, giga_backward and its workspace functions, the launch probe and counter, giga_forget_device_state, the event
+// helpers and host register / unregister.  Every other entry point stands in the file of its kernels, after them (giga_post.hip,
+// giga_eval.hip, giga_mesh.hip, ...); host checks that several of those share are in giga_check.h.
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
 
@@ -30,18 +34,6 @@ int launch_decoder_backward(const float* planes, const float* p, const uint8_t* 
                             float* grads, int head_present, float* scratch, int B, int N, hipStream_t s, bool writes_planes,
                             SideScope* side);
 int launch_plane_gather(const float* dcbuf, const float* p, float* gplanes, int B, int N, hipStream_t s);
-// giga_decoder_pgrad.hip
-int launch_decoder_point_grad(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob, int head_mask,
-                              const float* const* douts, float* const* outs, float* dp, int B, int N, hipStream_t s);
-int launch_decoder_point_hess(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob, float* logit,
-                              float* dp, float* hess, int B, int N, hipStream_t s);
-// giga_refine.hip
-int launch_refine_face_points(const float* vertices, const int* faces, const float* eps_in, float* eps, float* points, int V, int F,
-                              unsigned long long seed, int step, hipStream_t s);
-int launch_refine_face_grad(const float* vertices, const int* faces, const float* eps, const float* logit, const float* dp,
-                            const float* hess, double threshold, float* floss, float* fgrad, int V, int F, hipStream_t s);
-int launch_refine_vertex_step(const float* fgrad, const int* corner_order, const int* vertex_offsets, float* vertices,
-                              float* square_avg, float* grad, int V, int F, hipStream_t s);
 // giga_decoder_train16.hip (bf16 decoder of the bf16 training step)
 int launch_dect_forward(const float* planes, const float* p, const uint8_t* blob, int head_mask, float* const* outs, int B, int N,
                         int post, hipStream_t s);
@@ -50,105 +42,12 @@ int launch_dect_backward(const float* planes, const float* p, const uint8_t* blo
                          const float* const* outs, const float* const* douts, float* gplanes, float* dcbuf, float* scratch, int B,
                          int N, hipStream_t s, DectPending* pend);
 int launch_dect_reduce(const DectPending& pend, float* grads, int head_present, hipStream_t s);
-// giga_loss.hip
-int launch_train_loss(const float* qual, const float* rot, const float* width, const float* occ, const float* label,
-                      const float* rot_t, const float* width_t, const float* occ_t, int B, int M, float* losses,
-                      float* scene_loss, hipStream_t s);
-int launch_train_loss_metrics(const float* qual, const float* rot, const float* width, const float* occ, const float* label,
-                              const float* rot_t, const float* width_t, const float* occ_t, int B, int M, float* losses,
-                              float* scene_loss, void* acc, hipStream_t s);
-int launch_train_loss_backward(const float* qual, const float* rot, const float* width, const float* occ,
-                               const float* label, const float* rot_t, const float* width_t, const float* occ_t,
-                               const float* gout, int B, int M, float* dqual, float* drot, float* dwidth, float* docc,
-                               hipStream_t s);
-int launch_train_occ_loss(const float* occ, const float* occ_t, int B, int M, float* loss, float* scene_loss, unsigned* scene_counts,
-                          void* acc, hipStream_t s);
-int launch_train_occ_loss_backward(const float* occ, const float* occ_t, const float* gout, int B, int M, float* docc, hipStream_t s);
-// giga_tsdf.hip
-int launch_tsdf_scatter(const int* index, const float* value, const int* offsets, int B, int R, int n, float* grid,
-                        int* winner, hipStream_t s);
-size_t tsdf_integrate_workspace_bytes(int B, int n_views);
-int launch_tsdf_integrate(const float* depth, const int* view_offsets, const double* extrinsics, const double* intrinsics, int B,
-                          int W, int H, double length, int R, double sdf_trunc, double depth_scale, double depth_trunc, float* tsdf,
-                          float* weight, float* grid, uint8_t* ws, hipStream_t s);
-size_t tsdf_cloud_workspace_bytes(int B, int R);
-int launch_tsdf_cloud_count(const float* tsdf, const float* weight, int B, int R, uint8_t* ws, int* counts, hipStream_t s);
-int launch_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, double length, const uint8_t* ws, float* points,
-                           size_t cap, int* shortfall, hipStream_t s);
-// giga_render.hip
-size_t depth_render_workspace_bytes(int B, int n_views);
-int launch_depth_render(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
-                        const int* view_offsets, const double* extrinsics, const double* intrinsics, int B, int W, int H, double near,
-                        double far, double pixel_offset, float* depth, uint8_t* ws, hipStream_t s);
-// giga_noise.hip
-size_t depth_noise_workspace_bytes(int n);
-int launch_depth_noise(const float* in, float* out, int n, int W, int H, int model, const double* p, unsigned long long seed,
-                       const unsigned long long* image_ids, uint8_t* ws, hipStream_t s);
-// giga_batch.hip
-int launch_batch_draw(const GigaBatchSet& set, const int32_t* ordinals, const int32_t* rows, int B, int M, int epoch,
-                      unsigned long long seed, int32_t* quarter, double* u, int32_t* file, int32_t* index, hipStream_t s);
-int launch_batch_assemble(const GigaBatchSet& set, const int32_t* rows, const int32_t* quarter, const double* u, const int32_t* file,
-                          const int32_t* index, int B, int M, int augment, float* x, float* pos, float* pos_occ, float* label,
-                          float* rotations, float* width, float* occ, hipStream_t s);
-// giga_mesh.hip
-size_t mesh_workspace_bytes(int B, int nx, int ny, int nz);
-int launch_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, uint8_t* ws, int* counts, hipStream_t s);
-int launch_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso, double box, const uint8_t* ws, float* vertices,
-                     size_t cap_v, int* triangles, size_t cap_t, int* shortfall, hipStream_t s);
-// giga_simplify.hip
-long long simplify_ref_capacity(int n_triangles_of_mesh, int ref_extra);
-size_t simplify_workspace_bytes(int B, long long n_vertices, long long n_triangles, long long ref_total);
-int launch_mesh_simplify(const void* vertices, int vertices_f64, const int* vertex_offsets, const int* triangles,
-                         const int* triangle_offsets, const int* targets, int B, double agressiveness, int ref_extra,
-                         double* out_vertices, int* out_triangles, int* out_counts, int* stats, uint8_t* ws, hipStream_t st);
-// giga_mise.hip
-size_t mise_workspace_bytes(int B, int res0, int depth);
-int launch_mise_init(int B, int res0, int depth, uint8_t* ws, hipStream_t s);
-int launch_mise_count(int B, int res0, int depth, uint8_t* ws, int* counts, hipStream_t s);
-int launch_mise_emit(int B, int res0, int depth, const uint8_t* ws, int* query, size_t cap, int* shortfall, const float* lin,
-                     float* points, hipStream_t s);
-int launch_mise_update(const float* values, const int* query, size_t cap, int B, int res0, int depth, double thr, uint8_t* ws,
-                       hipStream_t s);
-int launch_mise_to_dense(int B, int res0, int depth, const uint8_t* ws, float* grid, hipStream_t s);
-// giga_eval.hip
-size_t nn_workspace_bytes(int B, int n_src);
-int launch_nn_query(const float* src, const int* src_offsets, const float* tgt, const int* tgt_offsets, int B, float* dist,
-                    int* idx, uint8_t* ws, hipStream_t s);
-size_t sample_workspace_bytes(int B, int n_tri);
-int launch_mesh_sample(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets, int B,
-                       int n, unsigned long long seed, int first_scene, float* points, int* face, float* normals, int* counts,
-                       uint8_t* ws, hipStream_t s);
-size_t contains_workspace_bytes(int B, int n_tri, int n_pts);
-int launch_mesh_contains(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
-                         const double* points, const int* point_offsets, int B, int resolution, uint8_t* inside, uint8_t* ws,
-                         hipStream_t s);
-// giga_collide.hip
-size_t collide_workspace_bytes(int M, int P);
-int launch_mesh_collide(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets, int M,
-                        const int* pairs, int P, uint8_t* hit, uint8_t* ws, hipStream_t s);
-// giga_geometry.hip
-size_t roi_workspace_bytes(int G);
-int launch_roi_points(const double* grasps, const int* offsets, const int* scene, const int* first, int G, unsigned long long seed,
-                      double extent, double size, double* world, float* normalised, uint8_t* ws, hipStream_t s);
-size_t confusion_workspace_bytes(int B);
-int launch_occ_confusion(const float* logits, const uint8_t* pred, double th, const uint8_t* target, const int* offsets, int B,
-                         unsigned long long* counts, uint8_t* ws, hipStream_t s);
-// giga_affordance.hip
-size_t affordance_workspace_bytes(int B, int R);
-void affordance_colormap(uint8_t* rgba);
-int launch_affordance_points(const float* qual, const float* rot, int B, int R, const GigaAffordanceParams* prm, double* points,
-                             int* counts, uint8_t* ws, hipStream_t s);
-int launch_affordance_faces(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
-                            const double* points, const int* counts, int B, int R, const GigaAffordanceParams* prm,
-                            double* affordance, uint8_t* rgba, uint8_t* ws, hipStream_t s);
 // giga_encoder.hip
 EncWs enc_workspace(int B, int precision);
 int launch_encoder(const float* tsdf, const uint8_t* blob, void* planes_nhwc, float* planes_nchw, int B,
                    int precision, uint8_t* ws, hipStream_t s, int probe_stage, void* ev0, void* ev1);
 // giga_decoder.hip
 int launch_decoder(const DecArgs& a, int precision, hipStream_t s, void* ev0, void* ev1);
-int launch_adam_flat(float* p, const float* g, float* m, float* v, size_t n, double lr, double b1, double b2, double eps, double wd,
-                     int step, hipStream_t s);
 int launch_planes_pack(const float* xz, const float* xy, const float* yz, void* dst, int B, int precision, hipStream_t s);
 int launch_lattice_resample(const void* planes, const float* lin, void* out, int B, int R, int precision, hipStream_t s,
                             bool planes_fp32 = false);
@@ -521,17 +420,6 @@ static int dec_args_heads(DecArgs& a, int head_mask, float* const (&outs)[NHEADS
 
 int giga_decoder_forward_probe(const void* planes_nhwc, const float* p, const void* packed, int head_mask,
                                float* qual, float* rot, float* width, float* occ, int B, int N, int precision,
-                               int post, void* stream, void* ev_start, void* ev_stop);
-
-int giga_decoder_forward(const void* planes_nhwc, const float* p, const void* packed, int head_mask, float* qual,
-                         float* rot, float* width, float* occ, int B, int N, int precision, int post,
-                         void* stream) {
-    return giga_decoder_forward_probe(planes_nhwc, p, packed, head_mask, qual, rot, width, occ, B, N, precision,
-                                      post, stream, nullptr, nullptr);
-}
-
-int giga_decoder_forward_probe(const void* planes_nhwc, const float* p, const void* packed, int head_mask,
-                               float* qual, float* rot, float* width, float* occ, int B, int N, int precision,
                                int post, void* stream, void* ev_start, void* ev_stop) {
     if (B < 0 || N < 0) return -1;
     const bool fold = (precision & GIGA_FOLD_FINAL) != 0;     // planes are the encoder output BEFORE conv_final
@@ -556,6 +444,13 @@ int giga_decoder_forward_probe(const void* planes_nhwc, const float* p, const vo
     if (const int rc = dec_args_heads(a, head_mask, outs, pack_offsets(), precision, fold)) return rc;
     a.B = B; a.N = N; a.P = (long long)B * N; a.post = post;
     return launch_decoder(a, precision, static_cast<hipStream_t>(stream), ev_start, ev_stop);
+}
+
+int giga_decoder_forward(const void* planes_nhwc, const float* p, const void* packed, int head_mask, float* qual,
+                         float* rot, float* width, float* occ, int B, int N, int precision, int post,
+                         void* stream) {
+    return giga_decoder_forward_probe(planes_nhwc, p, packed, head_mask, qual, rot, width, occ, B, N, precision,
+                                      post, stream, nullptr, nullptr);
 }
 
 size_t giga_lattice_workspace_bytes(int B, int R, int precision) {
@@ -704,72 +599,6 @@ int giga_backward(const float* tsdf, const void* packed, const void* bwd_packed,
     return rc;
 }
 
-int giga_decoder_point_grad(const void* planes_nhwc, const float* p, const void* packed, const void* bwd_packed,
-                            int head_mask, const float* dqual, const float* drot, const float* dwidth, const float* dtsdf,
-                            float* dp, float* out_qual, float* out_rot, float* out_width, float* out_tsdf,
-                            int B, int N, int flags, void* stream) {
-    if (head_mask <= 0 || (head_mask & ~15) != 0) return -1;
-    if (B <= 0 || N <= 0) return -1;
-    if (B > GIGA_MAX_SCENES) return -7;
-    if ((long long)B * N >= (1LL << 31)) return -1;         // split_scene's point index is exact below 2^31
-    if (flags != 0) return -5;
-    if (!planes_nhwc || !p || !packed || !bwd_packed || !dp) return -1;
-    const float* douts[NHEADS] = {dqual, drot, dwidth, dtsdf};
-    float* outs[NHEADS] = {out_qual, out_rot, out_width, out_tsdf};
-    for (int h = 0; h < NHEADS; ++h)
-        if ((head_mask >> h & 1) && !douts[h]) return -6;
-    return launch_decoder_point_grad(static_cast<const float*>(planes_nhwc), p, static_cast<const uint8_t*>(packed),
-                                     static_cast<const uint8_t*>(bwd_packed), head_mask, douts, outs, dp, B, N,
-                                     static_cast<hipStream_t>(stream));
-}
-
-int giga_decoder_point_hess(const void* planes_nhwc, const float* p, const void* packed, const void* bwd_packed, float* logit,
-                            float* dp, float* hess, int B, int N, void* stream) {
-    if (B <= 0 || N <= 0) return -1;
-    if (B > GIGA_MAX_SCENES) return -7;
-    if ((long long)B * N >= (1LL << 31)) return -1;         // split_scene's point index is exact below 2^31
-    if (!planes_nhwc || !p || !packed || !bwd_packed || !logit || !dp || !hess) return -1;
-    return launch_decoder_point_hess(static_cast<const float*>(planes_nhwc), p, static_cast<const uint8_t*>(packed),
-                                     static_cast<const uint8_t*>(bwd_packed), logit, dp, hess, B, N,
-                                     static_cast<hipStream_t>(stream));
-}
-
-// 3 F corner indices and 9 F gradient floats are indexed with int / 32-bit products of the face count
-static bool refine_sizes_ok(int n_vertices, int n_faces) {
-    return n_vertices >= 0 && n_faces >= 0 && n_vertices <= GIGA_REFINE_MAX_VERTICES && n_faces <= GIGA_REFINE_MAX_FACES;
-}
-
-int giga_refine_face_points(const float* vertices, const int* faces, const float* eps_in, float* eps, float* points,
-                            int n_vertices, int n_faces, unsigned long long seed, int step, void* stream) {
-    if (!refine_sizes_ok(n_vertices, n_faces) || step < 0) return -1;
-    if (n_faces == 0) return 0;
-    if (!vertices || !faces) return -1;
-    if (!eps || !points) return -6;
-    return launch_refine_face_points(vertices, faces, eps_in, eps, points, n_vertices, n_faces, seed, step,
-                                     static_cast<hipStream_t>(stream));
-}
-
-int giga_refine_face_grad(const float* vertices, const int* faces, const float* eps, const float* logit, const float* dp,
-                          const float* hess, double threshold, float* face_loss, float* face_grad, int n_vertices, int n_faces,
-                          void* stream) {
-    if (!refine_sizes_ok(n_vertices, n_faces) || !(threshold > 0.0 && threshold < 1.0)) return -1;
-    if (n_faces == 0) return 0;
-    if (!vertices || !faces || !eps || !logit || !dp || !hess) return -1;
-    if (!face_loss || !face_grad) return -6;
-    return launch_refine_face_grad(vertices, faces, eps, logit, dp, hess, threshold, face_loss, face_grad, n_vertices, n_faces,
-                                   static_cast<hipStream_t>(stream));
-}
-
-int giga_refine_vertex_step(const float* face_grad, const int* corner_order, const int* vertex_offsets, float* vertices,
-                            float* square_avg, float* grad, int n_vertices, int n_faces, void* stream) {
-    if (!refine_sizes_ok(n_vertices, n_faces)) return -1;
-    if (n_vertices == 0) return 0;
-    if (!vertex_offsets || !vertices || !square_avg || (n_faces > 0 && (!face_grad || !corner_order))) return -1;
-    if (!grad) return -6;
-    return launch_refine_vertex_step(face_grad, corner_order, vertex_offsets, vertices, square_avg, grad, n_vertices, n_faces,
-                                     static_cast<hipStream_t>(stream));
-}
-
 /* page-lock (and map for DMA) a host range the caller owns, e.g. a shared-memory batch ring written by reader processes */
 int giga_host_register(void* ptr, size_t bytes) {
     if (!ptr || bytes == 0) return -1;
@@ -778,619 +607,6 @@ int giga_host_register(void* ptr, size_t bytes) {
 int giga_host_unregister(void* ptr) {
     if (!ptr) return -1;
     return hipHostUnregister(ptr) == hipSuccess ? 0 : -10;
-}
-
-size_t giga_tsdf_scatter_workspace_bytes(int B, int R) {
-    if (B <= 0 || R <= 0) return 0;
-    return (size_t)B * R * R * R * sizeof(int32_t);
-}
-
-int giga_tsdf_scatter(const int32_t* voxel_index, const float* voxel_value, const int32_t* scene_offsets, int B, int R,
-                      int n_voxels, float* grid, void* workspace, size_t workspace_bytes, void* stream) {
-    if (B < 0 || R <= 0 || R > 1024 || n_voxels < 0) return -1;
-    if (B == 0) return 0;
-    if (!grid || !scene_offsets) return -1;
-    if (n_voxels > 0 && (!voxel_index || !voxel_value || !workspace)) return -1;
-    if (n_voxels > 0 && workspace_bytes < giga_tsdf_scatter_workspace_bytes(B, R)) return -4;
-    return launch_tsdf_scatter(voxel_index, voxel_value, scene_offsets, B, R, n_voxels, grid, static_cast<int*>(workspace),
-                               static_cast<hipStream_t>(stream));
-}
-
-int giga_train_loss(const float* qual, const float* rot, const float* width, const float* occ_logits, const float* label,
-                    const float* rot_targets, const float* width_target, const float* occ_target, int B, int M,
-                    float* losses, float* scene_losses, void* stream) {
-    if (B < 0 || M < 0) return -1;
-    if (B == 0) return 0;
-    if (!qual || !rot || !width || !label || !rot_targets || !width_target || !losses || !scene_losses) return -1;
-    if (M > 0 && (!occ_logits || !occ_target)) return -1;
-    return launch_train_loss(qual, rot, width, occ_logits, label, rot_targets, width_target, occ_target, B, M, losses,
-                             scene_losses, static_cast<hipStream_t>(stream));
-}
-
-int giga_train_loss_metrics(const float* qual, const float* rot, const float* width, const float* occ_logits, const float* label,
-                            const float* rot_targets, const float* width_target, const float* occ_target, int B, int M,
-                            float* losses, float* scene_losses, void* acc, void* stream) {
-    if (B < 0 || M < 0) return -1;
-    if (!acc || (reinterpret_cast<uintptr_t>(acc) & 7)) return -1;
-    if (B == 0) return 0;
-    if (!qual || !rot || !width || !label || !rot_targets || !width_target || !losses || !scene_losses) return -1;
-    if (M > 0 && (!occ_logits || !occ_target)) return -1;
-    return launch_train_loss_metrics(qual, rot, width, occ_logits, label, rot_targets, width_target, occ_target, B, M, losses,
-                                     scene_losses, acc, static_cast<hipStream_t>(stream));
-}
-
-int giga_train_loss_backward(const float* qual, const float* rot, const float* width, const float* occ_logits,
-                             const float* label, const float* rot_targets, const float* width_target,
-                             const float* occ_target, const float* grad_loss, int B, int M, float* dqual, float* drot,
-                             float* dwidth, float* docc, void* stream) {
-    if (B < 0 || M < 0) return -1;
-    if (B == 0) return 0;
-    if (!qual || !rot || !width || !label || !rot_targets || !width_target || !grad_loss || !dqual || !drot || !dwidth)
-        return -1;
-    if (M > 0 && (!occ_logits || !occ_target || !docc)) return -1;
-    return launch_train_loss_backward(qual, rot, width, occ_logits, label, rot_targets, width_target, occ_target, grad_loss,
-                                      B, M, dqual, drot, dwidth, docc, static_cast<hipStream_t>(stream));
-}
-
-int giga_train_occ_loss(const float* occ_logits, const float* occ_target, int B, int M, float* loss, float* scene_losses,
-                        void* stream) {
-    if (B < 0 || M < 0) return -1;
-    if (B == 0) return 0;
-    if (M == 0) return -1;                                  // the loss of a scene is a mean over its points
-    if (!occ_logits || !occ_target || !loss || !scene_losses) return -1;
-    return launch_train_occ_loss(occ_logits, occ_target, B, M, loss, scene_losses, nullptr, nullptr, static_cast<hipStream_t>(stream));
-}
-
-int giga_train_occ_loss_metrics(const float* occ_logits, const float* occ_target, int B, int M, float* loss, float* scene_losses,
-                                uint32_t* scene_counts, void* acc, void* stream) {
-    if (B < 0 || M < 0) return -1;
-    if (!acc || (reinterpret_cast<uintptr_t>(acc) & 7)) return -1;
-    if (B == 0) return 0;
-    if (M == 0) return -1;
-    if (!occ_logits || !occ_target || !loss || !scene_losses || !scene_counts) return -1;
-    return launch_train_occ_loss(occ_logits, occ_target, B, M, loss, scene_losses, scene_counts, acc, static_cast<hipStream_t>(stream));
-}
-
-int giga_train_occ_loss_backward(const float* occ_logits, const float* occ_target, const float* grad_loss, int B, int M, float* docc,
-                                 void* stream) {
-    if (B < 0 || M < 0) return -1;
-    if (B == 0) return 0;
-    if (M == 0) return -1;
-    if (!occ_logits || !occ_target || !grad_loss || !docc) return -1;
-    return launch_train_occ_loss_backward(occ_logits, occ_target, grad_loss, B, M, docc, static_cast<hipStream_t>(stream));
-}
-
-int giga_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
-                   double beta2, double eps, double weight_decay, int step, void* stream) {
-    if (n == 0) return 0;
-    if (!params || !grads || !exp_avg || !exp_avg_sq || step < 1) return -1;
-    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0)) return -1;
-    // the kernel moves float4: all four buffers must be 16-byte aligned (whole torch allocations are; a view at an odd offset is not)
-    if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
-         reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) return -1;
-    return launch_adam_flat(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step,
-                            static_cast<hipStream_t>(stream));
-}
-
-// ---- marching cubes (giga_mesh.hip) ----
-// counts and triangle entries are int32: a scene has at most 3 vertices and 5 triangles per cell
-static_assert(5LL * (GIGA_MESH_MAX_N + 1) * (GIGA_MESH_MAX_N + 1) * (GIGA_MESH_MAX_N + 1) < (1LL << 31), "per-scene counts are int32");
-// 0 when the shape is supported, else the error code
-static int mesh_shape_check(int B, int nx, int ny, int nz) {
-    if (B < 0 || nx < 2 || ny < 2 || nz < 2) return -1;
-    if (nx > GIGA_MESH_MAX_N || ny > GIGA_MESH_MAX_N || nz > GIGA_MESH_MAX_N) return -1;
-    if (B > GIGA_MAX_SCENES) return -7;
-    if ((long long)B * (nx + 1) * (ny + 1) * (nz + 1) >= (1LL << 31)) return -1;      // cell numbers are 32-bit
-    return 0;
-}
-
-size_t giga_mesh_workspace_bytes(int B, int nx, int ny, int nz) {
-    if (B <= 0 || mesh_shape_check(B, nx, ny, nz) != 0) return 0;
-    return mesh_workspace_bytes(B, nx, ny, nz);
-}
-
-int giga_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, void* workspace, size_t workspace_bytes,
-                    int32_t* counts, void* stream) {
-    if (const int rc = mesh_shape_check(B, nx, ny, nz)) return rc;
-    if (B == 0) return 0;
-    if (!grids || !workspace || !counts || !(iso == iso)) return -1;
-    if (workspace_bytes < giga_mesh_workspace_bytes(B, nx, ny, nz)) return -4;
-    return launch_mesh_count(grids, B, nx, ny, nz, iso, static_cast<uint8_t*>(workspace), counts, static_cast<hipStream_t>(stream));
-}
-
-int giga_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso, double box_size, const void* workspace,
-                   size_t workspace_bytes, float* vertices, size_t cap_v, int32_t* triangles, size_t cap_t, int32_t* shortfall,
-                   void* stream) {
-    if (const int rc = mesh_shape_check(B, nx, ny, nz)) return rc;
-    if (B == 0) return 0;
-    if (!grids || !workspace || !(iso == iso) || !(box_size == box_size)) return -1;
-    if ((cap_v > 0 && !vertices) || (cap_t > 0 && !triangles)) return -6;
-    if (workspace_bytes < giga_mesh_workspace_bytes(B, nx, ny, nz)) return -4;
-    return launch_mesh_emit(grids, B, nx, ny, nz, iso, box_size, static_cast<const uint8_t*>(workspace), vertices, cap_v, triangles,
-                            cap_t, shortfall, static_cast<hipStream_t>(stream));
-}
-
-// ---- MISE (giga_mise.hip) ----
-// 0 when the tree shape is supported, else the error code
-static int mise_shape_check(int B, int res0, int depth) {
-    if (B < 0 || res0 < 1 || depth < 1 || depth > 30) return -1;
-    if (((long long)res0 << depth) + 1 > GIGA_MISE_MAX_N) return -1;
-    if (B > GIGA_MAX_SCENES) return -7;
-    const long long N = ((long long)res0 << depth) + 1;
-    if ((long long)B * N * N * N >= (1LL << 31)) return -1;                           // sample numbers are 32-bit
-    return 0;
-}
-
-size_t giga_mise_workspace_bytes(int B, int resolution0, int depth) {
-    if (B <= 0 || mise_shape_check(B, resolution0, depth) != 0) return 0;
-    return mise_workspace_bytes(B, resolution0, depth);
-}
-
-int giga_mise_init(int B, int resolution0, int depth, void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
-    if (B == 0) return 0;
-    if (!workspace) return -1;
-    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
-    return launch_mise_init(B, resolution0, depth, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
-}
-
-int giga_mise_count(int B, int resolution0, int depth, void* workspace, size_t workspace_bytes, int32_t* counts, void* stream) {
-    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
-    if (B == 0) return 0;
-    if (!workspace || !counts) return -1;
-    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
-    return launch_mise_count(B, resolution0, depth, static_cast<uint8_t*>(workspace), counts, static_cast<hipStream_t>(stream));
-}
-
-int giga_mise_emit(int B, int resolution0, int depth, const void* workspace, size_t workspace_bytes, int32_t* query, size_t cap,
-                   int32_t* shortfall, const float* lin, float* points, void* stream) {
-    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
-    if (B == 0) return 0;
-    if (!workspace || (points && !lin)) return -1;
-    if (cap > 0 && !query) return -6;
-    if ((unsigned long long)B * cap >= (1ull << 31)) return -1;
-    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
-    return launch_mise_emit(B, resolution0, depth, static_cast<const uint8_t*>(workspace), query, cap, shortfall, lin, points,
-                            static_cast<hipStream_t>(stream));
-}
-
-int giga_mise_update(const float* values, const int32_t* query, size_t cap, int B, int resolution0, int depth, double threshold,
-                     void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
-    if (!(threshold == threshold)) return -1;
-    if (B == 0) return 0;
-    if (!workspace || (cap > 0 && (!values || !query))) return -1;
-    if ((unsigned long long)B * cap >= (1ull << 31)) return -1;
-    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
-    return launch_mise_update(values, query, cap, B, resolution0, depth, threshold, static_cast<uint8_t*>(workspace),
-                              static_cast<hipStream_t>(stream));
-}
-
-int giga_mise_to_dense(int B, int resolution0, int depth, const void* workspace, size_t workspace_bytes, float* grid, void* stream) {
-    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
-    if (B == 0) return 0;
-    if (!workspace || !grid) return -1;
-    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
-    return launch_mise_to_dense(B, resolution0, depth, static_cast<const uint8_t*>(workspace), grid, static_cast<hipStream_t>(stream));
-}
-
-// ---- mesh evaluation (giga_eval.hip) ----
-// offsets of a ragged batch (host array of B + 1 entries): starts at 0 and never decreases
-static bool ragged_ok(const int32_t* offs, int B) {
-    if (!offs || offs[0] != 0) return false;
-    for (int b = 0; b < B; ++b)
-        if (offs[b + 1] < offs[b]) return false;
-    return true;
-}
-static int ragged_batch_check(int B) { return B < 0 ? -1 : (B > GIGA_MAX_SCENES ? -7 : 0); }
-
-// a ragged batch of B meshes: both offset arrays are well formed, and data that is not empty has a pointer
-static bool mesh_batch_check(const int32_t* vertex_offsets, const int32_t* triangle_offsets, int B, const void* vertices,
-                             const void* triangles) {
-    if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B)) return false;
-    return (vertex_offsets[B] == 0 || vertices) && (triangle_offsets[B] == 0 || triangles);
-}
-
-static bool finite_f64(double x) { return x - x == 0.0; }
-
-// n cameras (extrinsics [n][16], intrinsics [n][4] = fx, fy, cx, cy): every number finite, no focal length zero
-static bool camera_check(int n, const double* extrinsics, const double* intrinsics) {
-    if (n > 0 && (!extrinsics || !intrinsics)) return false;
-    for (size_t i = 0; i < (size_t)n * 16; ++i)
-        if (!finite_f64(extrinsics[i])) return false;
-    for (size_t i = 0; i < (size_t)n * 4; ++i)
-        if (!finite_f64(intrinsics[i])) return false;
-    for (int v = 0; v < n; ++v)
-        if (intrinsics[4 * (size_t)v] == 0.0 || intrinsics[4 * (size_t)v + 1] == 0.0) return false;
-    return true;
-}
-
-// ---- mesh simplification (giga_simplify.hip) ----
-// the reference-list entries of a batch of B meshes with n_triangles faces in all (every mesh: 3 F entries + the appended room)
-static long long simplify_ref_total(int B, long long n_triangles, int ref_extra) {
-    return ref_extra < 0 ? 6 * n_triangles + (long long)GIGA_SIMPLIFY_MIN_REF_EXTRA * B : 3 * n_triangles + (long long)ref_extra * B;
-}
-static int simplify_shape_check(int B, long long n_vertices, long long n_triangles, int ref_extra) {
-    if (B < 0 || n_vertices < 0 || n_triangles < 0) return -1;
-    if (ref_extra >= 0 && ref_extra < GIGA_SIMPLIFY_MIN_REF_EXTRA) return -1;
-    if (B > GIGA_MAX_SCENES) return -7;
-    if (n_vertices > GIGA_SIMPLIFY_MAX_FACES || n_triangles > GIGA_SIMPLIFY_MAX_FACES) return -1;
-    if (simplify_ref_total(B, n_triangles, ref_extra) >= (1LL << 31)) return -1;
-    return 0;
-}
-
-size_t giga_simplify_workspace_bytes(int B, int n_vertices, int n_triangles, int ref_extra) {
-    if (B <= 0 || simplify_shape_check(B, n_vertices, n_triangles, ref_extra) != 0) return 0;
-    return simplify_workspace_bytes(B, n_vertices, n_triangles, simplify_ref_total(B, n_triangles, ref_extra));
-}
-
-int giga_mesh_simplify(const void* vertices, int vertices_f64, const int32_t* vertex_offsets, const int32_t* triangles,
-                       const int32_t* triangle_offsets, const int32_t* targets, int B, double agressiveness, int ref_extra,
-                       double* out_vertices, int32_t* out_triangles, int32_t* out_counts, int32_t* stats, void* workspace,
-                       size_t workspace_bytes, void* stream) {
-    if (const int rc = ragged_batch_check(B)) return rc;
-    if (B == 0) return 0;
-    if (!(agressiveness == agressiveness) || (vertices_f64 != 0 && vertices_f64 != 1)) return -1;
-    // (every check from here to the workspace pointer answers -1: simplify_shape_check has no other code once B is in range)
-    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !targets || !workspace) return -1;
-    if (const int rc = simplify_shape_check(B, vertex_offsets[B], triangle_offsets[B], ref_extra)) return rc;
-    for (int b = 0; b < B; ++b)
-        if (targets[b] < 0) return -1;
-    if (!out_counts || (vertex_offsets[B] > 0 && triangle_offsets[B] > 0 && (!out_vertices || !out_triangles))) return -6;
-    if (workspace_bytes < giga_simplify_workspace_bytes(B, vertex_offsets[B], triangle_offsets[B], ref_extra)) return -4;
-    return launch_mesh_simplify(vertices, vertices_f64, vertex_offsets, triangles, triangle_offsets, targets, B, agressiveness, ref_extra,
-                                out_vertices, out_triangles, out_counts, stats, static_cast<uint8_t*>(workspace),
-                                static_cast<hipStream_t>(stream));
-}
-
-size_t giga_nn_query_workspace_bytes(int B, int n_src) {
-    if (B <= 0 || B > GIGA_MAX_SCENES || n_src < 0) return 0;
-    return nn_workspace_bytes(B, n_src);
-}
-
-int giga_nn_query(const float* src, const int32_t* src_offsets, const float* tgt, const int32_t* tgt_offsets, int B, float* dist,
-                  int32_t* idx, void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = ragged_batch_check(B)) return rc;
-    if (B == 0) return 0;
-    if (!ragged_ok(src_offsets, B) || !ragged_ok(tgt_offsets, B)) return -1;
-    if (src_offsets[B] == 0) return 0;
-    if (!src || (tgt_offsets[B] > 0 && !tgt) || !workspace) return -1;
-    if (!dist || !idx) return -6;
-    if (workspace_bytes < giga_nn_query_workspace_bytes(B, src_offsets[B])) return -4;
-    return launch_nn_query(src, src_offsets, tgt, tgt_offsets, B, dist, idx, static_cast<uint8_t*>(workspace),
-                           static_cast<hipStream_t>(stream));
-}
-
-size_t giga_mesh_sample_workspace_bytes(int B, int n_triangles) {
-    if (B <= 0 || B > GIGA_MAX_SCENES || n_triangles < 0) return 0;
-    return sample_workspace_bytes(B, n_triangles);
-}
-
-int giga_mesh_sample(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
-                     int B, int n, uint64_t seed, int first_scene, float* points, int32_t* face, float* normals, int32_t* counts,
-                     void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = ragged_batch_check(B)) return rc;
-    if (n < 0 || first_scene < 0 || (long long)B * n >= (1LL << 31)) return -1;
-    if (B == 0) return 0;
-    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !workspace) return -1;
-    if (!counts || (n > 0 && (!points || !face || !normals))) return -6;
-    if (workspace_bytes < giga_mesh_sample_workspace_bytes(B, triangle_offsets[B])) return -4;
-    return launch_mesh_sample(vertices, vertex_offsets, triangles, triangle_offsets, B, n, seed, first_scene, points, face, normals, counts,
-                              static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
-}
-
-size_t giga_mesh_contains_workspace_bytes(int B, int n_triangles, int n_points) {
-    if (B <= 0 || B > GIGA_MAX_SCENES || n_triangles < 0 || n_points < 0) return 0;
-    return contains_workspace_bytes(B, n_triangles, n_points);
-}
-
-int giga_mesh_contains(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
-                       const double* points, const int32_t* point_offsets, int B, int resolution, uint8_t* inside, void* workspace,
-                       size_t workspace_bytes, void* stream) {
-    if (const int rc = ragged_batch_check(B)) return rc;
-    if (resolution < 2 || resolution > GIGA_CONTAINS_MAX_RESOLUTION) return -1;
-    if (B == 0) return 0;
-    if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B) || !ragged_ok(point_offsets, B)) return -1;
-    if (point_offsets[B] == 0) return 0;                    // (whatever the data pointers: only the offsets are looked at before)
-    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !points || !workspace) return -1;
-    if (!inside) return -6;
-    if (workspace_bytes < giga_mesh_contains_workspace_bytes(B, triangle_offsets[B], point_offsets[B])) return -4;
-    return launch_mesh_contains(vertices, vertex_offsets, triangles, triangle_offsets, points, point_offsets, B, resolution, inside,
-                                static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
-}
-
-// ---- mesh against mesh (giga_collide.hip) ----
-size_t giga_mesh_collide_workspace_bytes(int M, int P) {
-    if (M <= 0 || M > GIGA_MAX_SCENES || P < 0) return 0;
-    return collide_workspace_bytes(M, P);
-}
-
-int giga_mesh_collide(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
-                      int M, const int32_t* pairs, int P, uint8_t* hit, void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = ragged_batch_check(M)) return rc;
-    if (P < 0) return -1;
-    if (M == 0 || P == 0) return 0;
-    if (!mesh_batch_check(vertex_offsets, triangle_offsets, M, vertices, triangles) || !pairs || !workspace) return -1;
-    for (size_t i = 0; i < (size_t)P; ++i) {
-        const int32_t a = pairs[2 * i], b = pairs[2 * i + 1];
-        if (a < 0 || a >= M || b < 0 || b >= M || a == b) return -1;
-    }
-    if (!hit) return -6;
-    if (workspace_bytes < giga_mesh_collide_workspace_bytes(M, P)) return -4;
-    return launch_mesh_collide(vertices, vertex_offsets, triangles, triangle_offsets, M, pairs, P, hit, static_cast<uint8_t*>(workspace),
-                               static_cast<hipStream_t>(stream));
-}
-
-// ---- geometry scoring (giga_geometry.hip) ----
-size_t giga_roi_points_workspace_bytes(int n_grasps) {
-    if (n_grasps <= 0) return 0;
-    return roi_workspace_bytes(n_grasps);
-}
-
-int giga_roi_points(const double* grasps, const int32_t* point_offsets, const int32_t* grasp_scene, const int32_t* grasp_first,
-                    int n_grasps, uint64_t seed, double finger_depth, double roi_scale, double size, double* world,
-                    float* normalised, void* workspace, size_t workspace_bytes, void* stream) {
-    if (n_grasps < 0) return -1;
-    if (!finite_f64(finger_depth) || !finite_f64(roi_scale) || !finite_f64(size) || size == 0.0) return -1;
-    if (n_grasps == 0) return 0;
-    if (!ragged_ok(point_offsets, n_grasps)) return -1;
-    if (point_offsets[n_grasps] == 0) return 0;
-    if (!grasps || !grasp_scene || !grasp_first || !workspace) return -1;
-    for (int g = 0; g < n_grasps; ++g) {
-        // (the point index inside the scene is one 32-bit counter word)
-        if (grasp_scene[g] < 0 || grasp_first[g] < 0 ||
-            (long long)grasp_first[g] + (point_offsets[g + 1] - point_offsets[g]) > 0x7fffffffLL)
-            return -1;
-        for (int q = 0; q < 13; ++q)
-            if (!finite_f64(grasps[13 * (size_t)g + q])) return -1;
-    }
-    if (!world || !normalised) return -6;
-    if (workspace_bytes < giga_roi_points_workspace_bytes(n_grasps)) return -4;
-    return launch_roi_points(grasps, point_offsets, grasp_scene, grasp_first, n_grasps, seed, finger_depth * roi_scale, size, world,
-                             normalised, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
-}
-
-size_t giga_occ_confusion_workspace_bytes(int B) {
-    if (B <= 0 || B > GIGA_MAX_SCENES) return 0;
-    return confusion_workspace_bytes(B);
-}
-
-int giga_occ_confusion(const float* logits, const uint8_t* pred, double logit_threshold, const uint8_t* target,
-                       const int32_t* offsets, int B, uint64_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = ragged_batch_check(B)) return rc;
-    if (B == 0) return 0;
-    if (!ragged_ok(offsets, B)) return -1;
-    if ((logits != nullptr) == (pred != nullptr) && offsets[B] > 0) return -1;         // exactly one form of the prediction
-    if ((offsets[B] > 0 && !target) || !workspace) return -1;
-    if (logits && !(logit_threshold == logit_threshold)) return -1;
-    if (!counts) return -6;
-    if (workspace_bytes < giga_occ_confusion_workspace_bytes(B)) return -4;
-    return launch_occ_confusion(logits, pred, logit_threshold, target, offsets, B, reinterpret_cast<unsigned long long*>(counts),
-                                static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
-}
-
-// ---- depth fusion (giga_tsdf.hip) ----
-static int tsdf_volume_check(int B, int R) {
-    if (B < 0 || R < 2 || R > GIGA_TSDF_MAX_R) return -1;
-    if (B > GIGA_MAX_SCENES) return -7;
-    return 0;
-}
-
-size_t giga_tsdf_integrate_workspace_bytes(int B, int n_views) {
-    if (B <= 0 || B > GIGA_MAX_SCENES || n_views < 0) return 0;
-    return tsdf_integrate_workspace_bytes(B, n_views);
-}
-
-int giga_tsdf_integrate(const float* depth, const int32_t* view_offsets, const double* extrinsics, const double* intrinsics, int B,
-                        int width, int height, double length, int R, double sdf_trunc, double depth_scale, double depth_trunc,
-                        float* tsdf, float* weight, float* grid, void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = tsdf_volume_check(B, R)) return rc;
-    if (width < 1 || height < 1 || width > GIGA_TSDF_MAX_IMAGE || height > GIGA_TSDF_MAX_IMAGE) return -1;
-    if (!finite_f64(length) || !(length > 0.0) || !finite_f64(sdf_trunc) || !(sdf_trunc > 0.0) || !finite_f64(depth_scale) ||
-        !(depth_scale > 0.0) || !(depth_trunc == depth_trunc))
-        return -1;
-    if (B == 0) return 0;
-    if (!ragged_ok(view_offsets, B)) return -1;
-    const int n = view_offsets[B];
-    if ((long long)n * width * height >= (1LL << 40)) return -1;
-    if (!camera_check(n, extrinsics, intrinsics) || (n > 0 && !depth)) return -1;
-    if (!tsdf || !weight || !workspace) return -1;
-    if (workspace_bytes < giga_tsdf_integrate_workspace_bytes(B, n)) return -4;
-    return launch_tsdf_integrate(depth, view_offsets, extrinsics, intrinsics, B, width, height, length, R, sdf_trunc, depth_scale,
-                                 depth_trunc, tsdf, weight, grid, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
-}
-
-size_t giga_tsdf_cloud_workspace_bytes(int B, int R) {
-    if (B <= 0 || tsdf_volume_check(B, R) != 0) return 0;
-    return tsdf_cloud_workspace_bytes(B, R);
-}
-
-int giga_tsdf_cloud_count(const float* tsdf, const float* weight, int B, int R, void* workspace, size_t workspace_bytes,
-                          int32_t* counts, void* stream) {
-    if (const int rc = tsdf_volume_check(B, R)) return rc;
-    if (B == 0) return 0;
-    if (!tsdf || !weight || !workspace || !counts) return -1;
-    if (workspace_bytes < giga_tsdf_cloud_workspace_bytes(B, R)) return -4;
-    return launch_tsdf_cloud_count(tsdf, weight, B, R, static_cast<uint8_t*>(workspace), counts, static_cast<hipStream_t>(stream));
-}
-
-int giga_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, double length, const void* workspace,
-                         size_t workspace_bytes, float* points, size_t cap, int32_t* shortfall, void* stream) {
-    if (const int rc = tsdf_volume_check(B, R)) return rc;
-    if (!finite_f64(length) || !(length > 0.0)) return -1;
-    if (B == 0) return 0;
-    if (!tsdf || !weight || !workspace) return -1;
-    if (cap > 0 && !points) return -6;
-    if (workspace_bytes < giga_tsdf_cloud_workspace_bytes(B, R)) return -4;
-    return launch_tsdf_cloud_emit(tsdf, weight, B, R, length, static_cast<const uint8_t*>(workspace), points, cap, shortfall,
-                                  static_cast<hipStream_t>(stream));
-}
-
-// ---- depth rendering (giga_render.hip) ----
-size_t giga_depth_render_workspace_bytes(int B, int n_views, int n_vertices, int n_triangles) {
-    if (B <= 0 || B > GIGA_MAX_SCENES || n_views < 0 || n_vertices < 0 || n_triangles < 0) return 0;
-    return depth_render_workspace_bytes(B, n_views);
-}
-
-int giga_depth_render(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
-                      const int32_t* view_offsets, const double* extrinsics, const double* intrinsics, int B, int W, int H, double near,
-                      double far, double pixel_offset, float* depth, void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = ragged_batch_check(B)) return rc;
-    if (W < 1 || H < 1 || W > GIGA_RENDER_MAX_IMAGE || H > GIGA_RENDER_MAX_IMAGE) return -1;
-    if (!finite_f64(near) || !finite_f64(far) || !(near > 0.0) || !(far > near) || !finite_f64(pixel_offset)) return -1;
-    if (B == 0) return 0;
-    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !ragged_ok(view_offsets, B)) return -1;
-    const int n = view_offsets[B];
-    if ((long long)n * W * H >= (1LL << 31)) return -1;
-    if (n == 0) return 0;
-    if (!camera_check(n, extrinsics, intrinsics) || !workspace) return -1;
-    if (!depth) return -6;
-    if (workspace_bytes < giga_depth_render_workspace_bytes(B, n, vertex_offsets[B], triangle_offsets[B])) return -4;
-    return launch_depth_render(vertices, vertex_offsets, triangles, triangle_offsets, view_offsets, extrinsics, intrinsics, B, W, H, near,
-                               far, pixel_offset, depth, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
-}
-
-// ---- grasp affordance of a scene mesh (giga_affordance.hip) ----
-static int affordance_check(int B, int R, const GigaAffordanceParams* p) {
-    if (const int rc = ragged_batch_check(B)) return rc;
-    if (!p || R < 2 || R > GIGA_TSDF_MAX_R) return -1;
-    const int mode = p->aggregation & ~GIGA_AFFORDANCE_DENSE;
-    if (mode != GIGA_AFFORDANCE_MAX && mode != GIGA_AFFORDANCE_SOFTMAX && mode != GIGA_AFFORDANCE_MEAN) return -1;
-    if (!finite_f64(p->size) || !finite_f64(p->th) || !finite_f64(p->temp) || !finite_f64(p->rad) || !finite_f64(p->finger_depth) ||
-        !finite_f64(p->finger_offset))
-        return -1;
-    return 0;
-}
-
-size_t giga_affordance_workspace_bytes(int B, int R, int n_faces_total) {
-    if (B <= 0 || B > GIGA_MAX_SCENES || R < 2 || R > GIGA_TSDF_MAX_R || n_faces_total < 0) return 0;
-    return affordance_workspace_bytes(B, R);
-}
-
-int giga_affordance_points(const float* qual, const float* rot, int B, int R, const GigaAffordanceParams* params, double* points,
-                           int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = affordance_check(B, R, params)) return rc;
-    if (B == 0) return 0;
-    if (!qual || (params->move_center && !rot) || !points || !counts || !workspace) return -1;
-    if (workspace_bytes < giga_affordance_workspace_bytes(B, R, 0)) return -4;
-    return launch_affordance_points(qual, rot, B, R, params, points, counts, static_cast<uint8_t*>(workspace),
-                                    static_cast<hipStream_t>(stream));
-}
-
-int giga_affordance_faces(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
-                          const double* points, const int32_t* counts, int B, int R, const GigaAffordanceParams* params,
-                          double* affordance, uint8_t* rgba, void* workspace, size_t workspace_bytes, void* stream) {
-    if (const int rc = affordance_check(B, R, params)) return rc;
-    if (B == 0) return 0;
-    if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B)) return -1;
-    if (triangle_offsets[B] == 0) return 0;                 // (whatever the data pointers: only the offsets are looked at before)
-    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !points || !counts || !affordance || !rgba ||
-        !workspace)
-        return -1;
-    if (workspace_bytes < giga_affordance_workspace_bytes(B, R, triangle_offsets[B])) return -4;
-    return launch_affordance_faces(vertices, vertex_offsets, triangles, triangle_offsets, points, counts, B, R, params, affordance, rgba,
-                                   static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
-}
-
-void giga_affordance_colormap(uint8_t* rgba) {
-    if (rgba) affordance_colormap(rgba);
-}
-
-// ---- depth noise (giga_noise.hip) ----
-static bool noise_positive(double x) { return finite_f64(x) && x > 0.0; }
-
-static bool noise_shape_ok(int n, int W, int H, int model) {
-    if (n < 0 || W < 1 || H < 1 || W > GIGA_TSDF_MAX_IMAGE || H > GIGA_TSDF_MAX_IMAGE) return false;
-    if ((long long)n * W * H >= (1LL << 31)) return false;
-    return model >= GIGA_NOISE_DEX && model <= GIGA_NOISE_NORM;
-}
-
-size_t giga_depth_noise_workspace_bytes(int n_images, int width, int height, int model) {
-    if (!noise_shape_ok(n_images, width, height, model) || n_images == 0) return 0;
-    return depth_noise_workspace_bytes(n_images);
-}
-
-int giga_depth_noise(const float* depth_in, float* depth_out, int n_images, int width, int height, int model, const double* params,
-                     unsigned long long seed, const unsigned long long* image_ids, void* workspace, size_t workspace_bytes,
-                     void* stream) {
-    if (!noise_shape_ok(n_images, width, height, model)) return -1;
-    static const double defaults[3][5] = {{1000.0, 0.001, 0.005, 4.0, 0.5}, {1.0, 0.005, 0, 0, 0}, {0.005, 0, 0, 0, 0}};
-    static const int count[3] = {5, 2, 1};
-    double p[5] = {0, 0, 0, 0, 0};
-    for (int i = 0; i < count[model - 1]; ++i) p[i] = params ? params[i] : defaults[model - 1][i];
-    if (model == GIGA_NOISE_DEX) {
-        if (!noise_positive(p[0]) || !noise_positive(p[1]) || !noise_positive(p[2]) || !noise_positive(p[3])) return -1;
-        if (!(p[4] >= 0.0 && p[4] <= 1.0)) return -1;
-        if (p[3] < 1.0 || (double)height < p[3] || (double)width < p[3]) return -1;
-    } else {
-        for (int i = 0; i < count[model - 1]; ++i)
-            if (!noise_positive(p[i])) return -1;
-    }
-    if (n_images == 0) return 0;
-    if (!depth_in || !depth_out || !workspace) return -1;
-    const size_t bytes = (size_t)n_images * width * height * sizeof(float);
-    const uintptr_t a = reinterpret_cast<uintptr_t>(depth_in), b = reinterpret_cast<uintptr_t>(depth_out);
-    if (a < b + bytes && b < a + bytes) return -1;                               // out of place: trans is a gather
-    if (workspace_bytes < giga_depth_noise_workspace_bytes(n_images, width, height, model)) return -4;
-    return launch_depth_noise(depth_in, depth_out, n_images, width, height, model, p, seed, image_ids,
-                              static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
-}
-
-// ---- training batches from a resident set (giga_batch.hip) ----
-// everything about the set that can be checked on the host; `all`: giga_batch_assemble reads every array, giga_batch_draw the tables
-// behind the file sizes only
-static int batch_set_check(const GigaBatchSet* set, bool all) {
-    if (!set) return -1;
-    if (set->n_scenes < 0 || set->n_rows < 0 || set->n_files < 0 || set->n_points < 0) return -1;
-    if (!set->row_scene || !set->scene_files || !set->file_points) return -1;
-    if (all) {
-        if (!set->grids || !set->row_pos || !set->row_quat || !set->row_rotations || !set->row_width || !set->row_label ||
-            !set->points || !set->occ)
-            return -1;
-        if (set->point_dtype != GIGA_BATCH_POINTS_F32 && set->point_dtype != GIGA_BATCH_POINTS_F16) return -1;
-        if (!finite_f64(set->size) || !(set->size > 0.0)) return -1;
-        if (reinterpret_cast<uintptr_t>(set->grids) % 16 != 0) return -1;
-    }
-    if (set->scene_files_host) {
-        const int32_t* f = set->scene_files_host;
-        if (f[0] != 0 || f[set->n_scenes] != set->n_files) return -1;
-        for (int i = 0; i < set->n_scenes; ++i)
-            if (f[i + 1] < f[i]) return -1;
-    }
-    if (set->file_points_host) {
-        const int64_t* p = set->file_points_host;
-        if (p[0] != 0 || p[set->n_files] != set->n_points) return -1;
-        for (int i = 0; i < set->n_files; ++i)
-            if (p[i + 1] < p[i] || p[i + 1] - p[i] >= (1LL << 31)) return -1;
-    }
-    return 0;
-}
-
-static bool batch_shape_ok(int B, int M) {
-    return B >= 0 && M >= 0 && B <= GIGA_BATCH_MAX_ITEMS && (long long)B * M < (1LL << 31);
-}
-
-int giga_batch_draw(const GigaBatchSet* set, const int32_t* ordinals, const int32_t* rows, int B, int M, int epoch,
-                    unsigned long long seed, int32_t* quarter, double* u, int32_t* file, int32_t* index, void* stream) {
-    if (!batch_shape_ok(B, M) || epoch < 0) return -1;
-    if (const int rc = batch_set_check(set, false)) return rc;
-    if (B == 0) return 0;
-    if (!ordinals || !rows) return -1;
-    if (!quarter || !u || !file || (M > 0 && !index)) return -6;
-    return launch_batch_draw(*set, ordinals, rows, B, M, epoch, seed, quarter, u, file, index, static_cast<hipStream_t>(stream));
-}
-
-int giga_batch_assemble(const GigaBatchSet* set, const int32_t* rows, const int32_t* quarter, const double* u, const int32_t* file,
-                        const int32_t* index, int B, int M, int augment, float* x, float* pos, float* pos_occ, float* label,
-                        float* rotations, float* width, float* occ, void* stream) {
-    if (!batch_shape_ok(B, M)) return -1;
-    if (const int rc = batch_set_check(set, true)) return rc;
-    if (B == 0) return 0;
-    if (!rows || !file || (M > 0 && !index) || (augment && (!quarter || !u))) return -1;
-    if (!x || !pos || !label || !rotations || !width || (M > 0 && (!pos_occ || !occ))) return -6;
-    if (reinterpret_cast<uintptr_t>(x) % 16 != 0) return -1;
-    return launch_batch_assemble(*set, rows, quarter, u, file, index, B, M, augment, x, pos, pos_occ, label, rotations, width, occ,
-                                 static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

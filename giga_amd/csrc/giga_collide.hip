@@ -16,6 +16,7 @@
 // depends on its two bodies alone.  No atomics, no scratch.
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "giga_check.h"
 #include "giga_scan.h"
 #include "giga_ws.h"
 #include <cmath>
@@ -209,10 +210,8 @@ static CollideWs collide_workspace(int M, int P) {
     w.total = L.total;
     return w;
 }
-size_t collide_workspace_bytes(int M, int P) { return collide_workspace(M, P).total; }
-
-int launch_mesh_collide(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets, int M,
-                        const int* pairs, int P, uint8_t* hit, uint8_t* ws, hipStream_t s) {
+static int launch_mesh_collide(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets, int M,
+                               const int* pairs, int P, uint8_t* hit, uint8_t* ws, hipStream_t s) {
     const CollideWs w = collide_workspace(M, P);
     int* vo = reinterpret_cast<int*>(ws + w.offs);
     int* fo = vo + (M + 1);
@@ -223,8 +222,7 @@ int launch_mesh_collide(const float* vertices, const int* vertex_offsets, const 
     if (hipMemcpyAsync(fo, triangle_offsets, (size_t)(M + 1) * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return -10;
     if (hipMemcpyAsync(pr, pairs, (size_t)2 * P * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return -10;
     GIGA_LAUNCH(collide_init_kernel, dim3((P + CO_BLOCK - 1) / CO_BLOCK), dim3(CO_BLOCK), 0, s, hit, P);
-    int max_f = 0;
-    for (int m = 0; m < M; ++m) max_f = triangle_offsets[m + 1] - triangle_offsets[m] > max_f ? triangle_offsets[m + 1] - triangle_offsets[m] : max_f;
+    const int max_f = ragged_max_count(triangle_offsets, M);
     if (max_f > 0) {
         GIGA_LAUNCH(collide_bbox_kernel, dim3(M), dim3(CO_BLOCK), 0, s, vertices, vo, triangles, fo, bbox);
         const int tiles = (max_f + CO_BLOCK - 1) / CO_BLOCK;
@@ -235,3 +233,30 @@ int launch_mesh_collide(const float* vertices, const int* vertex_offsets, const 
 }
 
 }  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+size_t giga_mesh_collide_workspace_bytes(int M, int P) {
+    if (M <= 0 || M > GIGA_MAX_SCENES || P < 0) return 0;
+    return collide_workspace(M, P).total;
+}
+
+int giga_mesh_collide(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                      int M, const int32_t* pairs, int P, uint8_t* hit, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = ragged_batch_check(M)) return rc;
+    if (P < 0) return -1;
+    if (M == 0 || P == 0) return 0;
+    if (!mesh_batch_check(vertex_offsets, triangle_offsets, M, vertices, triangles) || !pairs || !workspace) return -1;
+    for (size_t i = 0; i < (size_t)P; ++i) {
+        const int32_t a = pairs[2 * i], b = pairs[2 * i + 1];
+        if (a < 0 || a >= M || b < 0 || b >= M || a == b) return -1;
+    }
+    if (!hit) return -6;
+    if (workspace_bytes < giga_mesh_collide_workspace_bytes(M, P)) return -4;
+    return launch_mesh_collide(vertices, vertex_offsets, triangles, triangle_offsets, M, pairs, P, hit, static_cast<uint8_t*>(workspace),
+                               static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

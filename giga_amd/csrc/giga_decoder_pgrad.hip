@@ -21,6 +21,7 @@
 // holds anyway.  That instantiation runs the occupancy head alone with upstream gradient 1 and writes the raw logit, dp and
 // (H_xy, H_xz, H_yz); logit and dp are <false>'s bit for bit.  <false> is the point gradient as it was before the template.
 #include "giga_dec_common.h"
+#include "../../include/giga_hip.h"
 
 namespace giga {
 
@@ -228,17 +229,42 @@ static int launch_pgrad(const float* planes, const float* p, const uint8_t* blob
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-int launch_decoder_point_grad(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob, int head_mask,
-                              const float* const* douts, float* const* outs, float* dp, int B, int N, hipStream_t s) {
-    return launch_pgrad<false>(planes, p, blob, bwd_blob, head_mask, douts, outs, dp, nullptr, B, N, s);
+}  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+int giga_decoder_point_grad(const void* planes_nhwc, const float* p, const void* packed, const void* bwd_packed,
+                            int head_mask, const float* dqual, const float* drot, const float* dwidth, const float* dtsdf,
+                            float* dp, float* out_qual, float* out_rot, float* out_width, float* out_tsdf,
+                            int B, int N, int flags, void* stream) {
+    if (head_mask <= 0 || (head_mask & ~15) != 0) return -1;
+    if (B <= 0 || N <= 0) return -1;
+    if (B > GIGA_MAX_SCENES) return -7;
+    if ((long long)B * N >= (1LL << 31)) return -1;         // split_scene's point index is exact below 2^31
+    if (flags != 0) return -5;
+    if (!planes_nhwc || !p || !packed || !bwd_packed || !dp) return -1;
+    const float* douts[NHEADS] = {dqual, drot, dwidth, dtsdf};
+    float* outs[NHEADS] = {out_qual, out_rot, out_width, out_tsdf};
+    for (int h = 0; h < NHEADS; ++h)
+        if ((head_mask >> h & 1) && !douts[h]) return -6;
+    return launch_pgrad<false>(static_cast<const float*>(planes_nhwc), p, static_cast<const uint8_t*>(packed),
+                               static_cast<const uint8_t*>(bwd_packed), head_mask, douts, outs, dp, nullptr, B, N,
+                               static_cast<hipStream_t>(stream));
 }
 
 // occupancy head alone, upstream gradient 1: raw logit, dp and the three Hessian entries per point
-int launch_decoder_point_hess(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob, float* logit,
-                              float* dp, float* hess, int B, int N, hipStream_t s) {
+int giga_decoder_point_hess(const void* planes_nhwc, const float* p, const void* packed, const void* bwd_packed, float* logit,
+                            float* dp, float* hess, int B, int N, void* stream) {
+    if (B <= 0 || N <= 0) return -1;
+    if (B > GIGA_MAX_SCENES) return -7;
+    if ((long long)B * N >= (1LL << 31)) return -1;         // split_scene's point index is exact below 2^31
+    if (!planes_nhwc || !p || !packed || !bwd_packed || !logit || !dp || !hess) return -1;
     const float* douts[NHEADS] = {nullptr, nullptr, nullptr, nullptr};
     float* outs[NHEADS] = {nullptr, nullptr, nullptr, logit};
-    return launch_pgrad<true>(planes, p, blob, bwd_blob, 8, douts, outs, dp, hess, B, N, s);
+    return launch_pgrad<true>(static_cast<const float*>(planes_nhwc), p, static_cast<const uint8_t*>(packed),
+                              static_cast<const uint8_t*>(bwd_packed), 8, douts, outs, dp, hess, B, N, static_cast<hipStream_t>(stream));
 }
 
-}  // namespace giga
+}  // extern "C"

@@ -18,6 +18,7 @@
 // No float atomics anywhere: equal input gives equal bytes, a batch gives scene b the bytes of a call on scene b alone.
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "giga_check.h"
 #include "giga_philox.h"
 #include "giga_scan.h"
 #include "giga_ws.h"
@@ -112,14 +113,6 @@ static NnWs nn_workspace(int B, int n_src) {
     w.total = L.total;
     return w;
 }
-size_t nn_workspace_bytes(int B, int n_src) { return nn_workspace(B, n_src).total; }
-
-// max over scenes of offs[b+1] - offs[b]
-static int ev_max_count(const int* offs, int B) {
-    int m = 0;
-    for (int b = 0; b < B; ++b) m = offs[b + 1] - offs[b] > m ? offs[b + 1] - offs[b] : m;
-    return m;
-}
 
 // how many ways to split `tiles` tiles of the inner set when the outer set alone gives `blocks` workgroups
 static int ev_split(int tiles, long long blocks) {
@@ -128,8 +121,8 @@ static int ev_split(int tiles, long long blocks) {
     return want < 1 ? 1 : want;
 }
 
-int launch_nn_query(const float* src, const int* src_offsets, const float* tgt, const int* tgt_offsets, int B, float* dist,
-                    int* idx, uint8_t* ws, hipStream_t s) {
+static int launch_nn_query(const float* src, const int* src_offsets, const float* tgt, const int* tgt_offsets, int B, float* dist,
+                           int* idx, uint8_t* ws, hipStream_t s) {
     const int n_src = src_offsets[B] - src_offsets[0], base = src_offsets[0];
     if (n_src == 0) return 0;
     const NnWs w = nn_workspace(B, src_offsets[B]);
@@ -141,7 +134,7 @@ int launch_nn_query(const float* src, const int* src_offsets, const float* tgt, 
     if (hipMemcpyAsync(to, tgt_offsets, (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return -10;
     const int nblk = ev_div_up(n_src, EV_BLOCK);
     GIGA_LAUNCH(nn_init_kernel, dim3(nblk), dim3(EV_BLOCK), 0, s, best + base, n_src);
-    const int max_s = ev_max_count(src_offsets, B), max_t = ev_max_count(tgt_offsets, B);
+    const int max_s = ragged_max_count(src_offsets, B), max_t = ragged_max_count(tgt_offsets, B);
     if (max_t > 0) {
         const int bx = ev_div_up(max_s, EV_BLOCK * NN_PTS), tiles = ev_div_up(max_t, NN_TILE);
         const int split = ev_split(tiles, (long long)bx * B), tps = ev_div_up(tiles, split);
@@ -269,11 +262,10 @@ static SampleWs sample_workspace(int B, int n_tri) {
     w.total = L.total;
     return w;
 }
-size_t sample_workspace_bytes(int B, int n_tri) { return sample_workspace(B, n_tri).total; }
 
-int launch_mesh_sample(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets, int B,
-                       int n, unsigned long long seed, int first_scene, float* points, int* face, float* normals, int* counts,
-                       uint8_t* ws, hipStream_t s) {
+static int launch_mesh_sample(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets, int B,
+                              int n, unsigned long long seed, int first_scene, float* points, int* face, float* normals, int* counts,
+                              uint8_t* ws, hipStream_t s) {
     const SampleWs w = sample_workspace(B, triangle_offsets[B]);
     int* vo = reinterpret_cast<int*>(ws + w.offs);
     int* fo = vo + (B + 1);
@@ -281,7 +273,7 @@ int launch_mesh_sample(const float* vertices, const int* vertex_offsets, const i
     double* totals = reinterpret_cast<double*>(ws + w.totals);
     if (hipMemcpyAsync(vo, vertex_offsets, (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return -10;
     if (hipMemcpyAsync(fo, triangle_offsets, (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return -10;
-    const int max_f = ev_max_count(triangle_offsets, B);
+    const int max_f = ragged_max_count(triangle_offsets, B);
     if (max_f > 0)
         GIGA_LAUNCH(sample_area_kernel, dim3(ev_div_up(max_f, EV_BLOCK), B), dim3(EV_BLOCK), 0, s, vertices, vo, triangles, fo, cum);
     GIGA_LAUNCH(sample_scan_kernel, dim3(B), dim3(EV_SCAN), 0, s, cum, fo, n, totals, counts);
@@ -477,11 +469,10 @@ static ContainsWs contains_workspace(int B, int n_tri, int n_pts) {
     w.total = L.total;
     return w;
 }
-size_t contains_workspace_bytes(int B, int n_tri, int n_pts) { return contains_workspace(B, n_tri, n_pts).total; }
 
-int launch_mesh_contains(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
-                         const double* points, const int* point_offsets, int B, int resolution, uint8_t* inside, uint8_t* ws,
-                         hipStream_t s) {
+static int launch_mesh_contains(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
+                                const double* points, const int* point_offsets, int B, int resolution, uint8_t* inside, uint8_t* ws,
+                                hipStream_t s) {
     const int n_pts = point_offsets[B] - point_offsets[0], pbase = point_offsets[0];
     if (n_pts == 0) return 0;
     const ContainsWs w = contains_workspace(B, triangle_offsets[B], point_offsets[B]);
@@ -497,7 +488,7 @@ int launch_mesh_contains(const float* vertices, const int* vertex_offsets, const
     if (hipMemcpyAsync(po, point_offsets, (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return -10;
     const int nblk = ev_div_up(n_pts, EV_BLOCK);
     GIGA_LAUNCH(contains_init_kernel, dim3(nblk), dim3(EV_BLOCK), 0, s, hits + pbase, n_pts);
-    const int max_f = ev_max_count(triangle_offsets, B), max_p = ev_max_count(point_offsets, B);
+    const int max_f = ragged_max_count(triangle_offsets, B), max_p = ragged_max_count(point_offsets, B);
     if (max_f > 0) {
         GIGA_LAUNCH(contains_bbox_kernel, dim3(B), dim3(EV_SCAN), 0, s, vertices, vo, triangles, fo, resolution, xform);
         GIGA_LAUNCH(contains_prep_kernel, dim3(ev_div_up(max_f, EV_BLOCK), B), dim3(EV_BLOCK), 0, s, vertices, vo, triangles, fo,
@@ -512,3 +503,65 @@ int launch_mesh_contains(const float* vertices, const int* vertex_offsets, const
 }
 
 }  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+size_t giga_nn_query_workspace_bytes(int B, int n_src) {
+    if (B <= 0 || B > GIGA_MAX_SCENES || n_src < 0) return 0;
+    return nn_workspace(B, n_src).total;
+}
+
+int giga_nn_query(const float* src, const int32_t* src_offsets, const float* tgt, const int32_t* tgt_offsets, int B, float* dist,
+                  int32_t* idx, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = ragged_batch_check(B)) return rc;
+    if (B == 0) return 0;
+    if (!ragged_ok(src_offsets, B) || !ragged_ok(tgt_offsets, B)) return -1;
+    if (src_offsets[B] == 0) return 0;
+    if (!src || (tgt_offsets[B] > 0 && !tgt) || !workspace) return -1;
+    if (!dist || !idx) return -6;
+    if (workspace_bytes < giga_nn_query_workspace_bytes(B, src_offsets[B])) return -4;
+    return launch_nn_query(src, src_offsets, tgt, tgt_offsets, B, dist, idx, static_cast<uint8_t*>(workspace),
+                           static_cast<hipStream_t>(stream));
+}
+
+size_t giga_mesh_sample_workspace_bytes(int B, int n_triangles) {
+    if (B <= 0 || B > GIGA_MAX_SCENES || n_triangles < 0) return 0;
+    return sample_workspace(B, n_triangles).total;
+}
+
+int giga_mesh_sample(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                     int B, int n, uint64_t seed, int first_scene, float* points, int32_t* face, float* normals, int32_t* counts,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = ragged_batch_check(B)) return rc;
+    if (n < 0 || first_scene < 0 || (long long)B * n >= (1LL << 31)) return -1;
+    if (B == 0) return 0;
+    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !workspace) return -1;
+    if (!counts || (n > 0 && (!points || !face || !normals))) return -6;
+    if (workspace_bytes < giga_mesh_sample_workspace_bytes(B, triangle_offsets[B])) return -4;
+    return launch_mesh_sample(vertices, vertex_offsets, triangles, triangle_offsets, B, n, seed, first_scene, points, face, normals, counts,
+                              static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+size_t giga_mesh_contains_workspace_bytes(int B, int n_triangles, int n_points) {
+    if (B <= 0 || B > GIGA_MAX_SCENES || n_triangles < 0 || n_points < 0) return 0;
+    return contains_workspace(B, n_triangles, n_points).total;
+}
+
+int giga_mesh_contains(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                       const double* points, const int32_t* point_offsets, int B, int resolution, uint8_t* inside, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    if (const int rc = ragged_batch_check(B)) return rc;
+    if (resolution < 2 || resolution > GIGA_CONTAINS_MAX_RESOLUTION) return -1;
+    if (B == 0) return 0;
+    if (!ragged_ok(vertex_offsets, B) || !ragged_ok(triangle_offsets, B) || !ragged_ok(point_offsets, B)) return -1;
+    if (point_offsets[B] == 0) return 0;                    // (whatever the data pointers: only the offsets are looked at before)
+    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !points || !workspace) return -1;
+    if (!inside) return -6;
+    if (workspace_bytes < giga_mesh_contains_workspace_bytes(B, triangle_offsets[B], point_offsets[B])) return -4;
+    return launch_mesh_contains(vertices, vertex_offsets, triangles, triangle_offsets, points, point_offsets, B, resolution, inside,
+                                static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -15,6 +15,7 @@
 //               Both loops stride over the grid inside the scene.  A wave adds its four sums once.
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "giga_check.h"
 #include "giga_philox.h"
 #include "giga_ws.h"
 #include <cstdint>
@@ -62,10 +63,9 @@ static RoiWs roi_workspace(int G) {
     w.total = L.total;
     return w;
 }
-size_t roi_workspace_bytes(int G) { return roi_workspace(G).total; }
 
-int launch_roi_points(const double* grasps, const int* offsets, const int* scene, const int* first, int G, unsigned long long seed,
-                      double extent, double size, double* world, float* normalised, uint8_t* ws, hipStream_t s) {
+static int launch_roi_points(const double* grasps, const int* offsets, const int* scene, const int* first, int G, unsigned long long seed,
+                             double extent, double size, double* world, float* normalised, uint8_t* ws, hipStream_t s) {
     const int n = offsets[G];
     if (n == 0) return 0;
     const RoiWs w = roi_workspace(G);
@@ -151,17 +151,16 @@ __global__ __launch_bounds__(GEO_BLOCK) void occ_confusion_kernel(const float* _
     }
 }
 
-size_t confusion_workspace_bytes(int B) {
+static size_t confusion_workspace_bytes(int B) {
     WsLayout L;
     L.take<int>((size_t)B + 1);
     return L.total;
 }
 
-int launch_occ_confusion(const float* logits, const uint8_t* pred, double th, const uint8_t* target, const int* offsets, int B,
-                         unsigned long long* counts, uint8_t* ws, hipStream_t s) {
+static int launch_occ_confusion(const float* logits, const uint8_t* pred, double th, const uint8_t* target, const int* offsets, int B,
+                                unsigned long long* counts, uint8_t* ws, hipStream_t s) {
     if (hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(unsigned long long), s) != hipSuccess) return -10;
-    int max_n = 0;
-    for (int b = 0; b < B; ++b) max_n = offsets[b + 1] - offsets[b] > max_n ? offsets[b + 1] - offsets[b] : max_n;
+    const int max_n = ragged_max_count(offsets, B);
     if (max_n == 0) return 0;
     int* d_off = reinterpret_cast<int*>(ws);
     if (hipMemcpyAsync(d_off, offsets, (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return -10;
@@ -178,3 +177,56 @@ int launch_occ_confusion(const float* logits, const uint8_t* pred, double th, co
 }
 
 }  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+size_t giga_roi_points_workspace_bytes(int n_grasps) {
+    if (n_grasps <= 0) return 0;
+    return roi_workspace(n_grasps).total;
+}
+
+int giga_roi_points(const double* grasps, const int32_t* point_offsets, const int32_t* grasp_scene, const int32_t* grasp_first,
+                    int n_grasps, uint64_t seed, double finger_depth, double roi_scale, double size, double* world,
+                    float* normalised, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_grasps < 0) return -1;
+    if (!finite_f64(finger_depth) || !finite_f64(roi_scale) || !finite_f64(size) || size == 0.0) return -1;
+    if (n_grasps == 0) return 0;
+    if (!ragged_ok(point_offsets, n_grasps)) return -1;
+    if (point_offsets[n_grasps] == 0) return 0;
+    if (!grasps || !grasp_scene || !grasp_first || !workspace) return -1;
+    for (int g = 0; g < n_grasps; ++g) {
+        // (the point index inside the scene is one 32-bit counter word)
+        if (grasp_scene[g] < 0 || grasp_first[g] < 0 ||
+            (long long)grasp_first[g] + (point_offsets[g + 1] - point_offsets[g]) > 0x7fffffffLL)
+            return -1;
+        for (int q = 0; q < 13; ++q)
+            if (!finite_f64(grasps[13 * (size_t)g + q])) return -1;
+    }
+    if (!world || !normalised) return -6;
+    if (workspace_bytes < giga_roi_points_workspace_bytes(n_grasps)) return -4;
+    return launch_roi_points(grasps, point_offsets, grasp_scene, grasp_first, n_grasps, seed, finger_depth * roi_scale, size, world,
+                             normalised, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+size_t giga_occ_confusion_workspace_bytes(int B) {
+    if (B <= 0 || B > GIGA_MAX_SCENES) return 0;
+    return confusion_workspace_bytes(B);
+}
+
+int giga_occ_confusion(const float* logits, const uint8_t* pred, double logit_threshold, const uint8_t* target,
+                       const int32_t* offsets, int B, uint64_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = ragged_batch_check(B)) return rc;
+    if (B == 0) return 0;
+    if (!ragged_ok(offsets, B)) return -1;
+    if ((logits != nullptr) == (pred != nullptr) && offsets[B] > 0) return -1;         // exactly one form of the prediction
+    if ((offsets[B] > 0 && !target) || !workspace) return -1;
+    if (logits && !(logit_threshold == logit_threshold)) return -1;
+    if (!counts) return -6;
+    if (workspace_bytes < giga_occ_confusion_workspace_bytes(B)) return -4;
+    return launch_occ_confusion(logits, pred, logit_threshold, target, offsets, B, reinterpret_cast<unsigned long long*>(counts),
+                                static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -15,6 +15,7 @@
 // reference's helpers to fp32 rounding (tests/test_gpu_training.py, golden G11).
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "../../include/giga_hip.h"
 #include <cmath>
 
 namespace giga {
@@ -168,34 +169,6 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
     }
 }
 
-int launch_train_loss(const float* qual, const float* rot, const float* width, const float* occ, const float* label,
-                      const float* rot_t, const float* width_t, const float* occ_t, int B, int M, float* losses,
-                      float* scene_loss, hipStream_t s) {
-    GIGA_LAUNCH(loss_scene_kernel, dim3(B), dim3(256), 0, s, qual, rot, width, occ, label, rot_t, width_t, occ_t, M,
-                       scene_loss);
-    GIGA_LAUNCH(loss_mean_kernel, dim3(1), dim3(64), 0, s, scene_loss, B, losses);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-int launch_train_loss_metrics(const float* qual, const float* rot, const float* width, const float* occ, const float* label,
-                              const float* rot_t, const float* width_t, const float* occ_t, int B, int M, float* losses,
-                              float* scene_loss, void* acc, hipStream_t s) {
-    GIGA_LAUNCH(loss_scene_kernel, dim3(B), dim3(256), 0, s, qual, rot, width, occ, label, rot_t, width_t, occ_t, M,
-                       scene_loss);
-    GIGA_LAUNCH(loss_mean_metrics_kernel, dim3(1), dim3(256), 0, s, scene_loss, qual, label, B, losses,
-                       static_cast<unsigned long long*>(acc));
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-int launch_train_loss_backward(const float* qual, const float* rot, const float* width, const float* occ,
-                               const float* label, const float* rot_t, const float* width_t, const float* occ_t,
-                               const float* gout, int B, int M, float* dqual, float* drot, float* dwidth, float* docc,
-                               hipStream_t s) {
-    GIGA_LAUNCH(loss_grad_kernel, dim3(B), dim3(256), 0, s, qual, rot, width, occ, label, rot_t, width_t, occ_t, gout,
-                       B, M, dqual, drot, dwidth, docc);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The occupancy-only objective of giga_geo (scripts/train_giga_geo.py:152-165: loss = mean_B mean_M BCE(sigmoid(z), t)) and its
@@ -303,22 +276,6 @@ __global__ __launch_bounds__(256) void occ_grad_kernel(const float* __restrict__
     }
 }
 
-int launch_train_occ_loss(const float* occ, const float* occ_t, int B, int M, float* loss, float* scene_loss, unsigned* scene_counts,
-                          void* acc, hipStream_t s) {
-    GIGA_LAUNCH(occ_scene_kernel, dim3(B), dim3(256), 0, s, occ, occ_t, M, scene_loss, acc ? scene_counts : nullptr);
-    if (acc)
-        GIGA_LAUNCH(occ_mean_metrics_kernel, dim3(1), dim3(128), 0, s, scene_loss, scene_counts, B, loss,
-                           static_cast<unsigned long long*>(acc));
-    else
-        GIGA_LAUNCH(occ_mean_kernel, dim3(1), dim3(64), 0, s, scene_loss, B, loss);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-int launch_train_occ_loss_backward(const float* occ, const float* occ_t, const float* gout, int B, int M, float* docc, hipStream_t s) {
-    GIGA_LAUNCH(occ_grad_kernel, dim3(B), dim3(256), 0, s, occ, occ_t, gout, B, M, docc);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Adam over ONE flat fp32 parameter buffer (the module's flattened parameters, 581 863 elements): torch.optim.Adam's update
@@ -350,15 +307,112 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(float4* __restrict__ p, 
     }
 }
 
-int launch_adam_flat(float* p, const float* g, float* m, float* v, size_t n, double lr, double b1, double b2, double eps, double wd,
-                     int step, hipStream_t s) {
-    if (n == 0) return 0;
-    const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);     // (hyper-parameters stay double on the host, as in torch)
-    const size_t n4 = n / 4;
-    GIGA_LAUNCH(adam_flat_kernel, dim3((unsigned)((n4 + 1 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<float4*>(p),
-                       reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v), n4, n,
-                       (float)(lr / bc1), (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)eps, (float)wd, (float)sqrt(bc2));
+}  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+int giga_train_loss(const float* qual, const float* rot, const float* width, const float* occ_logits, const float* label,
+                    const float* rot_targets, const float* width_target, const float* occ_target, int B, int M,
+                    float* losses, float* scene_losses, void* stream) {
+    if (B < 0 || M < 0) return -1;
+    if (B == 0) return 0;
+    if (!qual || !rot || !width || !label || !rot_targets || !width_target || !losses || !scene_losses) return -1;
+    if (M > 0 && (!occ_logits || !occ_target)) return -1;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GIGA_LAUNCH(loss_scene_kernel, dim3(B), dim3(256), 0, s, qual, rot, width, occ_logits, label, rot_targets, width_target, occ_target,
+                M, scene_losses);
+    GIGA_LAUNCH(loss_mean_kernel, dim3(1), dim3(64), 0, s, scene_losses, B, losses);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-}  // namespace giga
+int giga_train_loss_metrics(const float* qual, const float* rot, const float* width, const float* occ_logits, const float* label,
+                            const float* rot_targets, const float* width_target, const float* occ_target, int B, int M,
+                            float* losses, float* scene_losses, void* acc, void* stream) {
+    if (B < 0 || M < 0) return -1;
+    if (!acc || (reinterpret_cast<uintptr_t>(acc) & 7)) return -1;
+    if (B == 0) return 0;
+    if (!qual || !rot || !width || !label || !rot_targets || !width_target || !losses || !scene_losses) return -1;
+    if (M > 0 && (!occ_logits || !occ_target)) return -1;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GIGA_LAUNCH(loss_scene_kernel, dim3(B), dim3(256), 0, s, qual, rot, width, occ_logits, label, rot_targets, width_target, occ_target,
+                M, scene_losses);
+    GIGA_LAUNCH(loss_mean_metrics_kernel, dim3(1), dim3(256), 0, s, scene_losses, qual, label, B, losses,
+                static_cast<unsigned long long*>(acc));
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int giga_train_loss_backward(const float* qual, const float* rot, const float* width, const float* occ_logits,
+                             const float* label, const float* rot_targets, const float* width_target,
+                             const float* occ_target, const float* grad_loss, int B, int M, float* dqual, float* drot,
+                             float* dwidth, float* docc, void* stream) {
+    if (B < 0 || M < 0) return -1;
+    if (B == 0) return 0;
+    if (!qual || !rot || !width || !label || !rot_targets || !width_target || !grad_loss || !dqual || !drot || !dwidth)
+        return -1;
+    if (M > 0 && (!occ_logits || !occ_target || !docc)) return -1;
+    GIGA_LAUNCH(loss_grad_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), qual, rot, width, occ_logits, label,
+                rot_targets, width_target, occ_target, grad_loss, B, M, dqual, drot, dwidth, docc);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+// the occupancy objective: with `acc` the epoch metrics too (scene_counts is read only then)
+static int launch_train_occ_loss(const float* occ, const float* occ_t, int B, int M, float* loss, float* scene_loss, unsigned* scene_counts,
+                                 void* acc, hipStream_t s) {
+    GIGA_LAUNCH(occ_scene_kernel, dim3(B), dim3(256), 0, s, occ, occ_t, M, scene_loss, acc ? scene_counts : nullptr);
+    if (acc)
+        GIGA_LAUNCH(occ_mean_metrics_kernel, dim3(1), dim3(128), 0, s, scene_loss, scene_counts, B, loss,
+                    static_cast<unsigned long long*>(acc));
+    else
+        GIGA_LAUNCH(occ_mean_kernel, dim3(1), dim3(64), 0, s, scene_loss, B, loss);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int giga_train_occ_loss(const float* occ_logits, const float* occ_target, int B, int M, float* loss, float* scene_losses,
+                        void* stream) {
+    if (B < 0 || M < 0) return -1;
+    if (B == 0) return 0;
+    if (M == 0) return -1;                                  // the loss of a scene is a mean over its points
+    if (!occ_logits || !occ_target || !loss || !scene_losses) return -1;
+    return launch_train_occ_loss(occ_logits, occ_target, B, M, loss, scene_losses, nullptr, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int giga_train_occ_loss_metrics(const float* occ_logits, const float* occ_target, int B, int M, float* loss, float* scene_losses,
+                                uint32_t* scene_counts, void* acc, void* stream) {
+    if (B < 0 || M < 0) return -1;
+    if (!acc || (reinterpret_cast<uintptr_t>(acc) & 7)) return -1;
+    if (B == 0) return 0;
+    if (M == 0) return -1;
+    if (!occ_logits || !occ_target || !loss || !scene_losses || !scene_counts) return -1;
+    return launch_train_occ_loss(occ_logits, occ_target, B, M, loss, scene_losses, scene_counts, acc, static_cast<hipStream_t>(stream));
+}
+
+int giga_train_occ_loss_backward(const float* occ_logits, const float* occ_target, const float* grad_loss, int B, int M, float* docc,
+                                 void* stream) {
+    if (B < 0 || M < 0) return -1;
+    if (B == 0) return 0;
+    if (M == 0) return -1;
+    if (!occ_logits || !occ_target || !grad_loss || !docc) return -1;
+    GIGA_LAUNCH(occ_grad_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), occ_logits, occ_target, grad_loss, B, M, docc);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int giga_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
+                   double beta2, double eps, double weight_decay, int step, void* stream) {
+    if (n == 0) return 0;
+    if (!params || !grads || !exp_avg || !exp_avg_sq || step < 1) return -1;
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0)) return -1;
+    // the kernel moves float4: all four buffers must be 16-byte aligned (whole torch allocations are; a view at an odd offset is not)
+    if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
+         reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) return -1;
+    const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);     // (hyper-parameters stay double on the host, as in torch)
+    const size_t n4 = n / 4;
+    GIGA_LAUNCH(adam_flat_kernel, dim3((unsigned)((n4 + 1 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                reinterpret_cast<float4*>(params), reinterpret_cast<const float4*>(grads), reinterpret_cast<float4*>(exp_avg),
+                reinterpret_cast<float4*>(exp_avg_sq), n4, n, (float)(lr / bc1), (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
+                (float)eps, (float)weight_decay, (float)sqrt(bc2));
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+}  // extern "C"

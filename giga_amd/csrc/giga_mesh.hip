@@ -22,6 +22,7 @@
 // Integer work on a few bytes per cell: no MFMA, 4.3 KB of LDS for the case tables (read with a divergent index).
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "giga_check.h"
 #include "giga_scan.h"
 #include "giga_ws.h"
 #define GIGA_MC_QUAL __device__ __attribute__((aligned(16)))
@@ -218,7 +219,7 @@ MeshDims mesh_dims(int nx, int ny, int nz) {
 }
 
 struct MeshWs { size_t words, blk, bases, total; };
-MeshWs mesh_workspace(int B, int nx, int ny, int nz) {
+static MeshWs mesh_workspace(int B, int nx, int ny, int nz) {
     const MeshDims d = mesh_dims(nx, ny, nz);
     WsLayout L;
     MeshWs w;
@@ -229,8 +230,6 @@ MeshWs mesh_workspace(int B, int nx, int ny, int nz) {
     return w;
 }
 
-size_t mesh_workspace_bytes(int B, int nx, int ny, int nz) { return mesh_workspace(B, nx, ny, nz).total; }
-
 // the largest float <= iso: (double)v <= iso  <=>  v <= isof for every float v
 static float iso_floor(double iso) {
     float f = (float)iso;
@@ -238,7 +237,36 @@ static float iso_floor(double iso) {
     return f;
 }
 
-int launch_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, uint8_t* ws, int* counts, hipStream_t s) {
+}  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+// counts and triangle entries are int32: a scene has at most 3 vertices and 5 triangles per cell
+static_assert(5LL * (GIGA_MESH_MAX_N + 1) * (GIGA_MESH_MAX_N + 1) * (GIGA_MESH_MAX_N + 1) < (1LL << 31), "per-scene counts are int32");
+// 0 when the shape is supported, else the error code
+static int mesh_shape_check(int B, int nx, int ny, int nz) {
+    if (B < 0 || nx < 2 || ny < 2 || nz < 2) return -1;
+    if (nx > GIGA_MESH_MAX_N || ny > GIGA_MESH_MAX_N || nz > GIGA_MESH_MAX_N) return -1;
+    if (B > GIGA_MAX_SCENES) return -7;
+    if ((long long)B * (nx + 1) * (ny + 1) * (nz + 1) >= (1LL << 31)) return -1;      // cell numbers are 32-bit
+    return 0;
+}
+
+size_t giga_mesh_workspace_bytes(int B, int nx, int ny, int nz) {
+    if (B <= 0 || mesh_shape_check(B, nx, ny, nz) != 0) return 0;
+    return mesh_workspace(B, nx, ny, nz).total;
+}
+
+int giga_mesh_count(const float* grids, int B, int nx, int ny, int nz, double iso, void* workspace, size_t workspace_bytes,
+                    int32_t* counts, void* stream) {
+    if (const int rc = mesh_shape_check(B, nx, ny, nz)) return rc;
+    if (B == 0) return 0;
+    if (!grids || !workspace || !counts || !(iso == iso)) return -1;
+    if (workspace_bytes < giga_mesh_workspace_bytes(B, nx, ny, nz)) return -4;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
     const MeshDims d = mesh_dims(nx, ny, nz);
     const MeshWs w = mesh_workspace(B, nx, ny, nz);
     unsigned* words = reinterpret_cast<unsigned*>(ws + w.words);
@@ -251,15 +279,22 @@ int launch_mesh_count(const float* grids, int B, int nx, int ny, int nz, double 
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-int launch_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso, double box, const uint8_t* ws, float* vertices,
-                     size_t cap_v, int* triangles, size_t cap_t, int* shortfall, hipStream_t s) {
+int giga_mesh_emit(const float* grids, int B, int nx, int ny, int nz, double iso, double box_size, const void* workspace,
+                   size_t workspace_bytes, float* vertices, size_t cap_v, int32_t* triangles, size_t cap_t, int32_t* shortfall,
+                   void* stream) {
+    if (const int rc = mesh_shape_check(B, nx, ny, nz)) return rc;
+    if (B == 0) return 0;
+    if (!grids || !workspace || !(iso == iso) || !(box_size == box_size)) return -1;
+    if ((cap_v > 0 && !vertices) || (cap_t > 0 && !triangles)) return -6;
+    if (workspace_bytes < giga_mesh_workspace_bytes(B, nx, ny, nz)) return -4;
+    const uint8_t* ws = static_cast<const uint8_t*>(workspace);
     const MeshDims d = mesh_dims(nx, ny, nz);
     const MeshWs w = mesh_workspace(B, nx, ny, nz);
-    GIGA_LAUNCH(mesh_emit_kernel, dim3(d.nblk, B), dim3(MESH_BLOCK), 0, s, grids, d, iso_floor(iso), iso, box,
-                reinterpret_cast<const unsigned*>(ws + w.words), reinterpret_cast<const uint2*>(ws + w.blk),
+    GIGA_LAUNCH(mesh_emit_kernel, dim3(d.nblk, B), dim3(MESH_BLOCK), 0, static_cast<hipStream_t>(stream), grids, d, iso_floor(iso), iso,
+                box_size, reinterpret_cast<const unsigned*>(ws + w.words), reinterpret_cast<const uint2*>(ws + w.blk),
                 reinterpret_cast<const unsigned long long*>(ws + w.bases), B, vertices, (unsigned long long)cap_v, triangles,
                 (unsigned long long)cap_t, shortfall);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-}  // namespace giga
+}  // extern "C"

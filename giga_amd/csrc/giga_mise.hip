@@ -25,6 +25,7 @@
 // Integer work on one byte per sample: no MFMA, no LDS beyond the scan's few words.
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "giga_check.h"
 #include "giga_scan.h"
 #include "giga_ws.h"
 #include <cmath>
@@ -70,7 +71,7 @@ MiseDims mise_dims(int res0, int depth) {
 
 // counts | blk | dirty | state | tree | values : all but the values are cleared by one fill at init
 struct MiseWs { size_t counts, blk, dirty, state, tree, values, total; };
-MiseWs mise_workspace(int B, int res0, int depth) {
+static MiseWs mise_workspace(int B, int res0, int depth) {
     const MiseDims d = mise_dims(res0, depth);
     WsLayout L;
     MiseWs w;
@@ -83,7 +84,6 @@ MiseWs mise_workspace(int B, int res0, int depth) {
     w.total = L.total;
     return w;
 }
-size_t mise_workspace_bytes(int B, int res0, int depth) { return mise_workspace(B, res0, depth).total; }
 
 __global__ __launch_bounds__(MISE_BLOCK) void mise_fill_kernel(unsigned* __restrict__ p, size_t n, unsigned v) {
     for (size_t i = (size_t)blockIdx.x * MISE_BLOCK + threadIdx.x; i < n; i += (size_t)gridDim.x * MISE_BLOCK) p[i] = v;
@@ -342,7 +342,7 @@ __global__ __launch_bounds__(MISE_BLOCK) void mise_dense_z_kernel(MiseDims d, fl
 }
 
 // ---- launches ------------------------------------------------------------------------------------------------------------------
-int launch_mise_init(int B, int res0, int depth, uint8_t* ws, hipStream_t s) {
+static int launch_mise_init(int B, int res0, int depth, uint8_t* ws, hipStream_t s) {
     const MiseDims d = mise_dims(res0, depth);
     const MiseWs w = mise_workspace(B, res0, depth);
     const size_t nwords = w.values / 4;                     // counts, workgroup sums, dirty, state, tree
@@ -353,7 +353,7 @@ int launch_mise_init(int B, int res0, int depth, uint8_t* ws, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-int launch_mise_count(int B, int res0, int depth, uint8_t* ws, int* counts, hipStream_t s) {
+static int launch_mise_count(int B, int res0, int depth, uint8_t* ws, int* counts, hipStream_t s) {
     const MiseDims d = mise_dims(res0, depth);
     const MiseWs w = mise_workspace(B, res0, depth);
     unsigned* blk = reinterpret_cast<unsigned*>(ws + w.blk);
@@ -364,8 +364,8 @@ int launch_mise_count(int B, int res0, int depth, uint8_t* ws, int* counts, hipS
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-int launch_mise_emit(int B, int res0, int depth, const uint8_t* ws, int* query, size_t cap, int* shortfall, const float* lin,
-                     float* points, hipStream_t s) {
+static int launch_mise_emit(int B, int res0, int depth, const uint8_t* ws, int* query, size_t cap, int* shortfall, const float* lin,
+                            float* points, hipStream_t s) {
     const MiseDims d = mise_dims(res0, depth);
     const MiseWs w = mise_workspace(B, res0, depth);
     const int* ws_counts = reinterpret_cast<const int*>(ws + w.counts);
@@ -377,8 +377,8 @@ int launch_mise_emit(int B, int res0, int depth, const uint8_t* ws, int* query, 
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-int launch_mise_update(const float* values, const int* query, size_t cap, int B, int res0, int depth, double thr, uint8_t* ws,
-                       hipStream_t s) {
+static int launch_mise_update(const float* values, const int* query, size_t cap, int B, int res0, int depth, double thr, uint8_t* ws,
+                              hipStream_t s) {
     const MiseDims d = mise_dims(res0, depth);
     const MiseWs w = mise_workspace(B, res0, depth);
     unsigned* tree = reinterpret_cast<unsigned*>(ws + w.tree);
@@ -392,7 +392,7 @@ int launch_mise_update(const float* values, const int* query, size_t cap, int B,
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-int launch_mise_to_dense(int B, int res0, int depth, const uint8_t* ws, float* grid, hipStream_t s) {
+static int launch_mise_to_dense(int B, int res0, int depth, const uint8_t* ws, float* grid, hipStream_t s) {
     const MiseDims d = mise_dims(res0, depth);
     const MiseWs w = mise_workspace(B, res0, depth);
     const unsigned plane = d.N * d.N;
@@ -404,3 +404,72 @@ int launch_mise_to_dense(int B, int res0, int depth, const uint8_t* ws, float* g
 }
 
 }  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+// 0 when the tree shape is supported, else the error code
+static int mise_shape_check(int B, int res0, int depth) {
+    if (B < 0 || res0 < 1 || depth < 1 || depth > 30) return -1;
+    if (((long long)res0 << depth) + 1 > GIGA_MISE_MAX_N) return -1;
+    if (B > GIGA_MAX_SCENES) return -7;
+    const long long N = ((long long)res0 << depth) + 1;
+    if ((long long)B * N * N * N >= (1LL << 31)) return -1;                           // sample numbers are 32-bit
+    return 0;
+}
+
+size_t giga_mise_workspace_bytes(int B, int resolution0, int depth) {
+    if (B <= 0 || mise_shape_check(B, resolution0, depth) != 0) return 0;
+    return mise_workspace(B, resolution0, depth).total;
+}
+
+int giga_mise_init(int B, int resolution0, int depth, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
+    if (B == 0) return 0;
+    if (!workspace) return -1;
+    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
+    return launch_mise_init(B, resolution0, depth, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+int giga_mise_count(int B, int resolution0, int depth, void* workspace, size_t workspace_bytes, int32_t* counts, void* stream) {
+    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
+    if (B == 0) return 0;
+    if (!workspace || !counts) return -1;
+    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
+    return launch_mise_count(B, resolution0, depth, static_cast<uint8_t*>(workspace), counts, static_cast<hipStream_t>(stream));
+}
+
+int giga_mise_emit(int B, int resolution0, int depth, const void* workspace, size_t workspace_bytes, int32_t* query, size_t cap,
+                   int32_t* shortfall, const float* lin, float* points, void* stream) {
+    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
+    if (B == 0) return 0;
+    if (!workspace || (points && !lin)) return -1;
+    if (cap > 0 && !query) return -6;
+    if ((unsigned long long)B * cap >= (1ull << 31)) return -1;
+    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
+    return launch_mise_emit(B, resolution0, depth, static_cast<const uint8_t*>(workspace), query, cap, shortfall, lin, points,
+                            static_cast<hipStream_t>(stream));
+}
+
+int giga_mise_update(const float* values, const int32_t* query, size_t cap, int B, int resolution0, int depth, double threshold,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
+    if (!(threshold == threshold)) return -1;
+    if (B == 0) return 0;
+    if (!workspace || (cap > 0 && (!values || !query))) return -1;
+    if ((unsigned long long)B * cap >= (1ull << 31)) return -1;
+    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
+    return launch_mise_update(values, query, cap, B, resolution0, depth, threshold, static_cast<uint8_t*>(workspace),
+                              static_cast<hipStream_t>(stream));
+}
+
+int giga_mise_to_dense(int B, int resolution0, int depth, const void* workspace, size_t workspace_bytes, float* grid, void* stream) {
+    if (const int rc = mise_shape_check(B, resolution0, depth)) return rc;
+    if (B == 0) return 0;
+    if (!workspace || !grid) return -1;
+    if (workspace_bytes < giga_mise_workspace_bytes(B, resolution0, depth)) return -4;
+    return launch_mise_to_dense(B, resolution0, depth, static_cast<const uint8_t*>(workspace), grid, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -13,6 +13,7 @@
 // Every operation is one IEEE rounding (no contraction); log, cos, sin and pow are the only places a device and numpy may differ.
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "giga_check.h"
 #include "giga_philox.h"
 #include "giga_ws.h"
 #include <cmath>
@@ -187,10 +188,10 @@ __global__ __launch_bounds__(NOISE_BLOCK) void depth_noise_kernel(NoiseArgs a) {
     }
 }
 
-size_t depth_noise_workspace_bytes(int n) { return ws_align((size_t)(n > 0 ? n : 1) * sizeof(unsigned long long)); }
+static size_t depth_noise_workspace_bytes(int n) { return ws_align((size_t)(n > 0 ? n : 1) * sizeof(unsigned long long)); }
 
-int launch_depth_noise(const float* in, float* out, int n, int W, int H, int model, const double* p, unsigned long long seed,
-                       const unsigned long long* image_ids, uint8_t* ws, hipStream_t s) {
+static int launch_depth_noise(const float* in, float* out, int n, int W, int H, int model, const double* p, unsigned long long seed,
+                              const unsigned long long* image_ids, uint8_t* ws, hipStream_t s) {
     NoiseArgs a{};
     a.in = in; a.out = out;
     a.ids = nullptr;
@@ -225,3 +226,48 @@ int launch_depth_noise(const float* in, float* out, int n, int W, int H, int mod
 }
 
 }  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+static bool noise_positive(double x) { return finite_f64(x) && x > 0.0; }
+
+static bool noise_shape_ok(int n, int W, int H, int model) {
+    if (n < 0 || W < 1 || H < 1 || W > GIGA_TSDF_MAX_IMAGE || H > GIGA_TSDF_MAX_IMAGE) return false;
+    if ((long long)n * W * H >= (1LL << 31)) return false;
+    return model >= GIGA_NOISE_DEX && model <= GIGA_NOISE_NORM;
+}
+
+size_t giga_depth_noise_workspace_bytes(int n_images, int width, int height, int model) {
+    if (!noise_shape_ok(n_images, width, height, model) || n_images == 0) return 0;
+    return depth_noise_workspace_bytes(n_images);
+}
+
+int giga_depth_noise(const float* depth_in, float* depth_out, int n_images, int width, int height, int model, const double* params,
+                     unsigned long long seed, const unsigned long long* image_ids, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+    if (!noise_shape_ok(n_images, width, height, model)) return -1;
+    static const double defaults[3][5] = {{1000.0, 0.001, 0.005, 4.0, 0.5}, {1.0, 0.005, 0, 0, 0}, {0.005, 0, 0, 0, 0}};
+    static const int count[3] = {5, 2, 1};
+    double p[5] = {0, 0, 0, 0, 0};
+    for (int i = 0; i < count[model - 1]; ++i) p[i] = params ? params[i] : defaults[model - 1][i];
+    if (model == GIGA_NOISE_DEX) {
+        if (!noise_positive(p[0]) || !noise_positive(p[1]) || !noise_positive(p[2]) || !noise_positive(p[3])) return -1;
+        if (!(p[4] >= 0.0 && p[4] <= 1.0)) return -1;
+        if (p[3] < 1.0 || (double)height < p[3] || (double)width < p[3]) return -1;
+    } else {
+        for (int i = 0; i < count[model - 1]; ++i)
+            if (!noise_positive(p[i])) return -1;
+    }
+    if (n_images == 0) return 0;
+    if (!depth_in || !depth_out || !workspace) return -1;
+    const size_t bytes = (size_t)n_images * width * height * sizeof(float);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(depth_in), b = reinterpret_cast<uintptr_t>(depth_out);
+    if (a < b + bytes && b < a + bytes) return -1;                               // out of place: trans is a gather
+    if (workspace_bytes < giga_depth_noise_workspace_bytes(n_images, width, height, model)) return -4;
+    return launch_depth_noise(depth_in, depth_out, n_images, width, height, model, p, seed, image_ids,
+                              static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -153,28 +153,51 @@ __global__ __launch_bounds__(REFINE_BLOCK) void refine_vertex_step_kernel(const 
     }
 }
 
-int launch_refine_face_points(const float* vertices, const int* faces, const float* eps_in, float* eps, float* points, int V, int F,
-                              unsigned long long seed, int step, hipStream_t s) {
-    const int blocks = (F + REFINE_BLOCK - 1) / REFINE_BLOCK;
-    GIGA_LAUNCH(refine_face_points_kernel, dim3(blocks), dim3(REFINE_BLOCK), 0, s, vertices, faces, eps_in, eps, points, V, F,
-                (unsigned)seed, (unsigned)(seed >> 32), (unsigned)step);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-int launch_refine_face_grad(const float* vertices, const int* faces, const float* eps, const float* logit, const float* dp,
-                            const float* hess, double threshold, float* floss, float* fgrad, int V, int F, hipStream_t s) {
-    const int blocks = (F + REFINE_BLOCK - 1) / REFINE_BLOCK;
-    GIGA_LAUNCH(refine_face_grad_kernel, dim3(blocks), dim3(REFINE_BLOCK), 0, s, vertices, faces, eps, logit, dp, hess, threshold,
-                floss, fgrad, V, F);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-int launch_refine_vertex_step(const float* fgrad, const int* corner_order, const int* vertex_offsets, float* vertices,
-                              float* square_avg, float* grad, int V, int F, hipStream_t s) {
-    const int blocks = (V + REFINE_BLOCK - 1) / REFINE_BLOCK;
-    GIGA_LAUNCH(refine_vertex_step_kernel, dim3(blocks), dim3(REFINE_BLOCK), 0, s, fgrad, corner_order, vertex_offsets, vertices,
-                square_avg, grad, V, F);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
 }  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+// 3 F corner indices and 9 F gradient floats are indexed with int / 32-bit products of the face count
+static bool refine_sizes_ok(int n_vertices, int n_faces) {
+    return n_vertices >= 0 && n_faces >= 0 && n_vertices <= GIGA_REFINE_MAX_VERTICES && n_faces <= GIGA_REFINE_MAX_FACES;
+}
+
+static unsigned refine_blocks(int n) { return (unsigned)((n + REFINE_BLOCK - 1) / REFINE_BLOCK); }
+
+int giga_refine_face_points(const float* vertices, const int* faces, const float* eps_in, float* eps, float* points,
+                            int n_vertices, int n_faces, unsigned long long seed, int step, void* stream) {
+    if (!refine_sizes_ok(n_vertices, n_faces) || step < 0) return -1;
+    if (n_faces == 0) return 0;
+    if (!vertices || !faces) return -1;
+    if (!eps || !points) return -6;
+    GIGA_LAUNCH(refine_face_points_kernel, dim3(refine_blocks(n_faces)), dim3(REFINE_BLOCK), 0, static_cast<hipStream_t>(stream),
+                vertices, faces, eps_in, eps, points, n_vertices, n_faces, (unsigned)seed, (unsigned)(seed >> 32), (unsigned)step);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int giga_refine_face_grad(const float* vertices, const int* faces, const float* eps, const float* logit, const float* dp,
+                          const float* hess, double threshold, float* face_loss, float* face_grad, int n_vertices, int n_faces,
+                          void* stream) {
+    if (!refine_sizes_ok(n_vertices, n_faces) || !(threshold > 0.0 && threshold < 1.0)) return -1;
+    if (n_faces == 0) return 0;
+    if (!vertices || !faces || !eps || !logit || !dp || !hess) return -1;
+    if (!face_loss || !face_grad) return -6;
+    GIGA_LAUNCH(refine_face_grad_kernel, dim3(refine_blocks(n_faces)), dim3(REFINE_BLOCK), 0, static_cast<hipStream_t>(stream),
+                vertices, faces, eps, logit, dp, hess, threshold, face_loss, face_grad, n_vertices, n_faces);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int giga_refine_vertex_step(const float* face_grad, const int* corner_order, const int* vertex_offsets, float* vertices,
+                            float* square_avg, float* grad, int n_vertices, int n_faces, void* stream) {
+    if (!refine_sizes_ok(n_vertices, n_faces)) return -1;
+    if (n_vertices == 0) return 0;
+    if (!vertex_offsets || !vertices || !square_avg || (n_faces > 0 && (!face_grad || !corner_order))) return -1;
+    if (!grad) return -6;
+    GIGA_LAUNCH(refine_vertex_step_kernel, dim3(refine_blocks(n_vertices)), dim3(REFINE_BLOCK), 0, static_cast<hipStream_t>(stream),
+                face_grad, corner_order, vertex_offsets, vertices, square_avg, grad, n_vertices, n_faces);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+}  // extern "C"

@@ -19,6 +19,7 @@
 //   test of its pixel against each entry; all lanes read the same entry, so the LDS read is a broadcast.
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "giga_check.h"
 #include "giga_ws.h"
 #include <cstdint>
 #include <cstring>
@@ -176,11 +177,10 @@ static RenderWs render_workspace(int B, int n_views) {
     w.total = L.total;
     return w;
 }
-size_t depth_render_workspace_bytes(int B, int n_views) { return render_workspace(B, n_views).total; }
 
-int launch_depth_render(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
-                        const int* view_offsets, const double* extrinsics, const double* intrinsics, int B, int W, int H, double near,
-                        double far, double pixel_offset, float* depth, uint8_t* ws, hipStream_t s) {
+static int launch_depth_render(const float* vertices, const int* vertex_offsets, const int* triangles, const int* triangle_offsets,
+                               const int* view_offsets, const double* extrinsics, const double* intrinsics, int B, int W, int H, double near,
+                               double far, double pixel_offset, float* depth, uint8_t* ws, hipStream_t s) {
     const int n = view_offsets[B];
     const RenderWs w = render_workspace(B, n);
     // one staging buffer, one copy (pageable host memory: the copy has left it when the call returns)
@@ -213,3 +213,32 @@ int launch_depth_render(const float* vertices, const int* vertex_offsets, const 
 }
 
 }  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+size_t giga_depth_render_workspace_bytes(int B, int n_views, int n_vertices, int n_triangles) {
+    if (B <= 0 || B > GIGA_MAX_SCENES || n_views < 0 || n_vertices < 0 || n_triangles < 0) return 0;
+    return render_workspace(B, n_views).total;
+}
+
+int giga_depth_render(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                      const int32_t* view_offsets, const double* extrinsics, const double* intrinsics, int B, int W, int H, double near,
+                      double far, double pixel_offset, float* depth, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = ragged_batch_check(B)) return rc;
+    if (W < 1 || H < 1 || W > GIGA_RENDER_MAX_IMAGE || H > GIGA_RENDER_MAX_IMAGE) return -1;
+    if (!finite_f64(near) || !finite_f64(far) || !(near > 0.0) || !(far > near) || !finite_f64(pixel_offset)) return -1;
+    if (B == 0) return 0;
+    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !ragged_ok(view_offsets, B)) return -1;
+    const int n = view_offsets[B];
+    if ((long long)n * W * H >= (1LL << 31)) return -1;
+    if (n == 0) return 0;
+    if (!camera_check(n, extrinsics, intrinsics) || !workspace) return -1;
+    if (!depth) return -6;
+    if (workspace_bytes < giga_depth_render_workspace_bytes(B, n, vertex_offsets[B], triangle_offsets[B])) return -4;
+    return launch_depth_render(vertices, vertex_offsets, triangles, triangle_offsets, view_offsets, extrinsics, intrinsics, B, W, H, near,
+                               far, pixel_offset, depth, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

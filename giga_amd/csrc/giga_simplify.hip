@@ -40,6 +40,7 @@
 // changed), its triangle stays pending, a flag is raised; the host rebuilds the lists from the live faces and goes on.
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "giga_check.h"
 #include "giga_scan.h"
 #include "giga_ws.h"
 #include <climits>
@@ -522,7 +523,7 @@ __global__ void simp_emit_faces_kernel(SimpDev s, int* out) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-long long simplify_ref_capacity(int n_triangles_of_mesh, int ref_extra) {
+static long long simplify_ref_capacity(int n_triangles_of_mesh, int ref_extra) {
     return 3LL * n_triangles_of_mesh + (ref_extra < 0 ? 3LL * n_triangles_of_mesh + SIMP_MIN_REF_EXTRA : ref_extra);
 }
 
@@ -555,10 +556,6 @@ size_t simp_carve(uint8_t* base, int B, size_t Vt, size_t Tt, size_t R, SimpDev*
     return L.total;
 }
 }  // namespace
-
-size_t simplify_workspace_bytes(int B, long long n_vertices, long long n_triangles, long long ref_total) {
-    return simp_carve(nullptr, B, (size_t)n_vertices, (size_t)n_triangles, (size_t)ref_total, nullptr, nullptr);
-}
 
 #define SIMP_HIP(call)                      \
     do {                                    \
@@ -659,9 +656,9 @@ struct SimpHost {
 };
 }  // namespace
 
-int launch_mesh_simplify(const void* vertices, int vertices_f64, const int* vertex_offsets, const int* triangles,
-                         const int* triangle_offsets, const int* targets, int B, double agressiveness, int ref_extra,
-                         double* out_vertices, int* out_triangles, int* out_counts, int* stats, uint8_t* ws, hipStream_t st) {
+static int launch_mesh_simplify(const void* vertices, int vertices_f64, const int* vertex_offsets, const int* triangles,
+                                const int* triangle_offsets, const int* targets, int B, double agressiveness, int ref_extra,
+                                double* out_vertices, int* out_triangles, int* out_counts, int* stats, uint8_t* ws, hipStream_t st) {
     SimpHost h;
     h.st = st;
     h.mesh.resize(B);
@@ -802,3 +799,47 @@ int launch_mesh_simplify(const void* vertices, int vertices_f64, const int* vert
 }
 
 }  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+// the reference-list entries of a batch of B meshes with n_triangles faces in all (every mesh: 3 F entries + the appended room)
+static long long simplify_ref_total(int B, long long n_triangles, int ref_extra) {
+    return ref_extra < 0 ? 6 * n_triangles + (long long)GIGA_SIMPLIFY_MIN_REF_EXTRA * B : 3 * n_triangles + (long long)ref_extra * B;
+}
+static int simplify_shape_check(int B, long long n_vertices, long long n_triangles, int ref_extra) {
+    if (B < 0 || n_vertices < 0 || n_triangles < 0) return -1;
+    if (ref_extra >= 0 && ref_extra < GIGA_SIMPLIFY_MIN_REF_EXTRA) return -1;
+    if (B > GIGA_MAX_SCENES) return -7;
+    if (n_vertices > GIGA_SIMPLIFY_MAX_FACES || n_triangles > GIGA_SIMPLIFY_MAX_FACES) return -1;
+    if (simplify_ref_total(B, n_triangles, ref_extra) >= (1LL << 31)) return -1;
+    return 0;
+}
+
+size_t giga_simplify_workspace_bytes(int B, int n_vertices, int n_triangles, int ref_extra) {
+    if (B <= 0 || simplify_shape_check(B, n_vertices, n_triangles, ref_extra) != 0) return 0;
+    return simp_carve(nullptr, B, (size_t)n_vertices, (size_t)n_triangles, (size_t)simplify_ref_total(B, n_triangles, ref_extra), nullptr,
+                      nullptr);
+}
+
+int giga_mesh_simplify(const void* vertices, int vertices_f64, const int32_t* vertex_offsets, const int32_t* triangles,
+                       const int32_t* triangle_offsets, const int32_t* targets, int B, double agressiveness, int ref_extra,
+                       double* out_vertices, int32_t* out_triangles, int32_t* out_counts, int32_t* stats, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    if (const int rc = ragged_batch_check(B)) return rc;
+    if (B == 0) return 0;
+    if (!(agressiveness == agressiveness) || (vertices_f64 != 0 && vertices_f64 != 1)) return -1;
+    // (every check from here to the workspace pointer answers -1: simplify_shape_check has no other code once B is in range)
+    if (!mesh_batch_check(vertex_offsets, triangle_offsets, B, vertices, triangles) || !targets || !workspace) return -1;
+    if (const int rc = simplify_shape_check(B, vertex_offsets[B], triangle_offsets[B], ref_extra)) return rc;
+    for (int b = 0; b < B; ++b)
+        if (targets[b] < 0) return -1;
+    if (!out_counts || (vertex_offsets[B] > 0 && triangle_offsets[B] > 0 && (!out_vertices || !out_triangles))) return -6;
+    if (workspace_bytes < giga_simplify_workspace_bytes(B, vertex_offsets[B], triangle_offsets[B], ref_extra)) return -4;
+    return launch_mesh_simplify(vertices, vertices_f64, vertex_offsets, triangles, triangle_offsets, targets, B, agressiveness, ref_extra,
+                                out_vertices, out_triangles, out_counts, stats, static_cast<uint8_t*>(workspace),
+                                static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -9,6 +9,7 @@
 // Indices outside [0, R) are ignored on the device (numpy would raise; the Python wrapper checks host-side inputs).
 #include <hip/hip_runtime.h>
 #include "giga_launch.h"
+#include "giga_check.h"
 #include "giga_scan.h"
 #include "giga_ws.h"
 #include <cmath>
@@ -49,19 +50,6 @@ __global__ void tsdf_write_kernel(const int* __restrict__ index, const float* __
     const size_t cell = ((size_t)b * R + i) * R * R + j * R + k;
     if (winner[cell] == v) grid[cell] = value[v];
 }
-
-int launch_tsdf_scatter(const int* index, const float* value, const int* offsets, int B, int R, int n, float* grid,
-                        int* winner, hipStream_t s) {
-    const size_t cells = (size_t)B * R * R * R;
-    if (hipMemsetAsync(grid, 0, cells * sizeof(float), s) != hipSuccess) return -10;
-    if (n <= 0) return 0;
-    if (hipMemsetAsync(winner, 0xFF, cells * sizeof(int), s) != hipSuccess) return -10;      // -1 everywhere
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    GIGA_LAUNCH(tsdf_claim_kernel, dim3(blocks), dim3(256), 0, s, index, offsets, B, R, n, winner);
-    GIGA_LAUNCH(tsdf_write_kernel, dim3(blocks), dim3(256), 0, s, index, value, offsets, B, R, n, winner, grid);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Fusion of depth images into the volume: the device counterpart of vgn.perception.TSDFVolume.integrate / get_grid / get_cloud
@@ -141,11 +129,10 @@ static IntegrateWs integrate_workspace(int B, int n_views) {
     w.total = L.total;
     return w;
 }
-size_t tsdf_integrate_workspace_bytes(int B, int n_views) { return integrate_workspace(B, n_views).total; }
 
-int launch_tsdf_integrate(const float* depth, const int* view_offsets, const double* extrinsics, const double* intrinsics, int B,
-                          int W, int H, double length, int R, double sdf_trunc, double depth_scale, double depth_trunc, float* tsdf,
-                          float* weight, float* grid, uint8_t* ws, hipStream_t s) {
+static int launch_tsdf_integrate(const float* depth, const int* view_offsets, const double* extrinsics, const double* intrinsics, int B,
+                                 int W, int H, double length, int R, double sdf_trunc, double depth_scale, double depth_trunc, float* tsdf,
+                                 float* weight, float* grid, uint8_t* ws, hipStream_t s) {
     const int n = view_offsets[B];
     const IntegrateWs w = integrate_workspace(B, n);
     int* offs = reinterpret_cast<int*>(ws + w.offs);
@@ -265,9 +252,80 @@ static CloudWs cloud_workspace(int B, int R) {
     w.total = L.total;
     return w;
 }
-size_t tsdf_cloud_workspace_bytes(int B, int R) { return cloud_workspace(B, R).total; }
 
-int launch_tsdf_cloud_count(const float* tsdf, const float* weight, int B, int R, uint8_t* ws, int* counts, hipStream_t s) {
+}  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+size_t giga_tsdf_scatter_workspace_bytes(int B, int R) {
+    if (B <= 0 || R <= 0) return 0;
+    return (size_t)B * R * R * R * sizeof(int32_t);
+}
+
+int giga_tsdf_scatter(const int32_t* voxel_index, const float* voxel_value, const int32_t* scene_offsets, int B, int R,
+                      int n_voxels, float* grid, void* workspace, size_t workspace_bytes, void* stream) {
+    if (B < 0 || R <= 0 || R > 1024 || n_voxels < 0) return -1;
+    if (B == 0) return 0;
+    if (!grid || !scene_offsets) return -1;
+    if (n_voxels > 0 && (!voxel_index || !voxel_value || !workspace)) return -1;
+    if (n_voxels > 0 && workspace_bytes < giga_tsdf_scatter_workspace_bytes(B, R)) return -4;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int* winner = static_cast<int*>(workspace);
+    const size_t cells = (size_t)B * R * R * R;
+    if (hipMemsetAsync(grid, 0, cells * sizeof(float), s) != hipSuccess) return -10;
+    if (n_voxels <= 0) return 0;
+    if (hipMemsetAsync(winner, 0xFF, cells * sizeof(int), s) != hipSuccess) return -10;      // -1 everywhere
+    const unsigned blocks = (unsigned)((n_voxels + 255) / 256);
+    GIGA_LAUNCH(tsdf_claim_kernel, dim3(blocks), dim3(256), 0, s, voxel_index, scene_offsets, B, R, n_voxels, winner);
+    GIGA_LAUNCH(tsdf_write_kernel, dim3(blocks), dim3(256), 0, s, voxel_index, voxel_value, scene_offsets, B, R, n_voxels, winner, grid);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+static int tsdf_volume_check(int B, int R) {
+    if (B < 0 || R < 2 || R > GIGA_TSDF_MAX_R) return -1;
+    if (B > GIGA_MAX_SCENES) return -7;
+    return 0;
+}
+
+size_t giga_tsdf_integrate_workspace_bytes(int B, int n_views) {
+    if (B <= 0 || B > GIGA_MAX_SCENES || n_views < 0) return 0;
+    return integrate_workspace(B, n_views).total;
+}
+
+int giga_tsdf_integrate(const float* depth, const int32_t* view_offsets, const double* extrinsics, const double* intrinsics, int B,
+                        int width, int height, double length, int R, double sdf_trunc, double depth_scale, double depth_trunc,
+                        float* tsdf, float* weight, float* grid, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = tsdf_volume_check(B, R)) return rc;
+    if (width < 1 || height < 1 || width > GIGA_TSDF_MAX_IMAGE || height > GIGA_TSDF_MAX_IMAGE) return -1;
+    if (!finite_f64(length) || !(length > 0.0) || !finite_f64(sdf_trunc) || !(sdf_trunc > 0.0) || !finite_f64(depth_scale) ||
+        !(depth_scale > 0.0) || !(depth_trunc == depth_trunc))
+        return -1;
+    if (B == 0) return 0;
+    if (!ragged_ok(view_offsets, B)) return -1;
+    const int n = view_offsets[B];
+    if ((long long)n * width * height >= (1LL << 40)) return -1;
+    if (!camera_check(n, extrinsics, intrinsics) || (n > 0 && !depth)) return -1;
+    if (!tsdf || !weight || !workspace) return -1;
+    if (workspace_bytes < giga_tsdf_integrate_workspace_bytes(B, n)) return -4;
+    return launch_tsdf_integrate(depth, view_offsets, extrinsics, intrinsics, B, width, height, length, R, sdf_trunc, depth_scale,
+                                 depth_trunc, tsdf, weight, grid, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+size_t giga_tsdf_cloud_workspace_bytes(int B, int R) {
+    if (B <= 0 || tsdf_volume_check(B, R) != 0) return 0;
+    return cloud_workspace(B, R).total;
+}
+
+int giga_tsdf_cloud_count(const float* tsdf, const float* weight, int B, int R, void* workspace, size_t workspace_bytes,
+                          int32_t* counts, void* stream) {
+    if (const int rc = tsdf_volume_check(B, R)) return rc;
+    if (B == 0) return 0;
+    if (!tsdf || !weight || !workspace || !counts) return -1;
+    if (workspace_bytes < giga_tsdf_cloud_workspace_bytes(B, R)) return -4;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
     const CloudWs w = cloud_workspace(B, R);
     unsigned* blk = reinterpret_cast<unsigned*>(ws + w.blk);
     unsigned long long* bases = reinterpret_cast<unsigned long long*>(ws + w.bases);
@@ -277,13 +335,20 @@ int launch_tsdf_cloud_count(const float* tsdf, const float* weight, int B, int R
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-int launch_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, double length, const uint8_t* ws, float* points,
-                           size_t cap, int* shortfall, hipStream_t s) {
+int giga_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, double length, const void* workspace,
+                         size_t workspace_bytes, float* points, size_t cap, int32_t* shortfall, void* stream) {
+    if (const int rc = tsdf_volume_check(B, R)) return rc;
+    if (!finite_f64(length) || !(length > 0.0)) return -1;
+    if (B == 0) return 0;
+    if (!tsdf || !weight || !workspace) return -1;
+    if (cap > 0 && !points) return -6;
+    if (workspace_bytes < giga_tsdf_cloud_workspace_bytes(B, R)) return -4;
+    const uint8_t* ws = static_cast<const uint8_t*>(workspace);
     const CloudWs w = cloud_workspace(B, R);
-    GIGA_LAUNCH(tsdf_cloud_emit_kernel, dim3(w.nblk, B), dim3(TSDF_BLOCK), 0, s, tsdf, weight, (unsigned)R, w.cells, w.nblk,
-                length / (double)R, reinterpret_cast<const unsigned*>(ws + w.blk),
+    GIGA_LAUNCH(tsdf_cloud_emit_kernel, dim3(w.nblk, B), dim3(TSDF_BLOCK), 0, static_cast<hipStream_t>(stream), tsdf, weight, (unsigned)R,
+                w.cells, w.nblk, length / (double)R, reinterpret_cast<const unsigned*>(ws + w.blk),
                 reinterpret_cast<const unsigned long long*>(ws + w.bases), B, points, (unsigned long long)cap, shortfall);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-}  // namespace giga
+}  // extern "C"

@@ -15,8 +15,7 @@ import logging
 import numpy as np
 import torch
 
-from . import _capi
-from .mesh import Mesh
+from . import _capi, ragged
 
 # Maximum values for the bounding box [-0.5, 0.5]^3
 EMPTY_PCL_DICT = {
@@ -37,113 +36,45 @@ DEFAULT_THRESHOLDS = np.linspace(1. / 1000, 1, 1000)
 logger = logging.getLogger(__name__)
 
 
-# ------------------------------------------------------------------------------------------------------------------ plumbing
-def _device(*xs):
-    ts = [x for x in xs if torch.is_tensor(x)]
-    dev = _capi.device_of(*ts) if ts else None
-    if dev is None:
-        if not torch.cuda.is_available():
-            raise _capi.GigaHipError("giga_amd runs only on a HIP device; there is no CPU fallback. "
-                                     "Use the reference implementation for CPU execution.")
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
-
-
-def _to(x, dev, dtype, cols=3):
-    """numpy array or device tensor -> contiguous (n, cols) device tensor of `dtype`"""
-    if x is None:
-        return None
-    t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-    t = t.detach()
-    if cols:
-        t = t.reshape(-1, cols)
-    return t.to(dtype).contiguous()
-
-
-def _mesh_parts(mesh):
-    if isinstance(mesh, Mesh) or (hasattr(mesh, "vertices") and hasattr(mesh, "faces")):
-        return mesh.vertices, mesh.faces
-    v, f = mesh
-    return v, f
-
-
-def _offsets(counts):
-    o = np.zeros(len(counts) + 1, np.int64)
-    np.cumsum(counts, out=o[1:])
-    if o[-1] >= 2 ** 31:
-        raise ValueError("a ragged batch holds at most 2^31 - 1 rows")
-    return np.ascontiguousarray(o, np.int32)
-
-
-def _hptr(a):
-    return a.ctypes.data_as(_capi.ctypes.c_void_p)
-
-
-def _cat(ts, dev, dtype, cols=3):
-    ts = [_to(t, dev, dtype, cols) for t in ts]
-    return (ts[0] if len(ts) == 1 else torch.cat(ts)), _offsets([len(t) for t in ts])
-
-
-def _pack_meshes(meshes, dev):
-    parts = [_mesh_parts(m) for m in meshes]
-    v, vo = _cat([p[0] for p in parts], dev, torch.float32)
-    f, fo = _cat([p[1] for p in parts], dev, torch.int32)
-    return v, vo, f, fo
-
-
-def _mesh_devices(meshes):
-    return [x for m in meshes for x in _mesh_parts(m)]
-
-
 # --------------------------------------------------------------------------------------------------------- the three kernels
 def nn_query_batch(points_src, points_tgt):
     """lists of B source / target clouds -> (dist float32, idx int64 relative to the scene's targets, source offsets), packed"""
-    dev = _device(*points_src, *points_tgt)
-    src, so = _cat(points_src, dev, torch.float32)
-    tgt, to = _cat(points_tgt, dev, torch.float32)
+    dev = _capi.hip_device(*points_src, *points_tgt)
+    src, so = ragged.pack(points_src, dev, torch.float32)
+    tgt, to = ragged.pack(points_tgt, dev, torch.float32)
     B, n = len(so) - 1, int(so[-1])
-    L = _capi.lib()
     dist = torch.empty(n, dtype=torch.float32, device=dev)
     idx = torch.empty(n, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(L.giga_nn_query_workspace_bytes(B, n), 256), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check(L.giga_nn_query(_capi.ptr(src), _hptr(so), _capi.ptr(tgt), _hptr(to), B, _capi.ptr(dist), _capi.ptr(idx),
-                                    _capi.ptr(ws), ws.numel(), _capi.stream_ptr(dev)), "giga_nn_query")
+    ws = _capi.workspace("giga_nn_query", dev, B, n)
+    _capi.call("giga_nn_query", dev, src, so, tgt, to, B, dist, idx, ws, ws.numel())
     return dist, idx.to(torch.int64), so
 
 
 def sample_surface_batch(meshes, n, seed=0, first_scene=0):
     """B meshes -> (points (B,n,3) float32, face (B,n) int64, normals (B,n,3) float32, counts (B,) int64 on the host); a scene
     whose count is 0 (no faces, no area) has zero rows.  Scene b draws with the generator's scene word first_scene + b"""
-    dev = _device(*_mesh_devices(meshes))
-    v, vo, f, fo = _pack_meshes(meshes, dev)
+    dev = _capi.hip_device(*ragged.mesh_arrays(meshes))
+    v, vo, f, fo = ragged.pack_meshes(meshes, dev)
     B = len(vo) - 1
-    L = _capi.lib()
     points = torch.zeros((B, n, 3), dtype=torch.float32, device=dev)
     face = torch.zeros((B, n), dtype=torch.int32, device=dev)
     normals = torch.zeros((B, n, 3), dtype=torch.float32, device=dev)
     counts = torch.zeros(B, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(L.giga_mesh_sample_workspace_bytes(B, int(fo[-1])), 256), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check(L.giga_mesh_sample(_capi.ptr(v), _hptr(vo), _capi.ptr(f), _hptr(fo), B, int(n), int(seed) & (2 ** 64 - 1), int(first_scene),
-                                       _capi.ptr(points), _capi.ptr(face), _capi.ptr(normals), _capi.ptr(counts), _capi.ptr(ws),
-                                       ws.numel(), _capi.stream_ptr(dev)), "giga_mesh_sample")
+    ws = _capi.workspace("giga_mesh_sample", dev, B, int(fo[-1]))
+    _capi.call("giga_mesh_sample", dev, v, vo, f, fo, B, int(n), int(seed) & (2 ** 64 - 1), int(first_scene), points, face, normals,
+               counts, ws, ws.numel())
     return points, face.to(torch.int64), normals, counts.cpu().to(torch.int64)
 
 
 def mesh_contains_batch(meshes, points, hash_resolution=512):
     """B meshes, B query clouds -> (inside bool, packed; point offsets)"""
-    dev = _device(*_mesh_devices(meshes), *points)
-    v, vo, f, fo = _pack_meshes(meshes, dev)
-    p, po = _cat(points, dev, torch.float64)
+    dev = _capi.hip_device(*ragged.mesh_arrays(meshes), *points)
+    v, vo, f, fo = ragged.pack_meshes(meshes, dev)
+    p, po = ragged.pack(points, dev, torch.float64)
     B, n = len(vo) - 1, int(po[-1])
-    L = _capi.lib()
     inside = torch.zeros(n, dtype=torch.uint8, device=dev)
-    ws = torch.empty(max(L.giga_mesh_contains_workspace_bytes(B, int(fo[-1]), n), 256), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check(L.giga_mesh_contains(_capi.ptr(v), _hptr(vo), _capi.ptr(f), _hptr(fo), _capi.ptr(p), _hptr(po), B,
-                                         int(hash_resolution), _capi.ptr(inside), _capi.ptr(ws), ws.numel(),
-                                         _capi.stream_ptr(dev)), "giga_mesh_contains")
+    ws = _capi.workspace("giga_mesh_contains", dev, B, int(fo[-1]), n)
+    _capi.call("giga_mesh_contains", dev, v, vo, f, fo, p, po, B, int(hash_resolution), inside, ws, ws.numel())
     return inside.to(torch.bool), po
 
 
@@ -162,7 +93,7 @@ def check_mesh_contains(mesh, points, hash_resolution=512):
 
 
 def _normal_dots(idx, normals_src, normals_tgt, dev):
-    ns, nt = _to(normals_src, dev, torch.float32), _to(normals_tgt, dev, torch.float32)
+    ns, nt = ragged.to_device(normals_src, dev, torch.float32), ragged.to_device(normals_tgt, dev, torch.float32)
     ns = ns / ns.norm(dim=-1, keepdim=True)
     nt = nt / nt.norm(dim=-1, keepdim=True)
     return (nt[idx] * ns).sum(dim=-1).abs()
@@ -235,7 +166,7 @@ def _empty_dict(with_normals):
 
 
 def _is_empty(mesh):
-    v, f = _mesh_parts(mesh)
+    v, f = ragged.mesh_parts(mesh)
     return len(v) == 0 or len(f) == 0
 
 

@@ -30,9 +30,9 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import _capi, render
+from . import _capi, ragged, render
 from .dataset import read_voxel_grid
-from .eval import MeshEvaluator, _hptr, _offsets, mesh_contains_batch, sample_surface_batch
+from .eval import MeshEvaluator, mesh_contains_batch, sample_surface_batch
 from .generation import Generator3D
 
 MEAN_KEYS = ("iou", "chamfer-L1", "normals accuracy", "f-score")          # eval_geometry_voxel.py:45-51
@@ -141,13 +141,6 @@ class VoxelOccGeoDataset:
     def __len__(self):
         return len(self.scene_list)
 
-    def _device(self):
-        if self.device is not None:
-            return torch.device(self.device)
-        if not torch.cuda.is_available():
-            raise _capi.GigaHipError("geometry scoring runs only on a HIP device; there is no CPU fallback")
-        return torch.device("cuda", torch.cuda.current_device())
-
     def scene(self, i):
         """(grid (40,40,40) float32, scene mesh (vertices float32, faces int32) in world coordinates, mesh list)"""
         scene_id = self.scene_list[i]
@@ -157,7 +150,7 @@ class VoxelOccGeoDataset:
 
     def _occ(self, i, mesh_list):
         """dataset_voxel_occ.py:35-36, 40-45: (points (n,3) float32 normalised, occ (n,) bool) on the device"""
-        dev = self._device()
+        dev = _capi.hip_device(device=self.device, what="geometry scoring runs only on a HIP device")
         gen = torch.Generator(device=dev)
         gen.manual_seed(_scene_seed(self.seed, i))
         kwargs = dict(uniform=True, size=self.size, padding=0) if self.uniform else dict(uniform=False, padding=self.padding)
@@ -191,11 +184,7 @@ def roi_points(grasps, counts, scenes, seed, finger_depth, ROI_scale, size, devi
     pos (k,3), width (k,)) float64, counts = (k,) points per grasp, scenes = its index in the data set (the generator's scene
     word).  Returns (world (n,3) float64, normalised (n,3) float32 = float32(world / size - 0.5), scene offsets (len + 1) int32 on
     the host); a scene's rows list its grasps in order."""
-    if device is None:
-        if not torch.cuda.is_available():
-            raise _capi.GigaHipError("the ROI points are drawn on a HIP device; there is no CPU fallback")
-        device = torch.device("cuda", torch.cuda.current_device())
-    dev = torch.device(device)
+    dev = _capi.hip_device(device=device, what="the ROI points are drawn on a HIP device")
     table, scene, first, per_scene = [], [], [], []
     for (R, pos, width), cnt, i in zip(grasps, counts, scenes):
         cnt = np.asarray(cnt, np.int64).reshape(-1)
@@ -206,23 +195,19 @@ def roi_points(grasps, counts, scenes, seed, finger_depth, ROI_scale, size, devi
         scene.append(np.full(len(cnt), int(i), np.int64))
         first.append(np.cumsum(cnt) - cnt)
         per_scene.append(int(cnt.sum()))
-    scene_offsets = _offsets(per_scene)
+    scene_offsets = ragged.offsets(per_scene)
     n = int(scene_offsets[-1])
     world = torch.empty((n, 3), dtype=torch.float64, device=dev)
     normalised = torch.empty((n, 3), dtype=torch.float32, device=dev)
     if n:
         table = np.ascontiguousarray(np.concatenate(table), np.float64)
-        offs = _offsets(np.concatenate([np.asarray(c, np.int64).reshape(-1) for c in counts]))
+        offs = ragged.offsets(np.concatenate([np.asarray(c, np.int64).reshape(-1) for c in counts]))
         scene = np.ascontiguousarray(np.concatenate(scene), np.int32)
         first = np.ascontiguousarray(np.concatenate(first), np.int32)
         G = len(scene)
-        L = _capi.lib()
-        ws = torch.empty(max(L.giga_roi_points_workspace_bytes(G), 256), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _capi.check(L.giga_roi_points(_hptr(table), _hptr(offs), _hptr(scene), _hptr(first), G, int(seed) & (2 ** 64 - 1),
-                                          float(finger_depth), float(ROI_scale), float(size), _capi.ptr(world),
-                                          _capi.ptr(normalised), _capi.ptr(ws), ws.numel(), _capi.stream_ptr(dev)),
-                        "giga_roi_points")
+        ws = _capi.workspace("giga_roi_points", dev, G)
+        _capi.call("giga_roi_points", dev, table, offs, scene, first, G, int(seed) & (2 ** 64 - 1), float(finger_depth),
+                   float(ROI_scale), float(size), world, normalised, ws, ws.numel())
     return world, normalised, scene_offsets
 
 
@@ -271,7 +256,7 @@ class VoxelOccGeoROIDataset(VoxelOccGeoDataset):
         whatever else is in the call."""
         grasps = [self.roi_grasps(i) for i in indices]
         counts = [roi_point_counts(g[2], self.num_point_occ) for g in grasps]
-        return roi_points(grasps, counts, indices, self.seed, self.finger_depth, self.ROI_scale, self.size, self._device())
+        return roi_points(grasps, counts, indices, self.seed, self.finger_depth, self.ROI_scale, self.size, self.device)
 
     @staticmethod
     def roi_labels(world, scene_offsets, mesh_lists):
@@ -333,12 +318,9 @@ def occ_confusion(pred_or_logits, target, offsets, threshold=None):
             raise ValueError(f"threshold {threshold} has no logit")
     if B == 0:
         return np.zeros((0, 4), np.int64)
-    L = _capi.lib()
     counts = torch.empty((B, 4), dtype=torch.int64, device=dev)
-    ws = torch.empty(max(L.giga_occ_confusion_workspace_bytes(B), 256), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check(L.giga_occ_confusion(_capi.ptr(logits), _capi.ptr(pred), th, _capi.ptr(tgt), _hptr(offs), B, _capi.ptr(counts),
-                                         _capi.ptr(ws), ws.numel(), _capi.stream_ptr(dev)), "giga_occ_confusion")
+    ws = _capi.workspace("giga_occ_confusion", dev, B)
+    _capi.call("giga_occ_confusion", dev, logits, pred, th, tgt, offs, B, counts, ws, ws.numel())
     return counts.cpu().numpy()
 
 
@@ -454,7 +436,7 @@ class GeometryEvaluator:
             with torch.no_grad():
                 logits = self.net.decode_occ(p, c).logits
             packed = torch.cat([logits[b, :lens[b]] for b in live])
-            counts = occ_confusion(packed, torch.cat([items[b]["roi_occ"] for b in live]), _offsets([lens[b] for b in live]),
+            counts = occ_confusion(packed, torch.cat([items[b]["roi_occ"] for b in live]), ragged.offsets([lens[b] for b in live]),
                                    threshold=self.threshold)
             for k, b in enumerate(live):
                 outs[b].update(occ_scores(counts[k], "_ROI_infer"))

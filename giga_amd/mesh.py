@@ -35,19 +35,15 @@ def marching_cubes(grids, iso, box_size=1.0):
     dev = _capi.device_of(grids)
     g = grids.detach().contiguous().float()
     B, nx, ny, nz = g.shape
-    L = _capi.lib()
     counts_dev = torch.zeros((max(B, 1), 2), dtype=torch.int32, device=dev)
-    ws = torch.empty(max(L.giga_mesh_workspace_bytes(B, nx, ny, nz), 256), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check(L.giga_mesh_count(_capi.ptr(g), B, nx, ny, nz, float(iso), _capi.ptr(ws), ws.numel(), _capi.ptr(counts_dev),
-                                      _capi.stream_ptr(dev)), "giga_mesh_count")
-        counts = counts_dev[:B].cpu().to(torch.int64)
-        cap_v, cap_t = int(counts[:, 0].sum()), int(counts[:, 1].sum())
-        vertices = torch.empty((cap_v, 3), dtype=torch.float32, device=dev)
-        triangles = torch.empty((cap_t, 3), dtype=torch.int32, device=dev)
-        _capi.check(L.giga_mesh_emit(_capi.ptr(g), B, nx, ny, nz, float(iso), float(box_size), _capi.ptr(ws), ws.numel(),
-                                     _capi.ptr(vertices), cap_v, _capi.ptr(triangles), cap_t, None,
-                                     _capi.stream_ptr(dev)), "giga_mesh_emit")
+    ws = _capi.workspace("giga_mesh", dev, B, nx, ny, nz)
+    _capi.call("giga_mesh_count", dev, g, B, nx, ny, nz, float(iso), ws, ws.numel(), counts_dev)
+    counts = counts_dev[:B].cpu().to(torch.int64)
+    cap_v, cap_t = int(counts[:, 0].sum()), int(counts[:, 1].sum())
+    vertices = torch.empty((cap_v, 3), dtype=torch.float32, device=dev)
+    triangles = torch.empty((cap_t, 3), dtype=torch.int32, device=dev)
+    _capi.call("giga_mesh_emit", dev, g, B, nx, ny, nz, float(iso), float(box_size), ws, ws.numel(), vertices, cap_v, triangles, cap_t,
+               None)
     return vertices, triangles, counts
 
 
@@ -86,20 +82,15 @@ def simplify_mesh(vertices, faces, f_target, agressiveness=7., counts=None, stat
     voff = torch.cat((zero, counts_h[:, :1].cumsum(0))).to(torch.int32).reshape(-1).contiguous()
     foff = torch.cat((zero, counts_h[:, 1:].cumsum(0))).to(torch.int32).reshape(-1).contiguous()
     extra = -1 if ref_extra is None else int(ref_extra)
-    L = _capi.lib()
     out_v = torch.empty((v.shape[0], 3), dtype=torch.float64, device=dev)
     out_f = torch.empty((f.shape[0], 3), dtype=torch.int32, device=dev)
     out_c = torch.zeros((max(B, 1), 2), dtype=torch.int32, device=dev)
     st = torch.zeros((max(B, 1), 4), dtype=torch.int32)
-    need = L.giga_simplify_workspace_bytes(B, v.shape[0], f.shape[0], extra) if B else 0
-    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check(L.giga_mesh_simplify(_capi.ptr(v), int(v.dtype == torch.float64), _capi.ptr(voff), _capi.ptr(f), _capi.ptr(foff),
-                                         _capi.ptr(targets), B, float(agressiveness), extra, _capi.ptr(out_v), _capi.ptr(out_f),
-                                         _capi.ptr(out_c), _capi.ptr(st), _capi.ptr(ws), ws.numel() if need else 0,
-                                         _capi.stream_ptr(dev)), "giga_mesh_simplify")
-        out_counts = out_c[:B].to(torch.int64)
-        totals = out_counts.sum(0).tolist() if B else [0, 0]
+    ws = _capi.workspace("giga_simplify", dev, B, v.shape[0], f.shape[0], extra)       # (0 bytes for a shape the call rejects)
+    _capi.call("giga_mesh_simplify", dev, v, int(v.dtype == torch.float64), voff, f, foff, targets, B, float(agressiveness), extra,
+               out_v, out_f, out_c, st, ws, ws.numel())
+    out_counts = out_c[:B].to(torch.int64)
+    totals = out_counts.sum(0).tolist() if B else [0, 0]
     if stats is not None:
         for k, name in enumerate(("iterations", "rounds", "repeated passes", "list rebuilds")):
             stats[name] = st[:B, k].tolist()

@@ -44,9 +44,7 @@ class MISE:
         self._query = None
         self.counts = None                 # host list of the last query's lengths
         self.points = None                 # (B, L, 3) coordinates of the last query (with a `lin` table)
-        with torch.cuda.device(self.device):
-            _capi.check(L.giga_mise_init(*self._shape(), _capi.ptr(self._ws), self._ws.numel(), _capi.stream_ptr(self.device)),
-                        "giga_mise_init")
+        _capi.call("giga_mise_init", self.device, *self._shape(), self._ws, self._ws.numel())
 
     def _shape(self):
         return self.batch, self.resolution0, self.depth
@@ -55,17 +53,13 @@ class MISE:
         """The unknown points of every scene: (B, L) int32 linear indices on the device, ascending inside a scene, L = the longest
         list; `self.counts` (host) holds the B lengths, and entries past a scene's length are 0 (a valid index).  With a `lin` table
         `self.points` (B, L, 3) holds the coordinates, padded with a repeated valid point."""
-        L = _capi.lib()
-        with torch.cuda.device(self.device):
-            s = _capi.stream_ptr(self.device)
-            _capi.check(L.giga_mise_count(*self._shape(), _capi.ptr(self._ws), self._ws.numel(), _capi.ptr(self._counts_dev), s),
-                        "giga_mise_count")
-            self.counts = self._counts_dev.cpu().tolist()
-            cap = max(self.counts)
-            self._query = torch.zeros((self.batch, cap), dtype=torch.int32, device=self.device)
-            self.points = torch.empty((self.batch, cap, 3), dtype=torch.float32, device=self.device) if self._lin is not None else None
-            _capi.check(L.giga_mise_emit(*self._shape(), _capi.ptr(self._ws), self._ws.numel(), _capi.ptr(self._query), cap, None,
-                                         _capi.ptr(self._lin), _capi.ptr(self.points), s), "giga_mise_emit")
+        _capi.call("giga_mise_count", self.device, *self._shape(), self._ws, self._ws.numel(), self._counts_dev)
+        self.counts = self._counts_dev.cpu().tolist()
+        cap = max(self.counts)
+        self._query = torch.zeros((self.batch, cap), dtype=torch.int32, device=self.device)
+        self.points = torch.empty((self.batch, cap, 3), dtype=torch.float32, device=self.device) if self._lin is not None else None
+        _capi.call("giga_mise_emit", self.device, *self._shape(), self._ws, self._ws.numel(), self._query, cap, None, self._lin,
+                   self.points)
         return self._query
 
     def update(self, values):
@@ -77,18 +71,14 @@ class MISE:
         if tuple(values.shape) != tuple(self._query.shape):
             raise ValueError(f"expected values of shape {tuple(self._query.shape)}, got {tuple(values.shape)}")
         v = values.detach().to(self.device, torch.float32).contiguous()
-        with torch.cuda.device(self.device):
-            _capi.check(_capi.lib().giga_mise_update(_capi.ptr(v), _capi.ptr(self._query), self._query.shape[1], *self._shape(),
-                                                     self.threshold, _capi.ptr(self._ws), self._ws.numel(),
-                                                     _capi.stream_ptr(self.device)), "giga_mise_update")
+        _capi.call("giga_mise_update", self.device, v, self._query, self._query.shape[1], *self._shape(), self.threshold, self._ws,
+                   self._ws.numel())
         self._query = None
 
     def to_dense(self):
         """(B, N, N, N) float32 on the device (mise.pyx:130-164)."""
         out = torch.empty((self.batch, self.n, self.n, self.n), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _capi.check(_capi.lib().giga_mise_to_dense(*self._shape(), _capi.ptr(self._ws), self._ws.numel(), _capi.ptr(out),
-                                                       _capi.stream_ptr(self.device)), "giga_mise_to_dense")
+        _capi.call("giga_mise_to_dense", self.device, *self._shape(), self._ws, self._ws.numel(), out)
         return out
 
 

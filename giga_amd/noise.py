@@ -57,13 +57,9 @@ class DepthNoise(object):
         if n == 0 or H == 0 or W == 0:
             return out.reshape(depth.shape)
         p = np.array([self.params[k] for k, _ in PARAMS[self.kind]], np.float64)
-        L = _capi.lib()
         model = _capi.NOISE_MODEL[self.kind]
-        ws = torch.empty(max(L.giga_depth_noise_workspace_bytes(n, W, H, model), 16), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _capi.check(L.giga_depth_noise(_capi.ptr(src), _capi.ptr(out), n, W, H, model, p.ctypes.data, self.seed,
-                                           ids.ctypes.data if ids is not None else None, _capi.ptr(ws), ws.numel(),
-                                           _capi.stream_ptr(dev)), "giga_depth_noise")
+        ws = _capi.workspace("giga_depth_noise", dev, n, W, H, model)
+        _capi.call("giga_depth_noise", dev, src, out, n, W, H, model, p, self.seed, ids, ws, ws.numel())
         return out.reshape(depth.shape)
 
 

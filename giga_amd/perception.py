@@ -55,11 +55,8 @@ def dense_grids(scenes, resolution=40, device=None):
     index = torch.cat(idx_l).to(device).contiguous() if n else None
     value = torch.cat(val_l).to(device).contiguous() if n else None
     offsets = torch.tensor(offs, dtype=torch.int32).to(device)
-    L = _capi.lib()
-    ws = torch.empty(max(L.giga_tsdf_scatter_workspace_bytes(B, R), 16), dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        _capi.check(L.giga_tsdf_scatter(_capi.ptr(index), _capi.ptr(value), _capi.ptr(offsets), B, R, n, _capi.ptr(grid),
-                                        _capi.ptr(ws), ws.numel(), _capi.stream_ptr(device)), "giga_tsdf_scatter")
+    ws = _capi.workspace("giga_tsdf_scatter", device, B, R)
+    _capi.call("giga_tsdf_scatter", device, index, value, offsets, B, R, n, grid, ws, ws.numel())
     return grid
 
 
@@ -143,13 +140,7 @@ def camera_on_sphere(origin, radius, theta, phi):
 # ------------------------------------------------------------------------------------------------ fusion
 DEPTH_SCALE, DEPTH_TRUNC = 1.0, 2.0              # perception.py:89-90
 CLOUD_LOWER, CLOUD_UPPER = np.array([0.02, 0.02, 0.055]), np.array([0.28, 0.28, 0.3])      # construct_dataset_parallel.py:31-32
-
-
-def _device(device):
-    device = torch.device(device if device is not None else "cuda")
-    if device.type != "cuda":
-        raise _capi.GigaHipError("depth fusion runs on a HIP device; there is no CPU fallback")
-    return device
+FUSION_DEVICE = "depth fusion runs on a HIP device"
 
 
 def integrate_batch(tsdf, weight, depth, view_offsets, intrinsic, extrinsics, size, grid=None):
@@ -172,12 +163,9 @@ def integrate_batch(tsdf, weight, depth, view_offsets, intrinsic, extrinsics, si
         raise ValueError(f"depth images are {H}x{W}, the intrinsic says {intrinsic.height}x{intrinsic.width}")
     ext = np.ascontiguousarray(np.stack([extrinsic_matrix(e) for e in extrinsics]).reshape(n, 16)) if n else np.zeros((0, 16))
     cam = np.ascontiguousarray(np.tile(np.array([intrinsic.fx, intrinsic.fy, intrinsic.cx, intrinsic.cy], np.float64), (n, 1)))
-    L = _capi.lib()
-    ws = torch.empty(max(L.giga_tsdf_integrate_workspace_bytes(B, n), 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check(L.giga_tsdf_integrate(_capi.ptr(depth), offs.ctypes.data, ext.ctypes.data, cam.ctypes.data, B, W, H, float(size), R,
-                                          4.0 * (float(size) / R), DEPTH_SCALE, DEPTH_TRUNC, _capi.ptr(tsdf), _capi.ptr(weight),
-                                          _capi.ptr(grid), _capi.ptr(ws), ws.numel(), _capi.stream_ptr(dev)), "giga_tsdf_integrate")
+    ws = _capi.workspace("giga_tsdf_integrate", dev, B, n)
+    _capi.call("giga_tsdf_integrate", dev, depth, offs, ext, cam, B, W, H, float(size), R, 4.0 * (float(size) / R), DEPTH_SCALE,
+               DEPTH_TRUNC, tsdf, weight, grid, ws, ws.numel())
 
 
 def cloud_batch(tsdf, weight, size, capacity=None):
@@ -187,17 +175,13 @@ def cloud_batch(tsdf, weight, size, capacity=None):
     B, R = tsdf.shape[0], tsdf.shape[-1]
     if B == 0:
         return torch.empty((0, 3), device=dev), np.zeros(1, np.int64)
-    L = _capi.lib()
-    ws = torch.empty(max(L.giga_tsdf_cloud_workspace_bytes(B, R), 16), dtype=torch.uint8, device=dev)
+    ws = _capi.workspace("giga_tsdf_cloud", dev, B, R)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check(L.giga_tsdf_cloud_count(_capi.ptr(tsdf), _capi.ptr(weight), B, R, _capi.ptr(ws), ws.numel(), _capi.ptr(counts),
-                                            _capi.stream_ptr(dev)), "giga_tsdf_cloud_count")
-        offsets = np.concatenate(([0], np.cumsum(counts.cpu().numpy().astype(np.int64))))
-        cap = int(offsets[-1]) if capacity is None else min(int(capacity), int(offsets[-1]))
-        points = torch.empty((cap, 3), dtype=torch.float32, device=dev)
-        _capi.check(L.giga_tsdf_cloud_emit(_capi.ptr(tsdf), _capi.ptr(weight), B, R, float(size), _capi.ptr(ws), ws.numel(),
-                                           _capi.ptr(points) if cap else None, cap, None, _capi.stream_ptr(dev)), "giga_tsdf_cloud_emit")
+    _capi.call("giga_tsdf_cloud_count", dev, tsdf, weight, B, R, ws, ws.numel(), counts)
+    offsets = np.concatenate(([0], np.cumsum(counts.cpu().numpy().astype(np.int64))))
+    cap = int(offsets[-1]) if capacity is None else min(int(capacity), int(offsets[-1]))
+    points = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+    _capi.call("giga_tsdf_cloud_emit", dev, tsdf, weight, B, R, float(size), ws, ws.numel(), points if cap else None, cap, None)
     return points, offsets
 
 
@@ -209,7 +193,7 @@ class TSDFVolume(object):
         self.resolution = resolution
         self.voxel_size = self.size / self.resolution
         self.sdf_trunc = 4 * self.voxel_size
-        self.device = _device(device)
+        self.device = _capi.hip_device(device=device, what=FUSION_DEVICE)
         R = int(resolution)
         if not 2 <= R <= _capi.TSDF_MAX_R:
             raise ValueError(f"resolution outside 2 .. {_capi.TSDF_MAX_R}")
@@ -253,7 +237,7 @@ def create_tsdf(size, resolution, depth_imgs, intrinsic, extrinsics, device=None
 def fuse_scenes(size, resolution, depth_batches, intrinsic, extrinsics_batches, device=None):
     """B scenes with ragged view counts in one launch: depth_batches[b] (V_b, H, W), extrinsics_batches[b] V_b extrinsics.
     Returns (tsdf, weight, grid), each a (B, R, R, R) float32 device tensor."""
-    device = _device(device)
+    device = _capi.hip_device(device=device, what=FUSION_DEVICE)
     B, R = len(depth_batches), int(resolution)
     if len(extrinsics_batches) != B:
         raise ValueError("one list of extrinsics per scene")
@@ -288,7 +272,7 @@ def _fuse_to_host(size, resolution, depth_batches, intrinsic, extrinsics_batches
 def _noise_scenes(noise, depth_batches, image_ids, device=None):
     """noise.apply on the images of several scenes in one launch: depth_batches[b] (V_b, H, W), image_ids one id per image, scenes
     back to back.  Returns the noised (V_b, H, W) float32 device tensors, one per scene."""
-    device = _device(device)
+    device = _capi.hip_device(device=device, what=FUSION_DEVICE)
     imgs = [torch.as_tensor(d).to(torch.float32) for d in depth_batches]
     out = noise.apply(torch.cat(imgs).to(device), image_ids)
     return list(torch.split(out, [len(d) for d in imgs]))

@@ -66,27 +66,20 @@ class MeshRefiner:
     def step(self, eps=None):
         V, F = self.vertices.shape[0], self.faces.shape[0]
         dev = self.vertices.device
-        L = _capi.lib()
         eps_in = None
         if eps is not None:
             eps_in = torch.as_tensor(eps).to(dev, torch.float32).contiguous()
             if tuple(eps_in.shape) != (F, 3):
                 raise ValueError(f"expected ({F},3) barycentric weights, got {tuple(eps_in.shape)}")
         with torch.no_grad(), torch.cuda.device(dev):
-            s = _capi.stream_ptr(dev)
-            _capi.check(L.giga_refine_face_points(_capi.ptr(self.vertices), _capi.ptr(self.faces), _capi.ptr(eps_in),
-                                                  _capi.ptr(self.eps), _capi.ptr(self.face_points), V, F, self.seed, self.steps, s),
-                        "giga_refine_face_points")
+            _capi.call("giga_refine_face_points", dev, self.vertices, self.faces, eps_in, self.eps, self.face_points, V, F, self.seed,
+                       self.steps)
             self.logit, self.dp, self.hess = (t[0] for t in decoder_point_hess(self.nhwc, self.face_points[None], self.blob,
                                                                               self.bwd_blob))
-            _capi.check(L.giga_refine_face_grad(_capi.ptr(self.vertices), _capi.ptr(self.faces), _capi.ptr(self.eps),
-                                                _capi.ptr(self.logit), _capi.ptr(self.dp), _capi.ptr(self.hess), self.threshold,
-                                                _capi.ptr(self.face_loss), _capi.ptr(self.face_grad), V, F, s),
-                        "giga_refine_face_grad")
-            _capi.check(L.giga_refine_vertex_step(_capi.ptr(self.face_grad), _capi.ptr(self.corner_order),
-                                                  _capi.ptr(self.vertex_offsets), _capi.ptr(self.vertices),
-                                                  _capi.ptr(self.square_avg), _capi.ptr(self.grad), V, F, s),
-                        "giga_refine_vertex_step")
+            _capi.call("giga_refine_face_grad", dev, self.vertices, self.faces, self.eps, self.logit, self.dp, self.hess,
+                       self.threshold, self.face_loss, self.face_grad, V, F)
+            _capi.call("giga_refine_vertex_step", dev, self.face_grad, self.corner_order, self.vertex_offsets, self.vertices,
+                       self.square_avg, self.grad, V, F)
         self.steps += 1
         return self
 

@@ -20,8 +20,8 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import _capi, perception
-from .eval import _device, _hptr, _mesh_devices, _mesh_parts, _offsets, _pack_meshes, mesh_contains_batch
+from . import _capi, perception, ragged
+from .eval import mesh_contains_batch
 
 SIM_INTRINSIC = (640, 480, 540.0, 540.0, 320.0, 240.0)       # simulation.py:38: width, height, fx, fy, cx, cy
 SIM_NEAR, SIM_FAR = 0.1, 2.0                                  # simulation.py:39
@@ -56,26 +56,19 @@ def render_depth_batch(meshes, intrinsic, extrinsics_batches, near=SIM_NEAR, far
     if len(extrinsics_batches) != len(meshes):
         raise ValueError("one list of extrinsics per mesh")
     B = len(meshes)
-    tensors = _mesh_devices(meshes)
-    dev = torch.device(device) if device is not None else _device(*tensors)
-    if dev.type != "cuda":
-        raise _capi.GigaHipError("depth rendering runs on a HIP device; there is no CPU fallback")
-    _capi.device_of(*[t for t in tensors if torch.is_tensor(t)], torch.empty(0, device=dev))
+    dev = _capi.hip_device(*ragged.mesh_arrays(meshes), device=device, what="depth rendering runs on a HIP device")
     H, W = int(intrinsic.height), int(intrinsic.width)
-    view_offsets = _offsets([len(e) for e in extrinsics_batches])
+    view_offsets = ragged.offsets([len(e) for e in extrinsics_batches])
     n = int(view_offsets[-1])
     depth = torch.empty((n, H, W), dtype=torch.float32, device=dev)
     if B == 0 or n == 0:
         return depth, view_offsets
-    v, vo, f, fo = _pack_meshes(meshes, dev)
+    v, vo, f, fo = ragged.pack_meshes(meshes, dev)
     ext = np.ascontiguousarray(np.stack([perception.extrinsic_matrix(e) for batch in extrinsics_batches for e in batch]).reshape(n, 16))
     cam = np.ascontiguousarray(np.tile(np.array([intrinsic.fx, intrinsic.fy, intrinsic.cx, intrinsic.cy], np.float64), (n, 1)))
-    L = _capi.lib()
-    ws = torch.empty(max(L.giga_depth_render_workspace_bytes(B, n, int(vo[-1]), int(fo[-1])), 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check(L.giga_depth_render(_capi.ptr(v), _hptr(vo), _capi.ptr(f), _hptr(fo), _hptr(view_offsets), ext.ctypes.data,
-                                        cam.ctypes.data, B, W, H, float(near), float(far), float(pixel_offset), _capi.ptr(depth),
-                                        _capi.ptr(ws), ws.numel(), _capi.stream_ptr(dev)), "giga_depth_render")
+    ws = _capi.workspace("giga_depth_render", dev, B, n, int(vo[-1]), int(fo[-1]))
+    _capi.call("giga_depth_render", dev, v, vo, f, fo, view_offsets, ext, cam, B, W, H, float(near), float(far), float(pixel_offset),
+               depth, ws, ws.numel())
     if stats is not None:
         stats["tile_pairs"] = stats.get("tile_pairs", 0) + int(ws[:8].cpu().numpy().view(np.uint64)[0])
     return depth, view_offsets
@@ -204,7 +197,7 @@ def write_raw_scenes(raw_root, scene_ids, meshes, n, N=None, size=0.3, batch=32,
 # ------------------------------------------------------------------------------------------------ occupancy labels
 def mesh_bounds(mesh_list):
     """(2, 3) float64: the axis-aligned bounds of all vertices (trimesh's scene.bounds)."""
-    vs = [_mesh_parts(m)[0] for m in mesh_list]
+    vs = [ragged.mesh_parts(m)[0] for m in mesh_list]
     vs = [(v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)).reshape(-1, 3).astype(np.float64) for v in vs]
     v = np.concatenate(vs)
     return np.stack([v.min(axis=0), v.max(axis=0)])
@@ -216,12 +209,9 @@ def sample_iou_points(mesh_list, bounds, num_point, padding=0.02, uniform=False,
     The points come from torch.rand on the device (`generator`: a device generator); the affine map is evaluated in float64 as
     numpy does and rounded to float32 once, and the containment is tested on those float32 points, so the labels belong to the
     returned points.  One ragged giga_mesh_contains launch with one scene per mesh."""
-    tensors = [t for t in _mesh_devices(mesh_list) if torch.is_tensor(t)]
     if generator is not None and device is None:
         device = generator.device
-    dev = torch.device(device) if device is not None else _device(*tensors)
-    if dev.type != "cuda":
-        raise _capi.GigaHipError("occupancy labels are computed on a HIP device; there is no CPU fallback")
+    dev = _capi.hip_device(*ragged.mesh_arrays(mesh_list), device=device, what="occupancy labels are computed on a HIP device")
     points = torch.rand((int(num_point), 3), dtype=torch.float32, device=dev, generator=generator)
     p = points.double()
     if uniform:
@@ -231,7 +221,7 @@ def sample_iou_points(mesh_list, bounds, num_point, padding=0.02, uniform=False,
         p = p * (b[1] + 2 * padding - b[0]) + b[0] - padding
     points = p.float()
     occ = torch.zeros(int(num_point), dtype=torch.bool, device=dev)
-    live = [m for m in mesh_list if len(_mesh_parts(m)[1])]
+    live = [m for m in mesh_list if len(ragged.mesh_parts(m)[1])]
     if live and num_point:
         inside, po = mesh_contains_batch(live, [points] * len(live))
         occ = inside.reshape(len(live), int(num_point)).any(dim=0)

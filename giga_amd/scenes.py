@@ -100,13 +100,6 @@ def resolve_packed(hit, table_hit, object_count):
     return kept
 
 
-def _device_collide(device):
-    def collide(meshes, pairs):
-        from . import collision
-        return collision.mesh_collide(meshes, pairs, containment=True, device=device).cpu().numpy()
-    return collide
-
-
 def generate_packed_scenes(object_set, n_scenes, seed=0, first_scene=0, batch=32, device=None, collide=None):
     """Scenes first_scene .. first_scene + n_scenes - 1 of `seed`.  Per batch of scenes: the 12 x batch candidate bodies are built
     with `render.scene_mesh([entry])` -- the very float32 vertices that are rendered later -- the 66 pairs inside each scene are
@@ -116,7 +109,9 @@ def generate_packed_scenes(object_set, n_scenes, seed=0, first_scene=0, batch=32
     `device`).  A scene's result depends on (seed, scene) only, not on `batch` or `first_scene`."""
     if int(batch) < 1:
         raise ValueError("batch must be at least 1")
-    collide = collide if collide is not None else _device_collide(device)
+    if collide is None:
+        from . import collision
+        collide = lambda meshes, pairs: collision.mesh_collide(meshes, pairs, containment=True, device=device).cpu().numpy()  # noqa: E731
     out = []
     for at in range(0, int(n_scenes), int(batch)):
         ids = range(int(first_scene) + at, int(first_scene) + min(at + int(batch), int(n_scenes)))

@@ -15,15 +15,13 @@ stores.  Where the reference returns the mesh uncoloured (no voxel above `th`), 
 (102, 102, 102, 255) and the affordance is None.
 
 Not reproduced: rendering the composed scene to an image (`render_mesh`, pyrender, NViSII) and the matplotlib plotting helpers."""
-import ctypes
 from dataclasses import dataclass, field
 from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
 
-from . import _capi
-from .eval import _hptr, _mesh_devices, _mesh_parts, _pack_meshes
+from . import _capi, ragged
 
 REDS_ANCHORS = ("fff5f0", "fee0d2", "fcbba1", "fc9272", "fb6a4a", "ef3b2c", "cb181d", "a50f15", "67000d")    # ColorBrewer 'Reds', 9 classes
 DEFAULT_FACE_COLOR = (102, 102, 102, 255)         # trimesh's colour of a face that was given none
@@ -154,7 +152,7 @@ class _Affordance:
             raise ValueError(f"aggregation is 'max', 'softmax' or 'mean', not {aggregation!r}")
         if not (torch.is_tensor(qual_vol) and torch.is_tensor(rot_vol)):
             raise _capi.GigaHipError("affordance_faces takes the volumes as device tensors; there is no CPU fallback")
-        dev = _capi.device_of(qual_vol, rot_vol, *[x for x in _mesh_devices(meshes) if torch.is_tensor(x)])
+        dev = _capi.device_of(qual_vol, rot_vol, *[x for x in ragged.mesh_arrays(meshes) if torch.is_tensor(x)])
         R = int(qual_vol.shape[-1])
         if qual_vol.dim() not in (3, 4) or tuple(qual_vol.shape[-3:]) != (R, R, R):
             raise ValueError(f"expected a (B,R,R,R) or (R,R,R) quality volume, got {tuple(qual_vol.shape)}")
@@ -167,7 +165,7 @@ class _Affordance:
         self.B, self.R, self.dev = B, R, dev
         self.qual = qual_vol.detach().reshape(B, V).float().contiguous()
         self.rot = rot_vol.detach().reshape(B, V, 4).float().contiguous()
-        self.v, self.vo, self.f, self.fo = _pack_meshes(meshes, dev)
+        self.v, self.vo, self.f, self.fo = ragged.pack_meshes(meshes, dev)
         self.prm = _capi.AffordanceParams(float(size), float(th), float(temp), float(rad), float(finger_depth), float(finger_offset),
                                           int(bool(move_center)), _capi.AFFORDANCE[aggregation] | (_capi.AFFORDANCE_DENSE if dense else 0))
         F = int(self.fo[-1])
@@ -175,20 +173,13 @@ class _Affordance:
         self.counts = torch.zeros(B, dtype=torch.int32, device=dev)
         self.affordance = torch.empty(F, dtype=torch.float64, device=dev)
         self.rgba = torch.empty((F, 4), dtype=torch.uint8, device=dev)
-        L = _capi.lib()
-        self.ws = torch.empty(max(L.giga_affordance_workspace_bytes(B, R, F), 256), dtype=torch.uint8, device=dev)
+        self.ws = _capi.workspace("giga_affordance", dev, B, R, F)
 
     def launch(self):
-        L, B, R = _capi.lib(), self.B, self.R
-        with torch.cuda.device(self.dev):
-            s = _capi.stream_ptr(self.dev)
-            _capi.check(L.giga_affordance_points(_capi.ptr(self.qual), _capi.ptr(self.rot), B, R, ctypes.byref(self.prm),
-                                                 _capi.ptr(self.points), _capi.ptr(self.counts), _capi.ptr(self.ws), self.ws.numel(), s),
-                        "giga_affordance_points")
-            _capi.check(L.giga_affordance_faces(_capi.ptr(self.v), _hptr(self.vo), _capi.ptr(self.f), _hptr(self.fo),
-                                                _capi.ptr(self.points), _capi.ptr(self.counts), B, R, ctypes.byref(self.prm),
-                                                _capi.ptr(self.affordance), _capi.ptr(self.rgba), _capi.ptr(self.ws), self.ws.numel(), s),
-                        "giga_affordance_faces")
+        B, R, ws = self.B, self.R, self.ws
+        _capi.call("giga_affordance_points", self.dev, self.qual, self.rot, B, R, self.prm, self.points, self.counts, ws, ws.numel())
+        _capi.call("giga_affordance_faces", self.dev, self.v, self.vo, self.f, self.fo, self.points, self.counts, B, R, self.prm,
+                   self.affordance, self.rgba, ws, ws.numel())
         return self
 
     def finish(self):
@@ -231,7 +222,7 @@ def affordance_faces(qual_vol, rot_vol, meshes, size=0.3, th=0.5, temp=150, rad=
 
 
 def _colored(mesh, affordance, rgba):
-    v, f = _mesh_parts(mesh)
+    v, f = ragged.mesh_parts(mesh)
     v, f = (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x) for x in (v, f))
     m = ColoredMesh(v, f, rgba.cpu().numpy(), affordance=affordance)
     m.ranges["scene"] = (0, len(m.faces))

@@ -27,6 +27,50 @@ def test_library_exports_every_declared_symbol():
     assert lib.giga_strerror(0) == b"ok" and lib.giga_strerror(-4) == b"workspace too small"
 
 
+def test_python_signatures_equal_the_header_prototypes():
+    """_capi._SIGNATURES is the third copy of every prototype (the header, the definition, the ctypes table) and the only one no
+    compiler sees: a c_int where the header says size_t would truncate silently.  Every giga_* prototype of include/giga_hip.h,
+    comments stripped, against the table: the kind of the return value and of every argument."""
+    hdr = open(os.path.join(ROOT, "include", "giga_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    hdr = re.sub(r"^\s*#[^\n]*", " ", hdr, flags=re.M)
+
+    def kind_of_c(decl, ret=False):
+        decl = " ".join(decl.split())
+        if "*" in decl:
+            return "char_p" if ret and decl.replace(" ", "") == "constchar*" else "pointer"
+        words = decl.split()
+        if not ret and len(words) > 1:
+            words = words[:-1]                                               # the parameter's name
+        words = [w for w in words if w != "const"]
+        kind = {("int",): "int", ("int32_t",): "int", ("size_t",): "size_t", ("double",): "double", ("uint64_t",): "u64",
+                ("unsigned", "long", "long"): "u64", ("void",): "void"}.get(tuple(words))
+        assert kind is not None and (ret or kind != "void"), f"unreadable C type {decl!r}"
+        return kind
+
+    def agree(kind, t):
+        """(where size_t has 64 bits, c_size_t and c_uint64 are one class, so a kind names the types it accepts)"""
+        if kind == "u64":
+            return t in (ctypes.c_uint64, ctypes.c_ulonglong) and ctypes.sizeof(t) == 8
+        return t is {"void": None, "pointer": ctypes.c_void_p, "char_p": ctypes.c_char_p, "int": ctypes.c_int,
+                     "size_t": ctypes.c_size_t, "double": ctypes.c_double}[kind]
+
+    parsed = {}
+    for m in re.finditer(r"([\w\s\*]+?)\b(giga_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr):
+        ret, name, args = m.group(1), m.group(2), m.group(3).strip()
+        assert name not in parsed, f"{name} is declared twice"
+        args = [] if args in ("", "void") else [kind_of_c(a) for a in args.split(",")]
+        parsed[name] = (kind_of_c(ret, ret=True), args)
+    # as many prototypes as the table has entries: one the pattern fails to read cannot hide a mismatch
+    assert len(parsed) == len(_capi._SIGNATURES) and set(parsed) == set(_capi._SIGNATURES), set(parsed) ^ set(_capi._SIGNATURES)
+    for name, (res, argtypes) in _capi._SIGNATURES.items():
+        assert agree(parsed[name][0], res), (name, "return", parsed[name][0], res)
+        assert len(argtypes) == len(parsed[name][1]), (name, len(argtypes), len(parsed[name][1]))
+        for i, (have, want) in enumerate(zip(argtypes, parsed[name][1])):
+            assert agree(want, have), (name, f"argument {i}", have, want)
+
+
 def test_python_constants_equal_the_header_defines():
     """giga_amd._capi repeats the flag values of include/giga_hip.h; pin them to the header (a drifted flag bit would select
     another launch form or arithmetic mode silently), and check that the library masks every flag before validating."""

@@ -238,7 +238,7 @@ def test_sampler_seeds_batches_and_empty_meshes(cases):
     p, face, nr, counts = E.sample_surface_batch(meshes, 4000, seed=5)
     assert counts.tolist() == [4000, 0, 4000, 0, 4000]
     for k in (0, 2, 4):
-        sp, sf, sn = _sample(*E._mesh_parts(meshes[k]), 4000, 5, scene=k)
+        sp, sf, sn = _sample(*E.ragged.mesh_parts(meshes[k]), 4000, 5, scene=k)
         assert p[k].cpu().numpy().tobytes() == sp.tobytes() and np.array_equal(face[k].cpu().numpy(), sf), k
         assert nr[k].cpu().numpy().tobytes() == sn.tobytes(), k
     assert not np.array_equal(p[0].cpu().numpy(), p[4].cpu().numpy())       # the same mesh as another scene: other samples
