@@ -178,8 +178,10 @@ def test_f16_decoder_heads_against_f16_operand_oracle(sd7):
         print("f16 chain, lattice, one scene", h, _between_valid_evaluations(g1, a[:1], b[:1], ("lattice-1", h)))
 
 
-def _integer_state_dict(sd, seed):
-    """Heads whose arithmetic is exact in every mode: signed-permutation-like matrices (one +-1 per row), integer biases."""
+def _integer_state_dict(sd, seed, per_row=1, out_per_row=3, fc_p=False):
+    """Heads whose arithmetic is exact in every mode: signed-permutation-like matrices (one +-1 per row), integer biases.
+    per_row / out_per_row: +-1 entries per row of the hidden matrices / of fc_out; fc_p: fc_p.weight drawn from {-1, 0, 1}
+    instead of zero (tests/dect_exact.py: denser gradients for the bf16 training decoder)."""
     g = torch.Generator().manual_seed(seed)
     out = {k: v.clone() for k, v in sd.items()}
 
@@ -195,16 +197,16 @@ def _integer_state_dict(sd, seed):
 
     for h in weights.HEADS:
         od = out[f"{h}.fc_out.weight"].shape[0]
-        out[f"{h}.fc_p.weight"] = torch.zeros(32, 3)
+        out[f"{h}.fc_p.weight"] = torch.randint(-1, 2, (32, 3), generator=g).float() if fc_p else torch.zeros(32, 3)
         out[f"{h}.fc_p.bias"] = ibias(32)
         for i in range(5):
-            out[f"{h}.fc_c.{i}.weight"] = sparse(32, 96)
+            out[f"{h}.fc_c.{i}.weight"] = sparse(32, 96, per_row)
             out[f"{h}.fc_c.{i}.bias"] = ibias(32)
-            out[f"{h}.blocks.{i}.fc_0.weight"] = sparse(32, 32)
+            out[f"{h}.blocks.{i}.fc_0.weight"] = sparse(32, 32, per_row)
             out[f"{h}.blocks.{i}.fc_0.bias"] = ibias(32)
-            out[f"{h}.blocks.{i}.fc_1.weight"] = sparse(32, 32)
+            out[f"{h}.blocks.{i}.fc_1.weight"] = sparse(32, 32, per_row)
             out[f"{h}.blocks.{i}.fc_1.bias"] = ibias(32)
-        out[f"{h}.fc_out.weight"] = sparse(od, 32, per_row=3)
+        out[f"{h}.fc_out.weight"] = sparse(od, 32, per_row=out_per_row)
         out[f"{h}.fc_out.bias"] = ibias(od)
     return out
 
