@@ -7,6 +7,7 @@
     from giga_amd import Trainer, train_val_split               # the training loop of scripts/train_giga.py (giga_amd.trainer)
     from giga_amd import GeoTrainer, geo_loss                   # ... and of scripts/train_giga_geo.py: the occupancy-only giga_geo
     from giga_amd import affordance_visual, grasp2mesh          # the scene mesh coloured by grasp quality (giga_amd.visual)
+    from giga_amd import render_color, render_mesh, write_png   # shaded images of coloured meshes (giga_amd.render, giga_amd.visual)
     from giga_amd import GeometryEvaluator, VoxelOccGeoROIDataset   # scene IoU, chamfer, grasp-ROI occupancy (giga_amd.geometry)
     from giga_amd import mesh_collide, generate_packed_scenes, write_geo_dataset   # packed scenes from object meshes (giga_amd.scenes)
 
@@ -15,13 +16,14 @@ __version__ = "0.1.0"
 
 # names of giga_amd.render, resolved on first use (importing the package stays free of torch)
 _RENDER_EXPORTS = ("scene_mesh", "Camera", "render_depth", "render_depth_batch", "acquire_tsdf", "acquire_tsdfs", "write_raw_scenes",
-                   "sample_iou_points", "save_occ")
+                   "sample_iou_points", "save_occ", "render_color", "render_color_batch")
 # ... and of giga_amd.resident: the training set in device memory and its batch iterator
 _RESIDENT_EXPORTS = ("ResidentTrainingSet", "ResidentBatches")
 # ... and of giga_amd.trainer: the training loop, its device-side epoch metrics and the train / validation split
 _TRAINER_EXPORTS = ("Trainer", "TrainMetrics", "train_val_split", "GeoTrainer", "geo_loss")
 # ... and of giga_amd.visual: the affordance colours of a scene mesh, the gripper glyph, the composed scene
-_VISUAL_EXPORTS = ("affordance_faces", "affordance_points", "affordance_visual", "grasp2mesh", "ColoredMesh", "Scene")
+_VISUAL_EXPORTS = ("affordance_faces", "affordance_points", "affordance_visual", "grasp2mesh", "ColoredMesh", "Scene", "render_mesh",
+                   "get_camera_pose", "look_at", "extrinsic_from_camera_pose", "write_png")
 # ... and of giga_amd.geometry: the scoring of predicted geometry (scene IoU, chamfer, grasp-ROI occupancy) and its data sets
 _GEOMETRY_EXPORTS = ("GeometryEvaluator", "VoxelOccGeoDataset", "VoxelOccGeoROIDataset", "occ_confusion", "occ_scores",
                      "roi_point_counts", "load_obj", "default_mesh_loader", "read_mesh_pose_list")

@@ -35,6 +35,7 @@ SIMPLIFY_MIN_REF_EXTRA = 64      # GIGA_SIMPLIFY_MIN_REF_EXTRA: smallest appende
 MISE_MAX_N = 513        # GIGA_MISE_MAX_N: samples per axis of a MISE value grid (resolution0 << depth) + 1
 TSDF_MAX_R = 512         # GIGA_TSDF_MAX_R: cells per axis of a fused volume
 RENDER_MAX_IMAGE = 4096  # GIGA_RENDER_MAX_IMAGE: width and height of a rendered depth image
+DOWNSAMPLE_MAX_K = 4     # GIGA_DOWNSAMPLE_MAX_K: supersampling factor of a shaded image
 REFINE_MAX_FACES = 0x0FFFFFFF   # GIGA_REFINE_MAX_FACES (and _VERTICES)
 NOISE_MODEL = {"dex": 1, "trans": 2, "norm": 3}          # GIGA_NOISE_DEX / _TRANS / _NORM
 MAX_SCENES = 3072        # GIGA_MAX_SCENES: scenes per encoder / training call (error -7 beyond)
@@ -188,6 +189,10 @@ _SIGNATURES = {
     "giga_depth_render_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "giga_depth_render": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 3 + [ctypes.c_double] * 3 + [ctypes.c_void_p] * 2
                           + [ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_color_render_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "giga_color_render": (ctypes.c_int, [ctypes.c_void_p] * 9 + [ctypes.c_double, ctypes.c_void_p] + [ctypes.c_int] * 3
+                          + [ctypes.c_double] * 3 + [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_image_downsample": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
     "giga_depth_noise_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "giga_depth_noise": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_uint64,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

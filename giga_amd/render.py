@@ -11,7 +11,14 @@ attributes); loading mesh files stays with the caller.  There is no CPU path: CP
 The reference's depth noise (simulation.py:176, `--add-noise`) is the `noise=` argument of `acquire_tsdf` / `acquire_tsdfs`: a
 `giga_amd.noise.DepthNoise`, applied on the device between rendering and fusion.
 
-Not reproduced: PyBullet's fill rule at silhouettes, its z-buffer quantisation, RGB."""
+`render_color` / `render_color_batch` / `Camera.render_rgbd` are the RGB half, through `giga_color_render`: the depth renderer's
+visibility with the winning triangle kept (smallest z, then smallest index), and a flat, two-sided shade of the per-face colours
+under one light per view and an ambient term, all in double (include/giga_hip.h has the arithmetic).  `supersample=k` renders the
+k x k sample centres of every pixel and box-filters them with `giga_image_downsample`.  The shading model is the project's own,
+not PyBullet's or pyrender's: agreement with either is not claimed.
+
+Not reproduced: PyBullet's fill rule at silhouettes, its z-buffer quantisation, its lighting model; smooth shading, textures,
+shadows and transparency."""
 import json
 import os
 import time
@@ -79,13 +86,108 @@ def render_depth(vertices, faces, intrinsic, extrinsics, near=SIM_NEAR, far=SIM_
     return render_depth_batch([(vertices, faces)], intrinsic, [list(extrinsics)], near, far, pixel_offset, device)[0]
 
 
+HEADLIGHT = (0.0, 0.0, 0.0, 1.0)                              # a point light at the camera
+
+
+def supersample_camera(intrinsic, pixel_offset, k):
+    """((k W, k H, k fx, k fy, k cx, k cy), k (pixel_offset - 0.5) + 0.5): the camera whose pixels are the k x k sample centres
+    inside each pixel's footprint of `intrinsic`, symmetric about the pixel's centre.  k = 1 changes nothing."""
+    k = int(k)
+    if not 1 <= k <= _capi.DOWNSAMPLE_MAX_K:
+        raise ValueError(f"supersample is 1 .. {_capi.DOWNSAMPLE_MAX_K}, not {k}")
+    W, H = int(intrinsic.width), int(intrinsic.height)
+    if k == 1:
+        return (W, H, float(intrinsic.fx), float(intrinsic.fy), float(intrinsic.cx), float(intrinsic.cy)), float(pixel_offset)
+    return ((k * W, k * H, k * float(intrinsic.fx), k * float(intrinsic.fy), k * float(intrinsic.cx), k * float(intrinsic.cy)),
+            k * (float(pixel_offset) - 0.5) + 0.5)
+
+
+def downsample(rgba, k):
+    """(n, k H, k W, 4) uint8 device tensor -> (n, H, W, 4): the exact k x k box filter of giga_image_downsample."""
+    n, Hk, Wk = int(rgba.shape[0]), int(rgba.shape[1]), int(rgba.shape[2])
+    k = int(k)
+    if not 1 <= k <= _capi.DOWNSAMPLE_MAX_K or Hk % k or Wk % k or rgba.dim() != 4 or rgba.shape[3] != 4 or rgba.dtype != torch.uint8:
+        raise ValueError(f"downsample takes (n, k H, k W, 4) uint8 and k in 1 .. {_capi.DOWNSAMPLE_MAX_K}")
+    dev = _capi.hip_device(rgba, what="images are filtered on a HIP device")
+    src = rgba.contiguous()
+    dst = torch.empty((n, Hk // k, Wk // k, 4), dtype=torch.uint8, device=dev)
+    if n:
+        _capi.call("giga_image_downsample", dev, src, dst, n, Wk // k, Hk // k, k)
+    return dst
+
+
+def _lights(lights, n):
+    """None, one (lx, ly, lz, lw) or one per view -> (n, 4) float64"""
+    a = np.asarray(HEADLIGHT if lights is None else lights, np.float64)
+    if a.shape == (4,):
+        a = np.tile(a, (n, 1))
+    if a.shape != (n, 4):
+        raise ValueError(f"lights: one (lx, ly, lz, lw) or one per view ({n}), not an array of shape {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def render_color_batch(meshes, face_colors, intrinsic, extrinsics_batches, lights=None, ambient=0.3, background=(255, 255, 255, 255),
+                       near=SIM_NEAR, far=SIM_FAR, pixel_offset=0.0, supersample=1, return_buffers=False, device=None, stats=None):
+    """Shaded images of B coloured scenes with ragged view counts in one launch of giga_color_render (flat, two-sided shading of
+    the face colours: the project's own model, see include/giga_hip.h; not pyrender's).  face_colors[b]: (F_b, 4) uint8 RGBA per
+    face of meshes[b] (numpy or device tensor).  lights: None (the headlight), one (lx, ly, lz, lw) in the camera frame, or one per
+    view: lw = 1 a point light at that position, lw = 0 a direction towards the light.  supersample = k renders k x k samples per
+    pixel and box-filters them.
+    Returns (rgba (n, H, W, 4) uint8 device tensor, view_offsets); with return_buffers also depth (n, kH, kW) float32 and the
+    winning triangle's index in its scene (n, kH, kW) int32, -1 for none, both at the rendered (fine) resolution.  stats: as for
+    `render_depth_batch`."""
+    if len(extrinsics_batches) != len(meshes) or len(face_colors) != len(meshes):
+        raise ValueError("one list of extrinsics and one colour array per mesh")
+    B = len(meshes)
+    dev = _capi.hip_device(*ragged.mesh_arrays(meshes), *face_colors, device=device, what="colour rendering runs on a HIP device")
+    k = int(supersample)
+    (W, H, fx, fy, cx, cy), po = supersample_camera(intrinsic, pixel_offset, k)
+    view_offsets = ragged.offsets([len(e) for e in extrinsics_batches])
+    n = int(view_offsets[-1])
+    bg = np.ascontiguousarray(np.asarray(background).reshape(4), np.uint8)
+    if not np.array_equal(bg, np.asarray(background).reshape(4)):
+        raise ValueError("background is four bytes, RGBA")
+    fine = torch.empty((n, H, W, 4), dtype=torch.uint8, device=dev)
+    depth = torch.empty((n, H, W), dtype=torch.float32, device=dev) if return_buffers else None
+    index = torch.empty((n, H, W), dtype=torch.int32, device=dev) if return_buffers else None
+    if B and n:
+        v, vo, f, fo = ragged.pack_meshes(meshes, dev)
+        col, co = ragged.pack(face_colors, dev, torch.uint8, cols=4)
+        if not np.array_equal(co, fo):
+            raise ValueError("one colour per face")
+        ext = np.ascontiguousarray(np.stack([perception.extrinsic_matrix(e) for batch in extrinsics_batches for e in batch]).reshape(n, 16))
+        cam = np.ascontiguousarray(np.tile(np.array([fx, fy, cx, cy], np.float64), (n, 1)))
+        ws = _capi.workspace("giga_color_render", dev, B, n, int(vo[-1]), int(fo[-1]))
+        _capi.call("giga_color_render", dev, v, vo, f, fo, col, view_offsets, ext, cam, _lights(lights, n), float(ambient), bg, B, W, H,
+                   float(near), float(far), po, fine, depth, index, ws, ws.numel())
+        if stats is not None:
+            stats["tile_pairs"] = stats.get("tile_pairs", 0) + int(ws[:8].cpu().numpy().view(np.uint64)[0])
+    rgba = downsample(fine, k) if k > 1 else fine
+    return (rgba, view_offsets, depth, index) if return_buffers else (rgba, view_offsets)
+
+
+def render_color(vertices, faces, face_colors, intrinsic, extrinsics, **kwargs):
+    """`render_color_batch` for one mesh seen from n extrinsics: (n, H, W, 4) uint8 device tensor (with return_buffers: that,
+    depth and triangle index)."""
+    out = render_color_batch([(vertices, faces)], [face_colors], intrinsic, [list(extrinsics)], **kwargs)
+    return (out[0], out[2], out[3]) if kwargs.get("return_buffers") else out[0]
+
+
 class Camera(object):
-    """btsim.Camera (btsim.py:276-337) without the RGB image: the mesh is passed in instead of living in a physics world."""
+    """btsim.Camera (btsim.py:276-337): the mesh is passed in instead of living in a physics world.  `render` returns the depth
+    image, `render_rgbd` the (rgb, depth) pair of the reference's `render`."""
 
     def __init__(self, intrinsic, near, far):
         self.intrinsic = intrinsic
         self.near = near
         self.far = far
+
+    def render_rgbd(self, extrinsic, vertices, faces, face_colors, pixel_offset=0.0, device=None, **shade):
+        """(rgb (H, W, 3) uint8, depth (H, W) float32) device tensors; shade: lights, ambient, background of `render_color_batch`.
+        The depth is `render`'s, byte for byte."""
+        rgba, depth, _ = render_color(vertices, faces, face_colors, self.intrinsic, [extrinsic], near=self.near, far=self.far,
+                                      pixel_offset=pixel_offset, return_buffers=True, device=device, **shade)
+        return rgba[0, :, :, :3], depth[0]
 
     def render(self, extrinsic, vertices, faces, pixel_offset=0.0, device=None):
         """extrinsic: the transform from the world to the camera frame, T_cam_world (any extrinsic form).

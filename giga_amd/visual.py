@@ -14,7 +14,13 @@ own for `face_colors`, which could not be compared where this was written: a byt
 stores.  Where the reference returns the mesh uncoloured (no voxel above `th`), every face gets trimesh's default grey
 (102, 102, 102, 255) and the affordance is None.
 
-Not reproduced: rendering the composed scene to an image (`render_mesh`, pyrender, NViSII) and the matplotlib plotting helpers."""
+`render_mesh` / `Scene.render` / `Scene.save_image` turn the composed scene into a picture on a headless device (visual.py:147-164,
+pyrender there) through `giga_color_render` (giga_amd/render.py), with `get_camera_pose` (the reference's formula), `look_at` and
+`extrinsic_from_camera_pose` for the camera and `write_png` (zlib only) for the file.  The shading is flat and two-sided, one
+point or directional light plus an ambient term: the project's own model, not pyrender's metallic-roughness one.
+
+Not reproduced: pyrender's shading model, smooth shading, textures, shadows and transparency (the gripper's alpha of 180 is
+ignored); NViSII; the matplotlib plotting helpers."""
 from dataclasses import dataclass, field
 from typing import Dict, Optional, Tuple
 
@@ -114,6 +120,15 @@ class Scene(ColoredMesh):
     def geometry(self, name):
         a, b = self.ranges[name]
         return self.faces[a:b], self.face_colors[a:b]
+
+    def render(self, camera_pose=None, **kw):
+        """`render_mesh` of the composed scene: (H, W, 3) uint8 numpy array.  camera_pose: an OpenGL camera-to-world pose
+        (`get_camera_pose`, `look_at`); None is the side-view camera of `render.acquire_extrinsics(sideview=True)`."""
+        return render_mesh(self, camera_pose, **kw)
+
+    def save_image(self, path, **kw):
+        """`render` written as an 8-bit RGB .png; returns the path"""
+        return write_png(path, self.render(**kw))
 
 
 def _write_ply(path, vertices, faces, colors):
@@ -304,3 +319,84 @@ def grasp2mesh(grasp, score=None, finger_depth=0.05):
     vertex-for-vertex equality with trimesh.creation.cylinder is not claimed."""
     v, f = gripper_geometry(grasp, finger_depth)
     return ColoredMesh(v, f, np.tile(np.array(GRIPPER_COLOR, np.uint8), (len(f), 1)))
+
+
+# ---------------------------------------------------------------------------------------------------------------- rendering
+def get_camera_pose(radius, center=(0.0, 0.0, 0.0), ax=0, ay=0, az=0):
+    """visual.py:147-155: the OpenGL camera-to-world pose (the camera looks down its -z axis, y up) at distance `radius` from
+    `center`: rotation = Rotation.from_euler('xyz', (ax, ay, az)) = Rz(az) Ry(ay) Rx(ax), translation = rotation (0, 0, radius)
+    + center.  4x4 float64."""
+    (cx, sx), (cy, sy), (cz, sz) = ((np.cos(a), np.sin(a)) for a in (float(ax), float(ay), float(az)))
+    rx = np.array([[1.0, 0.0, 0.0], [0.0, cx, -sx], [0.0, sx, cx]])
+    ry = np.array([[cy, 0.0, sy], [0.0, 1.0, 0.0], [-sy, 0.0, cy]])
+    rz = np.array([[cz, -sz, 0.0], [sz, cz, 0.0], [0.0, 0.0, 1.0]])
+    pose = np.eye(4)
+    pose[:3, :3] = rz @ ry @ rx
+    pose[:3, 3] = pose[:3, :3] @ np.array([0.0, 0.0, float(radius)]) + np.asarray(center, np.float64)
+    return pose
+
+
+def look_at(eye, target, up=(0.0, 0.0, 1.0)):
+    """The OpenGL camera-to-world pose of a camera at `eye` that looks at `target` with `up` upwards in the image."""
+    eye, target, up = (np.asarray(x, np.float64).reshape(3) for x in (eye, target, up))
+    z = eye - target
+    z = z / np.linalg.norm(z)
+    x = np.cross(up, z)
+    if not np.linalg.norm(x) > 0:
+        raise ValueError("up is parallel to the viewing direction")
+    x = x / np.linalg.norm(x)
+    pose = np.eye(4)
+    pose[:3, 0], pose[:3, 1], pose[:3, 2], pose[:3, 3] = x, np.cross(z, x), z, eye
+    return pose
+
+
+def extrinsic_from_camera_pose(pose):
+    """OpenGL camera-to-world pose -> this package's extrinsic (world-to-camera, z forward, y down): diag(1, -1, -1, 1) pose^-1,
+    the inverse taken as that of a rigid transform."""
+    pose = np.asarray(pose, np.float64).reshape(4, 4)
+    inv = np.eye(4)
+    inv[:3, :3] = pose[:3, :3].T
+    inv[:3, 3] = -pose[:3, :3].T @ pose[:3, 3]
+    return np.diag([1.0, -1.0, -1.0, 1.0]) @ inv
+
+
+def render_mesh(mesh, camera_pose=None, light_pose=None, intrinsic=None, ambient=0.3, background=(255, 255, 255, 255), near=None,
+                far=None, pixel_offset=0.0, supersample=1, device=None):
+    """visual.py:157-164 without pyrender: a `ColoredMesh` / `Scene` seen from the OpenGL camera-to-world pose `camera_pose`
+    (None: the side view of `render.acquire_extrinsics`), lit by a point light at the origin of `light_pose` (a camera-to-world
+    style 4x4; None: a headlight at the camera).  intrinsic: a `perception.CameraIntrinsic`, default `render.sim_intrinsic()`;
+    near / far default to the simulated camera's 0.1 / 2.0.  Returns an (H, W, 3) uint8 numpy array.  Flat, two-sided shading of
+    the face colours through `giga_color_render`: the project's own model (include/giga_hip.h), not pyrender's
+    metallic-roughness one; the faces' alpha is not used."""
+    from . import render
+    intrinsic = render.sim_intrinsic() if intrinsic is None else intrinsic
+    ext = render.acquire_extrinsics(1, sideview=True)[0] if camera_pose is None else extrinsic_from_camera_pose(camera_pose)
+    light = None
+    if light_pose is not None:
+        at = ext @ np.r_[np.asarray(light_pose, np.float64).reshape(4, 4)[:3, 3], 1.0]
+        light = (at[0], at[1], at[2], 1.0)
+    rgba = render.render_color(mesh.vertices, mesh.faces, mesh.face_colors, intrinsic, [ext], lights=light, ambient=ambient,
+                               background=background, near=render.SIM_NEAR if near is None else near,
+                               far=render.SIM_FAR if far is None else far, pixel_offset=pixel_offset, supersample=supersample,
+                               device=device)
+    return np.ascontiguousarray(rgba[0, :, :, :3].cpu().numpy())
+
+
+def write_png(path, image):
+    """(H, W, 3) or (H, W, 4) uint8 array (numpy or tensor) -> an 8-bit RGB / RGBA .png without interlace, every row with filter
+    0, through the standard library's zlib.  Returns the path."""
+    import struct
+    import zlib
+    a = image.detach().cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("write_png takes an (H, W, 3) or (H, W, 4) uint8 image")
+    H, W, C = a.shape
+    rows = np.zeros((H, 1 + W * C), np.uint8)          # filter type 0 in front of every row
+    rows[:, 1:] = a.reshape(H, W * C)
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+    with open(str(path), "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2 if C == 3 else 6, 0, 0, 0))
+                + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+    return str(path)

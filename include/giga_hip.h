@@ -410,7 +410,7 @@ int giga_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, d
  * A triangle with a vertex index outside its scene is skipped; a triangle with a non-finite vertex is never accepted (its
  * comparisons are false).  The minimum does not depend on the order: equal input gives equal bytes, and a batch gives scene b
  * the bytes of a call on scene b alone.  No allocation; asynchronous on `stream`.
- * Not reproduced: PyBullet's TinyRenderer fill rule at silhouettes, its z-buffer quantisation, its RGB output.
+ * Not reproduced: PyBullet's TinyRenderer fill rule at silhouettes, its z-buffer quantisation (RGB: giga_color_render below).
  * Measurement aid: the first 8 bytes of the workspace hold, after the call, the number of (triangle, 16x16 pixel tile) pairs that
  * survived the kernel's culling (uint64).
  * Errors: -1 negative B, W or H outside 1 .. GIGA_RENDER_MAX_IMAGE, near / far / pixel_offset not finite, near <= 0, far <= near,
@@ -424,6 +424,48 @@ int giga_depth_render(const float* vertices, const int32_t* vertex_offsets, cons
                       const int32_t* view_offsets, const double* extrinsics, const double* intrinsics, int B, int W, int H,
                       double near, double far, double pixel_offset, float* depth, void* workspace, size_t workspace_bytes,
                       void* stream);
+
+/* ---- output side: shaded images of coloured meshes (render_mesh of src/vgn/utils/visual.py:147-164, pyrender there, and the RGB
+ * half of btsim.Camera.render) -----
+ * giga_color_render takes giga_depth_render's ragged mesh batch and cameras (the same layouts, HOST arrays and checks) and in
+ * addition face_colors [.][4] uint8 RGBA (device, 4-byte aligned), one per triangle in the order of `triangles`; lights [n][4]
+ * double (HOST, per view, camera frame: (lx, ly, lz, lw); NULL = (0, 0, 0, 1) for every view); ambient in [0, 1]; background [4] uint8
+ * RGBA (HOST; NULL = opaque white).  Outputs (device), per pixel: rgba [n][H][W] uint32 = R | G << 8 | B << 16 | A << 24 (in memory
+ * the bytes R, G, B, A); depth [n][H][W] float32, may be NULL; triangle_index [n][H][W] int32, the winning triangle counted from
+ * its scene's first triangle, or -1, may be NULL.
+ *   visibility   giga_depth_render's hit test and depth z, operation for operation.  Among the accepted triangles the winner is
+ *                the one with the smallest z, and among equal z the one with the smallest index: the image does not depend on the
+ *                order in which triangles are tested.  depth = float(z of the winner) or float(far): giga_depth_render's bytes.
+ *   shading      flat and two-sided, in double, one IEEE rounding per operation, sums of three left to right
+ *                ((x0 y0 + x1 y1) + x2 y2), with the winner's camera-space vertices a, b, c, its z and the pixel's direction d:
+ *                  p = (z d.x, z d.y, z)
+ *                  n = (b - a) x (c - a)          (the cross product as in the edge function)
+ *                  L = (lx - lw p.x, ly - lw p.y, lz - lw p.z): lw = 1 is a point light at (lx, ly, lz), (0, 0, 0, 1) the
+ *                      headlight at the camera; lw = 0 a direction towards the light
+ *                  q = (n . n) (L . L)
+ *                  k = ambient + ((1 - ambient) |n . L|) / sqrt(q);  k = ambient when q is 0 or not finite
+ *                  each of the face's R, G, B bytes C becomes min(floor(k C + 0.5), 255); alpha is 255.
+ *                A pixel without a winner gets `background`, all four bytes.
+ * This is the project's own shading model, not pyrender's metallic-roughness one; no smooth shading, textures, shadows or
+ * transparency (the face's alpha is not used).  Equal input gives equal bytes; a batch gives scene b the bytes of a call on
+ * scene b alone.  No allocation; asynchronous on `stream`.  The first 8 bytes of the workspace count the surviving (triangle,
+ * tile) pairs as for giga_depth_render.
+ * Errors: giga_depth_render's, and -1 ambient outside [0, 1] (or NaN), a non-finite light, null or misaligned face_colors with a
+ * non-zero triangle count; -6 null rgba (with views); -4 workspace smaller than giga_color_render_workspace_bytes(...).
+ *
+ * giga_image_downsample: k x k box filter of RGBA bytes, k in 1 .. GIGA_DOWNSAMPLE_MAX_K, in integers: src [n][k H][k W] uint32,
+ * dst [n][H][W] uint32 (device), per channel dst = (sum of the k k samples + (k k) / 2) / (k k), integer division.  Rendering at
+ * k W x k H with fx' = k fx, fy' = k fy, cx' = k cx, cy' = k cy, pixel_offset' = k (pixel_offset - 0.5) + 0.5 puts the k k samples
+ * on a regular grid inside each pixel's footprint, symmetric about its centre.
+ * Errors: -1 negative n, k outside 1 .. 4, W or H outside 1 .. GIGA_RENDER_MAX_IMAGE, n W H k k >= 2^31, null src; -6 null dst. */
+#define GIGA_DOWNSAMPLE_MAX_K 4
+size_t giga_color_render_workspace_bytes(int B, int n_views, int n_vertices, int n_triangles);
+int giga_color_render(const float* vertices, const int32_t* vertex_offsets, const int32_t* triangles, const int32_t* triangle_offsets,
+                      const uint8_t* face_colors, const int32_t* view_offsets, const double* extrinsics, const double* intrinsics,
+                      const double* lights, double ambient, const uint8_t* background, int B, int W, int H, double near, double far,
+                      double pixel_offset, uint32_t* rgba, float* depth, int32_t* triangle_index, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int giga_image_downsample(const uint32_t* src, uint32_t* dst, int n, int W, int H, int k, void* stream);
 
 /* ---- input side: depth-sensor noise, the dex, trans and norm models of vgn.utils.misc.apply_noise (src/vgn/utils/misc.py:18-69),
  * which the reference applies to every depth image before fusion (scripts/construct_dataset_parallel.py:21, simulation.py:176) -----
