@@ -19,6 +19,7 @@ piecewise entry points (`encode_inputs`, `decode`, `LocalDecoder.forward`, ...) 
 parameters require grad.  With frozen parameters, `forward`, `decode`, `decode_occ` and `infer_geo` are differentiable w.r.t. the query points
 (giga_decoder_point_grad; `grad_refine` uses it directly).
 """
+import ctypes
 import os
 
 import torch
@@ -413,6 +414,25 @@ def decode_heads(nhwc, p, blob, head_mask, precision, post, probe=None, folded=F
             _capi.stream_ptr(dev), ev0, ev1),
             "giga_decoder_forward")
     return out
+
+
+DECODER_PLAN_FIELDS = ("kernel", "T", "NW", "split", "dbuf", "grid_x", "grid_y", "block", "lds", "nbatch", "heads_per_wg", "lat_parts",
+                       "slots", "xcd_remap")          # struct DecPlan of csrc/giga_dec_plan.h
+DECODER_KERNELS = (None, "decoder_f16_kernel", "decoder_f16s_kernel", "decoder_lat_kernel", "decoder_f32_kernel",
+                   "decoder_f32_tile_kernel", "decoder_f32_point_kernel")     # GIGA_DEC_KERNEL_*
+
+
+def decoder_plan(B, N, R, nheads, precision):
+    """What a decoder launch of `nheads` heads would do now (giga_decoder_plan; host only, the GIGA_DEC* variables are read as a
+    launch reads them): B x N generic queries (R = 0) or the R^3 lattice (N is ignored), `precision` the decoder's code 0 fp32,
+    1 f16, 2 f16x3.  A dict of DECODER_PLAN_FIELDS, `kernel` as the kernel's name (None: nothing is launched), the flags as bools."""
+    words = (ctypes.c_int32 * len(DECODER_PLAN_FIELDS))()
+    _capi.check(_capi.lib().giga_decoder_plan(B, N, R, nheads, precision, words), "giga_decoder_plan")
+    plan = dict(zip(DECODER_PLAN_FIELDS, words))
+    plan["kernel"] = DECODER_KERNELS[plan["kernel"]]
+    for flag in ("split", "dbuf", "xcd_remap"):
+        plan[flag] = bool(plan[flag])
+    return plan
 
 
 _HEAD_SLOTS = ("decoder_qual", "decoder_rot", "decoder_width", "decoder_tsdf")

@@ -1,6 +1,6 @@
 // The extern "C" entry points of libgiga_hip.so (declared in include/giga_hip.h) that span kernel files or belong to none: version and
-// giga_strerror, packing / repacking / deriving the weight images (with their kernels), the encoder, planes and decoder forward calls
-// with their probes, giga_backward and its workspace functions, the launch probe and counter, giga_forget_device_state, the event
+// giga_strerror, packing / repacking / deriving the weight images (with their kernels), the encoder forward call
+// with its probe, giga_backward and its workspace functions, the launch probe and counter, giga_forget_device_state, the event
 // helpers and host register / unregister.  Every other entry point stands in the file of its kernels, after them (giga_post.hip,
 // giga_eval.hip, giga_mesh.hip, ...); host checks that several of those share are in giga_check.h.
 #include <hip/hip_runtime.h>
@@ -35,8 +35,6 @@ int launch_decoder_backward(const float* planes, const float* p, const uint8_t* 
                             SideScope* side);
 int launch_plane_gather(const float* dcbuf, const float* p, float* gplanes, int B, int N, hipStream_t s);
 // giga_decoder_train16.hip (bf16 decoder of the bf16 training step)
-int launch_dect_forward(const float* planes, const float* p, const uint8_t* blob, int head_mask, float* const* outs, int B, int N,
-                        int post, hipStream_t s);
 size_t dect_partial_floats(long long P, int nheads);
 int launch_dect_backward(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob, int head_mask,
                          const float* const* outs, const float* const* douts, float* gplanes, float* dcbuf, float* scratch, int B,
@@ -46,12 +44,6 @@ int launch_dect_reduce(const DectPending& pend, float* grads, int head_present, 
 EncWs enc_workspace(int B, int precision);
 int launch_encoder(const float* tsdf, const uint8_t* blob, void* planes_nhwc, float* planes_nchw, int B,
                    int precision, uint8_t* ws, hipStream_t s, int probe_stage, void* ev0, void* ev1);
-// giga_decoder.hip
-int launch_decoder(const DecArgs& a, int precision, hipStream_t s, void* ev0, void* ev1);
-int launch_planes_pack(const float* xz, const float* xy, const float* yz, void* dst, int B, int precision, hipStream_t s);
-int launch_lattice_resample(const void* planes, const float* lin, void* out, int B, int R, int precision, hipStream_t s,
-                            bool planes_fp32 = false);
-int launch_planes_unpack(const void* src, float* dst, int B, int precision, hipStream_t s);
 }  // namespace giga
 
 using namespace giga;
@@ -60,13 +52,6 @@ std::atomic<unsigned long long> giga::g_launch_count{0};
 std::atomic<unsigned long long> giga::g_probe_target{0};
 void* giga::g_probe_ev[2] = {nullptr, nullptr};
 const char* volatile giga::g_probe_name = "";
-
-// byte offset of head h's weight image for a precision (0 fp32, 1 f16, 2 f16x3 split), plain or with conv_final folded in
-static size_t head_image_offset(const PackOff& ko, int h, int precision, bool fold) {
-    if (precision == 2) return fold ? ko.dec16sf[h] : ko.dec16s[h];
-    if (precision == 1) return fold ? ko.dec16f[h] : ko.dec16[h];
-    return fold ? ko.dec32f[h] : ko.dec32[h];
-}
 
 // blob word w <- params[map[w]] (map >= 0) | 0 (map == -1) | untouched (map == -2)
 __global__ void repack_kernel(const float* __restrict__ params, const int32_t* __restrict__ map,
@@ -390,98 +375,6 @@ int giga_event_elapsed_ms(void* ev_start, void* ev_stop, float* ms) {
                ? 0 : -10;
 }
 
-int giga_planes_pack(const float* xz, const float* xy, const float* yz, void* planes_nhwc, int B, int precision,
-                     void* stream) {
-    if (B < 0 || (B > 0 && (!xz || !xy || !yz || !planes_nhwc))) return -1;
-    if (precision < 0 || precision > 2) return -5;
-    return launch_planes_pack(xz, xy, yz, planes_nhwc, B, precision, static_cast<hipStream_t>(stream));
-}
-
-int giga_planes_unpack(const void* planes_nhwc, float* planes_nchw, int B, int precision, void* stream) {
-    if (B < 0 || (B > 0 && (!planes_nhwc || !planes_nchw))) return -1;
-    if (precision < 0 || precision > 2) return -5;
-    return launch_planes_unpack(planes_nhwc, planes_nchw, B, precision, static_cast<hipStream_t>(stream));
-}
-
-// the head list of a decoder launch: the heads of `head_mask` in order, each with its image in the packed blob and its output.
-// -6: a requested head has no output
-static int dec_args_heads(DecArgs& a, int head_mask, float* const (&outs)[NHEADS], const PackOff& ko, int precision, bool fold) {
-    a.nheads = 0;
-    for (int h = 0; h < NHEADS; ++h) {
-        if (!(head_mask >> h & 1)) continue;
-        if (!outs[h]) return -6;
-        a.head_id[a.nheads] = h;
-        a.head_off[a.nheads] = head_image_offset(ko, h, precision, fold);
-        a.out[a.nheads] = outs[h];
-        ++a.nheads;
-    }
-    return 0;
-}
-
-int giga_decoder_forward_probe(const void* planes_nhwc, const float* p, const void* packed, int head_mask,
-                               float* qual, float* rot, float* width, float* occ, int B, int N, int precision,
-                               int post, void* stream, void* ev_start, void* ev_stop) {
-    if (B < 0 || N < 0) return -1;
-    const bool fold = (precision & GIGA_FOLD_FINAL) != 0;     // planes are the encoder output BEFORE conv_final
-    precision &= ~GIGA_FOLD_FINAL;
-    if (precision < 0 || precision > 3 || (precision == 3 && fold)) return -5;
-    if ((long long)B * N == 0 || (head_mask & 15) == 0) return 0;
-    if (!planes_nhwc || !p || !packed) return -1;
-    if (precision == 3) {                                     // bf16 operands / fp32 accumulate on fp32 planes: the bf16 training forward
-        float* outs3[NHEADS] = {qual, rot, width, occ};
-        for (int h = 0; h < NHEADS; ++h)
-            if ((head_mask >> h & 1) && !outs3[h]) return -6;
-        hipStream_t s3 = static_cast<hipStream_t>(stream);
-        if (ev_start && hipEventRecord(static_cast<hipEvent_t>(ev_start), s3) != hipSuccess) return -10;
-        const int rc3 = launch_dect_forward(static_cast<const float*>(planes_nhwc), p, static_cast<const uint8_t*>(packed), head_mask & 15,
-                                            outs3, B, N, post, s3);
-        if (ev_stop && hipEventRecord(static_cast<hipEvent_t>(ev_stop), s3) != hipSuccess) return -10;
-        return rc3;
-    }
-    DecArgs a{};
-    a.planes = planes_nhwc; a.p = p; a.blob = static_cast<const uint8_t*>(packed);
-    float* outs[NHEADS] = {qual, rot, width, occ};
-    if (const int rc = dec_args_heads(a, head_mask, outs, pack_offsets(), precision, fold)) return rc;
-    a.B = B; a.N = N; a.P = (long long)B * N; a.post = post;
-    return launch_decoder(a, precision, static_cast<hipStream_t>(stream), ev_start, ev_stop);
-}
-
-int giga_decoder_forward(const void* planes_nhwc, const float* p, const void* packed, int head_mask, float* qual,
-                         float* rot, float* width, float* occ, int B, int N, int precision, int post,
-                         void* stream) {
-    return giga_decoder_forward_probe(planes_nhwc, p, packed, head_mask, qual, rot, width, occ, B, N, precision,
-                                      post, stream, nullptr, nullptr);
-}
-
-size_t giga_lattice_workspace_bytes(int B, int R, int precision) {
-    precision &= ~(GIGA_FOLD_FINAL | GIGA_PLANES_FP32);
-    if (B <= 0 || R <= 0) return 0;
-    return (size_t)3 * B * R * R * CD * (precision == 1 ? 2 : 4);
-}
-
-int giga_decoder_forward_lattice(const void* planes_nhwc, const float* lin, const void* packed, int head_mask,
-                                 float* qual, float* rot, float* width, float* occ, int B, int R, int precision,
-                                 int post, void* workspace, size_t workspace_bytes, void* stream, void* ev_start,
-                                 void* ev_stop) {
-    if (B < 0 || R < 0 || R > 64) return -1;
-    const bool fold = (precision & GIGA_FOLD_FINAL) != 0;
-    const bool planes32 = (precision & GIGA_PLANES_FP32) != 0;        // fp32 planes into the plain-f16 decoder
-    precision &= ~(GIGA_FOLD_FINAL | GIGA_PLANES_FP32);
-    if (precision < 0 || precision > 2 || (planes32 && precision != 1)) return -5;
-    if (B == 0 || R == 0 || (head_mask & 15) == 0) return 0;
-    if (!planes_nhwc || !lin || !packed || !workspace) return -1;
-    if (workspace_bytes < giga_lattice_workspace_bytes(B, R, precision)) return -4;
-    float* outs[NHEADS] = {qual, rot, width, occ};
-    DecArgs a{};
-    int rc = dec_args_heads(a, head_mask, outs, pack_offsets(), precision, fold);      // (-6 before anything is enqueued)
-    if (rc) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = launch_lattice_resample(planes_nhwc, lin, workspace, B, R, precision, s, planes32);
-    if (rc) return rc;
-    a.planes = workspace; a.p = nullptr; a.blob = static_cast<const uint8_t*>(packed);
-    a.B = B; a.N = R * R * R; a.P = (long long)B * a.N; a.post = post; a.lin = lin; a.R = R;
-    return launch_decoder(a, precision, s, ev_start, ev_stop);
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // training path (fp32)

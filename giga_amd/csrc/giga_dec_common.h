@@ -16,6 +16,22 @@ __device__ __forceinline__ void lds_dma_frags(const uint8_t* src, uint8_t* lds_d
                                          (__attribute__((address_space(3))) void*)(lds_dst + c * FRAG), 16, 0, 0);
 }
 
+// Head-resident f16-class kernels (decoder_f16s_kernel, decoder_lat_kernel): workgroup -> (head, slot of the head's tile or slab
+// range), slots = workgroups per head.  Workgroup i runs on XCD i % 8; when the grid is a multiple of 8 * nheads the slots of one XCD
+// are made contiguous (an eighth of the points = an eighth of the scenes: their planes stay in that XCD's L2; with the plain
+// i % nheads / i / nheads map every XCD walked every scene: 527 MB of fabric traffic per launch).  dec_plan (giga_dec_plan.h) reports
+// the same condition as xcd_remap.
+__device__ __forceinline__ void dec16_head_slot(int nheads, int& hsel, int& slot, int& slots) {
+    slots = gridDim.x / nheads;
+    hsel = blockIdx.x % nheads;
+    slot = blockIdx.x / nheads;
+    if (gridDim.x % (8 * nheads) == 0) {
+        const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3, spx = slots >> 3;
+        hsel = k % nheads;
+        slot = xcd * spx + k / nheads;
+    }
+}
+
 // ---- D layout of the 32x32 MFMAs: register r of lane half hi holds feature (row) drow(r, hi) of the lane's point ----
 __device__ __forceinline__ int drow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 // row `row` of a head image's C table (32 biases) as an accumulator image

@@ -14,9 +14,11 @@
 // so the whole 11-layer chain runs without any cross-lane traffic.  The fp32 residual stream lives
 // in the accumulator (C-in = stream), biases ride in a constant-one k-slot or in the C operand.
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "giga_dec_common.h"
+#include "giga_dec_plan.h"
 #include "giga_args.h"
 
 namespace giga {
@@ -306,16 +308,8 @@ __global__ __launch_bounds__(NW * 64) void decoder_f16s_kernel(DecArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int n = lane & 31, hi = lane >> 5;
-    // workgroup -> (head, slot of the tile range).  Workgroup i runs on XCD i % 8; when the grid is a multiple of 8 * nheads the
-    // slots of one XCD are made contiguous (an eighth of the points = an eighth of the scenes: their planes stay in that XCD's
-    // L2; with the plain i % nheads / i / nheads map every XCD walked every scene: 527 MB of fabric traffic per launch)
-    const int slots = gridDim.x / a.nheads;
-    int hsel = blockIdx.x % a.nheads, slot = blockIdx.x / a.nheads;
-    if (gridDim.x % (8 * a.nheads) == 0) {
-        const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3, spx = slots >> 3;
-        hsel = k % a.nheads;
-        slot = xcd * spx + k / a.nheads;
-    }
+    int hsel, slot, slots;                                     // workgroup -> (head, slot of the tile range)
+    dec16_head_slot(a.nheads, hsel, slot, slots);
     DEC_T(0);
     lds_dma_frags<NW, NCH>(a.blob + a.head_off[hsel], smem, wave, lane);
     DEC_T(1);
@@ -560,16 +554,10 @@ __global__ __launch_bounds__(NW * 64) void decoder_f16s_kernel(DecArgs a) {
 // fc_1, fc_out, the C table: 33 KiB, f16x3 65 KiB), the line phase reads its weight fragments from the image in L2.
 // Head-resident persistent workgroups as decoder_f16s_kernel; slabs are handed out so that an XCD owns a contiguous eighth of
 // the scenes.  Needs R % 8 == 0 (R = 40: 50 tiles per slab, none ragged).
-constexpr int LAT_ROWS = 2 * NBLK + 1;     // line rows: G_xz[0..4], G_xy[0..4], and the bias of the last fc_1 as G_xy[5]
-constexpr int LAT_MAX_R = 40;
 // the low half of a line value is stored scaled by 2^11 and its selector slot carries 2^-11: hi and lo then have the same
 // magnitude class, so lo is a NORMAL f16 number whenever the value itself is above 2^-13 (unscaled it would be subnormal for
 // every |value| < 2^-3), and the product lo * 2^-11 is exact
 constexpr float LAT_LO_SCALE = 2048.0f, LAT_LO_INV = 1.0f / 2048.0f;
-template <bool SPLIT, bool DBUF>
-constexpr size_t lat_lds_bytes(int R) {
-    return (size_t)(32 * (SPLIT ? 2 : 1) + 1) * FRAG + (size_t)(DBUF ? 2 : 1) * LAT_ROWS * (R / 4) * 32 * 16 + 16;
-}
 
 // WORK DISTRIBUTION inside a workgroup is DYNAMIC: tiles (and, with two line buffers, the next slab's line jobs) are items of a
 // pool that the waves drain through one LDS counter.  A static tile -> wave map loses a third of the slab: the SIMD arbiter
@@ -590,13 +578,8 @@ __global__ __launch_bounds__(NW * 64) void decoder_lat_kernel(DecArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int n = lane & 31, hi = lane >> 5;
-    const int slots = gridDim.x / a.nheads;
-    int hsel = blockIdx.x % a.nheads, slot = blockIdx.x / a.nheads;
-    if (gridDim.x % (8 * a.nheads) == 0) {                     // XCD-contiguous slab ranges (workgroup i runs on XCD i % 8)
-        const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3, spx = slots >> 3;
-        hsel = k % a.nheads;
-        slot = xcd * spx + k / a.nheads;
-    }
+    int hsel, slot, slots;                                     // workgroup -> (head, slot of the slab range)
+    dec16_head_slot(a.nheads, hsel, slot, slots);
     const int R = a.R, R2 = R * R, RG = R >> 2;                // RG: groups of 4 line pixels
     // work units: a slab (scene, ix), or for small launches one of NP equal tile ranges of it (a.lat_parts divides the tile count);
     // a unit has its own pool and its own copy of the slab's lines
@@ -1194,7 +1177,6 @@ __global__ __launch_bounds__(256) void decoder_f32_tile_kernel(DecArgs a) {
         if (hi == 0 && valid) store_head(a, h, g, o[0], o[1], o[2], o[3]);
     }
 }
-constexpr size_t DEC32_TILE_LDS = 4 * 32 * 96 * sizeof(float) + NBLK * 4 * 64 * sizeof(float4) + 46 * FRAG;   // 4 gather stages, FC exchange, chain fragments
 
 // ------------------------------- exact fp32 path for ONE query per scene: a GEMV per point, no MFMA ------
 // With N == 1 the 32-point tile above holds one valid point per scene and nothing amortises the weights: the latency of a
@@ -1217,11 +1199,6 @@ __device__ __forceinline__ float hi_halves_sum(float v) {     // lane (n, 0) + l
     lane32_swap(lo, up);                                       // lo = lanes 0..31's value everywhere, up = lanes 32..63's
     return lo + up;
 }
-constexpr size_t DEC32_POINT_LDS = 46 * FRAG + (4 * 96 + NBLK * 32 + 32) * sizeof(float);   // chain fragments, 4 gather stages, FC exchange, GEMV input
-// Up to this many points the point kernel is the default (launch_decoder).  HIP-event medians of seven, mask 7, point / tile kernel
-// (profiles/dec_point/sweep.txt): P = 32 7.2 / 16.1 us, 256 9.7 / 16.1, 384 13.5 / 16.1, 512 15.0 / 16.2, 768 20.0 / 16.3: the curves
-// cross between 512 and 768; the bound sits at the last size with a margin well outside the run-to-run spread.
-constexpr int DEC32_POINT_MAX_P = 256;
 __global__ __launch_bounds__(256) void decoder_f32_point_kernel(DecArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & 63;
@@ -1441,160 +1418,47 @@ __global__ void lattice_resample_split_kernel(const float* __restrict__ planes, 
 }
 
 // ------------------------------- launchers ----------------------------------------------------------
-constexpr size_t DEC32_LDS = DEC32_BYTES + 4 * 32 * 96 * sizeof(float);     // weight image + the gather's per-wave stage
-static_assert(DEC32_LDS <= 160 * 1024, "LDS budget of the fp32 decoder");
-// Per-call knobs of the exact-fp32 one-query dispatch (read on every call: A/B runs and cross-checks in one process).
-//   GIGA_DEC32_TILE=0    neither one-query kernel: decoder_f32_kernel, the general kernel
-//   GIGA_DEC32_POINT=0   no point kernel: the tile kernel where its own rule holds
-//   GIGA_DEC32_POINT=n   n > 1: the point kernel up to n points instead of DEC32_POINT_MAX_P (sweeps; at most the tile rule's 3072)
-// Anything else (unset, 1, negative, not a number) leaves the default bound.
-static bool dec32_one_query_kernels() {
-    const char* e = getenv("GIGA_DEC32_TILE");
-    return e ? atoi(e) != 0 : true;
-}
-static long long dec32_point_bound() {
-    const char* e = getenv("GIGA_DEC32_POINT");
-    if (!e) return DEC32_POINT_MAX_P;
-    const int v = atoi(e);
-    if (v == 0 && e[0] == '0') return 0;
-    if (v <= 1) return DEC32_POINT_MAX_P;
-    return v < 3072 ? v : 3072;
-}
-int launch_decoder(const DecArgs& a0, int precision, hipStream_t s, void* ev0, void* ev1) {
+// The policy is dec_plan (giga_dec_plan.h); this function launches what the plan says.
+static int launch_decoder(const DecArgs& a0, int precision, hipStream_t s, void* ev0, void* ev1) {
     DecArgs a = a0;
     if (a.P <= 0 || a.nheads <= 0) return 0;
     if (ev0 && ev1) (void)hipEventRecord(static_cast<hipEvent_t>(ev0), s);
-    const long long tiles = (a.P + 31) / 32;
     const bool lat = a.R > 0;
     a.invN = 1.0f / (float)a.N;
     if (lat) {
         a.mR = (unsigned)((0x100000000ULL + a.R - 1) / a.R);
         a.mR2 = (unsigned)((0x100000000ULL + (unsigned long long)a.R * a.R - 1) / ((unsigned long long)a.R * a.R));
     }
-    // Head-resident kernel: always for the f16x3 split mode; for plain f16 when the launch is small (the shared-feature
-    // kernel below walks rounds of NW*T tiles per workgroup with all heads on the same CU: a single scene's 2000 tiles then
-    // keep only 84 CUs busy: 31.6 -> 16.3 us for the three grasp heads of one scene's 64 000 lattice points; from ~8 scenes
-    // up the shared-feature kernel is the faster one, 297 vs 323 us at 32 scenes).  grid = slots x nheads <= 256 (one workgroup per CU).  Two tiles per wave (the weight fragments
-    // are read from LDS once per two tiles) when every workgroup gets at least two such rounds, else one tile per wave.
-    // (tuning knob, read once: GIGA_DEC16_RESIDENT=0/1 forces the choice for plain f16; measurements in DESIGN.md)
-    // Lattice launches of the f16-class modes with R % 8 == 0 (the inference lattice: R = 40): the separable-fc_c kernel
-    // (decoder_lat_kernel) -- f16x3 always (1 scene 31.8 -> 27.8 us, 32 scenes 0.754 -> 0.583 ms), plain f16 from 4 scenes up (32 scenes
-    // 0.279 -> 0.260 ms; a single scene is latency-bound and 1 us faster on the head-resident kernel below, which also serves other
-    // lattices).  (tuning knob: GIGA_DEC_LAT=0 / 1 forces the choice)
-    const int force_lat = [] { const char* e = getenv("GIGA_DEC_LAT"); return e ? atoi(e) : -1; }();   // (per call: A/B runs in one process)
-    if (lat && (precision == 1 || precision == 2) && a.R <= LAT_MAX_R && a.R % 8 == 0 && (force_lat >= 0 ? force_lat != 0 : (precision == 2 || a.B >= 4))) {
-        const int cap = 256 / a.nheads, cap8 = 256 / (8 * a.nheads) * 8;
-        // small launches: hand a slab out in parts (NP divides the tile count), so that a single scene still covers the chip; a
-        // part costs its tiles plus one line phase (~ the time of 12 tiles on a workgroup)
-        const int ntile = (a.R / 4) * (a.R / 8);
-        int np = 1;
-        {
-            double best = 1e30;
-            for (int c : {1, 2, 5}) {
-                if (ntile % c) continue;
-                const long long units = (long long)a.B * a.R * c;
-                const long long rounds = (units + cap - 1) / cap;
-                const double cost = (double)rounds * ((double)ntile / c + 12.0);
-                if (cost < best - 1e-9) { best = cost; np = c; }
-            }
-        }
-        a.lat_parts = np;
-        const int nslab = a.B * a.R * np;
-        int slots = nslab < cap ? nslab : (nslab >= 2 * cap8 && cap8 > 0 ? cap8 : cap);
-        a.nbatch = slots;
-        // 16 waves per workgroup, four per SIMD (against 12: 0.267 -> 0.257 ms at 32 scenes)
-        auto go = [&](auto kern, size_t lds) {
-            giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)lds);
-            GIGA_LAUNCH(kern, dim3(slots * a.nheads), dim3(16 * 64), lds, s, a);
-        };
-        if (precision == 2) go(decoder_lat_kernel<true, 16, false>, lat_lds_bytes<true, false>(a.R));
-        else go(decoder_lat_kernel<false, 16, true>, lat_lds_bytes<false, true>(a.R));
-        if (ev0 && ev1) (void)hipEventRecord(static_cast<hipEvent_t>(ev1), s);
-        return hipGetLastError() == hipSuccess ? 0 : -10;
-    }
-    static const int force_resident = [] { const char* e = getenv("GIGA_DEC16_RESIDENT"); return e ? atoi(e) : -1; }();
-    const bool resident = precision == 2 ||
-                          (precision == 1 && (force_resident >= 0 ? force_resident != 0 : tiles * a.nheads < (lat ? 16000 : 6000)));
-    if (resident) {
-        const int cap = 256 / a.nheads;                        // one workgroup per CU
-        const int cap8 = 256 / (8 * a.nheads) * 8;             // ... or a multiple of 8 slots: XCD-contiguous ranges (L2 locality)
-        auto go = [&](auto kern, int NW, int T, size_t lds) {
-            const int per_round = NW * T;
-            int slots = (int)((tiles + per_round - 1) / per_round);
-            // large launches trade the last few CUs for L2 locality; small ones (a single scene: 2000 tiles) are latency-bound and
-            // take every CU -- 240 instead of 255 workgroups would add a third, nearly empty round
-            if (slots > cap) slots = tiles >= 8LL * cap * per_round ? cap8 : cap;
-            else if (slots >= 8 && tiles >= 8LL * slots) slots &= ~7;
-            a.nbatch = slots;
-            giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)lds);
-            GIGA_LAUNCH(kern, dim3(slots * a.nheads), dim3(NW * 64), lds, s, a);
-        };
-        if (precision == 2) {
-            constexpr int NW = 8;
-            const bool two = tiles >= 2LL * cap * NW * 2;
-            if (two) { if (lat) go(decoder_f16s_kernel<2, true, NW, true>, NW, 2, DEC16S_BYTES); else go(decoder_f16s_kernel<2, false, NW, true>, NW, 2, DEC16S_BYTES); }
-            else { if (lat) go(decoder_f16s_kernel<1, true, NW, true>, NW, 1, DEC16S_BYTES); else go(decoder_f16s_kernel<1, false, NW, true>, NW, 1, DEC16S_BYTES); }
-        } else {
-            // plain f16: 112-142 VGPRs with one tile per wave (12 waves), 2 tiles need the 256-register budget (8 waves)
-            const bool two = tiles >= 2LL * cap * 8 * 2;
-            if (two) { if (lat) go(decoder_f16s_kernel<2, true, 8, false>, 8, 2, DEC16_BYTES); else go(decoder_f16s_kernel<2, false, 8, false>, 8, 2, DEC16_BYTES); }
-            else { if (lat) go(decoder_f16s_kernel<1, true, 12, false>, 12, 1, DEC16_BYTES); else go(decoder_f16s_kernel<1, false, 12, false>, 12, 1, DEC16_BYTES); }
-        }
-    } else if (precision == 1 && lat) {
-        // lattice variant: 155 VGPRs -> 12 waves (3 per SIMD, phases 0/1/2 over the heads)
-        constexpr int T = 2, NW = 12;
-        a.nbatch = (int)((tiles + NW * T - 1) / (NW * T));
-        const int grid = a.nbatch < 256 ? a.nbatch : 256;      // one persistent workgroup per CU
-        auto kern = decoder_f16_kernel<T, true, NW>;
-        giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)(2 * DEC16_BYTES));
-        GIGA_LAUNCH(kern, dim3(grid), dim3(NW * 64), 2 * DEC16_BYTES, s, a);
-    } else if (precision == 1) {
-        constexpr int T = 2, NW = 8;
-        a.nbatch = (int)((tiles + NW * T - 1) / (NW * T));
-        const int grid = a.nbatch < 256 ? a.nbatch : 256;      // one persistent workgroup per CU
-        auto kern = decoder_f16_kernel<T, false, NW>;
-        giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)(2 * DEC16_BYTES));
-        GIGA_LAUNCH(kern, dim3(grid), dim3(NW * 64), 2 * DEC16_BYTES, s, a);
-    } else if (!lat && a.N == 1 && dec32_one_query_kernels() && a.P <= dec32_point_bound()) {
-        // ONE query per scene (train_giga's literal call): one point and head per workgroup, GEMVs on the VALU (no padded MFMA
-        // tile).  DEC32_POINT_MAX_P comes from the sweep against the tile kernel below (profiles/dec_point/sweep.txt).
-        // (Only for N == 1, like the tile kernel below and for the same reason.)
-        auto kern = decoder_f32_point_kernel;
-        giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)DEC32_POINT_LDS);
-        GIGA_LAUNCH(kern, dim3((unsigned)a.P, a.nheads), dim3(256), DEC32_POINT_LDS, s, a);
-    } else if (!lat && a.N == 1 && tiles * a.nheads <= 96 && dec32_one_query_kernels()) {
-        // ONE query per scene (train_giga's literal call) and few scenes: one tile and head per workgroup, four waves per chain.
-        // (Only for N == 1: the kernel sums the stream in a different order than decoder_f32_kernel, and callers that split a
-        // query set into chunks -- Generator3D.eval_points -- rely on a point's result not depending on the chunk it is in.)
-        auto kern = decoder_f32_tile_kernel;
-        giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)DEC32_TILE_LDS);
-        GIGA_LAUNCH(kern, dim3((unsigned)tiles, a.nheads), dim3(256), DEC32_TILE_LDS, s, a);
-    } else if (tiles >= 2 * 4 * 256) {
-        // enough work for two tiles per wave on every CU: the 111 KiB weight image is staged half as often
-        constexpr int T = 2;
-        a.nbatch = (int)((tiles + 4 * T - 1) / (4 * T));
-        const int grid = a.nbatch < 256 ? a.nbatch : 256;
-        auto kern = lat ? decoder_f32_kernel<T, true> : decoder_f32_kernel<T, false>;
-        a.heads_per_wg = a.nheads;
-        giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)DEC32_LDS);
-        GIGA_LAUNCH(kern, dim3(grid), dim3(256), DEC32_LDS, s, a);
-    } else {
-        constexpr int T = 1;
-        a.nbatch = (int)((tiles + 4 * T - 1) / (4 * T));
-        const int grid = a.nbatch < 256 ? a.nbatch : 256;
-        auto kern = lat ? decoder_f32_kernel<T, true> : decoder_f32_kernel<T, false>;
-        // when the point batches cannot fill the chip, give every head its own workgroups
-        const bool split = grid * a.nheads <= 256;
-        a.heads_per_wg = split ? 1 : a.nheads;
-        giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)DEC32_LDS);
-        GIGA_LAUNCH(kern, dim3(grid, split ? a.nheads : 1), dim3(256), DEC32_LDS, s, a);
+    const DecPlan pl = dec_plan(precision, a.B, a.N, a.R, a.nheads, dec_knobs_from_env());
+    a.nbatch = pl.nbatch; a.heads_per_wg = pl.heads_per_wg; a.lat_parts = pl.lat_parts;
+    auto go = [&](auto kern) {
+        giga::dyn_lds_once(reinterpret_cast<const void*>(kern), pl.lds);
+        GIGA_LAUNCH(kern, dim3(pl.grid_x, pl.grid_y), dim3(pl.block), (size_t)pl.lds, s, a);
+    };
+    // (kernel, instantiation): the template arguments a plan can name
+    auto f16s = [&](auto latc) {
+        constexpr bool L = decltype(latc)::value;
+        if (pl.split) pl.T == 2 ? go(decoder_f16s_kernel<2, L, 8, true>) : go(decoder_f16s_kernel<1, L, 8, true>);
+        else pl.T == 2 ? go(decoder_f16s_kernel<2, L, 8, false>) : go(decoder_f16s_kernel<1, L, 12, false>);
+    };
+    switch (pl.kernel) {
+        case DEC_K_LAT: pl.split ? go(decoder_lat_kernel<true, 16, false>) : go(decoder_lat_kernel<false, 16, true>); break;
+        case DEC_K_F16S: lat ? f16s(std::true_type{}) : f16s(std::false_type{}); break;
+        case DEC_K_F16: lat ? go(decoder_f16_kernel<2, true, 12>) : go(decoder_f16_kernel<2, false, 8>); break;
+        case DEC_K_F32_POINT: go(decoder_f32_point_kernel); break;
+        case DEC_K_F32_TILE: go(decoder_f32_tile_kernel); break;
+        case DEC_K_F32:
+            if (pl.T == 2) lat ? go(decoder_f32_kernel<2, true>) : go(decoder_f32_kernel<2, false>);
+            else lat ? go(decoder_f32_kernel<1, true>) : go(decoder_f32_kernel<1, false>);
+            break;
+        default: return -10;
     }
     if (ev0 && ev1) (void)hipEventRecord(static_cast<hipEvent_t>(ev1), s);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-int launch_lattice_resample(const void* planes, const float* lin, void* out, int B, int R, int precision,
-                            hipStream_t s, bool planes_fp32) {
+static int launch_lattice_resample(const void* planes, const float* lin, void* out, int B, int R, int precision,
+                                   hipStream_t s, bool planes_fp32) {
     const long long total = 3LL * B * R * R * 4;
     if (total <= 0) return 0;
     const unsigned grid = (unsigned)((total + 255) / 256);
@@ -1613,8 +1477,8 @@ int launch_lattice_resample(const void* planes, const float* lin, void* out, int
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-int launch_planes_pack(const float* xz, const float* xy, const float* yz, void* dst, int B, int precision,
-                       hipStream_t s) {
+static int launch_planes_pack(const float* xz, const float* xy, const float* yz, void* dst, int B, int precision,
+                              hipStream_t s) {
     if (B <= 0) return 0;
     if (precision == 1)
         GIGA_LAUNCH(planes_nchw_to_nhwc_kernel<half_t>, dim3(3 * B * RES), dim3(256), 0, s, xz, xy, yz,
@@ -1625,7 +1489,7 @@ int launch_planes_pack(const float* xz, const float* xy, const float* yz, void* 
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-int launch_planes_unpack(const void* src, float* dst, int B, int precision, hipStream_t s) {
+static int launch_planes_unpack(const void* src, float* dst, int B, int precision, hipStream_t s) {
     if (B <= 0) return 0;
     if (precision == 1)
         GIGA_LAUNCH(planes_nhwc_to_nchw_kernel<half_t>, dim3(3 * B * RES), dim3(256), 0, s,
@@ -1636,4 +1500,128 @@ int launch_planes_unpack(const void* src, float* dst, int B, int precision, hipS
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
+// giga_decoder_train16.hip (bf16 decoder of the bf16 training step)
+int launch_dect_forward(const float* planes, const float* p, const uint8_t* blob, int head_mask, float* const* outs, int B, int N,
+                        int post, hipStream_t s);
+
+// byte offset of head h's weight image for a precision (0 fp32, 1 f16, 2 f16x3 split), plain or with conv_final folded in
+static size_t head_image_offset(const PackOff& ko, int h, int precision, bool fold) {
+    if (precision == 2) return fold ? ko.dec16sf[h] : ko.dec16s[h];
+    if (precision == 1) return fold ? ko.dec16f[h] : ko.dec16[h];
+    return fold ? ko.dec32f[h] : ko.dec32[h];
+}
+
+// the head list of a decoder launch: the heads of `head_mask` in order, each with its image in the packed blob and its output.
+// -6: a requested head has no output
+static int dec_args_heads(DecArgs& a, int head_mask, float* const (&outs)[NHEADS], const PackOff& ko, int precision, bool fold) {
+    a.nheads = 0;
+    for (int h = 0; h < NHEADS; ++h) {
+        if (!(head_mask >> h & 1)) continue;
+        if (!outs[h]) return -6;
+        a.head_id[a.nheads] = h;
+        a.head_off[a.nheads] = head_image_offset(ko, h, precision, fold);
+        a.out[a.nheads] = outs[h];
+        ++a.nheads;
+    }
+    return 0;
+}
+
 }  // namespace giga
+
+using namespace giga;
+
+extern "C" {
+
+int giga_planes_pack(const float* xz, const float* xy, const float* yz, void* planes_nhwc, int B, int precision,
+                     void* stream) {
+    if (B < 0 || (B > 0 && (!xz || !xy || !yz || !planes_nhwc))) return -1;
+    if (precision < 0 || precision > 2) return -5;
+    return launch_planes_pack(xz, xy, yz, planes_nhwc, B, precision, static_cast<hipStream_t>(stream));
+}
+
+int giga_planes_unpack(const void* planes_nhwc, float* planes_nchw, int B, int precision, void* stream) {
+    if (B < 0 || (B > 0 && (!planes_nhwc || !planes_nchw))) return -1;
+    if (precision < 0 || precision > 2) return -5;
+    return launch_planes_unpack(planes_nhwc, planes_nchw, B, precision, static_cast<hipStream_t>(stream));
+}
+
+int giga_decoder_forward_probe(const void* planes_nhwc, const float* p, const void* packed, int head_mask,
+                               float* qual, float* rot, float* width, float* occ, int B, int N, int precision,
+                               int post, void* stream, void* ev_start, void* ev_stop) {
+    if (B < 0 || N < 0) return -1;
+    const bool fold = (precision & GIGA_FOLD_FINAL) != 0;     // planes are the encoder output BEFORE conv_final
+    precision &= ~GIGA_FOLD_FINAL;
+    if (precision < 0 || precision > 3 || (precision == 3 && fold)) return -5;
+    if ((long long)B * N == 0 || (head_mask & 15) == 0) return 0;
+    if (!planes_nhwc || !p || !packed) return -1;
+    if (precision == 3) {                                     // bf16 operands / fp32 accumulate on fp32 planes: the bf16 training forward
+        float* outs3[NHEADS] = {qual, rot, width, occ};
+        for (int h = 0; h < NHEADS; ++h)
+            if ((head_mask >> h & 1) && !outs3[h]) return -6;
+        hipStream_t s3 = static_cast<hipStream_t>(stream);
+        if (ev_start && hipEventRecord(static_cast<hipEvent_t>(ev_start), s3) != hipSuccess) return -10;
+        const int rc3 = launch_dect_forward(static_cast<const float*>(planes_nhwc), p, static_cast<const uint8_t*>(packed), head_mask & 15,
+                                            outs3, B, N, post, s3);
+        if (ev_stop && hipEventRecord(static_cast<hipEvent_t>(ev_stop), s3) != hipSuccess) return -10;
+        return rc3;
+    }
+    DecArgs a{};
+    a.planes = planes_nhwc; a.p = p; a.blob = static_cast<const uint8_t*>(packed);
+    float* outs[NHEADS] = {qual, rot, width, occ};
+    if (const int rc = dec_args_heads(a, head_mask, outs, pack_offsets(), precision, fold)) return rc;
+    a.B = B; a.N = N; a.P = (long long)B * N; a.post = post;
+    return launch_decoder(a, precision, static_cast<hipStream_t>(stream), ev_start, ev_stop);
+}
+
+int giga_decoder_forward(const void* planes_nhwc, const float* p, const void* packed, int head_mask, float* qual,
+                         float* rot, float* width, float* occ, int B, int N, int precision, int post,
+                         void* stream) {
+    return giga_decoder_forward_probe(planes_nhwc, p, packed, head_mask, qual, rot, width, occ, B, N, precision,
+                                      post, stream, nullptr, nullptr);
+}
+
+size_t giga_lattice_workspace_bytes(int B, int R, int precision) {
+    precision &= ~(GIGA_FOLD_FINAL | GIGA_PLANES_FP32);
+    if (B <= 0 || R <= 0) return 0;
+    return (size_t)3 * B * R * R * CD * (precision == 1 ? 2 : 4);
+}
+
+int giga_decoder_forward_lattice(const void* planes_nhwc, const float* lin, const void* packed, int head_mask,
+                                 float* qual, float* rot, float* width, float* occ, int B, int R, int precision,
+                                 int post, void* workspace, size_t workspace_bytes, void* stream, void* ev_start,
+                                 void* ev_stop) {
+    if (B < 0 || R < 0 || R > 64) return -1;
+    const bool fold = (precision & GIGA_FOLD_FINAL) != 0;
+    const bool planes32 = (precision & GIGA_PLANES_FP32) != 0;        // fp32 planes into the plain-f16 decoder
+    precision &= ~(GIGA_FOLD_FINAL | GIGA_PLANES_FP32);
+    if (precision < 0 || precision > 2 || (planes32 && precision != 1)) return -5;
+    if (B == 0 || R == 0 || (head_mask & 15) == 0) return 0;
+    if (!planes_nhwc || !lin || !packed || !workspace) return -1;
+    if (workspace_bytes < giga_lattice_workspace_bytes(B, R, precision)) return -4;
+    float* outs[NHEADS] = {qual, rot, width, occ};
+    DecArgs a{};
+    int rc = dec_args_heads(a, head_mask, outs, pack_offsets(), precision, fold);      // (-6 before anything is enqueued)
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = launch_lattice_resample(planes_nhwc, lin, workspace, B, R, precision, s, planes32);
+    if (rc) return rc;
+    a.planes = workspace; a.p = nullptr; a.blob = static_cast<const uint8_t*>(packed);
+    a.B = B; a.N = R * R * R; a.P = (long long)B * a.N; a.post = post; a.lin = lin; a.R = R;
+    return launch_decoder(a, precision, s, ev_start, ev_stop);
+}
+
+/* host only: the plan a decoder launch of these arguments would get now, environment knobs included (giga_dec_plan.h) */
+int giga_decoder_plan(int B, int N, int R, int nheads, int precision, int32_t* plan_words) {
+    if (B < 0 || N < 0 || R < 0 || R > 64 || nheads < 0 || nheads > NHEADS || !plan_words) return -1;
+    precision &= ~(GIGA_FOLD_FINAL | GIGA_PLANES_FP32);
+    if (precision < 0 || precision > 2) return -5;            // (precision 3, the bf16 training forward, has one launch form: no plan)
+    static_assert(DEC_PLAN_WORDS == GIGA_DECODER_PLAN_WORDS && sizeof(int) == sizeof(int32_t), "the plan's words are the header's");
+    static_assert(DEC_K_F16 == GIGA_DEC_KERNEL_F16 && DEC_K_F16S == GIGA_DEC_KERNEL_F16S && DEC_K_LAT == GIGA_DEC_KERNEL_LAT &&
+                  DEC_K_F32 == GIGA_DEC_KERNEL_F32 && DEC_K_F32_TILE == GIGA_DEC_KERNEL_F32_TILE &&
+                  DEC_K_F32_POINT == GIGA_DEC_KERNEL_F32_POINT, "the kernel ids are the header's");
+    const DecPlan pl = dec_plan(precision, B, R > 0 ? R * R * R : N, R, nheads, dec_knobs_from_env());
+    memcpy(plan_words, &pl, sizeof pl);
+    return 0;
+}
+
+}  // extern "C"

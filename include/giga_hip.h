@@ -198,6 +198,22 @@ int giga_decoder_forward_lattice(const void* planes_nhwc, const float* lin, cons
                                  float* qual, float* rot, float* width, float* occ, int B, int R, int precision,
                                  int post, void* workspace, size_t workspace_bytes, void* stream,
                                  void* ev_start, void* ev_stop);
+/* The launch plan giga_decoder_forward* (R == 0: B x N generic queries) or giga_decoder_forward_lattice (R > 0; N is ignored)
+ * would use for `nheads` heads at `precision` (0..2; GIGA_FOLD_FINAL / GIGA_PLANES_FP32 are ignored), decided NOW: the tuning
+ * variables GIGA_DEC_LAT, GIGA_DEC16_RESIDENT, GIGA_DEC32_TILE and GIGA_DEC32_POINT are read on every call, as a launch reads them.
+ * Host only: no device is touched.  -1 / -5 on the arguments those calls reject.  plan_words[GIGA_DECODER_PLAN_WORDS], in order
+ * (csrc/giga_dec_plan.h, struct DecPlan):
+ *   kernel (GIGA_DEC_KERNEL_*; 0: nothing is launched), T (32-point tiles per wave), NW (waves per workgroup), split (operands are
+ *   [hi, lo] f16 pairs), dbuf (two line buffers), grid_x, grid_y, block, lds (dynamic LDS bytes), nbatch, heads_per_wg, lat_parts,
+ *   slots (workgroups per head of the head-resident kernels), xcd_remap (their XCD-contiguous workgroup map applies). */
+#define GIGA_DECODER_PLAN_WORDS 14
+#define GIGA_DEC_KERNEL_F16 1        /* decoder_f16_kernel: shared features */
+#define GIGA_DEC_KERNEL_F16S 2       /* decoder_f16s_kernel: head-resident */
+#define GIGA_DEC_KERNEL_LAT 3        /* decoder_lat_kernel: separable fc_c on the lattice */
+#define GIGA_DEC_KERNEL_F32 4        /* decoder_f32_kernel: general exact kernel */
+#define GIGA_DEC_KERNEL_F32_TILE 5   /* decoder_f32_tile_kernel */
+#define GIGA_DEC_KERNEL_F32_POINT 6  /* decoder_f32_point_kernel */
+int giga_decoder_plan(int B, int N, int R, int nheads, int precision, int32_t* plan_words);
 
 /* ---- training path, fp32 (scripts/train_giga.py:198-211: forward, loss.backward(), optimizer.step()) -----
  * The forward is giga_encoder_forward + giga_decoder_forward at precision 0 with the encoder workspace

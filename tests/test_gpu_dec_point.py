@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from giga_amd import _capi, networks, synth, weights
-from giga_amd.convonet import _planes_to_nhwc, decode_heads
+from giga_amd.convonet import _planes_to_nhwc, decode_heads, decoder_plan
 from oracle import giga_oracle as O
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -21,7 +21,17 @@ import test_gpu_f16_exact as f16_exact  # noqa: E402  (its integer state dict)
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 HEADS = ref64.HEADS
-POINT_MAX_P = 256            # DEC32_POINT_MAX_P of csrc/giga_decoder.hip: set from profiles/dec_point/sweep.txt
+def _point_bound():
+    """DEC32_POINT_MAX_P of csrc/giga_dec_plan.h (set from profiles/dec_point/sweep.txt), asked of the library's plan: the largest
+    one-query launch that gets the point kernel when no knob is set (a bound can be at most the tile rule's 3072)."""
+    saved = {k: os.environ.pop(k) for k in ("GIGA_DEC32_POINT", "GIGA_DEC32_TILE") if k in os.environ}
+    try:
+        return max(P for P in range(1, 3073) if decoder_plan(P, 1, 0, 1, 0)["kernel"] == "decoder_f32_point_kernel")
+    finally:
+        os.environ.update(saved)
+
+
+POINT_MAX_P = _point_bound()
 ATOL = 1e-5                  # the bound tests/test_gpu_point_grad.py uses for N == 1 between the fp32 kernels
 MASKS = (7, 8, 2)            # the three grasp heads, occupancy, a single head (rot: the four-wide output)
 _CACHE = {}

@@ -12,9 +12,9 @@ out.  An indexing slip fails (2) whatever the arithmetic does.  LATTICE_STATS pr
 Lattices of one or two points per axis have outputs of (nearly) no range of their own: their errors are divided by the range of
 the same scene's float64 outputs on the 8^3 planner lattice instead (`_companion`).
 
-`dispatch` restates launch_decoder (giga_amd/csrc/giga_decoder.hip); tests/test_lattice_host.py::test_dispatch_cases_cover_every_branch
-proves from it, on the CPU, that the cases below take every lat_parts value, every `slots` branch and both settings of the XCD
-remap of decoder_lat_kernel.
+`plan` asks the library what a launch will do (convonet.decoder_plan: csrc/giga_dec_plan.h, the policy launch_decoder itself runs);
+tests/test_lattice_host.py::test_dispatch_cases_cover_every_branch proves from it, on the CPU, that the cases below take every
+lat_parts value, every `slots` branch and both settings of the XCD remap of decoder_lat_kernel.
 
 Deviations from a plain product of cases, and why:
   * family c (unsorted, duplicated) needs five entries, so R = 1 and 2 run families a and b only;
@@ -74,74 +74,51 @@ MASKS = {"15": (OUTS, (3, 1)),          # net(x, pos, p_tsdf=pos): the grasp lau
          "15x": (OUTS, (4,))}           # convonet.decode_heads with all four heads in ONE launch
 
 
-# ---- launch_decoder, restated -----------------------------------------------------------------------------------------
-def dispatch(code, B, R, nheads, force_lat=None):
-    """What launch_decoder (giga_amd/csrc/giga_decoder.hip) does with a lattice launch of precision `code`: the kernel, and for
-    decoder_lat_kernel ntile, lat_parts, the branch `slots` takes and whether the XCD remap applies."""
-    tiles = (B * R ** 3 + 31) // 32
-    if code in (1, 2) and R <= 40 and R % 8 == 0 and ((force_lat != 0) if force_lat is not None else (code == 2 or B >= 4)):
-        cap, cap8 = 256 // nheads, 256 // (8 * nheads) * 8
-        ntile = (R // 4) * (R // 8)
-        best, parts = 1e30, 1
-        for c in (1, 2, 5):
-            if ntile % c:
-                continue
-            units = B * R * c
-            rounds = (units + cap - 1) // cap
-            cost = rounds * (ntile / c + 12.0)
-            if cost < best - 1e-9:
-                best, parts = cost, c
-        nslab = B * R * parts
-        if nslab < cap:
-            slots, branch = nslab, "nslab"
-        elif nslab >= 2 * cap8 and cap8 > 0:
-            slots, branch = cap8, "cap8"
-        else:
-            slots, branch = cap, "cap"
-        return dict(kernel="lat", ntile=ntile, parts=parts, branch=branch, slots=slots, xcd=(slots * nheads) % (8 * nheads) == 0)
-    if code == 2 or (code == 1 and tiles * nheads < 16000):
-        cap = 256 // nheads
-        two = tiles >= 2 * cap * 8 * 2
-        return dict(kernel="f16s", T=2 if two else 1)
-    if code == 1:
-        return dict(kernel="f16", T=2)
-    if tiles >= 2 * 4 * 256:
-        return dict(kernel="f32", T=2)
-    grid = min((tiles + 3) // 4, 256)
-    return dict(kernel="f32", T=1, split=grid * nheads <= 256)
+# ---- the launch plan, from the library ---------------------------------------------------------------------------------
+SHORT = {"decoder_lat_kernel": "lat", "decoder_f16s_kernel": "f16s", "decoder_f16_kernel": "f16", "decoder_f32_kernel": "f32"}
+
+
+def plan(code, B, R, nheads):
+    """convonet.decoder_plan of a lattice launch of precision `code` (csrc/giga_dec_plan.h, through giga_decoder_plan: host only;
+    GIGA_DEC_LAT and the other knobs are read from the environment as the launch itself reads them), `kernel` shortened."""
+    d = convonet.decoder_plan(B, 0, R, nheads, code)
+    d["kernel"] = SHORT[d["kernel"]]
+    return d
 
 
 # ---- cases --------------------------------------------------------------------------------------------------------------
 # decoder_lat_kernel: 'fp16x3' at any B, plain 'fp16' (and 'fp16x3+fp16') from 4 scenes up; R in {8, 16, 24, 32, 40}.
-# launch_decoder's formula per launch (nh = heads of the launch; cap = 256 / nh, cap8 = 256 / (8 nh) * 8; ntile = (R/4)(R/8);
-# lat_parts = the c of {1, 2, 5} dividing ntile with the least ceil(B R c / cap) * (ntile / c + 12); nslab = B R lat_parts;
-# slots = nslab if nslab < cap, else cap8 if nslab >= 2 cap8, else cap; XCD remap iff slots * nh % (8 nh) == 0):
-#
-#    R   B  mask  launch  ntile  lat_parts  nslab  slots (branch)  XCD remap
-#    8   1  15    nh 3        2      2         16     16 (nslab)      on
-#    8   1  15    nh 1        2      2         16     16 (nslab)      on
-#    8  13  15    nh 3        2      1        104     85 (cap)        off
-#    8  13  15    nh 1        2      2        208    208 (nslab)      on
-#    8   5  15x   nh 4        2      1         40     40 (nslab)      on
-#   16   1  7     nh 3        8      2         32     32 (nslab)      on
-#   16   4  15    nh 3        8      1         64     64 (nslab)      on
-#   16   4  15    nh 1        8      2        128    128 (nslab)      on
-#   16  13  7     nh 3        8      1        208     80 (cap8)       on
-#   24   1  8     nh 1       18      2         48     48 (nslab)      on
-#   24   5  15    nh 3       18      1        120     85 (cap)        off
-#   24   5  15    nh 1       18      2        240    240 (nslab)      on
-#   24  13  8     nh 1       18      1        312    256 (cap)        on
-#   32   1  15x   nh 4       32      2         64     64 (cap)        on
-#   32   4  15    nh 3       32      1        128     85 (cap)        off
-#   32   4  15    nh 1       32      2        256    256 (cap)        on
-#   32   5  7     nh 3       32      1        160     80 (cap8)       on
-#   40   1  15    nh 3       50      2         80     80 (nslab)      on
-#   40   1  15    nh 1       50      5        200    200 (nslab)      on
-#   40   5  15    nh 3       50      2        400     80 (cap8)       on
-#   40   5  15    nh 1       50      1        200    200 (nslab)      on
-#   40  13  15    nh 3       50      1        520     80 (cap8)       on
-#   40  13  15    nh 1       50      2       1040    256 (cap8)       on
-#
+# The policy per launch (nh = heads of the launch; cap = 256 / nh, cap8 = 256 / (8 nh) * 8; ntile = (R/4)(R/8); lat_parts = the c of
+# {1, 2, 5} dividing ntile with the least ceil(B R c / cap) * (ntile / c + 12); nslab = B R lat_parts; slots = nslab if nslab < cap,
+# else cap8 if nslab >= 2 cap8, else cap; XCD remap iff slots * nh % (8 nh) == 0), written out by hand for every launch of
+# LAT_CASES: tests/test_lattice_host.py::test_lat_table_equals_the_plan holds the plan to these rows, so a change of the policy
+# shows here.
+# (R, B, mask, nh, ntile, lat_parts, nslab, slots, branch of `slots`, XCD remap)
+LAT_TABLE = [
+    (8, 1, "15", 3, 2, 2, 16, 16, "nslab", True),
+    (8, 1, "15", 1, 2, 2, 16, 16, "nslab", True),
+    (8, 13, "15", 3, 2, 1, 104, 85, "cap", False),
+    (8, 13, "15", 1, 2, 2, 208, 208, "nslab", True),
+    (8, 5, "15x", 4, 2, 1, 40, 40, "nslab", True),
+    (16, 1, "7", 3, 8, 2, 32, 32, "nslab", True),
+    (16, 4, "15", 3, 8, 1, 64, 64, "nslab", True),
+    (16, 4, "15", 1, 8, 2, 128, 128, "nslab", True),
+    (16, 13, "7", 3, 8, 1, 208, 80, "cap8", True),
+    (24, 1, "8", 1, 18, 2, 48, 48, "nslab", True),
+    (24, 5, "15", 3, 18, 1, 120, 85, "cap", False),
+    (24, 5, "15", 1, 18, 2, 240, 240, "nslab", True),
+    (24, 13, "8", 1, 18, 1, 312, 256, "cap", True),
+    (32, 1, "15x", 4, 32, 2, 64, 64, "cap", True),
+    (32, 4, "15", 3, 32, 1, 128, 85, "cap", False),
+    (32, 4, "15", 1, 32, 2, 256, 256, "cap", True),
+    (32, 5, "7", 3, 32, 1, 160, 80, "cap8", True),
+    (40, 1, "15", 3, 50, 2, 80, 80, "nslab", True),
+    (40, 1, "15", 1, 50, 5, 200, 200, "nslab", True),
+    (40, 5, "15", 3, 50, 2, 400, 80, "cap8", True),
+    (40, 5, "15", 1, 50, 1, 200, 200, "nslab", True),
+    (40, 13, "15", 3, 50, 1, 520, 80, "cap8", True),
+    (40, 13, "15", 1, 50, 2, 1040, 256, "cap8", True),
+]
 # (R, B, mask, lin family, weight family, input family, precisions)
 LAT_CASES = [
     (8, 1, "15", "a", "he-7", "realistic", ("fp16x3",)),
@@ -315,7 +292,7 @@ def _plain_points(pos, B, R):
     return plain, j
 
 
-def _check_case(dev, case, prec, force_lat=None):
+def _check_case(dev, case, prec):
     """Both assertions of the module docstring for one case; returns the lattice-path outputs."""
     R, B, mask, fam, wfam, ifam = case
     outs, launches = MASKS[mask]
@@ -346,7 +323,7 @@ def _check_case(dev, case, prec, force_lat=None):
     fails = []
     for what in outs:
         nh = launches[0] if what != "tsdf" or len(launches) == 1 else launches[1]
-        form = dispatch(PREC_CODE[prec], B, R, nh, force_lat)["kernel"]
+        form = plan(PREC_CODE[prec], B, R, nh)["kernel"]
         a, b = fast[what], slow[what]
         assert a.shape == b.shape and a.shape[:2] == (B, N), (what, a.shape, b.shape)
         h = HEAD_OF[what]
@@ -412,11 +389,12 @@ def test_lat_kernel_equals_head_resident_lattice_kernel(dev, case, monkeypatch):
     decoder_f16s_kernel<LATTICE> agree to the fast-versus-generic bound, and each meets the float64 tolerance."""
     R, B, mask = case[:3]
     assert R in (8, 24, 40) and case[3] == "c"
-    assert all(dispatch(2, B, R, nh)["kernel"] == "lat" and dispatch(2, B, R, nh, 0)["kernel"] == "f16s" for nh in MASKS[mask][1])
     monkeypatch.delenv("GIGA_DEC_LAT", raising=False)
+    assert all(plan(2, B, R, nh)["kernel"] == "lat" for nh in MASKS[mask][1])
     lat = _check_case(dev, case, "fp16x3")
     monkeypatch.setenv("GIGA_DEC_LAT", "0")
-    res = _check_case(dev, case, "fp16x3", force_lat=0)
+    assert all(plan(2, B, R, nh)["kernel"] == "f16s" for nh in MASKS[mask][1])
+    res = _check_case(dev, case, "fp16x3")
     for what in MASKS[mask][0]:
         d = (lat[what] - res[what]).abs().max().item()
         _record(("lat-vs-f16s", "fp16x3", R, "generic"), d)
@@ -436,8 +414,7 @@ def test_scene_of_a_batch_equals_the_scene_alone(dev, monkeypatch, form, prec, R
         monkeypatch.delenv("GIGA_DEC_LAT", raising=False)
     else:
         monkeypatch.setenv("GIGA_DEC_LAT", force)
-    fl = None if force is None else int(force)
-    assert dispatch(PREC_CODE[prec], B, R, 4, fl)["kernel"] == form and dispatch(PREC_CODE[prec], 1, R, 4, fl)["kernel"] == form
+    assert plan(PREC_CODE[prec], B, R, 4)["kernel"] == form and plan(PREC_CODE[prec], 1, R, 4)["kernel"] == form
     net = _net("he-7", dev)
     pos, _ = _pos(R, "c", dev)
     x = torch.from_numpy(ref64.input_family("realistic", B)).to(dev)
@@ -505,7 +482,7 @@ def test_writes_stay_inside_outputs_and_workspace(dev, monkeypatch, label, prec_
         monkeypatch.delenv("GIGA_DEC_LAT", raising=False)
     else:
         monkeypatch.setenv("GIGA_DEC_LAT", force)
-    assert (dispatch(prec_flags & 3, B, R, 4, None if force is None else int(force))["kernel"] == "lat") == label.startswith("lat")
+    assert (plan(prec_flags & 3, B, R, 4)["kernel"] == "lat") == label.startswith("lat")
     L = _capi.lib()
     net = _net("he-7", dev)
     blob = net.packed_blob(dev)
@@ -583,7 +560,7 @@ def test_occupancy_grid_small_and_too_large(dev):
             assert tuple(got.shape) == (3, R, R, R)
             for k in range(3):
                 e = ref64.range_err(got[k].reshape(-1), ref["decoder_tsdf"][k])
-                _record((dispatch(PREC_CODE[prec], 3, R, 1)["kernel"], prec, R, "f64"), e)
+                _record((plan(PREC_CODE[prec], 3, R, 1)["kernel"], prec, R, "f64"), e)
                 assert e <= _tol(prec), (prec, k, e)
         net.set_precision("fp32")
         c = gen.encode(x)

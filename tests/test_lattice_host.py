@@ -1,7 +1,8 @@
 """CPU tests of the lattice recognition (giga_amd.convonet._detect_lattice / register_lattice): which query tensors are promoted
 to the lattice decoder without the caller asking, and which are not.  _detect_lattice runs on CPU tensors as it is (only
-_lattice_of asks for a device tensor), so nothing here needs a GPU.  Also the proof, from the restated launch formula, that the cases
-of tests/test_gpu_lattice_shapes.py reach every dispatch branch of the lattice decoders."""
+_lattice_of asks for a device tensor), so nothing here needs a GPU.  Also the proof, from the library's own launch plan
+(giga_decoder_plan: host only, it needs the built library and no device), that the cases of tests/test_gpu_lattice_shapes.py reach
+every dispatch branch of the lattice decoders, and that the plan equals the hand-written table of those cases."""
 import os
 import sys
 
@@ -11,7 +12,7 @@ import torch
 from giga_amd import convonet
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_gpu_lattice_shapes as G  # noqa: E402  (its case tables and the restated launch formula; nothing in it runs here)
+import test_gpu_lattice_shapes as G  # noqa: E402  (its case tables and its `plan`; none of its tests runs here)
 from lattice_lins import FAMILIES, grid_points, lin_family  # noqa: E402
 
 
@@ -94,21 +95,54 @@ def test_registration_is_tied_to_the_tensor_version():
     del p
 
 
+@pytest.fixture(autouse=True)
+def _no_decoder_knobs(monkeypatch):
+    for k in ("GIGA_DEC_LAT", "GIGA_DEC16_RESIDENT", "GIGA_DEC32_TILE", "GIGA_DEC32_POINT"):
+        monkeypatch.delenv(k, raising=False)
+
+
+def test_lat_table_equals_the_plan():
+    """G.LAT_TABLE, written by hand, against the library's plan, field for field, for every launch of G.LAT_CASES in every
+    precision the case runs: ntile (lat_parts divides it), lat_parts, nslab, slots and its branch, the XCD remap -- and the grid,
+    the two line buffers of plain fp16 and the operand form, which follow from them."""
+    rows = {(r[0], r[1], r[3]): r for r in G.LAT_TABLE}
+    assert len(rows) == len(G.LAT_TABLE) == 23
+    launches = set()
+    for R, B, mask, _, _, _, precs in G.LAT_CASES:
+        for nh in G.MASKS[mask][1]:
+            launches.add((R, B, nh))
+            _, _, tmask, _, ntile, parts, nslab, slots, branch, remap = rows[(R, B, nh)]
+            assert tmask == mask and ntile == (R // 4) * (R // 8) and nslab == B * R * parts
+            assert slots == {"nslab": nslab, "cap": 256 // nh, "cap8": 256 // (8 * nh) * 8}[branch]
+            for prec in precs:
+                code = G.PREC_CODE[prec]
+                d = G.plan(code, B, R, nh)
+                assert d["kernel"] == "lat", (R, B, nh, prec)
+                assert ntile % d["lat_parts"] == 0
+                assert (d["lat_parts"], B * R * d["lat_parts"], d["slots"], d["xcd_remap"]) == (parts, nslab, slots, remap), (R, B, nh, prec, d)
+                assert (d["grid_x"], d["grid_y"], d["nbatch"], d["block"], d["NW"]) == (slots * nh, 1, slots, 1024, 16), d
+                assert (d["split"], d["dbuf"]) == (code == 2, code == 1), d
+    assert launches == set(rows)
+
+
 def test_dispatch_cases_cover_every_branch():
-    """The coverage proof of tests/test_gpu_lattice_shapes.py, which needs no device.  From launch_decoder's formula alone
-    (G.dispatch restates it): the decoder_lat_kernel cases take lat_parts 1 and 2 at every R and 5 at R = 40, each
-    of the three `slots` branches, the XCD remap on and off, and plain fp16 (two line buffers) at every R; the other cases never
-    reach decoder_lat_kernel and run every LATTICE = true kernel in both tile counts."""
+    """The coverage proof of tests/test_gpu_lattice_shapes.py, which needs no device.  From the library's plan (G.plan; the branch
+    of `slots` from G.LAT_TABLE, which test_lat_table_equals_the_plan holds to the plan): the decoder_lat_kernel cases take
+    lat_parts 1 and 2 at every R and 5 at R = 40, each of the three `slots` branches, the XCD remap on and off, and plain fp16 (two
+    line buffers) at every R; the other cases never reach decoder_lat_kernel and run every LATTICE = true kernel in both tile
+    counts."""
+    branch_of = {(r[0], r[1], r[3]): r[8] for r in G.LAT_TABLE}
     parts, branches, xcd, dbuf = {}, set(), set(), set()
     for R, B, mask, _, _, _, precs in G.LAT_CASES:
         for prec in precs:
             for nh in G.MASKS[mask][1]:
-                d = G.dispatch(G.PREC_CODE[prec], B, R, nh)
+                d = G.plan(G.PREC_CODE[prec], B, R, nh)
                 assert d["kernel"] == "lat", (R, B, mask, prec)
-                parts.setdefault(R, set()).add(d["parts"])
-                branches.add(d["branch"])
-                xcd.add(d["xcd"])
-                if G.PREC_CODE[prec] == 1:
+                parts.setdefault(R, set()).add(d["lat_parts"])
+                branches.add(branch_of[(R, B, nh)])
+                xcd.add(d["xcd_remap"])
+                if d["dbuf"]:
+                    assert G.PREC_CODE[prec] == 1
                     dbuf.add(R)
     assert parts == {8: {1, 2}, 16: {1, 2}, 24: {1, 2}, 32: {1, 2}, 40: {1, 2, 5}}, parts
     assert branches == {"nslab", "cap", "cap8"} and xcd == {True, False} and dbuf == {8, 16, 24, 32, 40}
@@ -116,11 +150,15 @@ def test_dispatch_cases_cover_every_branch():
     for R, B, mask, _, _, _, precs in G.GEN_CASES:
         for prec in precs:
             for nh in G.MASKS[mask][1]:
-                d = G.dispatch(G.PREC_CODE[prec], B, R, nh)
+                d = G.plan(G.PREC_CODE[prec], B, R, nh)
                 assert d["kernel"] != "lat", (R, B, mask, prec)
-                seen.add((d["kernel"], d["T"], d.get("split")))
+                # fp32, one tile per wave: whether every head gets its own workgroups (blockIdx.y)
+                per_head = (d["heads_per_wg"] == 1 and d["grid_y"] == nh) if (d["kernel"], d["T"]) == ("f32", 1) else None
+                if per_head is False:
+                    assert (d["heads_per_wg"], d["grid_y"]) == (nh, 1)
+                seen.add((d["kernel"], d["T"], per_head))
     assert seen == {("f32", 1, True), ("f32", 1, False), ("f32", 2, None), ("f16s", 1, None), ("f16s", 2, None), ("f16", 2, None)}, seen
     assert {c[0] for c in G.GEN_CASES} == {1, 2, 7, 9, 17, 33, 41, 48, 63, 64}
-    assert G.dispatch(1, 2, 48, 3)["kernel"] == "f16" and G.dispatch(1, 2, 48, 1)["kernel"] == "f16s"
+    assert G.plan(1, 2, 48, 3)["kernel"] == "f16" and G.plan(1, 2, 48, 1)["kernel"] == "f16s"
     # the batch-versus-single-scene check of the shared-feature kernel: one scene of 64^3 points is already past its threshold
-    assert G.dispatch(1, 2, 64, 4)["kernel"] == "f16" and G.dispatch(1, 1, 64, 4)["kernel"] == "f16"
+    assert G.plan(1, 2, 64, 4)["kernel"] == "f16" and G.plan(1, 1, 64, 4)["kernel"] == "f16"
