@@ -53,39 +53,49 @@ def head_forward(sd, prefix, c, p, acc=torch.float64):
     return out.float(), saved
 
 
-def head_backward(sd, prefix, saved, dO, acc=torch.float64, relu_mask=None):
+def head_backward(sd, prefix, saved, dO, acc=torch.float64, relu_mask=None, pairs=None):
     """dO (P, out_dim): gradient w.r.t. the RAW head output.  Returns ({param name: grad}, dc (P, 96)) and leaves the chain's last
     DN, rounded as fc_p's weight gradient takes it, in saved["dn0"].  relu_mask: the ReLU mask of a rounded activation (default
-    x != 0, the kernel's; tests/test_dect_exact_host.py passes a wrong one to show that its data sees the difference)."""
+    x != 0, the kernel's; tests/test_dect_exact_host.py passes a wrong one to show that its data sees the difference).
+    pairs: a dict that receives {param name: (dY, X)}, the operands of every weight gradient dY^T X (X is None for a bias, the
+    column sum of dY), for tests that bound the partial sums."""
     mask = relu_mask if relu_mask is not None else (lambda x: x != 0)
     W = lambda k: sd[prefix + k + ".weight"].float()  # noqa: E731
     cb, xn, xh, xo = saved["cb"], saved["xn"], saved["xh"], saved["xo"]
     g = {}
+
+    def wgrad(name, dY, X):
+        g[name] = dY.T @ X if X is not None else dY.sum(0)
+        if pairs is not None:
+            pairs[name] = (dY, X)
+
     dOb = bf(dO.float()).to(acc)
-    g["fc_out.weight"] = dOb.T @ xo.to(acc)
-    g["fc_out.bias"] = dOb.sum(0)
+    wgrad("fc_out.weight", dOb, xo.to(acc))
+    wgrad("fc_out.bias", dOb, None)
     G = (dO.float().to(acc) @ bf(W("fc_out")).to(acc)) * mask(xo)
     G = G.float()                                           # the kernel holds DN in fp32 registers
     Gb = bf(G)
-    g[f"blocks.{NBLK - 1}.fc_1.bias"] = Gb.to(acc).sum(0)
+    wgrad(f"blocks.{NBLK - 1}.fc_1.bias", Gb.to(acc), None)
     dc = torch.zeros_like(cb)
     for b in range(NBLK - 1, -1, -1):
-        g[f"blocks.{b}.fc_1.weight"] = Gb.to(acc).T @ xh[b].to(acc)
+        wgrad(f"blocks.{b}.fc_1.weight", Gb.to(acc), xh[b].to(acc))
         dh = (Gb.to(acc) @ bf(W(f"blocks.{b}.fc_1")).to(acc)).float() * mask(xh[b])
         Hb = bf(dh)
-        g[f"blocks.{b}.fc_0.weight"] = Hb.to(acc).T @ xn[b].to(acc)
-        g[f"blocks.{b}.fc_0.bias"] = Hb.to(acc).sum(0)
+        wgrad(f"blocks.{b}.fc_0.weight", Hb.to(acc), xn[b].to(acc))
+        wgrad(f"blocks.{b}.fc_0.bias", Hb.to(acc), None)
         dn = (Hb.to(acc) @ bf(W(f"blocks.{b}.fc_0")).to(acc)).float() * mask(xn[b])
         G = G + dn
         Gb = bf(G)
-        g[f"fc_c.{b}.weight"] = Gb.to(acc).T @ cb
-        g[f"fc_c.{b}.bias"] = Gb.to(acc).sum(0)
+        wgrad(f"fc_c.{b}.weight", Gb.to(acc), cb)
+        wgrad(f"fc_c.{b}.bias", Gb.to(acc), None)
         if b > 0:
-            g[f"blocks.{b - 1}.fc_1.bias"] = Gb.to(acc).sum(0)
+            wgrad(f"blocks.{b - 1}.fc_1.bias", Gb.to(acc), None)
         dc = dc + Gb.to(acc) @ bf(W(f"fc_c.{b}")).to(acc)
     saved["dn0"] = Gb
     g["fc_p.weight"] = Gb.to(acc).T @ saved["p_hi"].to(acc) + Gb.to(acc).T @ saved["p_lo"].to(acc)
-    g["fc_p.bias"] = Gb.to(acc).sum(0)
+    if pairs is not None:
+        pairs["fc_p.weight"] = (Gb.to(acc), saved["p_hi"].to(acc) + saved["p_lo"].to(acc))
+    wgrad("fc_p.bias", Gb.to(acc), None)
     return {k: v.float() for k, v in g.items()}, dc.float()
 
 

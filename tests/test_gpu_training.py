@@ -97,7 +97,8 @@ def test_plane_gradient_gather_with_all_queries_in_one_cell(sd7):
     """The worst case of the binned gather: every occupancy query of a scene in ONE pixel cell (scene 0: 4096 points inside a
     1e-3 cube; scene 1: all points clamped onto one corner of the volume) -- cell lists of 4096 points, which the workgroup ranks
     cooperatively instead of one lane sorting them by insertion (8 M serial LDS steps: the step took milliseconds).  Gradients
-    against the oracle; the step must also stay in the time of a normal one."""
+    against the oracle; the step must also stay in the time of a normal one.
+    (The plane gradient itself, with 64 long cells and with one: tests/test_gpu_dec32_shapes.py.)"""
     import time
     dev = torch.device("cuda:0")
     B, M = 2, 4096
@@ -133,7 +134,8 @@ def test_plane_gradient_gather_path(sd7, B, M):
     (footprints in the last pixel row / column, the clamped coordinates of common.py:238-261) and many queries in ONE pixel
     cell (long cell lists); gradients against the oracle, and the encoder gradients -- which only see the decoders through
     the plane gradient -- again after a second identical step (the gather sums in a fixed order; what remains of run-to-run
-    differences are the atomics of the weight-gradient reductions)."""
+    differences are the atomics of the weight-gradient reductions).
+    The plane gradient itself is held bit for bit, on exact data, by tests/test_gpu_dec32_shapes.py."""
     dev = torch.device("cuda:0")
     x, pos, pos_occ, y = _batch(700, B, M)
     pos_occ = pos_occ.clone()
