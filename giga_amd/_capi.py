@@ -147,6 +147,7 @@ _SIGNATURES = {
                                                     ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_void_p]),
     "giga_decoder_plan": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_void_p]),
+    "giga_decoder_backward_plan": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.c_void_p]),
     "giga_grasp_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "giga_grasp_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,

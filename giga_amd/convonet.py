@@ -435,6 +435,51 @@ def decoder_plan(B, N, R, nheads, precision):
     return plan
 
 
+# struct TrainDecPlan / DecBwdCall of csrc/giga_dec_bwd_plan.h: the 32-bit fields, then the 64-bit ones (two words each, low first)
+DECODER_BACKWARD_MAX_LAUNCHES = 8
+DECODER_BACKWARD_CALL_FIELDS = (("runs", "kernel", "nheads", "planes", "gather", "nbatch", "grid_x", "grid_y", "block", "lds", "heads_per_wg",
+                                 "wgrad_merged", "wgrad_launches", "nb_total", "ksplit_cap", "ksplit", "pts_per_block", "launches",
+                                 "fwd_grid_x", "fwd_block", "fwd_lds", "bf16"),
+                                ("P", "tiles", "head_off", "head_stride", "cbuf_off", "pbuf_off", "dcbuf_off", "scratch_floats"))
+DECODER_BACKWARD_PLAN_FIELDS = (("bf16", "clear_planes", "reduce", "launches"), ("occ_base", "grasp_base", "scratch_floats"))
+DECODER_BACKWARD_KERNELS = (None, "decoder_bwd_kernel", "plane_gather_kernel", "linear_wgrad_kernel", "dect_kernel",
+                            "dect_reduce_kernel")     # GIGA_DEC_BWD_KERNEL_*
+_CALL_WORDS = len(DECODER_BACKWARD_CALL_FIELDS[0]) + 2 * len(DECODER_BACKWARD_CALL_FIELDS[1])
+_PLAN_WORDS = len(DECODER_BACKWARD_PLAN_FIELDS[0]) + DECODER_BACKWARD_MAX_LAUNCHES + 2 * len(DECODER_BACKWARD_PLAN_FIELDS[1]) + 2 * _CALL_WORDS
+
+
+def _plan_words(words, at, ints, longs, skip=0):
+    """({field: value} of the 32-bit fields `ints`, `skip` words, the 64-bit fields `longs` from words[at:], the index behind them)."""
+    d = dict(zip(ints, words[at:at + len(ints)]))
+    at += len(ints) + skip
+    for k in longs:
+        d[k] = (words[at] & 0xFFFFFFFF) | (words[at + 1] << 32)
+        at += 2
+    return d, at
+
+
+def decoder_backward_plan(B, N, M, head_present):
+    """What the decoder part of giga_backward(B, N, M, head_present) would do (giga_decoder_backward_plan; host only): head_present
+    with its DETACH_OCC and BF16_DECODER flag bits.  A dict of the fields of struct TrainDecPlan (csrc/giga_dec_bwd_plan.h): `order`
+    the kernel names of its `launches` launches as enqueued, "occ" and "grasp" the two calls (dicts of struct DecBwdCall, `kernel` as
+    a name, the flags as bools)."""
+    words = (ctypes.c_int32 * _PLAN_WORDS)()
+    _capi.check(_capi.lib().giga_decoder_backward_plan(B, N, M, head_present, words), "giga_decoder_backward_plan")
+    words = list(words)
+    ints, longs = DECODER_BACKWARD_PLAN_FIELDS
+    plan, at = _plan_words(words, 0, ints, longs, skip=DECODER_BACKWARD_MAX_LAUNCHES)
+    plan["order"] = [DECODER_BACKWARD_KERNELS[k] for k in words[len(ints):len(ints) + plan["launches"]]]
+    for flag in ("bf16", "clear_planes", "reduce"):
+        plan[flag] = bool(plan[flag])
+    for name in ("occ", "grasp"):
+        call, at = _plan_words(words, at, *DECODER_BACKWARD_CALL_FIELDS)
+        call["kernel"] = DECODER_BACKWARD_KERNELS[call["kernel"]]
+        for flag in ("runs", "planes", "gather", "wgrad_merged", "bf16"):
+            call[flag] = bool(call[flag])
+        plan[name] = call
+    return plan
+
+
 _HEAD_SLOTS = ("decoder_qual", "decoder_rot", "decoder_width", "decoder_tsdf")
 
 

@@ -4,6 +4,9 @@
 // helpers and host register / unregister.  Every other entry point stands in the file of its kernels, after them (giga_post.hip,
 // giga_eval.hip, giga_mesh.hip, ...); host checks that several of those share are in giga_check.h.
 #include <hip/hip_runtime.h>
+
+#include <cstring>
+
 #include "giga_launch.h"
 
 #include "../../include/giga_hip.h"
@@ -12,6 +15,7 @@
 #include "giga_dect.h"
 #include "giga_args.h"
 #include "giga_side.h"
+#include "giga_dec_bwd_launch.h"
 
 namespace giga {
 // giga_pack.cpp
@@ -22,24 +26,11 @@ size_t bwd_packed_bytes();
 int pack_bwd_host(const float* P, size_t n_params, int head_present, uint8_t* blob, size_t blob_bytes);
 int pack_bwd_map_host(int head_present, int32_t* map, size_t nwords);
 int packed_check_host(const uint8_t* blob, size_t bytes, int backward);
-// giga_encoder_bwd.hip / giga_decoder_bwd.hip
+// giga_encoder_bwd.hip (the training decoder's launchers: giga_dec_bwd_launch.h)
 void persistent_forget();
 int launch_encoder_backward(const float* tsdf, const uint8_t* blob, const uint8_t* bwd_blob, const uint8_t* fws,
                             float* gplanes, uint8_t* gws, float* grads, int head_present, int B, hipStream_t s, bool bf16_convs, bool convin_mask,
                             SideScope& side);
-size_t dec_bwd_scratch_floats(long long P, int nheads);
-bool dec_bwd_writes_planes(int nheads, int B, int N);
-int launch_decoder_backward(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob,
-                            int head_mask, const float* const* outs, const float* const* douts, float* gplanes,
-                            float* grads, int head_present, float* scratch, int B, int N, hipStream_t s, bool writes_planes,
-                            SideScope* side);
-int launch_plane_gather(const float* dcbuf, const float* p, float* gplanes, int B, int N, hipStream_t s);
-// giga_decoder_train16.hip (bf16 decoder of the bf16 training step)
-size_t dect_partial_floats(long long P, int nheads);
-int launch_dect_backward(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob, int head_mask,
-                         const float* const* outs, const float* const* douts, float* gplanes, float* dcbuf, float* scratch, int B,
-                         int N, hipStream_t s, DectPending* pend);
-int launch_dect_reduce(const DectPending& pend, float* grads, int head_present, hipStream_t s);
 // giga_encoder.hip
 EncWs enc_workspace(int B, int precision);
 int launch_encoder(const float* tsdf, const uint8_t* blob, void* planes_nhwc, float* planes_nchw, int B,
@@ -391,23 +382,15 @@ int giga_pack_bwd_map(int head_present, int32_t* map_host, size_t nwords) {
     return pack_bwd_map_host(head_present & 15, map_host, nwords);
 }
 
-static size_t train_dec_scratch_bytes(int B, int N, int M, int head_present) {
-    const int ng = __builtin_popcount(head_present & 7), nt = (head_present >> 3) & 1;
-    const size_t a = ng ? dec_bwd_scratch_floats((long long)B * N, ng) : 0;
-    const size_t b = nt && M > 0 ? dec_bwd_scratch_floats((long long)B * M, 1) : 0;
-    // bf16 decoder (GIGA_BF16_DECODER): the dc rows of the occupancy head + the partial gradient tiles of both calls (they are
-    // reduced together at the end); far below the fp32 path's row arrays except for a handful of points
-    const size_t c = (nt && M > 0 ? (size_t)B * M * 96 + dect_partial_floats((long long)B * M, 1) : 0) +
-                     (ng ? dect_partial_floats((long long)B * N, ng) : 0);
-    const size_t m = a + b;                          // (both: the occupancy call's weight gradients run beside the grasp call, giga_side.h)
-    return align_up((m > c ? m : c) * sizeof(float), 256);
-}
-
 size_t giga_backward_workspace_bytes(int B, int N, int M, int head_present) {
     if (B <= 0) return 0;
     head_present &= 15;
+    // (the size call does not know the decoder's precision: the larger of the two needs.  bf16 -- the dc rows of the occupancy head and
+    //  the partial gradient tiles of both calls -- is far below the fp32 path's row arrays except for a handful of points)
+    const long long f32 = train_dec_plan(B, N, M, head_present, false, false).scratch_floats;
+    const long long b16 = train_dec_plan(B, N, M, head_present, false, true).scratch_floats;
     return align_up((size_t)3 * B * RES * RES * CD * sizeof(float), 256) + enc_bwd_workspace(B).total +
-           train_dec_scratch_bytes(B, N, M, head_present);
+           align_up((size_t)(f32 > b16 ? f32 : b16) * sizeof(float), 256);
 }
 
 int giga_backward_workspace_layout(int B, size_t* offsets) {
@@ -449,47 +432,54 @@ int giga_backward(const float* tsdf, const void* packed, const void* bwd_packed,
     float* scratch = reinterpret_cast<float*>(gws + enc_bwd_workspace(B).total);
     const uint8_t* blob = static_cast<const uint8_t*>(packed);
     const uint8_t* bblob = static_cast<const uint8_t*>(bwd_packed);
-    const bool occ_runs = (head_present & 8) && M > 0 && p_tsdf;
-    // The occupancy head with many queries per scene WRITES the plane gradients (plane_gather_kernel: a gather over binned points
-    // instead of global atomics), so it runs first and nothing needs clearing; the grasp heads then add theirs with atomics.
-    const bool occ_writes = occ_runs && !detach_occ && dec_bwd_writes_planes(1, B, M);
-    if (!occ_writes && hipMemsetAsync(gplanes, 0, gp_bytes, s) != hipSuccess) return -10;
+    // The decoder part as train_dec_plan lays it out (giga_dec_bwd_plan.h): the occupancy call first -- with many queries per scene
+    // it WRITES the plane gradients (plane_gather_kernel: a gather over binned points instead of global atomics) and nothing needs
+    // clearing -- then the grasp call, which adds its own with atomics.
+    const TrainDecPlan plan = train_dec_plan(B, N, M, p_tsdf ? head_present : head_present & 7, detach_occ, bf16_dec);
+    if (plan.clear_planes && hipMemsetAsync(gplanes, 0, gp_bytes, s) != hipSuccess) return -10;
     if (hipMemsetAsync(grads, 0, n_params * sizeof(float), s) != hipSuccess) return -10;
     int rc = 0;
     // work that waits for ONE launch of the caller's stream only goes to the device's side stream (giga_side.h; GIGA_WGRAD_STREAM=0: none)
     SideScope side(s, [] { const char* e = getenv("GIGA_WGRAD_STREAM"); return !e || atoi(e) != 0; }());
-    if (bf16_dec) {
-        // one fused launch per call (recompute, gradient chain, weight gradients), ONE reduce for every head of the step
-        DectPending pend{};
-        float* sc = scratch;
-        if (occ_runs) {
-            float* dcbuf = occ_writes ? sc : nullptr;
-            if (dcbuf) sc += (size_t)B * M * 96;
-            rc |= launch_dect_backward(static_cast<const float*>(planes_nhwc), p_tsdf, blob, bblob, 8, outs, douts,
-                                       detach_occ ? nullptr : gplanes, dcbuf, sc, B, M, s, &pend);
-            sc += dect_partial_floats((long long)B * M, 1);
-            if (dcbuf) rc |= launch_plane_gather(dcbuf, p_tsdf, gplanes, B, M, s);
-        }
-        if ((head_present & 7) && N > 0)
-            rc |= launch_dect_backward(static_cast<const float*>(planes_nhwc), p, blob, bblob, head_present & 7, outs, douts,
-                                       gplanes, nullptr, sc, B, N, s, &pend);
-        // (on the caller's stream: moved to the side stream it delays the first weight gradients there, 894 -> 899 us per step)
-        rc |= launch_dect_reduce(pend, grads, head_present, s);
-    } else {
-    float* sc = scratch;
-    if (occ_runs) {
-        rc |= launch_decoder_backward(static_cast<const float*>(planes_nhwc), p_tsdf, blob, bblob, 8, outs, douts,
-                                      detach_occ ? nullptr : gplanes, grads, head_present, sc, B, M, s, occ_writes, &side);
-        sc += dec_bwd_scratch_floats((long long)B * M, 1);       // (its weight gradients may still be reading their rows)
+    const float* nhwc = static_cast<const float*>(planes_nhwc);
+    DectPending pend{};
+    struct { const DecBwdCall& c; long long base; const float* p; int mask, n; } calls[2] = {
+        {plan.occ, plan.occ_base, p_tsdf, 8, M}, {plan.grasp, plan.grasp_base, p, head_present & 7, N}};
+    for (const auto& k : calls) {
+        if (!k.c.runs) continue;
+        float* sc = scratch + k.base;
+        float* gp = k.c.planes ? gplanes : nullptr;
+        float* dcbuf = k.c.gather ? sc + k.c.dcbuf_off : nullptr;
+        // fp32: the weight gradients go to the side stream (the occupancy call's may still be reading their rows while the grasp call
+        // runs: the calls' scratch lies apart).  bf16: one fused launch, its partial tiles wait for the reduce below.
+        if (bf16_dec) rc |= launch_dect_backward(k.c, nhwc, k.p, blob, bblob, k.mask, outs, douts, gp, dcbuf, sc, B, k.n, s, &pend);
+        else rc |= launch_decoder_backward(k.c, nhwc, k.p, blob, bblob, k.mask, outs, douts, gp, dcbuf, grads, head_present, sc, B, k.n, s, &side);
+        if (dcbuf && bf16_dec) rc |= launch_plane_gather(dcbuf, k.p, gplanes, B, k.n, s);   // (fp32: in front of its weight gradients)
     }
-    if ((head_present & 7) && N > 0) {
-        rc |= launch_decoder_backward(static_cast<const float*>(planes_nhwc), p, blob, bblob, head_present & 7, outs,
-                                      douts, gplanes, grads, head_present, sc, B, N, s, false, &side);
-    }
-    }
+    // ONE reduce for every head of the bf16 step (on the caller's stream: moved to the side stream it delays the first weight gradients
+    // there, 894 -> 899 us per step)
+    if (plan.reduce) rc |= launch_dect_reduce(pend, grads, head_present, s);
     rc |= launch_encoder_backward(tsdf, blob, bblob, static_cast<const uint8_t*>(enc_workspace_fwd), gplanes, gws,
                                   grads, head_present, B, s, bf16_convs, convin_mask, side);
     return rc;
+}
+
+/* host only: what the decoder part of giga_backward would do for these arguments (giga_dec_bwd_plan.h) */
+int giga_decoder_backward_plan(int B, int N, int M, int head_present, int32_t* plan_words) {
+    static_assert(TRAIN_DEC_PLAN_WORDS == GIGA_DECODER_BACKWARD_PLAN_WORDS && DEC_BWD_CALL_WORDS == GIGA_DECODER_BACKWARD_CALL_WORDS &&
+                  TRAIN_DEC_MAX_LAUNCHES == GIGA_DECODER_BACKWARD_MAX_LAUNCHES && sizeof(int) == sizeof(int32_t), "the plan's words are the header's");
+    static_assert(DBK_DECODER_BWD == GIGA_DEC_BWD_KERNEL_DECODER_BWD && DBK_PLANE_GATHER == GIGA_DEC_BWD_KERNEL_PLANE_GATHER &&
+                  DBK_LINEAR_WGRAD == GIGA_DEC_BWD_KERNEL_LINEAR_WGRAD && DBK_DECT == GIGA_DEC_BWD_KERNEL_DECT &&
+                  DBK_DECT_REDUCE == GIGA_DEC_BWD_KERNEL_DECT_REDUCE, "the kernel ids are the header's");
+    if (!plan_words) return -1;
+    TrainDecPlan plan{};
+    if (B > 0) {
+        if (B > GIGA_MAX_SCENES) return -7;
+        if (N < 0 || M < 0) return -1;
+        plan = train_dec_plan(B, N, M, head_present & 15, (head_present & GIGA_DETACH_OCC) != 0, (head_present & GIGA_BF16_DECODER) != 0);
+    }
+    memcpy(plan_words, &plan, sizeof plan);
+    return 0;
 }
 
 /* page-lock (and map for DMA) a host range the caller owns, e.g. a shared-memory batch ring written by reader processes */

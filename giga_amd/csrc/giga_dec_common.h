@@ -1,6 +1,6 @@
 // Pieces shared by the decoder kernels (giga_decoder.hip, giga_decoder_bwd.hip, giga_decoder_pgrad.hip, giga_decoder_train16.hip):
 // the LDS-DMA fill of a fragment image, the D-register layout idioms, the bilinear gather of the 96 plane features in its two
-// fp32 forms, the f16 aux operand, and the fp32 recompute / gradient chain that the backward and the point-gradient kernel run on
+// fp32 forms, the [.][96] row store of the training decoders, the f16 aux operand, and the fp32 recompute / gradient chain that the backward and the point-gradient kernel run on
 // the same fragments in the same MFMA order.
 #pragma once
 #include "giga_dev.h"
@@ -131,6 +131,21 @@ __device__ __forceinline__ void gather_staged48(float* S, const float* planes, s
             const float4 v = *reinterpret_cast<const float4*>(S + n * 96 + pl * 32 + 16 * hi + 4 * q);
             cf[16 * pl + 4 * q + 0] = v.x; cf[16 * pl + 4 * q + 1] = v.y; cf[16 * pl + 4 * q + 2] = v.z; cf[16 * pl + 4 * q + 3] = v.w;
         }
+}
+
+// ---- rows of [.][96] from D-layout images (lane = point, registers = features drow(r, hi)), features 0..95 in order: the training
+// decoders' dc rows for plane_gather_kernel in HBM and the value part of their scatter stages in LDS.  One plane's 32 features:
+template <class Row>
+__device__ __forceinline__ void store_row96_plane(float* dst, Row row, int hi, int pl, const f32x16& v) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        *reinterpret_cast<float4*>(dst + row * 96 + pl * 32 + 8 * q + 4 * hi) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+}
+// all three planes
+template <class Row>
+__device__ __forceinline__ void store_row96(float* dst, Row row, int hi, const f32x16 (&v)[3]) {
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) store_row96_plane(dst, row, hi, pl, v[pl]);
 }
 
 // aux operand of the f16 chains: [p_hi(3), 1, p_lo(3), 1] on hi = 0 lanes, [p_hi(3), 0 ...] on hi = 1 lanes (exact by itself)

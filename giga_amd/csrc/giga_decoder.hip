@@ -19,6 +19,7 @@
 
 #include "giga_dec_common.h"
 #include "giga_dec_plan.h"
+#include "giga_dec_bwd_launch.h"
 #include "giga_args.h"
 
 namespace giga {
@@ -1499,10 +1500,6 @@ static int launch_planes_unpack(const void* src, float* dst, int B, int precisio
                            reinterpret_cast<const float*>(src), dst);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
-
-// giga_decoder_train16.hip (bf16 decoder of the bf16 training step)
-int launch_dect_forward(const float* planes, const float* p, const uint8_t* blob, int head_mask, float* const* outs, int B, int N,
-                        int post, hipStream_t s);
 
 // byte offset of head h's weight image for a precision (0 fp32, 1 f16, 2 f16x3 split), plain or with conv_final folded in
 static size_t head_image_offset(const PackOff& ko, int h, int precision, bool fold) {

@@ -15,16 +15,12 @@
 // linear_wgrad_kernel then reduces dW = dY^T X and db = colsum(dY) for all layers of a head in ONE launch
 // (MFMA 32x32x2 over pairs of points, operands straight from HBM, one atomic per gradient element per block).
 #include "giga_args.h"
-#include "giga_side.h"
+#include "giga_dec_bwd_launch.h"
 #include "giga_dec_common.h"
 
 namespace giga {
 
-// per-head scratch arrays, each [P][32] fp32 (row = point, D-layout feature order restored to 0..31)
-//   0..5 DN[i]   6..10 DH[i]   11..15 XN[i]   16..20 XH[i]   21 XO   22 DO (cols >= out_dim zero)
-constexpr int DB_NARR = 23;
-// shared per call: C [P][96], PP [P][32] (cols 0..2 = p, rest zero)
-
+// (the scratch of a call -- DB_NARR row arrays per head, C, PP, the dc rows -- and every launch shape: giga_dec_bwd_plan.h)
 struct DecBwdArgs {
     const float* planes;        // NHWC fp32 [3][B][40][40][32]
     const float* p;             // [P][3]
@@ -129,12 +125,9 @@ __global__ __launch_bounds__(256, 1) void decoder_bwd_kernel(DecBwdArgs a) {
             // ================= 2. epilogue backward: dO (<= 4 values, identical in both lane halves) ============
             const int id = a.head_id[h];
             float dO[4] = {0.f, 0.f, 0.f, 0.f};
-            if (id == 1) {          // rot = z / max(|z|, eps): dz = (dr - r (r.dr)) / |z|   (F.normalize backward)
-                const float4 r4 = *reinterpret_cast<const float4*>(a.out[h] + 4 * g);
+            if (id == 1) {          // rot = z / max(|z|, eps): dz = (dr - r (r.dr)) / |z|   (F.normalize backward, finished below)
                 const float4 d4 = *reinterpret_cast<const float4*>(a.dout[h] + 4 * g);
-                // |z| from the recomputed raw output would need fc_out; use r = z/|z| and z.r = |z|: recompute z below
                 dO[0] = d4.x; dO[1] = d4.y; dO[2] = d4.z; dO[3] = d4.w;
-                (void)r4;
             } else {
                 float d = a.dout[h][g];
                 if (id == 0) { const float q = a.out[h][g]; d *= q * (1.0f - q); }      // sigmoid'
@@ -147,8 +140,9 @@ __global__ __launch_bounds__(256, 1) void decoder_bwd_kernel(DecBwdArgs a) {
             __syncthreads();
             const float* wout = reinterpret_cast<const float*>(smem + (size_t)DECB_FRAGS * FRAG);   // [4][32]
             if (id == 1) {
-                // raw z = fc_out(relu(net5)) + b is needed for the normalize backward: z_o = sum_f Wout[o][f] relu(net5)[f] + b_o
-                // (this lane holds 16 of the 32 features; the other half lives in lane^32)
+                // the normalize backward needs the raw z = fc_out(relu(net5)) + b: z_o = sum_f Wout[o][f] relu(net5)[f] is recomputed
+                // from wout (this lane holds 16 of the 32 features, lane ^ 32 the others) and the bias b_o is read from the forward
+                // blob in global memory (the forward C table has left LDS)
                 float z[4];
 #pragma unroll
                 for (int o = 0; o < 4; ++o) {
@@ -158,9 +152,6 @@ __global__ __launch_bounds__(256, 1) void decoder_bwd_kernel(DecBwdArgs a) {
                     s += __shfl_xor(s, 32);
                     z[o] = s;
                 }
-                // bias of fc_out: forward C-table row 5 is gone from LDS; the caller passes post-normalize outputs,
-                // and r = z/|z| with |z| = z.r, so recover |z| from the bias-free part plus the known direction:
-                // z = zb + bias  =>  we instead read the bias from the forward blob in global memory
                 const float* fb = reinterpret_cast<const float*>(a.blob + a.head_off[h] + (size_t)DEC32_FRAGS * FRAG) + NBLK * 32;
                 const float4 r4 = *reinterpret_cast<const float4*>(a.out[h] + 4 * g);
                 float nrm2 = 0.f;
@@ -187,8 +178,8 @@ __global__ __launch_bounds__(256, 1) void decoder_bwd_kernel(DecBwdArgs a) {
         // 64 scattered words: float atomics are resolved outside the XCD-local L2, one fabric operation per touched
         // line, so the transposition through LDS (the weight image is dead by now) cuts that traffic 16-fold.
         if (a.gplanes && a.dcbuf) {               // the scatter is plane_gather_kernel's: hand over dc as rows of [P][96]
-            if (valid) {
-#pragma unroll
+            if (valid) {                          // (this kernel sits at 256 VGPRs: through giga_dec_common.h's store_row96, here or in the
+#pragma unroll                                    //  stage fill below, it is allocated two more AGPRs, so both rows are written out)
                 for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
@@ -247,10 +238,7 @@ __global__ __launch_bounds__(256, 1) void decoder_bwd_kernel(DecBwdArgs a) {
 // with the weights bilin_setup gives (the forward's own).  The result is WRITTEN (no memset, no read-modify-write): a head that
 // uses this path runs before the heads that add with atomics.  Unlike atomics, the sum is in a fixed order (by point index
 // inside a cell, cells in a fixed order): the plane gradient of this head is reproducible bit for bit.
-constexpr int PS_NW = 16;                                   // waves per workgroup
-constexpr int PS_MAXN = 4096;                               // points per scene this path takes (LDS: 6 + 16 bytes per point)
-constexpr int PS_CELLS = RES * RES;
-constexpr size_t PS_LDS = (size_t)(2 * PS_CELLS + 64) * 4 + (size_t)PS_MAXN * (6 + 16);
+// (PS_NW waves per workgroup, at most PS_MAXN points per scene, PS_LDS bytes: giga_dec_bwd_plan.h)
 __global__ __launch_bounds__(PS_NW * 64) void plane_gather_kernel(const float* __restrict__ dcbuf, const float* __restrict__ p,
                                                                   float* __restrict__ gplanes, int B, int N) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -382,7 +370,6 @@ struct LinProblem {
     float* db;           // mvalid entries (may be null)
     int ncol, sM, mvalid, nvalid;
 };
-constexpr int LIN_MAX = 52;                          // 17 problems per head: up to three heads in one launch (the struct stays under the 4-KiB kernarg limit)
 struct LinArgs { LinProblem pr[LIN_MAX]; int nprob; long long P; int pts_per_block; int ksplit; int nb_total; int nb_start[LIN_MAX + 1]; };
 
 __global__ __launch_bounds__(256) void linear_wgrad_kernel(LinArgs a) {
@@ -433,73 +420,46 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(LinArgs a) {
     }
 }
 
-// ------------------------------- launcher ------------------------------------------------------------------------
-// plane gradients of a many-point head from its dc rows [B * N][96] (WRITTEN; the caller has checked dec_bwd_writes_planes(1, B, N))
+// ------------------------------- launchers (giga_dec_bwd_launch.h) ----------------------------------------------
 int launch_plane_gather(const float* dcbuf, const float* p, float* gplanes, int B, int N, hipStream_t s) {
     giga::dyn_lds_once(reinterpret_cast<const void*>(plane_gather_kernel), (int)PS_LDS);
     GIGA_LAUNCH(plane_gather_kernel, dim3(2, 3, B), dim3(PS_NW * 64), PS_LDS, s, dcbuf, p, gplanes, B, N);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-size_t dec_bwd_scratch_floats(long long P, int nheads) { return (size_t)P * 32 * DB_NARR * nheads + (size_t)P * (96 + 32 + 96); }
-
-// the plane gradients of this call are gathered and WRITTEN (plane_gather_kernel) instead of added with atomics
-bool dec_bwd_writes_planes(int nheads, int B, int N) { return nheads == 1 && N >= 256 && N <= PS_MAXN && B > 0; }
-
-int launch_decoder_backward(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob,
-                            int head_mask, const float* const* outs, const float* const* douts, float* gplanes,
-                            float* grads, int head_present, float* scratch, int B, int N, hipStream_t s, bool writes_planes,
-                            SideScope* side) {
-    // side: the weight-gradient launches (they wait for decoder_bwd_kernel's row arrays only) go to the device's side stream
-    // writes_planes: this call's plane gradient is built by plane_gather_kernel and WRITTEN into `gplanes` (the caller runs it before
-    // the calls that add with atomics and has checked dec_bwd_writes_planes); otherwise it is added to what `gplanes` holds
-    const long long P = (long long)B * N;
-    if (P <= 0 || (head_mask & 15) == 0) return 0;
+int launch_decoder_backward(const DecBwdCall& c, const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob,
+                            int head_mask, const float* const* outs, const float* const* douts, float* gplanes, float* dcbuf,
+                            float* grads, int head_present, float* scratch, int B, int N, hipStream_t s, SideScope* side) {
+    if (!c.runs) return 0;
+    const long long P = c.P;
     const PackOff ko = pack_offsets();
     const BwdPackOff bo = bwd_pack_offsets();
     const ParamOff po = param_offsets(head_present);
     DecBwdArgs a{};
-    a.planes = planes; a.p = p; a.blob = blob; a.bwd_blob = bwd_blob; a.gplanes = gplanes;
+    a.planes = planes; a.p = p; a.blob = blob; a.bwd_blob = bwd_blob; a.gplanes = gplanes; a.dcbuf = dcbuf;
     a.B = B; a.N = N; a.P = P; a.invN = 1.0f / (float)N;
-    float* sc = scratch;
     for (int h = 0; h < NHEADS; ++h) {
         if (!(head_mask >> h & 1)) continue;
         a.head_id[a.nheads] = h; a.head_off[a.nheads] = ko.dec32[h]; a.bwd_off[a.nheads] = bo.dec[h];
         a.out[a.nheads] = outs[h]; a.dout[a.nheads] = douts[h];
-        a.scratch[a.nheads] = sc; sc += (size_t)P * 32 * DB_NARR;
+        a.scratch[a.nheads] = scratch + c.head_off + a.nheads * c.head_stride;
         ++a.nheads;
     }
-    a.Cbuf = sc; a.Pbuf = sc + (size_t)P * 96;
-    a.dcbuf = gplanes && writes_planes && dec_bwd_writes_planes(a.nheads, B, N) ? a.Pbuf + (size_t)P * 32 : nullptr;
-    const long long tiles = (P + 31) / 32;
-    a.nbatch = (int)((tiles + 3) / 4);
-    const int grid = a.nbatch < 256 ? a.nbatch : 256;
-    const bool split = grid * a.nheads <= 256;                  // the point batches alone cannot fill the chip
-    a.heads_per_wg = split ? 1 : a.nheads;
-    const size_t lds = DEC32_BYTES > DECB_BYTES ? DEC32_BYTES : DECB_BYTES;
-    giga::dyn_lds_once(reinterpret_cast<const void*>(decoder_bwd_kernel), (int)lds);
-    GIGA_LAUNCH(decoder_bwd_kernel, dim3(grid, split ? a.nheads : 1), dim3(256), lds, s, a);
-    if (a.dcbuf) {
-        giga::dyn_lds_once(reinterpret_cast<const void*>(plane_gather_kernel), (int)PS_LDS);
-        GIGA_LAUNCH(plane_gather_kernel, dim3(2, 3, B), dim3(PS_NW * 64), PS_LDS, s, a.dcbuf, p, gplanes, B, N);
-    }
-    // weight / bias gradients: one launch per head, or ONE for all heads when their problems fit one argument struct (the three
-    // grasp heads of a one-query call: three 6-us launches of a handful of workgroups each)
-    const bool merged = a.nheads > 1 && 17 * a.nheads <= LIN_MAX;
+    if (a.nheads != c.nheads) return -1;                      // (the plan was made for another head set)
+    a.Cbuf = scratch + c.cbuf_off; a.Pbuf = scratch + c.pbuf_off;
+    a.nbatch = c.nbatch; a.heads_per_wg = c.heads_per_wg;
+    giga::dyn_lds_once(reinterpret_cast<const void*>(decoder_bwd_kernel), c.lds);
+    GIGA_LAUNCH(decoder_bwd_kernel, dim3(c.grid_x, c.grid_y), dim3(c.block), c.lds, s, a);
+    // (the gather goes between the kernel and the weight gradients, which fork from the stream behind it)
+    if (dcbuf && launch_plane_gather(dcbuf, p, gplanes, B, N, s) != 0) return -10;
+    // weight / bias gradients (they wait for decoder_bwd_kernel's row arrays only): on the device's side stream
     int frc = 0;
     if (side) { frc = side->fork(); s = side->stream(); }
     LinArgs L{};
     auto flush = [&]() {
         L.nb_start[L.nprob] = L.nb_total;
-        L.P = P;
-        int ksplit = 2048 / L.nb_total;
-        if (ksplit < 1) ksplit = 1;
-        long long ppb = (P + ksplit - 1) / ksplit;
-        ppb = (ppb + 31) / 32 * 32;
-        L.pts_per_block = (int)ppb;
-        ksplit = (int)((P + ppb - 1) / ppb);
-        L.ksplit = ksplit;
-        GIGA_LAUNCH(linear_wgrad_kernel, dim3(L.nb_total * ksplit), dim3(256), 0, s, L);
+        L.P = P; L.pts_per_block = c.pts_per_block; L.ksplit = c.ksplit;
+        GIGA_LAUNCH(linear_wgrad_kernel, dim3(L.nb_total * c.ksplit), dim3(256), 0, s, L);
         L = LinArgs{};
     };
     for (int hh = 0; hh < a.nheads; ++hh) {
@@ -521,9 +481,9 @@ int launch_decoder_backward(const float* planes, const float* p, const uint8_t* 
             add(S + i * AS, a.Cbuf, 96, grads + o.fc_c_w[i], grads + o.fc_c_b[i], 96, 32, 96);                   // fc_c: DN[i], C
         }
         add(S + 0 * AS, a.Pbuf, 32, grads + o.fc_p_w, grads + o.fc_p_b, 3, 32, 3);                             // fc_p: DN[0], p
-        if (!merged) flush();
+        if (!c.wgrad_merged) flush();
     }
-    if (merged) flush();
+    if (c.wgrad_merged) flush();
     return hipGetLastError() == hipSuccess ? frc : -10;
 }
 

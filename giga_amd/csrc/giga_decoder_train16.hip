@@ -23,6 +23,7 @@
 // through an LDS transposition (few queries), as in the fp32 path (giga_decoder_bwd.hip).
 // tools/tr16_probe.hip pins the lane map of ds_read_b64_tr_b16 and the tile layout on the device (profiles/r05/tr16_probe.txt).
 #include "giga_args.h"
+#include "giga_dec_bwd_launch.h"
 #include "giga_dec_common.h"
 #include "giga_dect.h"
 
@@ -38,11 +39,7 @@ __device__ __forceinline__ f32x16 mfma_bf(bf8 a, bf8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
-// ---- gradient tiles of a head ------------------------------------------------------------------------------------------
-// tile id 6 b + t: t = 0..2 fc_c[b] columns 32 t .. 32 t + 31, 3 bias tile of block b, 4 fc_1[b], 5 fc_0[b]; 30 fc_out.
-// bias tile columns: 0..2 dY x p_hi, 3 colsum(DN[b]), 4..6 dY x p_lo, 8 colsum(DH[b]), 9 colsum(DN[5]) (b = 4), 10 colsum(dO) (b = 4)
-constexpr int DECT_NTILES = 6 * NBLK + 1;                       // 31
-constexpr int DECT_TILE_FLOATS = 1024;
+// ---- gradient tiles of a head (DECT_NTILES tiles of DECT_TILE_FLOATS, their ids and the bias tile's columns: giga_dec_bwd_plan.h) ----
 // wave w plays role (w + b) & 3 in block b: role 0 -> tiles t = 0, 1; role 1 -> t = 2, 3; role 2 -> t = 4; role 3 -> t = 5.
 // accumulator slot of the first tile wave w owns in block b (blocks in ascending order); wave 2 also owns fc_out (slot 7)
 __host__ __device__ constexpr int dect_role_ntiles(int role) { return role < 2 ? 2 : 1; }
@@ -55,19 +52,7 @@ __host__ __device__ constexpr int dect_role_tile(int role) { return role == 0 ? 
 constexpr int DECT_ACC = 8;
 static_assert(dect_slot(0, NBLK) == 8 && dect_slot(1, NBLK) == 8 && dect_slot(2, NBLK) == 7 && dect_slot(3, NBLK) == 7, "tile ownership");
 
-// ---- LDS layout ---------------------------------------------------------------------------------------------------------------
-// [zone: per wave 2 x (XH, DH, XN) step buffers + 3 DN slots = 9 tiles; the forward image overlays it while the forward chain runs]
-// [per wave: C tiles (3), aux tile [8 columns][32 points], dO tile [4][32]] [backward image]
-constexpr int TILE_B = 2048;
-constexpr int ZONE_WAVE = 9 * TILE_B;                           // 18432
-constexpr int ZONE_B = 4 * ZONE_WAVE;                           // 73728 >= DECT_FWD_BYTES
-constexpr int CW_B = 3 * TILE_B + 512 + 256;                    // 6912
-constexpr int LDS_FWD = ZONE_B + 4 * CW_B;                      // 101376: end of the backward's per-wave regions
-constexpr int LDS_BWD = LDS_FWD + (int)DECT_BWD_BYTES;          // 153600
-constexpr int FWD_NW = 8;
-constexpr int LDS_FWD8 = ZONE_B + FWD_NW * CW_B;                // 129024: forward kernel (image in the zone + 8 waves' C tiles)
-static_assert(ZONE_B >= (int)DECT_FWD_BYTES && LDS_BWD <= 160 * 1024, "LDS budget of the bf16 training decoder");
-
+// ---- LDS layout: TILE_B, ZONE_WAVE, ZONE_B, CW_B, LDS_FWD, LDS_BWD, FWD_NW, LDS_FWD8 of giga_dec_bwd_plan.h ----
 // byte address of the 8-byte piece (point p, features 4q .. 4q+3) of a [32][32] bf16 tile: rows of 64 bytes, the pieces of a row
 // permuted by the row PAIR -- the ds_write_b64 of 16 consecutive points with one q and the transposing read of 4 consecutive points
 // x 8 pieces both touch every bank once (profiles/r05/tr16_probe.txt)
@@ -443,14 +428,7 @@ __global__ __launch_bounds__(NW * 64, 1) void dect_kernel(DectArgs a) {
                 tile_write(buf + TILE_B, wa, Hb0, Hb1);
                 tile_write(buf + 2 * TILE_B, wa, XN[blk][0], XN[blk][1]);
                 tile_write(zw + 6 * TILE_B + (blk % 3) * TILE_B, wa, Gb[0], Gb[1]);
-                if (blk == 0 && a.dcbuf && valid) {                      // rows of [P][96] for plane_gather_kernel
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            *reinterpret_cast<float4*>(a.dcbuf + g * 96 + pl * 32 + 8 * q + 4 * hi) =
-                                make_float4(dc[pl][4 * q], dc[pl][4 * q + 1], dc[pl][4 * q + 2], dc[pl][4 * q + 3]);
-                }
+                if (blk == 0 && a.dcbuf && valid) store_row96(a.dcbuf, g, hi, dc);      // rows of [P][96] for plane_gather_kernel
                 DT(7 + 3 * (4 - blk));
                 __syncthreads();
                 DT(8 + 3 * (4 - blk));
@@ -516,10 +494,7 @@ __global__ __launch_bounds__(NW * 64, 1) void dect_kernel(DectArgs a) {
                 const float nx = norm_coord(px), ny = norm_coord(py), nz = norm_coord(pz);
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        *reinterpret_cast<float4*>(T + n * 96 + pl * 32 + 8 * q + 4 * hi) =
-                            make_float4(dc[pl][4 * q], dc[pl][4 * q + 1], dc[pl][4 * q + 2], dc[pl][4 * q + 3]);
+                    store_row96_plane(T, n, hi, pl, dc[pl]);
                     if (hi == 0) {
                         const Bilin bl = bilin_setup(pl == 2 ? ny : nx, pl == 1 ? ny : nz);
                         const int base = (int)(pl * plane_stride + (size_t)bsc * RES * RES * CD);
@@ -651,57 +626,44 @@ __global__ __launch_bounds__(256) void dect_reduce_kernel(DectReduceArgs a) {
     }
 }
 
-// ------------------------------- launchers ---------------------------------------------------------------------------------------
-static int dect_grid(long long P) {
-    const long long tiles = (P + 31) / 32;
-    const long long wgs = (tiles + 3) / 4;
-    return (int)(wgs < 256 ? wgs : 256);
-}
-
+// ------------------------------- launchers (giga_dec_bwd_launch.h) ------------------------------------------------------------
 int launch_dect_forward(const float* planes, const float* p, const uint8_t* blob, int head_mask, float* const* outs, int B, int N,
                         int post, hipStream_t s) {
-    const long long P = (long long)B * N;
-    if (P <= 0 || (head_mask & 15) == 0) return 0;
+    const DecBwdCall c = dec_bwd_call_plan(true, B, N, __builtin_popcount(head_mask & 15), false, false);
+    if (!c.runs) return 0;
     const PackOff ko = pack_offsets();
     DectArgs a{};
-    a.planes = planes; a.p = p; a.B = B; a.N = N; a.P = P; a.invN = 1.0f / (float)N; a.post = post;
+    a.planes = planes; a.p = p; a.B = B; a.N = N; a.P = c.P; a.invN = 1.0f / (float)N; a.post = post;
     for (int h = 0; h < NHEADS; ++h) {
         if (!(head_mask >> h & 1)) continue;
         a.head_id[a.nheads] = h; a.img_fwd[a.nheads] = blob + ko.dect[h]; a.out[a.nheads] = outs[h];
         ++a.nheads;
     }
-    const long long tiles = (P + 31) / 32, wgs = (tiles + FWD_NW - 1) / FWD_NW;
-    giga::dyn_lds_once(reinterpret_cast<const void*>(dect_kernel<false, FWD_NW>), LDS_FWD8);
-    GIGA_LAUNCH((dect_kernel<false, FWD_NW>), dim3((unsigned)(wgs < 256 ? wgs : 256), a.nheads), dim3(FWD_NW * 64), LDS_FWD8, s, a);
+    giga::dyn_lds_once(reinterpret_cast<const void*>(dect_kernel<false, FWD_NW>), c.fwd_lds);
+    GIGA_LAUNCH((dect_kernel<false, FWD_NW>), dim3(c.fwd_grid_x, a.nheads), dim3(c.fwd_block), c.fwd_lds, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
-// scratch of one backward call: the partial tiles of its heads (+ the dc rows when the plane gradient is gathered)
-size_t dect_partial_floats(long long P, int nheads) { return P > 0 ? (size_t)dect_grid(P) * DECT_NTILES * DECT_TILE_FLOATS * nheads : 0; }
-
-// One decoder-backward call on the bf16 kernels.  `scratch` receives the partial tiles (dect_partial_floats) and, with dcrows, the
-// [P][96] rows behind them; the reduce is enqueued by launch_dect_reduce once all calls of the step have run.
-int launch_dect_backward(const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob, int head_mask,
-                         const float* const* outs, const float* const* douts, float* gplanes, float* dcbuf, float* scratch, int B,
-                         int N, hipStream_t s, DectPending* pend) {
-    const long long P = (long long)B * N;
-    if (P <= 0 || (head_mask & 15) == 0) return 0;
+int launch_dect_backward(const DecBwdCall& c, const float* planes, const float* p, const uint8_t* blob, const uint8_t* bwd_blob,
+                         int head_mask, const float* const* outs, const float* const* douts, float* gplanes, float* dcbuf,
+                         float* scratch, int B, int N, hipStream_t s, DectPending* pend) {
+    if (!c.runs) return 0;
     const PackOff ko = pack_offsets();
     const BwdPackOff bo = bwd_pack_offsets();
     DectArgs a{};
-    a.planes = planes; a.p = p; a.B = B; a.N = N; a.P = P; a.invN = 1.0f / (float)N;
+    a.planes = planes; a.p = p; a.B = B; a.N = N; a.P = c.P; a.invN = 1.0f / (float)N;
     a.gplanes = gplanes; a.dcbuf = dcbuf;
-    const int grid = dect_grid(P);
     for (int h = 0; h < NHEADS; ++h) {
         if (!(head_mask >> h & 1)) continue;
         a.head_id[a.nheads] = h; a.img_fwd[a.nheads] = blob + ko.dect[h]; a.img_bwd[a.nheads] = bwd_blob + bo.dect[h];
         a.out[a.nheads] = const_cast<float*>(outs[h]); a.dout[a.nheads] = douts[h];
-        a.partial[a.nheads] = scratch + (size_t)a.nheads * grid * DECT_NTILES * DECT_TILE_FLOATS;
-        pend->partial[pend->n] = a.partial[a.nheads]; pend->nwg[pend->n] = grid; pend->head_id[pend->n] = h; ++pend->n;
+        a.partial[a.nheads] = scratch + c.head_off + a.nheads * c.head_stride;
+        pend->partial[pend->n] = a.partial[a.nheads]; pend->nwg[pend->n] = c.grid_x; pend->head_id[pend->n] = h; ++pend->n;
         ++a.nheads;
     }
-    giga::dyn_lds_once(reinterpret_cast<const void*>(dect_kernel<true, 4>), LDS_BWD);
-    GIGA_LAUNCH((dect_kernel<true, 4>), dim3(grid, a.nheads), dim3(256), LDS_BWD, s, a);
+    if (a.nheads != c.nheads) return -1;                      // (the plan was made for another head set)
+    giga::dyn_lds_once(reinterpret_cast<const void*>(dect_kernel<true, 4>), c.lds);
+    GIGA_LAUNCH((dect_kernel<true, 4>), dim3(c.grid_x, c.grid_y), dim3(c.block), c.lds, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 

@@ -15,14 +15,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "giga_dec_bwd_plan.h"
 #include "giga_layout.h"
 
 namespace giga {
 
-constexpr int DECT_FWD_FRAGS = DEC16_FRAGS;                            // 58
-constexpr size_t DECT_FWD_BYTES = DEC16_BYTES;                         // 59 KiB
-constexpr int DECT_BWD_FRAGS = NBLK * 10;                              // 50
-constexpr size_t DECT_BWD_BYTES = (size_t)(DECT_BWD_FRAGS + 1) * FRAG; // 51 KiB
+// (DECT_FWD_FRAGS / DECT_FWD_BYTES / DECT_BWD_FRAGS / DECT_BWD_BYTES, the sizes of the two images: giga_dec_bwd_plan.h)
 
 // fp32 -> bf16 bits, round to nearest even (v_cvt_pk_bf16_f32 for finite values), and back
 __host__ __device__ inline uint16_t dect_bf(float x) {
@@ -130,10 +128,5 @@ __device__ inline void dect_derive_block(uint8_t* fwd_blob, uint8_t* bwd_blob, i
         }
     }
 }
-
-
-// partial weight-gradient tiles of the fused backward launches of one step, waiting for dect_reduce_kernel (ONE definition for
-// giga_decoder_train16.hip and its caller giga_capi.hip)
-struct DectPending { const float* partial[NHEADS]; int nwg[NHEADS]; int head_id[NHEADS]; int n; };
 
 }  // namespace giga

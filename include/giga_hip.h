@@ -268,6 +268,28 @@ size_t giga_backward_workspace_bytes(int B, int N, int M, int head_present);
  * up0.conv1).  gA6 gA5 gA4 gA3 gS2 gA2 gS1 gA1 gS0 gA0 are, with the ReLU mask already applied, the dY operands of the weight
  * gradients of layers 11, 10, 8, 7, 5, 4, 3, 2, 1, 0.  offsets must have room for 15 entries. */
 int giga_backward_workspace_layout(int B, size_t* offsets);
+/* What the decoder part of giga_backward(..., head_present, B, N, M, ...) would do: which calls run and in which order, every launch
+ * shape and every region of the decoder scratch (csrc/giga_dec_bwd_plan.h; giga_backward and giga_backward_workspace_bytes read the same
+ * plan).  head_present carries giga_backward's flag bits GIGA_DETACH_OCC and GIGA_BF16_DECODER (the others are ignored); an occupancy
+ * head with M > 0 is planned as if p_tsdf were given.  Host only: no device is touched.  Error codes as giga_backward's for the same
+ * arguments: -1 (N < 0, M < 0, NULL plan_words), -7 (B > GIGA_MAX_SCENES); B <= 0: all words zero.
+ * plan_words[GIGA_DECODER_BACKWARD_PLAN_WORDS], in order (struct TrainDecPlan; a 64-bit field is two words, low first):
+ *   bf16, clear_planes (the plane-gradient buffer is cleared first), reduce (dect_reduce_kernel ends the decoder part), launches (kernel
+ *   launches of the decoder part), order[GIGA_DECODER_BACKWARD_MAX_LAUNCHES] (their GIGA_DEC_BWD_KERNEL_*, as enqueued);
+ *   64-bit: occ_base, grasp_base (the calls' scratch bases in floats), scratch_floats (the step's decoder scratch at this precision);
+ *   then the occupancy call and the grasp call, GIGA_DECODER_BACKWARD_CALL_WORDS each (struct DecBwdCall):
+ *   runs, kernel, nheads, planes, gather, nbatch, grid_x, grid_y, block, lds, heads_per_wg, wgrad_merged, wgrad_launches, nb_total,
+ *   ksplit_cap, ksplit, pts_per_block, launches, fwd_grid_x, fwd_block, fwd_lds, bf16;
+ *   64-bit: P, tiles, head_off, head_stride, cbuf_off, pbuf_off, dcbuf_off (floats from the call's base, -1: none), scratch_floats. */
+#define GIGA_DECODER_BACKWARD_MAX_LAUNCHES 8
+#define GIGA_DECODER_BACKWARD_CALL_WORDS 38
+#define GIGA_DECODER_BACKWARD_PLAN_WORDS 94
+#define GIGA_DEC_BWD_KERNEL_DECODER_BWD 1    /* decoder_bwd_kernel */
+#define GIGA_DEC_BWD_KERNEL_PLANE_GATHER 2   /* plane_gather_kernel */
+#define GIGA_DEC_BWD_KERNEL_LINEAR_WGRAD 3   /* linear_wgrad_kernel */
+#define GIGA_DEC_BWD_KERNEL_DECT 4           /* dect_kernel<true, 4> */
+#define GIGA_DEC_BWD_KERNEL_DECT_REDUCE 5    /* dect_reduce_kernel */
+int giga_decoder_backward_plan(int B, int N, int M, int head_present, int32_t* plan_words);
 int giga_backward(const float* tsdf, const void* packed, const void* bwd_packed, const void* enc_workspace_fwd,
                   const void* planes_nhwc, const float* p, const float* p_tsdf, const float* const* outs,
                   const float* const* douts, float* grads, size_t n_params, int head_present, int B, int N, int M,

@@ -61,7 +61,7 @@ CASES = [
 ]
 FAMILIES = ("A", "B")
 FAMILY_C_PIXELS = (0, 12, 15, 18, 24, 27, 30, 33)
-# fp32 only (csrc/giga_decoder_bwd.hip launch_decoder_backward; bwd32_launch below restates its arithmetic)
+# fp32 only (csrc/giga_decoder_bwd.hip launch_decoder_backward; bwd32_launch below reads its plan)
 CASES32_NEW = [
     ((7, False, 32, 340, 0), ("A", "B")),     # 10 880 points, 85 batches: 85 x 3 = 255, the last shape with one workgroup per head
     ((7, False, 32, 341, 0), ("A", "B")),     # 10 912 points, 86 batches: 258 > 256, the first shape where one workgroup walks three heads
@@ -199,50 +199,43 @@ def cells(p):
     return torch.stack([footprint(p, k)[0][0] for k in O.PLANES])
 
 
-# ---- the fp32 backward's launch arithmetic, restated ------------------------------------------------------------------------------
+# ---- the fp32 backward's launch arithmetic, read from the library's plan --------------------------------------------------------
 def xcd_swizzle(i, n):
-    """csrc/giga_dev.h xcd_swizzle (lines 175-178), restated."""
+    """csrc/giga_dev.h xcd_swizzle, restated (kernel arithmetic, not launch policy: no plan holds it)."""
     m = n & ~7
     return (i & 7) * (m >> 3) + (i >> 3) if i < m else i
 
 
-def bwd32_launch(P, nheads, N=0):
-    """What launch_decoder_backward (csrc/giga_decoder_bwd.hip) derives from P points and nheads heads in one call, RESTATED in
-    Python so that the host test can say which regime a case reaches; a restatement, nothing reads the kernels' own values:
-      tiles, nbatch, grid, split      lines 474-478 (decoder_bwd_kernel: 32-point tiles, 4 per batch, at most 256 workgroups,
-                                      one workgroup per head while grid * nheads <= 256)
-      round2                          the batches of the persistent loop's later rounds (lines 73-74: bseq >= grid, xcd_swizzle)
-      nb_total, ksplit_cap, pts_per_block, ksplit, last_block      linear_wgrad_kernel's split over points, lines 488-501 and
-                                      510-523: 27 column blocks per head (81 for two or three merged heads), 2048 / nb_total
-                                      blocks of points, each rounded up to 32 points, then counted again
-      gather                          dec_bwd_writes_planes, line 447, for N points per scene (the caller, giga_backward, also
-                                      asks that the head is not detached: bwd32_calls)"""
-    tiles = (P + 31) // 32
-    nbatch = (tiles + 3) // 4
-    grid = min(nbatch, 256)
-    split = grid * nheads <= 256
-    merged = nheads > 1 and 17 * nheads <= 52
-    nb_total = 27 * (nheads if merged else 1)
-    cap = max(2048 // nb_total, 1)
-    ppb = ((P + cap - 1) // cap + 31) // 32 * 32
-    ksplit = (P + ppb - 1) // ppb
-    return dict(P=P, nheads=nheads, tiles=tiles, nbatch=nbatch, grid=grid, split=split,
+def _bwd32_dict(call):
+    """The fields of one fp32 call of convonet.decoder_backward_plan under the names the tests use; round2 and last_block follow
+    from them: the batches of decoder_bwd_kernel's later persistent rounds (bseq >= grid, through xcd_swizzle) and the points of
+    linear_wgrad_kernel's last block."""
+    P, nbatch, grid, ksplit, ppb = call["P"], call["nbatch"], call["grid_x"], call["ksplit"], call["pts_per_block"]
+    return dict(P=P, nheads=call["nheads"], tiles=call["tiles"], nbatch=nbatch, grid=grid, split=call["heads_per_wg"] == 1,
                 round2=sorted(xcd_swizzle(i, nbatch) for i in range(grid, nbatch)),
-                nb_total=nb_total, ksplit_cap=cap, pts_per_block=ppb, ksplit=ksplit, last_block=P - (ksplit - 1) * ppb,
-                gather=nheads == 1 and 256 <= N <= 4096)
+                nb_total=call["nb_total"], ksplit_cap=call["ksplit_cap"], pts_per_block=ppb, ksplit=ksplit,
+                last_block=P - (ksplit - 1) * ppb, gather=call["gather"])
+
+
+def bwd32_launch(P, nheads, N=0):
+    """What launch_decoder_backward (csrc/giga_decoder_bwd.hip) launches for P points and nheads heads in one call, as the
+    library's plan says (csrc/giga_dec_bwd_plan.h dec_bwd_call_plan, through convonet.decoder_backward_plan: host only, the built
+    library and no device): tiles, nbatch, grid, split (one workgroup per head), nb_total, ksplit_cap, pts_per_block, ksplit.
+    N > 0: the call is the occupancy call of P / N scenes, which may write the planes -- gather is the plan's rule for it (the
+    caller, giga_backward, also asks that the head is not detached: bwd32_calls); else a grasp call, which never gathers."""
+    from giga_amd import convonet
+    if N:
+        assert nheads == 1 and P % N == 0
+        return _bwd32_dict(convonet.decoder_backward_plan(P // N, 0, N, 8)["occ"])
+    return _bwd32_dict(convonet.decoder_backward_plan(1, P, 0, (1 << nheads) - 1)["grasp"])
 
 
 def bwd32_calls(case):
-    """{'occ' / 'grasp': bwd32_launch of the call} as giga_backward (csrc/giga_capi.hip) makes them for a case."""
+    """{'occ' / 'grasp': the fp32 calls giga_backward (csrc/giga_capi.hip) makes for a case, from its plan}."""
+    from giga_amd import _capi, convonet
     hp, detach, B, N, M = case
-    calls = {}
-    if hp & 8 and M > 0:
-        calls["occ"] = bwd32_launch(B * M, 1, M)
-        calls["occ"]["gather"] &= not detach
-    if hp & 7 and N > 0:
-        calls["grasp"] = bwd32_launch(B * N, bin(hp & 7).count("1"), N)
-        calls["grasp"]["gather"] = False                     # (the grasp call never asks for it)
-    return calls
+    plan = convonet.decoder_backward_plan(B, N, M, hp | (_capi.DETACH_OCC if detach else 0))
+    return {name: _bwd32_dict(plan[name]) for name in ("occ", "grasp") if plan[name]["runs"]}
 
 
 # ---- reference -----------------------------------------------------------------------------------------------------------------
@@ -390,7 +383,7 @@ def flat_params(sd, hp):
     return torch.cat([sd[k].reshape(-1).float() for k in shapes]), shapes
 
 
-def run_decoder(sd, hp, detach, x, pos, pos_occ, douts, planes=None, dev=None, precision="bf16"):
+def run_decoder(sd, hp, detach, x, pos, pos_occ, douts, planes=None, dev=None, precision="bf16", around_backward=None):
     """One training step's decoder calls on the C entry points as training.GigaFunction drives them, on the host packer's blobs:
     giga_encoder_forward (fp32, so that the backward has its workspace), then -- with `planes` (3, B, 40, 40, 32), they replace
     the encoder's -- giga_decoder_forward (raw outputs of every head, then the training call) and giga_backward:
@@ -398,7 +391,8 @@ def run_decoder(sd, hp, detach, x, pos, pos_occ, douts, planes=None, dev=None, p
       "fp32"  the decoders at precision 0, the backward with CONVIN_MASK_BWD (+ DETACH_OCC) alone (csrc/giga_decoder_bwd.hip), and
               `qual`'s forward output replaced by 0.5 in what the backward reads (sigmoid' = 1/4 exactly: see the module docstring).
     Returns {name: CPU tensor}: raw/<head>, out/<head> (what the training call returned), grad/<param> of every decoder parameter,
-    gplanes (3, B, 40, 40, 32) and planes (what the decoders sampled)."""
+    gplanes (3, B, 40, 40, 32) and planes (what the decoders sampled).  around_backward(call): runs instead of the one giga_backward
+    call; call() enqueues giga_backward on the same buffers and waits for it, as often as it is asked to."""
     assert precision in PRECISIONS
     from giga_amd import _capi
     L = _capi.lib()
@@ -456,10 +450,14 @@ def run_decoder(sd, hp, detach, x, pos, pos_occ, douts, planes=None, dev=None, p
         flags = hp | _capi.CONVIN_MASK_BWD | (_capi.DETACH_OCC if detach else 0)
         if precision == "bf16":
             flags |= _capi.BF16_DECODER | _capi.BF16_CONVS
-        _capi.check(L.giga_backward(_capi.ptr(xd), _capi.ptr(blob), _capi.ptr(bblob), _capi.ptr(ws), _capi.ptr(nhwc), _capi.ptr(p),
-                                    _capi.ptr(pt), arr_o, arr_d, _capi.ptr(grads), grads.numel(), flags, B, N, M, _capi.ptr(wsb),
-                                    wsb.numel(), s), "giga_backward")
-        torch.cuda.synchronize(dev)
+
+        def backward():
+            _capi.check(L.giga_backward(_capi.ptr(xd), _capi.ptr(blob), _capi.ptr(bblob), _capi.ptr(ws), _capi.ptr(nhwc), _capi.ptr(p),
+                                        _capi.ptr(pt), arr_o, arr_d, _capi.ptr(grads), grads.numel(), flags, B, N, M, _capi.ptr(wsb),
+                                        wsb.numel(), s), "giga_backward")
+            torch.cuda.synchronize(dev)
+
+        (around_backward or (lambda call: call()))(backward)
         gc, at = grads.cpu(), 0
         for k, shp in shapes.items():
             n = int(np.prod(shp))

@@ -14,6 +14,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dect_exact as X  # noqa: E402
 import ref64  # noqa: E402
+from giga_amd import _capi, convonet  # noqa: E402
 
 
 # A call of ONE point has rank-one weight gradients dY (x) X, whose density is the product of the two vectors' densities: dY of
@@ -71,9 +72,10 @@ SENSITIVITY_CASES = [X.CASES[2], X.CASES[3], X.CASES[11]]   # 129 ragged points 
 
 
 def _last_workgroup(P):
-    """Points of workgroup nwg - 1 under the kernel's tile_lo / tile_hi split (dect_kernel, dect_grid)."""
-    tiles = (P + 31) // 32
-    nwg = min((tiles + 3) // 4, 256)
+    """Points of workgroup nwg - 1 under the kernel's tile_lo / tile_hi split (dect_kernel), nwg the bf16 call's grid_x in the
+    library's plan."""
+    call = convonet.decoder_backward_plan(1, P, 0, 1 | _capi.BF16_DECODER)["grasp"]
+    tiles, nwg = call["tiles"], call["grid_x"]
     return torch.arange(32 * (tiles * (nwg - 1) // nwg), P)
 
 
@@ -233,7 +235,7 @@ def _long_cells(p):
 
 
 def test_the_fp32_cases_reach_every_launch_regime():
-    """With the launch arithmetic restated in dect_exact.bwd32_launch: the regimes of launch_decoder_backward that the table is for."""
+    """With the library's plan (dect_exact.bwd32_calls): the regimes of launch_decoder_backward that the table is for."""
     calls = [(cf, name, L) for cf in X.CASES32 for name, L in X.bwd32_calls(cf[0]).items()]
     several = [L for _, _, L in calls if L["nheads"] > 1]
     assert any(L["split"] for L in several) and any(not L["split"] for L in several)            # both sides of the head split ...
