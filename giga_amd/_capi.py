@@ -27,6 +27,7 @@ PERSIST_UNET = 32        # GIGA_PERSIST_UNET: OR-ed into `precision` of an encod
 LAYERWISE_UNET = 64      # GIGA_LAYERWISE_UNET: one launch per U-Net layer even for small batches
 CONV32_UNET = 128        # GIGA_CONV32_UNET: the f16-class U-Net on the conv32 kernels (the library's default)
 CONV16_UNET = 256        # GIGA_CONV16_UNET: ... on the conv16 kernels
+ENCODER_PLAN_NO_SLOT = 2048      # GIGA_ENCODER_PLAN_NO_SLOT: giga_encoder_plan only, the plan of a call that finds no room for a persistent launch
 DIRECT_CONV = 1024       # GIGA_DIRECT_CONV: precision 0 keeps the direct 3x3 convolutions (default: Winograd F(2x2, 3x3), csrc/giga_wino.h)
 PATH_PERSISTENT, PATH_CONV32, PATH_FUSED_PAIRS, PATH_WINOGRAD = 1, 2, 4, 8          # giga_encoder_last_path()
 BWD_PATH_PERSISTENT, BWD_PATH_WINOGRAD, BWD_PATH_BF16 = 1, 2, 4                      # giga_backward_last_path()
@@ -147,6 +148,7 @@ _SIGNATURES = {
                                                     ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_void_p]),
     "giga_decoder_plan": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_void_p]),
+    "giga_encoder_plan": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.c_void_p]),
     "giga_decoder_backward_plan": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.c_void_p]),
     "giga_grasp_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "giga_grasp_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

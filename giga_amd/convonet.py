@@ -228,6 +228,50 @@ _ENCODER_NUMEL = 476800
 # ------------------------------------------------------------------------------------------------
 # encoder
 # ------------------------------------------------------------------------------------------------
+def encoder_precision_word(prec, fold_final=False, persistent=False, unet_kernel="auto", convin_mask=False):
+    """The `precision` argument of giga_encoder_forward* and giga_encoder_plan: the encoder's code `prec` (0 fp32, 1 f16, 2 f16x3,
+    3 bf16) with the call's flags (include/giga_hip.h).  persistent: False (the library decides), True, or "layers"; unet_kernel:
+    "auto", "conv32" / "conv16" (precisions 1 and 2) or "direct" (precision 0)."""
+    return (prec | (_capi.FOLD_FINAL if fold_final else 0) |
+            {False: 0, True: _capi.PERSIST_UNET, "layers": _capi.LAYERWISE_UNET}[persistent] |
+            ({"conv32": _capi.CONV32_UNET, "conv16": _capi.CONV16_UNET}.get(unet_kernel, 0) if prec in (1, 2) else 0) |
+            (_capi.DIRECT_CONV if prec == 0 and unet_kernel == "direct" else 0) |
+            (_capi.CONVIN_MASK if convin_mask else 0))
+
+
+# struct EncPlan of csrc/giga_enc_plan.h, in the order giga_encoder_plan writes it; `layers` stands for layer_kernel[13]
+ENCODER_PLAN_FIELDS = ("nimg", "nlayers", "nxp", "ci_f16", "ci_lo", "ci_mask", "ci_sxw", "ci_nw", "ci_grid_x", "ci_grid_y", "ci_grid_z",
+                       "ci_block", "fin_grid", "fin_block", "form", "persistent", "conv32", "fused", "wino_mask", "groups", "grid", "block",
+                       "layers", "launches", "path")
+ENCODER_FORMS = (None, "layers_conv16", "layers_conv32", "persistent_conv16", "persistent_winograd", "persistent_conv32")   # GIGA_ENC_FORM_*
+ENCODER_LAYER_KERNELS = ("none", "conv16", "conv32", "winograd", "up_gemm")                                                # GIGA_ENC_LAYER_*
+ENCODER_PLAN_WORDS = len(ENCODER_PLAN_FIELDS) - 1 + 13
+
+
+def encoder_plan(B, precision, *, fold_final=False, persistent=False, unet_kernel="auto", convin_mask=False, cus=256, probe_stage=-1,
+                 slot_free=True):
+    """What an encoder call of B scenes would launch now (giga_encoder_plan; host only, GIGA_WINOGRAD and GIGA_C32_FUSE are read as
+    a launch reads them): `precision` a name of _capi.PRECISION or the encoder's code 0..3, the keywords as `encode_nhwc` and
+    `set_persistent_unet` / `set_unet_kernel` take them, `cus` the compute units of the device, `probe_stage` the stage a probe would
+    bracket.  slot_free=False: the plan of a call that finds four other persistent launches in flight (one launch per layer).
+    A dict of ENCODER_PLAN_FIELDS: `form` as a name of ENCODER_FORMS (None: nothing is launched), `layers` as 13 names of
+    ENCODER_LAYER_KERNELS, the flags as bools, `path` the word giga_encoder_last_path() reports after such a call."""
+    prec = _capi.ENCODER_PRECISION[_capi.PRECISION[precision]] if isinstance(precision, str) else precision
+    word = encoder_precision_word(prec, fold_final, persistent, unet_kernel, convin_mask) | (0 if slot_free else _capi.ENCODER_PLAN_NO_SLOT)
+    words = (ctypes.c_int32 * ENCODER_PLAN_WORDS)()
+    _capi.check(_capi.lib().giga_encoder_plan(B, word, cus, probe_stage, words), "giga_encoder_plan")
+    words = list(words)
+    at = ENCODER_PLAN_FIELDS.index("layers")
+    plan = dict(zip(ENCODER_PLAN_FIELDS[:at], words[:at]))
+    plan["layers"] = [ENCODER_LAYER_KERNELS[k] for k in words[at:at + 13]]
+    plan.update(zip(ENCODER_PLAN_FIELDS[at + 1:], words[at + 13:]))
+    plan["form"] = ENCODER_FORMS[plan["form"]]
+    plan["wino_mask"] &= 0xFFFFFFFF
+    for flag in ("ci_f16", "ci_lo", "ci_mask", "persistent", "conv32", "fused"):
+        plan[flag] = bool(plan[flag])
+    return plan
+
+
 class LocalVoxelEncoder(nn.Module):
     """voxels.py:10-121.  forward(x:(B,40,40,40)) -> {'xz','xy','yz': (B,32,40,40)} (PlaneDict)."""
 
@@ -276,10 +320,8 @@ class LocalVoxelEncoder(nn.Module):
             raise ValueError("fold_final planes are an internal representation; the reference layout needs the final planes")
         with torch.cuda.device(x.device):      # launch on the tensors' device and ITS current stream, whatever torch's current device is
             _capi.check(L.giga_encoder_forward_probe(_capi.ptr(x), _capi.ptr(blob), _capi.ptr(nhwc), _capi.ptr(nchw),
-                                                     B, prec | (_capi.FOLD_FINAL if fold_final else 0) |
-                                                     {False: 0, True: _capi.PERSIST_UNET, "layers": _capi.LAYERWISE_UNET}[getattr(self, "persistent_unet", False)] |
-                                                     ({"conv32": _capi.CONV32_UNET, "conv16": _capi.CONV16_UNET}.get(getattr(self, "unet_kernel", "auto"), 0) if prec in (1, 2) else 0) |
-                                                     (_capi.DIRECT_CONV if prec == 0 and getattr(self, "unet_kernel", "auto") == "direct" else 0),
+                                                     B, encoder_precision_word(prec, fold_final, getattr(self, "persistent_unet", False),
+                                                                               getattr(self, "unet_kernel", "auto")),
                                                      _capi.ptr(ws), ws.numel(), _capi.stream_ptr(x.device),
                                                      stage, ev0, ev1),
                         "giga_encoder_forward")

@@ -8,10 +8,6 @@
 
 namespace giga {
 
-// every per-call flag OR-ed into `precision` of giga_encoder_forward* (include/giga_hip.h); what is left is the precision 0..3
-constexpr int GIGA_ENCODER_FLAGS = GIGA_FOLD_FINAL | GIGA_PERSIST_UNET | GIGA_LAYERWISE_UNET | GIGA_CONV32_UNET | GIGA_CONV16_UNET |
-                                   GIGA_CONVIN_MASK | GIGA_DIRECT_CONV;
-
 struct DecArgs {
     const void* planes;      // [3][B][40][40][32]  (plane, scene, H, W, C)  half or float
     const float* p;          // [P][3]
@@ -30,13 +26,6 @@ struct DecArgs {
     float invN;              // 1 / N
     unsigned mR, mR2;        // ceil(2^32 / R), ceil(2^32 / R^2)   (lattice mode)
     int lat_parts;           // decoder_lat_kernel: a slab (scene, ix) is handed out in this many parts (tile ranges): small batches
-};
-
-// Byte offsets of the encoder's activations inside its caller-allocated workspace (giga_encoder.hip::enc_workspace).
-struct EncWs {
-    size_t P0, A0, S0, Q0, A1, S1, Q1, A2, S2, U0, A3, A4, U1, A5, A6, YZ, XZ, total;   // XZ unused (kept for the ABI)
-    size_t SYNC;               // barrier counter + timeout flag of the persistent U-Net kernel
-    size_t MASK;               // conv_in ReLU mask of a training forward (GIGA_CONVIN_MASK): [B][8][40][64 lanes] x 16 bytes
 };
 
 // gradient workspace of the encoder backward (giga_encoder_bwd.hip carves it, giga_capi.hip sizes the caller's buffer with it): ONE

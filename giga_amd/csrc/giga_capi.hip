@@ -14,6 +14,7 @@
 #include "giga_conv32_geom.h"
 #include "giga_dect.h"
 #include "giga_args.h"
+#include "giga_enc_plan.h"
 #include "giga_side.h"
 #include "giga_dec_bwd_launch.h"
 
@@ -32,7 +33,6 @@ int launch_encoder_backward(const float* tsdf, const uint8_t* blob, const uint8_
                             float* gplanes, uint8_t* gws, float* grads, int head_present, int B, hipStream_t s, bool bf16_convs, bool convin_mask,
                             SideScope& side);
 // giga_encoder.hip
-EncWs enc_workspace(int B, int precision);
 int launch_encoder(const float* tsdf, const uint8_t* blob, void* planes_nhwc, float* planes_nchw, int B,
                    int precision, uint8_t* ws, hipStream_t s, int probe_stage, void* ev0, void* ev1);
 }  // namespace giga
@@ -291,14 +291,13 @@ int giga_repack_device(const float* params_dev, const int32_t* map_dev, void* pa
 }
 
 size_t giga_encoder_workspace_bytes(int B, int precision) {
-    precision &= ~GIGA_ENCODER_FLAGS;
     if (B <= 0) return 0;
-    return enc_workspace(B, precision).total;
+    return enc_workspace(B, enc_call_from_flags(precision).precision).total;
 }
 
 int giga_encoder_workspace_layout(int B, int precision, size_t* offsets) {
     if (B <= 0 || !offsets) return -1;
-    precision &= ~GIGA_ENCODER_FLAGS;
+    precision = enc_call_from_flags(precision).precision;
     if (precision < 0 || precision > 3) return -5;
     const EncWs w = enc_workspace(B, precision);
     const size_t v[17] = {w.P0, w.A0, w.S0, w.Q0, w.A1, w.S1, w.Q1, w.A2, w.S2, w.U0, w.A3, w.A4, w.U1, w.A5, w.A6,
@@ -307,24 +306,45 @@ int giga_encoder_workspace_layout(int B, int precision, size_t* offsets) {
     return 0;
 }
 
+// the checks of an encoder call that need no pointer: giga_encoder_forward_probe and giga_encoder_plan answer alike
+static int enc_call_check(int B, const EncCall& c) {
+    if (B > GIGA_MAX_SCENES) return -7;
+    if (c.precision < 0 || c.precision > 3) return -5;
+    // only the fp32 and bf16 encoders store conv_in's ReLU mask: a precision 1 / 2 forward that claims to would leave giga_backward
+    // (GIGA_CONVIN_MASK_BWD) reading workspace bytes nobody wrote
+    if (c.convin_mask && (c.precision == 1 || c.precision == 2)) return -5;
+    return 0;
+}
+
 int giga_encoder_forward_probe(const float* tsdf, const void* packed, void* planes_nhwc, float* planes_nchw,
                                int B, int precision, void* workspace, size_t workspace_bytes, void* stream,
                                int probe_stage, void* ev_start, void* ev_stop) {
     if (B < 0 || (B > 0 && (!tsdf || !packed || !planes_nhwc || !workspace))) return -1;
-    if (B > GIGA_MAX_SCENES) return -7;
-    const bool fold = (precision & GIGA_FOLD_FINAL) != 0;     // stop before conv_final (folded decoder images)
-    const int persist = precision & (GIGA_PERSIST_UNET | GIGA_LAYERWISE_UNET | GIGA_CONV32_UNET | GIGA_CONV16_UNET | GIGA_CONVIN_MASK | GIGA_DIRECT_CONV);   // U-Net launch form and kernels (see the header)
-    precision &= ~GIGA_ENCODER_FLAGS;
-    if (precision < 0 || precision > 3) return -5;
-    // only the fp32 and bf16 encoders store conv_in's ReLU mask: a precision 1 / 2 forward that claims to would leave giga_backward
-    // (GIGA_CONVIN_MASK_BWD) reading workspace bytes nobody wrote
-    if ((persist & GIGA_CONVIN_MASK) && (precision == 1 || precision == 2)) return -5;
-    if (fold && planes_nchw) return -1;                       // the reference-layout copy is the FINAL planes only
-    if (workspace_bytes < giga_encoder_workspace_bytes(B, precision)) return -4;
-    return launch_encoder(tsdf, static_cast<const uint8_t*>(packed), planes_nhwc, planes_nchw, B,
-                          precision | (fold ? GIGA_FOLD_FINAL : 0) | persist,
+    const EncCall call = enc_call_from_flags(precision);
+    if (const int rc = enc_call_check(B, call)) return rc;
+    if (call.fold_final && planes_nchw) return -1;            // the reference-layout copy is the FINAL planes only
+    if (workspace_bytes < giga_encoder_workspace_bytes(B, call.precision)) return -4;
+    return launch_encoder(tsdf, static_cast<const uint8_t*>(packed), planes_nhwc, planes_nchw, B, precision,
                           static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream), probe_stage,
                           ev_start, ev_stop);
+}
+
+/* host only: the plan an encoder call of these arguments would get now on a device of `cus` compute units, environment knobs included
+   (giga_enc_plan.h) */
+int giga_encoder_plan(int B, int precision_word, int cus, int probe_stage, int32_t* plan_words) {
+    static_assert(ENC_PLAN_WORDS == GIGA_ENCODER_PLAN_WORDS && sizeof(int) == sizeof(int32_t), "the plan's words are the header's");
+    static_assert(ENC_FORM_LAYERS_CONV16 == GIGA_ENC_FORM_LAYERS_CONV16 && ENC_FORM_LAYERS_CONV32 == GIGA_ENC_FORM_LAYERS_CONV32 &&
+                  ENC_FORM_PERSIST_CONV16 == GIGA_ENC_FORM_PERSIST_CONV16 && ENC_FORM_PERSIST_WINO == GIGA_ENC_FORM_PERSIST_WINO &&
+                  ENC_FORM_PERSIST_CONV32 == GIGA_ENC_FORM_PERSIST_CONV32 && ENC_LAYER_CONV16 == GIGA_ENC_LAYER_CONV16 &&
+                  ENC_LAYER_CONV32 == GIGA_ENC_LAYER_CONV32 && ENC_LAYER_WINO == GIGA_ENC_LAYER_WINO && ENC_LAYER_UP == GIGA_ENC_LAYER_UP &&
+                  (GIGA_ENCODER_PLAN_NO_SLOT & GIGA_ENCODER_FLAGS) == 0, "the form and family ids are the header's");
+    if (B < 0 || !plan_words) return -1;
+    const bool slot_free = !(precision_word & GIGA_ENCODER_PLAN_NO_SLOT);
+    const EncCall call = enc_call_from_flags(precision_word & ~GIGA_ENCODER_PLAN_NO_SLOT);
+    if (const int rc = enc_call_check(B, call)) return rc;
+    const EncPlan pl = enc_plan(call, B, cus > 0 ? cus : ENC_FULL_DEVICE_CUS, probe_stage, slot_free, enc_knobs_from_env());
+    memcpy(plan_words, &pl, sizeof pl);
+    return 0;
 }
 
 int giga_encoder_forward(const float* tsdf, const void* packed, void* planes_nhwc, float* planes_nchw, int B,

@@ -3,6 +3,7 @@
 #pragma once
 #include <type_traits>
 #include "giga_dev.h"
+#include "giga_enc_plan.h"
 
 namespace giga {
 
@@ -46,16 +47,8 @@ __device__ __forceinline__ f32x4v mfma16_16_bf(bf16x8 a, bf16x8 b, f32x4v c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-constexpr int CONV_NW = 12;       // waves per workgroup (3 per SIMD; VGPR use is < 80)
-
-// Groups of the persistent U-Net launches (giga_encoder.hip) and of conv32's per-layer launches: 8 workgroups on one XCD each
-constexpr int MEGA_GROUP = 8;                     // workgroups per group
-constexpr int MEGA_SLOTS = 4;                     // group slots per XCD at most: 8 x 4 x 8 = 256 workgroups, one per CU
-inline int mega_groups(int nimg) {                // groups of a launch: 8 (one per XCD) per slot, a slot per 8 images
-    const int slots = (nimg + 7) / 8 < MEGA_SLOTS ? (nimg + 7) / 8 : MEGA_SLOTS;
-    return 8 * slots;
-}
-// group q of nq: a contiguous, balanced share of the images (group 0 is never empty)
+// (CONV_NW, the waves per workgroup, and the groups of the persistent launches -- MEGA_GROUP, MEGA_SLOTS, mega_groups -- are
+//  giga_enc_plan.h's.)  Group q of nq: a contiguous, balanced share of the images (group 0 is never empty)
 __device__ __forceinline__ void mega_group_images(int q, int nq, int nimg, int& img0, int& per) {
     img0 = (q * nimg + nq - 1) / nq;
     per = ((q + 1) * nimg + nq - 1) / nq - img0;

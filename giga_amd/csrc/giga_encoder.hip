@@ -7,14 +7,13 @@
 // 32x40^3 feature volume (8.2 MB/scene in the reference) is never written to memory.  Kernel 2
 // (conv16_kernel) is one LDS-staged implicit-GEMM convolution used for every U-Net layer.
 #include <atomic>
-#include <cstdlib>
 
 #include "../../include/giga_hip.h"
 #include "giga_dev.h"
 #include "giga_conv16.h"
 #include "giga_conv32.h"
 #include "giga_wino.h"
-#include "giga_args.h"
+#include "giga_enc_plan.h"
 
 namespace giga {
 
@@ -412,46 +411,14 @@ __global__ void plane_finalize_kernel(const float* __restrict__ xz_partial, cons
     }
 }
 
-// ----------------------------------------------------------------------------------------------------
-// Encoder driver.  Workspace carve (all NHWC, element type T):
-//   P0 planes_in [3B,40,40,32] | A0 | S0 (skip 0) | Q0 [3B,20,20,32] | A1 [..,20,20,64] | S1 | Q1 [..,10,10,64]
-//   | A2 [..,10,10,128] | S2 | U0 [..,20,20,64] | A3 | A4 | U1 [..,40,40,32] | A5 | A6 | YZ partials fp32
-// ----------------------------------------------------------------------------------------------------
-// x-parts of conv_in+project: 1 (8*B workgroups, five slices per wave) from 32 scenes up, else 5 (40*B workgroups)
-int enc_nxp(int B) { return B >= 32 ? 1 : 5; }
-// words of MegaArgs::sync (below), carved here: the barrier words of the persistent U-Net kernels, 8 per-XCD + 32 per-group counters, 128 B apart
-constexpr int MEGA_SYNC_WORDS = (8 + 32) * 32;
-
-EncWs enc_workspace(int B, int precision) {
-    const size_t es = precision == 1 ? 2 : 4;
-    const size_t n = 3 * (size_t)B;
-    EncWs w{};
-    size_t at = 0;
-    auto take = [&](size_t elems, size_t esz) { size_t o = at; at += align_up(elems * esz, 256); return o; };
-    auto in = [&](int l) { return take(n * conv_in_elems(l), es); };        // layer l's input, output, pooled output (kConv)
-    auto out = [&](int l) { return take(n * conv_out_elems(l), es); };
-    auto pool = [&](int l) { return take(n * conv_pool_elems(l), es); };
-    w.P0 = in(0);   w.A0 = out(0);  w.S0 = out(1);
-    w.Q0 = pool(1); w.A1 = out(2);  w.S1 = out(3);
-    w.Q1 = pool(3); w.A2 = out(4);  w.S2 = out(5);
-    w.U0 = out(6);  w.A3 = out(7);  w.A4 = out(8);
-    w.U1 = out(9);  w.A5 = out(10); w.A6 = out(11);
-    // conv_in's partials and its mask are not U-Net tensors: their sizes are conv_in's (40^2 pixels x 32 channels per scene, not per image)
-    w.YZ = take((size_t)(4 + enc_nxp(B)) * B * 1600 * 32, 4);   // 4 xz partials (iy-groups) + NXP yz partials (x-parts)
-    w.XZ = w.YZ;
-    w.SYNC = take(MEGA_SYNC_WORDS * 4, 4); // barrier counters of the persistent U-Net kernel (8 per-XCD + 32 per-group, 128 B apart)
-    w.MASK = take((size_t)B * 8 * RES * 64 * 4, 4);   // conv_in ReLU mask (training forward with GIGA_CONVIN_MASK; 10 MB at 32 scenes)
-    w.total = at;
-    return w;
-}
-
+// (The workspace carve -- EncWs, enc_workspace -- and the launch policy of the driver at the end of this file are giga_enc_plan.h's.)
 
 // ====================================================================================================
 // Persistent U-Net kernel: all 12 (13) layers of UNet.forward (encoder/unet.py:225-239) in ONE launch.
 //   At 32 scenes a U-Net layer is 10-55 us of which ~7 us is per-launch floor (dispatch gap, the weight fill into LDS, the
 //   first patch round trip, the tail) -- 13 launches, i.e. ~90 us of a 200-420 us encoder that no per-layer tuning removes.
 //   This is the DEFAULT form of the U-Net (every batch size in the f16-class modes, from 8 scenes up in fp32 / bf16; see
-//   encoder_run): workgroups stay resident and walk the layers, grouped by eight inside one XCD; between two layers there is
+//   giga_enc_plan.h::enc_plan): workgroups stay resident and walk the layers, grouped by eight inside one XCD; between two layers there is
 //   a barrier among the eight workgroups of a group only, and the NEXT layer's weight group is already streaming into LDS
 //   (LDS-DMA) while the workgroup waits at that barrier.
 //   The layer bodies are the conv16 stages (giga_conv16.h) and, in exact fp32, the Winograd stages (giga_wino.h), unchanged:
@@ -469,7 +436,7 @@ EncWs enc_workspace(int B, int precision) {
 #define GIGA_UNET_ROW(X, l, NB, NB16) \
     X(l, kConv[l].kind, kConv[l].cin0, kConv[l].cin1, kConv[l].cout, kConv[l].H, kConv[l].W, NB, kConv[l].pool, NB16)
 // the range guards of launch_wino (giga_wino.h) hold for every 3x3 layer at the largest call the C ABI admits, with dense strides:
-// the persistent kernel calls wino_run directly (encoder_run passes cs = 0), so launch_wino's run-time check never sees it
+// the persistent kernel calls wino_run directly (unet_table leaves cs = 0), so launch_wino's run-time check never sees it
 #define X(l, KIND, C0, C1, COUT, H, W, NB, POOL, NB16) \
     static_assert(KIND != CONV3 || wino_range_ok(C0, C1, COUT, H, W, 3 * GIGA_MAX_SCENES, 0, 0), \
                   "wino_run's 32-bit offsets / 2 GiB sentinel at 3 * GIGA_MAX_SCENES images");
@@ -502,8 +469,6 @@ struct MegaArgs {
     int nlayers;               // 12 (conv_final folded into the decoder) or 13
     unsigned wino_mask;        // bit l: layer l (a 3x3 layer of the exact-fp32 path) runs as Winograd F(2x2, 3x3) (giga_wino.h)
 };
-constexpr int MEGA_GROUP_MAX_IMG = 32;            // default form of the f16-class modes up to 32 images (one image per group)
-constexpr int MEGA_NW = CONV_NW;                  // waves per workgroup of the persistent kernel
 // A barrier wait is bounded by WALL CLOCK (s_memrealtime, 100 MHz): 20 s.  A group's partners can be late for honest reasons -- a long
 // kernel of another stream holding the CUs they need -- and a spin COUNT (rounds 2-3: 2^24 polls, a few seconds) does not
 // distinguish that from a group that can never fill.
@@ -814,239 +779,199 @@ void persistent_forget() {
     }
 }
 
-// probe: if probe_stage == k, ev0/ev1 (hipEvent_t) are recorded right before / after launch k
-// (k = 0 conv_in+project, 1 plane_finalize, 2..14 = U-Net layers 0..12).
-struct Probe { int stage; hipEvent_t ev0, ev1; };
+// probe: if probe_stage == k, ev0 / ev1 are recorded right before / after launch k (k = 0 conv_in+project, 1 plane_finalize,
+// 2..14 = U-Net layers 0..12, 15 = the whole U-Net; a folded layer that is not launched brackets nothing)
+struct Probe {
+    int stage; hipEvent_t ev0, ev1; hipStream_t s;
+    void pre(int k) const { if (stage == k) (void)hipEventRecord(ev0, s); }
+    void post(int k) const { if (stage == k) (void)hipEventRecord(ev1, s); }
+};
 
 // what the last encoder call of this process ran its U-Net on (giga_encoder_last_path: tests pin the kernel-choice flags to it)
 static std::atomic<int> g_last_unet_path{0};
 
-template <typename T, int MATH = MATH_NATIVE>
-static int encoder_run(const float* tsdf, const uint8_t* blob, void* planes_nhwc, float* planes_nchw, int B,
-                       uint8_t* ws, hipStream_t s, const Probe& pr, bool fold_final, int persist, int conv32, bool keep_mask = false,
-                       unsigned wino_req = 0) {
-    constexpr bool SPLIT = MATH == MATH_SPLIT;
-    int stage_no = 0;
-    auto pre = [&]() { if (pr.stage == stage_no) (void)hipEventRecord(pr.ev0, s); };
-    auto post = [&]() { if (pr.stage == stage_no) (void)hipEventRecord(pr.ev1, s); ++stage_no; };
-    constexpr int precision = sizeof(T) == 2 ? 1 : 0;
+using TT = std::true_type; using FF = std::false_type;
+// conv_in + projection: the instantiation the plan names.  The operand image (convin_ws) of the f16 forms is rebuilt on the device with
+// the other derived images (giga_derive_bf16_fragments).
+template <typename T>
+static void launch_convin(const EncPlan& pl, const float* tsdf, const uint8_t* blob, T* P0, float* XZP, float* YZP, int B, uint4* mask_out,
+                          hipStream_t s) {
     const PackOff ko = pack_offsets();
-    const EncWs w = enc_workspace(B, precision);
-    T* P0 = reinterpret_cast<T*>(ws + w.P0);
-    const size_t per = (size_t)B * RES * RES * CD;
-    float* XZP = reinterpret_cast<float*>(ws + w.YZ);
-    float* YZP = XZP + 4 * per;
-    const int nxp = enc_nxp(B);
-    // conv_in arithmetic: fp32 MFMA (precision 0), the f16 MFMA with hi only (plain f16) or with f16x3 split operands (precision 2).
-    // The bf16 training forward (MATH_BF16): PLAIN f16 operands when it also stores the ReLU mask for the backward (GIGA_CONVIN_MASK:
-    // the backward then uses the forward's own decisions; f16's 11 bits are finer than the bf16 rounding the next layer applies to
-    // this kernel's output; -17 us per step against the split form), else the f16x3 form -- fp32-grade (<= 1e-5 of the fp32 kernel),
-    // so that a backward that RECOMPUTES the mask in fp32 agrees with it.  The operand image (convin_ws) is rebuilt on the device with
-    // the other derived images (giga_derive_bf16_fragments).
-    uint4* mask_out = keep_mask ? reinterpret_cast<uint4*>(ws + w.MASK) : nullptr;
-    auto run_convin = [&](auto f16c, auto lo, auto msk) {
+    const float* cb = reinterpret_cast<const float*>(blob + ko.convin_b);
+    auto go = [&](auto sxw, auto f16c, auto lo, auto msk) {
+        constexpr int SXW = decltype(sxw)::value, XW = SXW * CI_NW;
         constexpr bool CI_F16 = decltype(f16c)::value, CI_LO = decltype(lo)::value, MK = decltype(msk)::value;
         const float* cw = reinterpret_cast<const float*>(blob + (CI_F16 ? ko.convin_ws : ko.convin_w));
-        const float* cb = reinterpret_cast<const float*>(blob + ko.convin_b);
-        // 8 waves x 5 slices.  (4 waves x 10 slices -- one wave per SIMD, half the yz partials -- measured slower for the fp32
-        // path, 50.5 vs 47.3 us at 32 scenes: the second wave of a SIMD hides the slice-boundary and LDS-issue bubbles.)
-        constexpr int NW = 8;
-        if (nxp == 1) {
-            auto kern = convin_project_kernel<T, RES / NW, CI_F16, NW, CI_LO, MK>;
-            constexpr size_t lds = ci_lds_bytes(RES, NW, CI_F16);
-            giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)lds);
-            GIGA_LAUNCH(kern, dim3(8 * B), dim3(NW * 64), lds, s, tsdf, cw, cb, P0, XZP, YZP, B, mask_out);
-        } else {
-            auto kern = convin_project_kernel<T, 8 / NW, CI_F16, NW, CI_LO, MK>;
-            constexpr size_t lds = ci_lds_bytes(8, NW, CI_F16);
-            giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)lds);
-            GIGA_LAUNCH(kern, dim3(5, 8, B), dim3(NW * 64), lds, s, tsdf, cw, cb, P0, XZP, YZP, B, mask_out);
-        }
+        auto kern = convin_project_kernel<T, SXW, CI_F16, CI_NW, CI_LO, MK>;
+        constexpr size_t lds = ci_lds_bytes(XW, CI_NW, CI_F16);
+        giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)lds);
+        GIGA_LAUNCH(kern, dim3(pl.ci_grid_x, pl.ci_grid_y, pl.ci_grid_z), dim3(pl.ci_block), lds, s, tsdf, cw, cb, P0, XZP, YZP, B, mask_out);
     };
-    pre();
-    using TT = std::true_type; using FF = std::false_type;
-    if constexpr (SPLIT) run_convin(TT{}, TT{}, FF{});
-    else if constexpr (sizeof(T) == 2) run_convin(TT{}, FF{}, FF{});
-    else if constexpr (MATH == MATH_BF16) { if (keep_mask) run_convin(TT{}, FF{}, TT{}); else run_convin(TT{}, TT{}, FF{}); }
-    else { if (keep_mask) run_convin(FF{}, FF{}, TT{}); else run_convin(FF{}, FF{}, FF{}); }
-    post();
-    {
-        pre();
-        GIGA_LAUNCH(plane_finalize_kernel<T>, dim3((unsigned)((per / 4 + 255) / 256)), dim3(256), 0, s, XZP, YZP, P0, B,
-                           nxp, reinterpret_cast<unsigned*>(ws + w.SYNC), MEGA_SYNC_WORDS);
-        post();
-    }
-    if (hipGetLastError() != hipSuccess) return -10;
+    auto form = [&](auto f16c, auto lo, auto msk) {
+        if (pl.ci_sxw == RES / CI_NW) go(std::integral_constant<int, RES / CI_NW>{}, f16c, lo, msk);
+        else go(std::integral_constant<int, 8 / CI_NW>{}, f16c, lo, msk);
+    };
+    if constexpr (sizeof(T) == 2) form(TT{}, FF{}, FF{});                    // plain f16
+    else if (!pl.ci_f16) { if (pl.ci_mask) form(FF{}, FF{}, TT{}); else form(FF{}, FF{}, FF{}); }   // fp32
+    else if (pl.ci_lo) form(TT{}, TT{}, FF{});                               // f16x3; bf16 without the mask
+    else form(TT{}, FF{}, TT{});                                             // bf16 with the mask
+}
 
-    const int nimg = 3 * B;
-    // exact fp32 only: the stride-1 3x3 layers whose bit is set run as Winograd F(2x2, 3x3) (giga_wino.h) on their own weight image
-    constexpr bool CAN_WINO = sizeof(T) == 4 && MATH == MATH_NATIVE;
-    unsigned wino_mask = 0;
-    if constexpr (CAN_WINO) {
-        for (int l = 0; l < NCONV; ++l)
-            if ((kConv[l].kind == CONV3 || kConv[l].kind == UPCONV) && (wino_req >> l & 1u)) wino_mask |= 1u << l;
-    }
-    auto W_ = [&](int l) {
-        if ((wino_mask >> l & 1u) && kConv[l].kind == CONV3) return blob + ko.conv[l].wino;    // (up_run reads the ordinary fp32 fragments)
-        return blob + (SPLIT ? ko.conv[l].w16s : MATH == MATH_BF16 ? ko.conv[l].wbf : precision == 1 ? ko.conv[l].w16 : ko.conv[l].w32);
+// The operands of every U-Net layer for the plan's form: one table for the persistent kernels (their argument) and the per-layer
+// launches (its rows).  The wiring, conv32's pooling rewiring, xcd_local and the weight image are data of the form.
+template <typename T, int MATH, int C32MODE>
+static MegaArgs unet_table(const EncPlan& pl, const uint8_t* blob, uint8_t* b, const EncWs& w, void* planes_nhwc, float* planes_nchw) {
+    const PackOff ko = pack_offsets();
+    auto weights = [&](int l) {
+        const auto& c = ko.conv[l];
+        if (pl.conv32) return blob + (C32MODE == C32_SPLIT ? c.c32s : C32MODE == C32_BF16 ? c.c32b : c.c32h);
+        if (pl.layer_kernel[l] == ENC_LAYER_WINO) return blob + c.wino;        // (up_run reads the ordinary fp32 fragments)
+        return blob + (MATH == MATH_SPLIT ? c.w16s : MATH == MATH_BF16 ? c.wbf : sizeof(T) == 2 ? c.w16 : c.w32);
     };
-    auto Bi = [&](int l) { return reinterpret_cast<const float*>(blob + ko.conv[l].bias); };
-    auto args = [&](int l, const void* i0, const void* i1, void* o, void* op) {
-        ConvArgs a{};
-        a.in0 = i0; a.in1 = i1; a.w = W_(l); a.bias = Bi(l); a.out = o; a.out_pool = op; a.out_nchw = nullptr;
-        a.nimg = nimg;
+    MegaArgs m{};
+    int l = 0;
+    auto row = [&](const void* i0, const void* i1, void* o, void* op) {
+        ConvArgs& a = m.layer[l];
+        a.in0 = i0; a.in1 = i1; a.w = weights(l); a.bias = reinterpret_cast<const float*>(blob + ko.conv[l].bias);
+        a.out = o; a.out_pool = pl.conv32 ? nullptr : op;
+        a.nimg = pl.nimg;
         a.trace_id = l;
-        a.xcd_local = 1;                  // per-layer launches: images onto XCDs, all weight groups of an image on one L2 (conv_wg_map)
-        return a;
+        // per-layer conv16 launches: images onto XCDs, all weight groups of an image on one L2 (conv_wg_map); the persistent kernels
+        // hand every group its images themselves, and so does conv32_kernel
+        a.xcd_local = pl.form == ENC_FORM_LAYERS_CONV16;
+        ++l;
     };
-    uint8_t* b = ws;
+    // GIGA_FOLD_FINAL: the caller's decoder carries conv_final inside its fc_c weights, so up1.conv2 writes straight into the output
+    // planes and the last layer is not launched
+    void* a6 = pl.nlayers < NCONV ? planes_nhwc : static_cast<void*>(b + w.A6);
+    row(b + w.P0, nullptr, b + w.A0, nullptr);  row(b + w.A0, nullptr, b + w.S0, b + w.Q0);
+    row(b + w.Q0, nullptr, b + w.A1, nullptr);  row(b + w.A1, nullptr, b + w.S1, b + w.Q1);
+    row(b + w.Q1, nullptr, b + w.A2, nullptr);  row(b + w.A2, nullptr, b + w.S2, nullptr);
+    row(b + w.S2, nullptr, b + w.U0, nullptr);  row(b + w.U0, b + w.S1, b + w.A3, nullptr);
+    row(b + w.A3, nullptr, b + w.A4, nullptr);  row(b + w.A4, nullptr, b + w.U1, nullptr);
+    row(b + w.U1, b + w.S0, b + w.A5, nullptr); row(b + w.A5, nullptr, a6, nullptr);
+    row(b + w.A6, nullptr, planes_nhwc, nullptr);
+    m.layer[12].out_nchw = planes_nchw;
+    if (pl.conv32) {                                          // layers 2 and 4 pool their input while staging it
+        m.layer[2].in0 = b + w.S0; m.layer[2].out_pool = b + w.Q0;
+        m.layer[4].in0 = b + w.S1; m.layer[4].out_pool = b + w.Q1;
+    }
+    m.sync = reinterpret_cast<unsigned*>(b + w.SYNC);
+    m.nlayers = pl.nlayers;
+    m.wino_mask = pl.wino_mask;
+    return m;
+}
+
+// One launch per layer, written once per kernel family; every layer's probe stage is bracketed here and nowhere else.  A layer whose
+// family this instantiation does not have is an error, not another kernel.
+template <typename T, int MATH>
+static int launch_layers_conv16(const EncPlan& pl, const MegaArgs& m, hipStream_t s, const Probe& pr) {
+    constexpr bool CAN_WINO = sizeof(T) == 4 && MATH == MATH_NATIVE;
     int rc = 0;
-    // GIGA_FOLD_FINAL: the caller's decoder carries conv_final inside its fc_c weights, so up1.conv2 writes straight
-    // into the output planes and the last layer is not launched (its probe stage then brackets nothing)
-    void* a6 = fold_final ? planes_nhwc : static_cast<void*>(b + w.A6);
-    ConvArgs L[NCONV] = {
-        args(0, b + w.P0, nullptr, b + w.A0, nullptr),  args(1, b + w.A0, nullptr, b + w.S0, b + w.Q0),
-        args(2, b + w.Q0, nullptr, b + w.A1, nullptr),  args(3, b + w.A1, nullptr, b + w.S1, b + w.Q1),
-        args(4, b + w.Q1, nullptr, b + w.A2, nullptr),  args(5, b + w.A2, nullptr, b + w.S2, nullptr),
-        args(6, b + w.S2, nullptr, b + w.U0, nullptr),  args(7, b + w.U0, b + w.S1, b + w.A3, nullptr),
-        args(8, b + w.A3, nullptr, b + w.A4, nullptr),  args(9, b + w.A4, nullptr, b + w.U1, nullptr),
-        args(10, b + w.U1, b + w.S0, b + w.A5, nullptr), args(11, b + w.A5, nullptr, a6, nullptr),
-        args(12, b + w.A6, nullptr, planes_nhwc, nullptr)};
-    L[12].out_nchw = planes_nchw;
-    const int nlayers = fold_final ? 12 : 13;
-    // One persistent launch for the whole U-Net (unet_mega_kernel) is the default, unless a single layer is being probed (stages
-    // 2..14) -- for every batch size in the f16-class modes, from 24 images (8 scenes) up in fp32 / bf16 (below that an fp32 layer's
-    // barrier + first patch cost what its launch costs: 152 vs 156 us at one scene).  The flag GIGA_LAYERWISE_UNET of the call keeps
-    // one launch per layer; GIGA_PERSIST_UNET forces the persistent form where the default would not take it.
-    const bool full_device = [] {                             // per call: the CURRENT device (a process may drive several)
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return false;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-        return cus == 256;                                    // 8 XCDs x 32 CUs, one workgroup per CU
-    }();
-    constexpr bool F16CLASS = sizeof(T) == 2 || MATH == MATH_SPLIT;
-    const bool probe_layer = pr.stage >= 2 && pr.stage <= 14;
-    const bool by_default = F16CLASS || nimg >= 24;
-    bool mega = full_device && !probe_layer && (persist > 0 || (persist == 0 && by_default));
-    int mega_slot = -2;
-    if (mega) { mega_slot = persistent_slot(s); mega = mega_slot != -1; }        // at most MEGA_MAX_IN_FLIGHT persistent launches in flight
-    // conv32 (giga_conv32.h) or conv16 for the f16-class modes.  A call (GIGA_CONV32_UNET / GIGA_CONV16_UNET) can force one;
-    // left alone, conv32 runs up to 16 scenes (48 images) and conv16 beyond: conv32's encoder is
-    // 3-9 % faster up to 32 scenes, but from ~24 scenes on -- every CU busy -- the chip holds a 3-5 % lower shader clock while and after
-    // the conv32 launch runs (at LOWER socket power: a current limit), which costs a sustained 32-scene step up to 4 % and a
-    // 128-scene step up to 6 % (tools/gpu_sustained_power.py, profiles/r04/final/sustained_power.txt).
-    constexpr int C32MODE = sizeof(T) == 2 ? C32_NATIVE : MATH == MATH_SPLIT ? C32_SPLIT : MATH == MATH_BF16 ? C32_BF16 : -1;
-    constexpr int C32_AUTO_MAX_IMAGES = 48;
-    if constexpr (C32MODE >= 0) {
-        const int want = conv32 != 0 ? conv32 : (nimg <= C32_AUTO_MAX_IMAGES ? 1 : -1);
-        if (want > 0) {
-            auto W32 = [&](int l) { return blob + (C32MODE == C32_SPLIT ? ko.conv[l].c32s : C32MODE == C32_BF16 ? ko.conv[l].c32b : ko.conv[l].c32h); };
-            ConvArgs M[NCONV];
-            for (int l = 0; l < NCONV; ++l) { M[l] = L[l]; M[l].w = W32(l); M[l].xcd_local = 0; M[l].out_pool = nullptr; }
-            M[2].in0 = b + w.S0; M[2].out_pool = b + w.Q0;      // layers 2 and 4 pool their input while staging it
-            M[4].in0 = b + w.S1; M[4].out_pool = b + w.Q1;
-            if (mega) {
-                MegaArgs m{};
-                for (int l = 0; l < NCONV; ++l) m.layer[l] = M[l];
-                m.sync = reinterpret_cast<unsigned*>(b + w.SYNC);
-                m.nlayers = nlayers;
-                const unsigned grid = (unsigned)mega_groups(nimg) * MEGA_GROUP;
-                // fused same-resolution pairs (C32Pair) while a member's rows fit ONE sub-band of the pair (up to two images per
-                // group: the halo rows a member recomputes are 2 of ~12; beyond that the pair needs smaller sub-bands than the
-                // single layers and measured slower, profiles/r04/conv32_fused_pairs.txt).  Bit-identical either way;
-                // GIGA_C32_FUSE=0 / 1 forces one form (A/B runs).
-                static const int env_fuse = [] { const char* e = getenv("GIGA_C32_FUSE"); return e ? atoi(e) : -1; }();
-                const int groups = mega_groups(nimg);
-                const bool fuse = env_fuse >= 0 ? env_fuse != 0 : (nimg + groups - 1) / groups <= 2;
-                stage_no = 15;
-                pre();
-                auto go = [&](auto kern) {
-                    giga::dyn_lds_once(reinterpret_cast<const void*>(kern), C32_LDS_TOTAL);
-                    GIGA_LAUNCH(kern, dim3(grid), dim3(C32_NW * 64), C32_LDS_TOTAL, s, m);
-                };
-                if (fuse) go(unet32_mega_kernel<C32MODE, true>); else go(unet32_mega_kernel<C32MODE, false>);
-                g_last_unet_path.store(GIGA_PATH_CONV32 | GIGA_PATH_PERSISTENT | (fuse ? GIGA_PATH_FUSED_PAIRS : 0), std::memory_order_relaxed);
-                persistent_launched(mega_slot, s);
-                post();
-                return hipGetLastError() == hipSuccess ? 0 : -10;
-            }
-            g_last_unet_path.store(GIGA_PATH_CONV32, std::memory_order_relaxed);
-            if (pr.stage == 15) (void)hipEventRecord(pr.ev0, s);
-#define X(l, KIND, C0, C1, COUT, H, W, POOLIN, SPW, SGN, SGS, KPS)                                                          \
-            if (l < nlayers) { pre(); rc |= launch_conv32<typename U32Layer<C32MODE, l>::G, U32Layer<C32MODE, l>::RELU>(M[l], s); post(); } \
-            else { pre(); post(); }
-            GIGA_UNET32_LAYERS(X)
-#undef X
-            if (pr.stage == 15) (void)hipEventRecord(pr.ev1, s);
-            return rc;
-        }
-    }
-    g_last_unet_path.store((mega ? GIGA_PATH_PERSISTENT : 0) | (wino_mask ? GIGA_PATH_WINOGRAD : 0), std::memory_order_relaxed);
-    if (mega) {
-        MegaArgs m{};
-        for (int l = 0; l < NCONV; ++l) { m.layer[l] = L[l]; m.layer[l].xcd_local = 0; }   // (the kernel hands every group its images itself)
-        m.sync = reinterpret_cast<unsigned*>(b + w.SYNC);
-        m.nlayers = nlayers;
-        m.wino_mask = wino_mask;
-        const unsigned grid = (unsigned)mega_groups(nimg) * MEGA_GROUP;
-        stage_no = 15;                                        // probe stage 15 = the whole U-Net
-        auto go = [&](auto kern, const size_t lds, const int nw) {
-            giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)lds);
-            pre();
-            GIGA_LAUNCH(kern, dim3(grid), dim3(nw * 64), lds, s, m);
-            persistent_launched(mega_slot, s);
-            post();
-        };
-        constexpr size_t lds = mega_lds_bytes<T, MATH>();
-        static_assert(lds <= 160 * 1024, "LDS budget of the persistent U-Net kernel");
-        if constexpr (CAN_WINO) {
-            constexpr size_t ldsw = mega_lds_bytes<T, MATH, true>();
-            static_assert(ldsw <= 160 * 1024, "LDS budget of the persistent U-Net kernel (Winograd stages)");
-            if (wino_mask) go(unet_mega_kernel<T, MATH, true>, ldsw, WINO_NW); else go(unet_mega_kernel<T, MATH, false>, lds, MEGA_NW);
-        } else {
-            go(unet_mega_kernel<T, MATH, false>, lds, MEGA_NW);
-        }
-        return hipGetLastError() == hipSuccess ? 0 : -10;
-    }
-    if (pr.stage == 15) (void)hipEventRecord(pr.ev0, s);
 #define X(l, KIND, C0, C1, COUT, H, W, NB, POOL, NB16)                                                                    \
-    if (l < nlayers) {                                                                                                    \
-        pre();                                                                                                            \
-        bool direct = true;                                                                                               \
+    {                                                                                                                     \
+        const int k = pl.layer_kernel[l];                                                                                 \
+        bool known = k == ENC_LAYER_NONE || k == ENC_LAYER_CONV16;                                                        \
+        pr.pre(ENC_STAGE_LAYER0 + l);                                                                                     \
         if constexpr (CAN_WINO && KIND == CONV3) {                                                                        \
-            if (wino_mask >> l & 1u) { direct = false; rc |= launch_wino<C0, C1, COUT, H, W, POOL>(L[l], s); }            \
+            if (k == ENC_LAYER_WINO) { known = true; rc |= launch_wino<C0, C1, COUT, H, W, POOL>(m.layer[l], s); }        \
         }                                                                                                                 \
         if constexpr (CAN_WINO && KIND == UPCONV) {                                                                       \
-            if (wino_mask >> l & 1u) { direct = false; rc |= launch_up<C0, COUT, H, W>(L[l], s); }                        \
+            if (k == ENC_LAYER_UP) { known = true; rc |= launch_up<C0, COUT, H, W>(m.layer[l], s); }                      \
         }                                                                                                                 \
-        if (direct) rc |= launch_conv<T, KIND, C0, C1, COUT, H, W, (sizeof(T) == 2 ? NB16 : NB), POOL, KIND == CONV3, MATH>(L[l], s); \
-        post();                                                                                                           \
-    }                                                                                                                     \
-    else { pre(); post(); }
+        if (k == ENC_LAYER_CONV16) rc |= launch_conv<T, KIND, C0, C1, COUT, H, W, (sizeof(T) == 2 ? NB16 : NB), POOL, KIND == CONV3, MATH>(m.layer[l], s); \
+        pr.post(ENC_STAGE_LAYER0 + l);                                                                                    \
+        if (!known) rc |= -5;                                                                                             \
+    }
     GIGA_UNET_LAYERS(X)
 #undef X
-    if (pr.stage == 15) (void)hipEventRecord(pr.ev1, s);
+    return rc;
+}
+template <int C32MODE>
+static int launch_layers_conv32(const EncPlan& pl, const MegaArgs& m, hipStream_t s, const Probe& pr) {
+    int rc = 0;
+#define X(l, KIND, C0, C1, COUT, H, W, POOLIN, SPW, SGN, SGS, KPS)                                                         \
+    pr.pre(ENC_STAGE_LAYER0 + l);                                                                                         \
+    if (pl.layer_kernel[l] == ENC_LAYER_CONV32) rc |= launch_conv32<typename U32Layer<C32MODE, l>::G, U32Layer<C32MODE, l>::RELU>(m.layer[l], s); \
+    else if (pl.layer_kernel[l] != ENC_LAYER_NONE) rc |= -5;                                                              \
+    pr.post(ENC_STAGE_LAYER0 + l);
+    GIGA_UNET32_LAYERS(X)
+#undef X
+    return rc;
+}
+
+// An encoder call in five steps: the plan (launch_encoder made it), conv_in, plane_finalize, the operand table, the U-Net in the
+// plan's form.  mega_slot: persistent_slot's answer for a persistent plan.
+template <typename T, int MATH = MATH_NATIVE>
+static int encoder_run(const EncPlan& pl, const float* tsdf, const uint8_t* blob, void* planes_nhwc, float* planes_nchw, int B,
+                       uint8_t* ws, hipStream_t s, const Probe& pr, int mega_slot) {
+    constexpr int C32MODE = sizeof(T) == 2 ? C32_NATIVE : MATH == MATH_SPLIT ? C32_SPLIT : MATH == MATH_BF16 ? C32_BF16 : -1;
+    const EncWs w = enc_workspace(B, sizeof(T) == 2 ? 1 : 0);
+    T* P0 = reinterpret_cast<T*>(ws + w.P0);
+    float* XZP = reinterpret_cast<float*>(ws + w.YZ);
+    float* YZP = XZP + 4 * (size_t)B * RES * RES * CD;
+    pr.pre(0);
+    launch_convin<T>(pl, tsdf, blob, P0, XZP, YZP, B, pl.ci_mask ? reinterpret_cast<uint4*>(ws + w.MASK) : nullptr, s);
+    pr.post(0);
+    pr.pre(1);
+    GIGA_LAUNCH(plane_finalize_kernel<T>, dim3(pl.fin_grid), dim3(pl.fin_block), 0, s, XZP, YZP, P0, B, pl.nxp,
+                reinterpret_cast<unsigned*>(ws + w.SYNC), MEGA_SYNC_WORDS);
+    pr.post(1);
+    if (hipGetLastError() != hipSuccess) return -10;
+
+    const MegaArgs m = unet_table<T, MATH, C32MODE>(pl, blob, ws, w, planes_nhwc, planes_nchw);
+    auto persistent = [&](auto kern, const size_t lds) {
+        giga::dyn_lds_once(reinterpret_cast<const void*>(kern), (int)lds);
+        GIGA_LAUNCH(kern, dim3(pl.grid), dim3(pl.block), lds, s, m);
+        persistent_launched(mega_slot, s);
+        return hipGetLastError() == hipSuccess ? 0 : -10;
+    };
+    constexpr size_t lds16 = mega_lds_bytes<T, MATH>();
+    static_assert(lds16 <= 160 * 1024, "LDS budget of the persistent U-Net kernel");
+    int rc = -5;                                              // a form this instantiation has no kernel for
+    pr.pre(ENC_STAGE_UNET);
+    switch (pl.form) {
+    case ENC_FORM_LAYERS_CONV16: rc = launch_layers_conv16<T, MATH>(pl, m, s, pr); break;
+    case ENC_FORM_PERSIST_CONV16: rc = persistent(unet_mega_kernel<T, MATH, false>, lds16); break;
+    case ENC_FORM_PERSIST_WINO:
+        if constexpr (sizeof(T) == 4 && MATH == MATH_NATIVE) {
+            constexpr size_t ldsw = mega_lds_bytes<T, MATH, true>();
+            static_assert(ldsw <= 160 * 1024, "LDS budget of the persistent U-Net kernel (Winograd stages)");
+            rc = persistent(unet_mega_kernel<T, MATH, true>, ldsw);
+        }
+        break;
+    case ENC_FORM_LAYERS_CONV32:
+        if constexpr (C32MODE >= 0) rc = launch_layers_conv32<C32MODE>(pl, m, s, pr);
+        break;
+    case ENC_FORM_PERSIST_CONV32:
+        if constexpr (C32MODE >= 0)
+            rc = pl.fused ? persistent(unet32_mega_kernel<C32MODE, true>, C32_LDS_TOTAL) : persistent(unet32_mega_kernel<C32MODE, false>, C32_LDS_TOTAL);
+        break;
+    }
+    pr.post(ENC_STAGE_UNET);
     return rc;
 }
 
 int launch_encoder(const float* tsdf, const uint8_t* blob, void* planes_nhwc, float* planes_nchw, int B,
                    int precision, uint8_t* ws, hipStream_t s, int probe_stage, void* ev0, void* ev1) {
     if (B <= 0) return 0;
-    Probe pr{ev0 && ev1 ? probe_stage : -1, static_cast<hipEvent_t>(ev0), static_cast<hipEvent_t>(ev1)};
-    const bool fold = (precision & GIGA_FOLD_FINAL) != 0;
-    const int persist = (precision & GIGA_LAYERWISE_UNET) ? -1 : (precision & GIGA_PERSIST_UNET) ? 1 : 0;   // -1 per-layer launches, 0 auto, 1 persistent
-    const int prec = precision & ~GIGA_ENCODER_FLAGS;
-    const int c32 = (precision & GIGA_CONV32_UNET) ? 1 : (precision & GIGA_CONV16_UNET) ? -1 : 0;      // 1 conv32, -1 conv16, 0 default
-    const bool km = (precision & GIGA_CONVIN_MASK) != 0;      // training forward (precisions 0 and 3): keep conv_in's ReLU mask for the backward
-    // Winograd F(2x2, 3x3) for the 3x3 layers of precision 0 (giga_wino.h): on unless the call says GIGA_DIRECT_CONV (a blob rebuilt on
-    // the device needs giga_derive_winograd first); GIGA_WINOGRAD=<mask> in the environment selects the layers of a whole process
-    // (0 = none; A/B runs)
-    static const unsigned env_wino = [] { const char* e = getenv("GIGA_WINOGRAD"); return e ? (unsigned)strtoul(e, nullptr, 0) : WINO_DEFAULT_MASK; }();
-    const unsigned wino = (precision & GIGA_DIRECT_CONV) ? 0u : env_wino;
-    if (prec == 2) return encoder_run<float, MATH_SPLIT>(tsdf, blob, planes_nhwc, planes_nchw, B, ws, s, pr, fold, persist, c32);
-    if (prec == 3) return encoder_run<float, MATH_BF16>(tsdf, blob, planes_nhwc, planes_nchw, B, ws, s, pr, fold, persist, c32, km);
-    return prec == 1 ? encoder_run<half_t>(tsdf, blob, planes_nhwc, planes_nchw, B, ws, s, pr, fold, persist, c32)
-                     : encoder_run<float>(tsdf, blob, planes_nhwc, planes_nchw, B, ws, s, pr, fold, persist, c32, km, wino);
+    const Probe pr{ev0 && ev1 ? probe_stage : -1, static_cast<hipEvent_t>(ev0), static_cast<hipEvent_t>(ev1), s};
+    const EncCall call = enc_call_from_flags(precision);
+    const EncKnobs knobs = enc_knobs_from_env();
+    int dev = 0, cus = 0;                                     // per call: the CURRENT device (a process may drive several)
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
+    // plan with a free slot; a persistent plan then reserves one (at most MEGA_MAX_IN_FLIGHT persistent launches in flight), and where
+    // there is none the call is planned again without.  -2 (a captured stream) keeps the persistent form, untracked.
+    EncPlan pl = enc_plan(call, B, cus, pr.stage, true, knobs);
+    int mega_slot = -2;
+    if (pl.persistent && (mega_slot = persistent_slot(s)) == -1) pl = enc_plan(call, B, cus, pr.stage, false, knobs);
+    g_last_unet_path.store(pl.path, std::memory_order_relaxed);
+    switch (call.precision) {
+    case 1: return encoder_run<half_t>(pl, tsdf, blob, planes_nhwc, planes_nchw, B, ws, s, pr, mega_slot);
+    case 2: return encoder_run<float, MATH_SPLIT>(pl, tsdf, blob, planes_nhwc, planes_nchw, B, ws, s, pr, mega_slot);
+    case 3: return encoder_run<float, MATH_BF16>(pl, tsdf, blob, planes_nhwc, planes_nchw, B, ws, s, pr, mega_slot);
+    default: return encoder_run<float>(pl, tsdf, blob, planes_nhwc, planes_nchw, B, ws, s, pr, mega_slot);
+    }
 }
 
 }  // namespace giga

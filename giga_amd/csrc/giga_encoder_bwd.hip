@@ -19,6 +19,7 @@
 
 #include "giga_side.h"
 #include "giga_args.h"
+#include "giga_enc_plan.h"
 
 namespace giga {
 
@@ -492,7 +493,7 @@ void side_streams_forget() {
 }
 
 // ------------------------------- driver -----------------------------------------------------------------------
-// forward activations: the encoder workspace (giga_encoder.hip::EncWs, fp32).  Gradient workspace carve:
+// forward activations: the encoder workspace (giga_enc_plan.h::EncWs, fp32).  Gradient workspace carve:
 // (struct BwdWs: giga_args.h)
 // what the last backward of this process ran its data-gradient chain on (giga_backward_last_path: tests pin the launch form to it)
 static std::atomic<int> g_last_bwd_path{0};
@@ -522,9 +523,6 @@ BwdWs enc_bwd_workspace(int B) {
     w.total = at;
     return w;
 }
-
-EncWs enc_workspace(int B, int precision);
-int enc_nxp(int B);
 
 // MATH: arithmetic of the thirteen data-gradient convolutions (MATH_NATIVE fp32 MFMA, or MATH_BF16: bf16 operands from the
 // backward blob's bf16 images, fp32 accumulate and fp32 gradients in memory); everything else is fp32.

@@ -32,11 +32,7 @@
 
 namespace giga {
 
-// layers that run as Winograd by default (bit l = U-Net layer l of giga_layout.h::kConv); settled by measurement
-constexpr unsigned WINO_DEFAULT_MASK = 0xFFF;     // all ten 3x3 layers (0, 1, 2, 3, 4, 5, 7, 8, 10, 11) as Winograd, the two ConvTranspose layers
-                                                  // (6, 9) as plain GEMMs on the same lane layout (up_run); profiles/r06/wino_ab_*.txt
-constexpr int WINO_NW = 8;                        // waves per workgroup: two per SIMD, 256 registers each (64 accumulators + 32 transformed
-                                                  // values + a prefetched chunk do not fit the 168 of three per SIMD)
+// (WINO_DEFAULT_MASK, the layers that run as Winograd by default, and WINO_NW = 8, the waves per workgroup, are giga_enc_plan.h's)
 constexpr int WINO_PS = 80;                       // LDS pixel stride: 16 channels x 4 B + 16 B pad
 template <int H, int W> struct WinoBlock {        // tiles per unit: 4 x 4 where the 20 x 20 tile grid of a 40^2 image divides, else 5 x 3
     static constexpr int TW = W / 2, TH = H / 2;

@@ -96,7 +96,7 @@ size_t giga_encoder_workspace_bytes(int B, int precision);
 
 /* Introspection for tests: byte offsets of the 17 intermediate activations inside the encoder
  * workspace, in order P0 (projected planes, U-Net input) A0 S0 Q0 A1 S1 Q1 A2 S2 U0 A3 A4 U1 A5 A6
- * YZ XZ (see giga_encoder.hip).  All NHWC [3B][H][W][C] in the precision's element type
+ * YZ XZ (csrc/giga_enc_plan.h: enc_workspace).  All NHWC [3B][H][W][C] in the precision's element type
  * (YZ/XZ: fp32 partial sums).  offsets must have room for 17 entries. */
 int giga_encoder_workspace_layout(int B, int precision, size_t* offsets);
 
@@ -177,10 +177,37 @@ int giga_decoder_forward(const void* planes_nhwc, const float* p, const void* pa
  * MFMA by default (csrc/giga_wino.h: 16 instead of 36 multiplies per 2x2 outputs; transforms in registers, Winograd-domain weights
  * from the packed blob).  fp32 Winograd is not the direct form's bitwise fma chain: planes differ from it by a few 1e-6 relative
  * (the suite holds both to 1e-4 of the oracle).  GIGA_DIRECT_CONV, OR-ed into `precision` (0) of giga_encoder_forward*, keeps the
- * direct convolutions for this call; the environment variable GIGA_WINOGRAD=0 does so for a whole process (a layer bit mask
- * otherwise).  A blob rebuilt by giga_repack_device (the training path) needs giga_derive_winograd before such a forward:
+ * direct convolutions for this call; the environment variable GIGA_WINOGRAD=0 does so for every call made while it is set (a layer bit
+ * mask otherwise; read on every call).  A blob rebuilt by giga_repack_device (the training path) needs giga_derive_winograd before such a forward:
  * giga_repack_device gathers parameters, and the Winograd image is not a gather. */
 #define GIGA_DIRECT_CONV 1024
+/* The launch plan giga_encoder_forward* would use for B scenes and this `precision` word (the precision 0..3 with the flags above)
+ * on a device of `cus` compute units (<= 0: assume 256, a whole MI355X), decided NOW: the tuning variables GIGA_WINOGRAD (the layer
+ * mask of the Winograd stages of precision 0) and GIGA_C32_FUSE (0 / 1: the fused pairs of the persistent conv32 launch off / on) are
+ * read on every call, as a launch reads them.  probe_stage: the stage a giga_encoder_forward_probe call would bracket (-1: none; a
+ * probed layer, stages 2..14, gets its own launch).  Host only: no device is touched.  The plan assumes that the device has room for
+ * one more persistent launch (see GIGA_PERSIST_UNET); GIGA_ENCODER_PLAN_NO_SLOT, OR-ed into the word of THIS function only, asks for
+ * the plan of a call that finds four others in flight.  Error codes as giga_encoder_forward_probe's for the same arguments: -1
+ * (B < 0, NULL plan_words), -7 (B > GIGA_MAX_SCENES), -5 (precision, GIGA_CONVIN_MASK with precision 1 / 2); B == 0: all words zero.
+ * plan_words[GIGA_ENCODER_PLAN_WORDS], in order (csrc/giga_enc_plan.h, struct EncPlan):
+ *   nimg (3 B), nlayers (12 with GIGA_FOLD_FINAL, else 13);
+ *   conv_in: nxp (x-parts), ci_f16 (f16 operand image), ci_lo (f16x3 split operands), ci_mask (stores the ReLU mask), ci_sxw (slices
+ *   per wave), ci_nw (waves), ci_grid_x, ci_grid_y, ci_grid_z, ci_block;  plane_finalize: fin_grid, fin_block;
+ *   form (GIGA_ENC_FORM_*), persistent, conv32, fused, wino_mask (bit l: layer l is a Winograd stage / an up-GEMM), groups (of 8
+ *   workgroups), grid, block (the persistent launch; 0: one launch per layer), layer_kernel[13] (GIGA_ENC_LAYER_*; 0: not launched),
+ *   launches (kernel launches of the call), path (the GIGA_PATH_* word giga_encoder_last_path reports after the call). */
+#define GIGA_ENCODER_PLAN_WORDS 37
+#define GIGA_ENCODER_PLAN_NO_SLOT 2048
+#define GIGA_ENC_FORM_LAYERS_CONV16 1    /* one launch per layer: conv16_kernel (precision 0: wino_kernel / up_kernel where wino_mask says) */
+#define GIGA_ENC_FORM_LAYERS_CONV32 2    /* one launch per layer: conv32_kernel */
+#define GIGA_ENC_FORM_PERSIST_CONV16 3   /* unet_mega_kernel<T, MATH, false> */
+#define GIGA_ENC_FORM_PERSIST_WINO 4     /* unet_mega_kernel<float, MATH_NATIVE, true> */
+#define GIGA_ENC_FORM_PERSIST_CONV32 5   /* unet32_mega_kernel<MODE, fused> */
+#define GIGA_ENC_LAYER_CONV16 1
+#define GIGA_ENC_LAYER_CONV32 2
+#define GIGA_ENC_LAYER_WINO 3
+#define GIGA_ENC_LAYER_UP 4
+int giga_encoder_plan(int B, int precision_word, int cus, int probe_stage, int32_t* plan_words);
 
 /* Inference fast path for the FIXED QUERY LATTICE of VGNImplicit (detection_implicit.py:28-31,107):
  * the R^3 points meshgrid(lin, lin, lin, 'ij') with z fastest, shared by all B scenes.  Each plane is

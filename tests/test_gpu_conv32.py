@@ -35,7 +35,7 @@ def _planes(net, x):
 def test_kernel_choice_flags_select_what_runs(net32):
     """`set_unet_kernel` / GIGA_CONV32_UNET / GIGA_CONV16_UNET must reach the launcher (a flag that is masked and dropped on the way
     leaves every comparison in this file comparing a kernel with itself): giga_encoder_last_path() says what the call ran."""
-    from giga_amd import _capi
+    from giga_amd import _capi, convonet
     L = _capi.lib()
     dev = torch.device("cuda:0")
     try:
@@ -53,10 +53,12 @@ def test_kernel_choice_flags_select_what_runs(net32):
                         # (f16x3 launches the fused-pairs instantiation too; none of its pairs fits two weight sets side by side)
                         exp = want | pbit | (_capi.PATH_FUSED_PAIRS if want and pbit and fused else 0)
                         assert got == exp, (prec, B, kernel, form, got, exp)
+                        assert got == convonet.encoder_plan(B, prec, persistent=form, unet_kernel=kernel)["path"]
         net32.set_precision("fp32")                       # fp32 has conv16 only, whatever is asked for
         net32.set_unet_kernel("conv32").set_persistent_unet(False)
         _planes(net32, torch.from_numpy(synth.tsdf_batch(3, 32)).to(dev))
         assert L.giga_encoder_last_path() == _capi.PATH_PERSISTENT | _capi.PATH_WINOGRAD     # (fp32: 3x3 layers as Winograd, giga_wino.h)
+        assert L.giga_encoder_last_path() == convonet.encoder_plan(32, "fp32", unet_kernel="conv32")["path"]
     finally:
         net32.set_unet_kernel("conv32").set_persistent_unet(False).set_precision("fp32")
 

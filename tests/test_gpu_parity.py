@@ -100,7 +100,7 @@ def test_auto_kernel_choice_across_the_16_scene_threshold(net, dev, sd7, prec, t
     in a batch of 16 and in a batch of 17 goes through different kernels.  Both stay inside the mode's envelope of each other
     (f16x3: 2e-5 -- fp32-grade either way; plain f16: the f16 envelope), a forced kernel makes the two batches agree bit for bit,
     and giga_encoder_last_path reports which kernels ran."""
-    from giga_amd import _capi
+    from giga_amd import _capi, convonet
     net.set_precision(prec)
     x17 = torch.from_numpy(synth.tsdf_batch(40, 17)).to(dev)
     p17 = torch.from_numpy(synth.query_points(40, 17, 512, stream=1)).to(dev)
@@ -109,6 +109,7 @@ def test_auto_kernel_choice_across_the_16_scene_threshold(net, dev, sd7, prec, t
         a = net(x17[:16], p17[:16]); path16 = L.giga_encoder_last_path()
         b = net(x17, p17); path17 = L.giga_encoder_last_path()
         assert (path16 & _capi.PATH_CONV32) and not (path17 & _capi.PATH_CONV32), (path16, path17)
+        assert (path16, path17) == (convonet.encoder_plan(16, prec)["path"], convonet.encoder_plan(17, prec)["path"])
         for u, v in zip(a, b):
             scale = max(1.0, float(v.abs().max()))
             assert maxerr(u[0], v[0].cpu().numpy()) <= tol * scale
