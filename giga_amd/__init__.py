@@ -10,6 +10,7 @@
     from giga_amd import render_color, render_mesh, write_png   # shaded images of coloured meshes (giga_amd.render, giga_amd.visual)
     from giga_amd import GeometryEvaluator, VoxelOccGeoROIDataset   # scene IoU, chamfer, grasp-ROI occupancy (giga_amd.geometry)
     from giga_amd import mesh_collide, generate_packed_scenes, write_geo_dataset   # packed scenes from object meshes (giga_amd.scenes)
+    from giga_amd import grasp_candidates, reduce_outcomes      # grasp candidates from the oriented TSDF cloud (giga_amd.candidates)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/giga_hip.h."""
 __version__ = "0.1.0"
@@ -30,6 +31,8 @@ _GEOMETRY_EXPORTS = ("GeometryEvaluator", "VoxelOccGeoDataset", "VoxelOccGeoROID
 # ... of giga_amd.collision (do two meshes intersect?) and of giga_amd.scenes (packed scenes and the geometry data set they make)
 _COLLISION_EXPORTS = ("mesh_collide", "mesh_bounds_batch")
 _SCENES_EXPORTS = ("ObjectSet", "packed_candidates", "resolve_packed", "generate_packed_scenes", "table_mesh", "write_geo_dataset")
+# ... and of giga_amd.candidates: grasp candidates from the oriented TSDF cloud and the reduction of an executor's outcomes
+_CANDIDATES_EXPORTS = ("workspace_bounds", "grasp_candidates", "reduce_outcomes", "label_scenes", "scene_views")
 
 
 def __getattr__(name):
@@ -54,4 +57,7 @@ def __getattr__(name):
     if name in _SCENES_EXPORTS:
         from . import scenes
         return getattr(scenes, name)
+    if name in _CANDIDATES_EXPORTS:
+        from . import candidates
+        return getattr(candidates, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -35,6 +35,7 @@ MESH_MAX_N = 513         # GIGA_MESH_MAX_N: samples per axis of a marching-cubes
 SIMPLIFY_MIN_REF_EXTRA = 64      # GIGA_SIMPLIFY_MIN_REF_EXTRA: smallest appended room of a mesh's reference lists
 MISE_MAX_N = 513        # GIGA_MISE_MAX_N: samples per axis of a MISE value grid (resolution0 << depth) + 1
 TSDF_MAX_R = 512         # GIGA_TSDF_MAX_R: cells per axis of a fused volume
+CANDIDATES_MAX_ROTATIONS = 32   # GIGA_CANDIDATES_MAX_ROTATIONS: yaw angles per grasp candidate
 RENDER_MAX_IMAGE = 4096  # GIGA_RENDER_MAX_IMAGE: width and height of a rendered depth image
 DOWNSAMPLE_MAX_K = 4     # GIGA_DOWNSAMPLE_MAX_K: supersampling factor of a shaded image
 REFINE_MAX_FACES = 0x0FFFFFFF   # GIGA_REFINE_MAX_FACES (and _VERTICES)
@@ -111,6 +112,9 @@ _SIGNATURES = {
                                              ctypes.c_void_p, ctypes.c_void_p]),
     "giga_tsdf_cloud_emit": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
                                             ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "giga_tsdf_cloud_emit_oriented": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                                     ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                     ctypes.c_void_p, ctypes.c_void_p]),
     "giga_train_loss": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                                ctypes.c_void_p]),
     "giga_train_loss_metrics": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4),
@@ -187,6 +191,10 @@ _SIGNATURES = {
     "giga_roi_points_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "giga_roi_points": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_uint64] + [ctypes.c_double] * 3
                         + [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "giga_grasp_candidates_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "giga_grasp_candidates": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64]
+                              + [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]),
     "giga_occ_confusion_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "giga_occ_confusion": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

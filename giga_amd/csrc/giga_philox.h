@@ -1,8 +1,8 @@
 // Philox-4x32 with 10 rounds (Salmon et al., SC 2011): the counter-based generator of giga_mesh_sample (giga_eval.hip),
-// giga_depth_noise (giga_noise.hip) and giga_refine_face_points (giga_refine.hip).  Pure integer arithmetic: a numpy restatement
-// reproduces every word (tests/eval_emu.py).  The double-precision uniforms and Box-Muller normals built on a block (noise_*) are
-// the depth noise's, shared with the refinement's barycentric draws; each of their operations is one IEEE rounding (there is no
-// multiply-add pair to contract).
+// giga_depth_noise (giga_noise.hip), giga_refine_face_points (giga_refine.hip) and giga_grasp_candidates (giga_candidates.hip).
+// Pure integer arithmetic: a numpy restatement reproduces every word (tests/eval_emu.py).  The double-precision uniforms and
+// Box-Muller normals built on a block (noise_*) are the depth noise's, shared with the refinement's barycentric draws and the
+// candidates' grasp depth; each of their operations is one IEEE rounding (there is no multiply-add pair to contract).
 #ifndef GIGA_PHILOX_H_
 #define GIGA_PHILOX_H_
 #include <hip/hip_runtime.h>

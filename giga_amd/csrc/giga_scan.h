@@ -1,5 +1,5 @@
 // The one place a prefix sum is written: the count / scan / emit stages (giga_mesh.hip, giga_tsdf.hip, giga_mise.hip,
-// giga_affordance.hip, giga_simplify.hip, giga_eval.hip) take every prefix from here.  Prefixes are taken in lane order by shuffles:
+// giga_affordance.hip, giga_simplify.hip, giga_eval.hip, giga_candidates.hip) take every prefix from here.  Prefixes are taken in lane order by shuffles:
 // no atomics, so equal input gives equal output positions.
 //
 // A ragged per-scene list is emitted in three steps.  Every workgroup of a count kernel leaves its sum in blk[scene][workgroup]

@@ -66,6 +66,8 @@ __global__ void tsdf_write_kernel(const int* __restrict__ index, const float* __
 //              (ballot + popcount inside a wave, LDS across the four waves, per-workgroup sums), scan (one workgroup per scene,
 //              then one wave over the scenes), emit at (scene base + workgroup offset + prefix).  Order: cell order, then axis
 //              0, 1, 2; no atomics decide it (giga_scan.h, the scheme of giga_mesh.hip).
+//              The oriented emit adds the normal of every point (GetNormalAt): 48 reads of the stored tsdf around the cell per
+//              point, through the caches; neighbouring lanes share most of them.
 #pragma clang fp contract(off)
 
 constexpr int TSDF_BLOCK = 256;
@@ -241,6 +243,111 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_cloud_emit_kernel(const float
     }
 }
 
+// ---- zero-crossing points with normals (UniformTSDFVolume::GetNormalAt, restated in include/giga_hip.h) ----
+// s = q / voxel - 0.5 along one axis, split into the cell index and the weight of the cell after it
+struct TriAxis { int i; double r; };
+__device__ __forceinline__ TriAxis tri_axis(double q, double voxel) {
+    const double s = q / voxel - 0.5, f = floor(s);
+    return TriAxis{(int)f, s - f};
+}
+
+// trilinear value of the stored tsdf (the weight is not consulted); a voxel outside the volume counts 0.0
+__device__ __forceinline__ double tsdf_trilinear(const float* __restrict__ tsdf, unsigned R, TriAxis x, TriAxis y, TriAxis z) {
+    const double wx[2] = {1.0 - x.r, x.r}, wy[2] = {1.0 - y.r, y.r}, wz[2] = {1.0 - z.r, z.r};
+    double acc = 0.0;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+        const int dx = d >> 2, dy = d >> 1 & 1, dz = d & 1;
+        const unsigned ix = (unsigned)(x.i + dx), iy = (unsigned)(y.i + dy), iz = (unsigned)(z.i + dz);
+        const bool inside = ix < R && iy < R && iz < R;                       // (a negative index wraps to a large one)
+        const double f = inside ? (double)tsdf[((size_t)ix * R + iy) * R + iz] : 0.0;
+        const double term = ((wx[dx] * wy[dy]) * wz[dz]) * f;
+        acc = d == 0 ? term : acc + term;
+    }
+    return acc;
+}
+
+// the normal at the float64 point p: central differences of the trilinear value at -g and +g along every axis
+__device__ __forceinline__ void tsdf_normal(const float* __restrict__ vol, unsigned R, double voxel, const double* p, float* nv) {
+    const double g = 0.99 * voxel;
+    TriAxis mid[3], lo[3], hi[3];                                             // the three axes at p, and each of them moved by -g and +g
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        mid[q] = tri_axis(p[q], voxel);
+        lo[q] = tri_axis(p[q] - g, voxel);
+        hi[q] = tri_axis(p[q] + g, voxel);
+    }
+    const double n0 = tsdf_trilinear(vol, R, hi[0], mid[1], mid[2]) - tsdf_trilinear(vol, R, lo[0], mid[1], mid[2]);
+    const double n1 = tsdf_trilinear(vol, R, mid[0], hi[1], mid[2]) - tsdf_trilinear(vol, R, mid[0], lo[1], mid[2]);
+    const double n2 = tsdf_trilinear(vol, R, mid[0], mid[1], hi[2]) - tsdf_trilinear(vol, R, mid[0], mid[1], lo[2]);
+    const double zz = (n0 * n0 + n1 * n1) + n2 * n2;
+    if (zz > 0.0) {
+        const double len = sqrt(zz);
+        nv[0] = (float)(n0 / len); nv[1] = (float)(n1 / len); nv[2] = (float)(n2 / len);
+    } else {
+        nv[0] = nv[1] = nv[2] = 0.f;
+    }
+}
+
+// The emit kernel's points, bit for bit -- one lane per cell, the same prefix and the same positions -- and the normal of each.
+// A crossing is rare (one cell in a hundred of a fused scene) and a normal is long (48 reads, a dozen float64 divisions), so the
+// lanes that hold one would drag their whole wave through the normal for one or two of 64 lanes.  Instead a lane leaves every
+// crossing in LDS, at its position inside the workgroup (cell | axis << 30, and the crossing's coordinate in float64), and after
+// a barrier the workgroup's first `tot` lanes take one crossing each: dense waves.  Measured in DESIGN section 3w.
+constexpr unsigned CLOUD_QUEUE = 3 * TSDF_BLOCK;   // a workgroup's crossings at most
+static_assert((unsigned long long)GIGA_TSDF_MAX_R * GIGA_TSDF_MAX_R * GIGA_TSDF_MAX_R <= 1ull << 30, "a cell index and an axis share a word");
+
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_cloud_emit_oriented_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight,
+                                                                              unsigned R, unsigned cells, unsigned nblk, double voxel,
+                                                                              const unsigned* __restrict__ blk,
+                                                                              const unsigned long long* __restrict__ bases, int B,
+                                                                              float* __restrict__ points, float* __restrict__ normals,
+                                                                              unsigned long long cap, int* __restrict__ shortfall) {
+    __shared__ unsigned wsum[TSDF_WAVES];
+    __shared__ unsigned q_cell[CLOUD_QUEUE];
+    __shared__ double q_at[CLOUD_QUEUE];
+    const unsigned cell = blockIdx.x * TSDF_BLOCK + threadIdx.x, scene = blockIdx.y;
+    if (shortfall && blockIdx.x == 0 && scene == 0 && threadIdx.x == 0) shortfall[0] = scan_shortfall(bases[B], cap);
+    const size_t base = (size_t)scene * cells;
+    CloudRead c;
+    c.flags = 0;
+    if (cell < cells) c = cloud_read(tsdf + base, weight + base, R, cell);
+    unsigned tot;
+    unsigned pre = cloud_prefix(c.flags, wsum, tot);
+    if (tot == 0) return;                                                     // (the whole workgroup)
+    const unsigned long long first = bases[scene] + blk[(size_t)scene * nblk + blockIdx.x];
+    if (c.flags) {
+        const double p0[3] = {((double)c.x + 0.5) * voxel, ((double)c.y + 0.5) * voxel, ((double)c.z + 0.5) * voxel};
+        const double a0 = fabs((double)c.f0);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            if (!(c.flags >> i & 1)) continue;
+            const double a1 = fabs((double)c.f1[i]);
+            const double r = (p0[i] * a1 + (p0[i] + voxel) * a0) / (a0 + a1);
+            q_cell[pre] = cell | (unsigned)i << 30;
+            q_at[pre] = r;
+            if (first + pre < cap) {
+                float* o = points + 3 * (first + pre);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) o[q] = (float)p0[q];
+                o[i] = (float)r;
+            }
+            ++pre;
+        }
+    }
+    __syncthreads();
+    const float* __restrict__ vol = tsdf + base;
+    for (unsigned t = threadIdx.x; t < tot; t += TSDF_BLOCK) {
+        if (first + t >= cap) break;
+        const unsigned at = q_cell[t] & 0x3fffffffu, axis = q_cell[t] >> 30;
+        const unsigned z = at % R, xy = at / R, y = xy % R, x = xy / R;
+        double p[3] = {((double)x + 0.5) * voxel, ((double)y + 0.5) * voxel, ((double)z + 0.5) * voxel};
+        const double r = q_at[t];
+        if (axis == 0) p[0] = r; else if (axis == 1) p[1] = r; else p[2] = r;
+        tsdf_normal(vol, R, voxel, p, normals + 3 * (first + t));
+    }
+}
+
 struct CloudWs { size_t blk, bases, total; unsigned cells, nblk; };
 static CloudWs cloud_workspace(int B, int R) {
     WsLayout L;
@@ -348,6 +455,22 @@ int giga_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, d
     GIGA_LAUNCH(tsdf_cloud_emit_kernel, dim3(w.nblk, B), dim3(TSDF_BLOCK), 0, static_cast<hipStream_t>(stream), tsdf, weight, (unsigned)R,
                 w.cells, w.nblk, length / (double)R, reinterpret_cast<const unsigned*>(ws + w.blk),
                 reinterpret_cast<const unsigned long long*>(ws + w.bases), B, points, (unsigned long long)cap, shortfall);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int giga_tsdf_cloud_emit_oriented(const float* tsdf, const float* weight, int B, int R, double length, const void* workspace,
+                                  size_t workspace_bytes, float* points, float* normals, size_t cap, int32_t* shortfall, void* stream) {
+    if (const int rc = tsdf_volume_check(B, R)) return rc;
+    if (!finite_f64(length) || !(length > 0.0)) return -1;
+    if (B == 0) return 0;
+    if (!tsdf || !weight || !workspace) return -1;
+    if (cap > 0 && (!points || !normals)) return -6;
+    if (workspace_bytes < giga_tsdf_cloud_workspace_bytes(B, R)) return -4;
+    const uint8_t* ws = static_cast<const uint8_t*>(workspace);
+    const CloudWs w = cloud_workspace(B, R);
+    GIGA_LAUNCH(tsdf_cloud_emit_oriented_kernel, dim3(w.nblk, B), dim3(TSDF_BLOCK), 0, static_cast<hipStream_t>(stream), tsdf, weight,
+                (unsigned)R, w.cells, w.nblk, length / (double)R, reinterpret_cast<const unsigned*>(ws + w.blk),
+                reinterpret_cast<const unsigned long long*>(ws + w.bases), B, points, normals, (unsigned long long)cap, shortfall);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 

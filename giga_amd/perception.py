@@ -168,19 +168,26 @@ def integrate_batch(tsdf, weight, depth, view_offsets, intrinsic, extrinsics, si
                DEPTH_TRUNC, tsdf, weight, grid, ws, ws.numel())
 
 
-def cloud_batch(tsdf, weight, size, capacity=None):
+def cloud_batch(tsdf, weight, size, capacity=None, normals=False):
     """Zero-crossing points of B volumes: ((n, 3) float32 device tensor, scenes back to back; B + 1 host offsets).  With
-    `capacity` the points beyond it are dropped (the offsets still count all of them)."""
+    `capacity` the points beyond it are dropped (the offsets still count all of them).  normals=True: (points, normals, offsets),
+    the normals an (n, 3) float32 device tensor, one per point (`giga_tsdf_cloud_emit_oriented`; the points are the same bytes)."""
     dev = _capi.device_of(tsdf, weight)
     B, R = tsdf.shape[0], tsdf.shape[-1]
     if B == 0:
-        return torch.empty((0, 3), device=dev), np.zeros(1, np.int64)
+        empty = torch.empty((0, 3), device=dev)
+        return (empty, torch.empty((0, 3), device=dev), np.zeros(1, np.int64)) if normals else (empty, np.zeros(1, np.int64))
     ws = _capi.workspace("giga_tsdf_cloud", dev, B, R)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
     _capi.call("giga_tsdf_cloud_count", dev, tsdf, weight, B, R, ws, ws.numel(), counts)
     offsets = np.concatenate(([0], np.cumsum(counts.cpu().numpy().astype(np.int64))))
     cap = int(offsets[-1]) if capacity is None else min(int(capacity), int(offsets[-1]))
     points = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+    if normals:
+        nrm = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+        _capi.call("giga_tsdf_cloud_emit_oriented", dev, tsdf, weight, B, R, float(size), ws, ws.numel(), points if cap else None,
+                   nrm if cap else None, cap, None)
+        return points, nrm, offsets
     _capi.call("giga_tsdf_cloud_emit", dev, tsdf, weight, B, R, float(size), ws, ws.numel(), points if cap else None, cap, None)
     return points, offsets
 
@@ -221,9 +228,11 @@ class TSDFVolume(object):
         """(tsdf, weight): the (1, R, R, R) float32 device tensors the volume integrates into."""
         return self._tsdf, self._weight
 
-    def get_cloud(self):
-        """(n, 3) float32 device tensor: the zero crossings of extract_point_cloud (points only)."""
-        return cloud_batch(self._tsdf, self._weight, self.size)[0]
+    def get_cloud(self, normals=False):
+        """(n, 3) float32 device tensor: the zero crossings of extract_point_cloud.  normals=True: (points, normals), the
+        normals of extract_point_cloud as a second (n, 3) float32 device tensor."""
+        out = cloud_batch(self._tsdf, self._weight, self.size, normals=normals)
+        return out[:2] if normals else out[0]
 
 
 def create_tsdf(size, resolution, depth_imgs, intrinsic, extrinsics, device=None):

@@ -15,7 +15,8 @@ Not reproduced:
   * `remove_and_wait`, the settling after each kept object: objects stay 2 mm above the table, and an unstable object does not
     topple;
   * inertial-frame offsets of URDFs: the pose is that of the mesh's own origin;
-  * pile scenes (`generate_pile_scene` needs rigid-body dynamics) and grasp labels;
+  * pile scenes (`generate_pile_scene` needs rigid-body dynamics) and the execution of a grasp: `write_geo_dataset` writes grasp
+    labels only for the outcomes of an executor that the caller brings (`giga_amd.candidates` makes the candidates);
   * the extent of the reference's `plane.urdf` (the file is not part of this project): `table_mesh` takes an `extent`;
   * agreement with PyBullet itself is unverified.
 The random stream is this module's own (`np.random.default_rng([seed, scene])`), so a scene depends on (seed, scene) alone."""
@@ -152,7 +153,8 @@ def write_mesh_pose_list(raw_root, sid, mesh_pose_list):
 
 
 def write_geo_dataset(object_set, raw_root, dataset_root, n_scenes, seed=0, first_scene=0, batch=32, n_views=6, num_point_per_file=2048,
-                      num_file=4, size=0.3, table_extent=0.6, device=None, collide=None):
+                      num_file=4, size=0.3, table_extent=0.6, device=None, collide=None, execute=None, grasps_per_scene=120,
+                      num_rotations=6):
     """From object meshes to the files `python -m giga_amd.train_geo` and `python -m giga_amd.eval_geometry` read, without leaving
     the package.  For the packed scenes first_scene .. first_scene + n_scenes - 1 of `seed` (a scene in which nothing was kept is
     left out) it writes
@@ -168,7 +170,16 @@ def write_geo_dataset(object_set, raw_root, dataset_root, n_scenes, seed=0, firs
                                              label 0.
     The placeholder exists because the data sets of `giga_amd.dataset` and `giga_amd.geometry` take their scene list from that
     file.  Such a set feeds `train_geo` and `eval_geometry` WITHOUT `--ROI` only: it holds no grasp labels.
-    Returns the scene ids that were written."""
+    Returns the scene ids that were written.
+
+    execute: a grasp executor (physics: a simulator or a robot; none is part of this package),
+        execute(scene_number, pos (K, 3), quat (K, Y, 4) xyzw, max_opening_width) -> (outcomes (K, Y), widths (K, Y)), numpy.
+    With one, grasps.csv holds `grasps_per_scene` labelled rows per scene in place of the placeholder, made the way
+    scripts/generate_data_parallel.py makes them (`giga_amd.candidates`): six views drawn by `candidates.scene_views(seed, scene)`
+    are rendered and fused at resolution 120, the oriented cloud inside `candidates.workspace_bounds(size, TABLE_HEIGHT)` gives the
+    candidates with `num_rotations` yaw angles each, `execute` tries them and `candidates.reduce_outcomes` picks the row.  Every
+    other file is written as without an executor.  A scene without an eligible cloud point gets no row (the reference skips such a
+    scene), and the return value becomes (scene ids, ids of the scenes without rows)."""
     import torch
 
     from . import perception
@@ -193,9 +204,43 @@ def write_geo_dataset(object_set, raw_root, dataset_root, n_scenes, seed=0, firs
     setup.update({"finger_depth": FINGER_DEPTH, "max_opening_width": MAX_OPENING_WIDTH})
     with (raw_root / "setup.json").open("w") as fh:
         json.dump(setup, fh)
+    labelled = None
+    if execute is not None:
+        labelled = label_packed_scenes([s for s, _ in scenes], rendered, execute, seed=seed, size=size, batch=batch,
+                                       grasps_per_scene=grasps_per_scene, num_rotations=num_rotations, device=dev)
+    unlabelled = write_grasps_csv(raw_root, ids, labelled, size)
+    perception.construct_dataset(raw_root, dataset_root, batch=batch, device=dev)
+    return ids if labelled is None else (ids, unlabelled)
+
+
+def write_grasps_csv(raw_root, ids, labelled=None, size=0.3):
+    """<raw_root>/grasps.csv.  labelled None: the placeholder row of `write_geo_dataset` for every scene.  Else one
+    `candidates.label_scenes` entry per scene: its rows, or none for an entry that is None; returns the ids of those scenes."""
+    from . import candidates
     with open(os.path.join(str(raw_root), "grasps.csv"), "w") as fh:
         fh.write("scene_id,qx,qy,qz,qw,x,y,z,width,label\n")
-        for sid in ids:
-            fh.write(",".join([sid] + [repr(float(x)) for x in (0.0, 0.0, 0.0, 1.0, 0.5 * size, 0.5 * size, 0.5 * size, 0.0)] + ["0"]) + "\n")
-    perception.construct_dataset(raw_root, dataset_root, batch=batch, device=dev)
-    return ids
+        for k, sid in enumerate(ids):
+            if labelled is None:
+                fh.write(",".join([sid] + [repr(float(x)) for x in (0.0, 0.0, 0.0, 1.0, 0.5 * size, 0.5 * size, 0.5 * size, 0.0)] + ["0"]) + "\n")
+            elif labelled[k] is not None:
+                fh.write("\n".join(candidates.grasp_rows(sid, labelled[k])) + "\n")
+    return [] if labelled is None else [sid for sid, rows in zip(ids, labelled) if rows is None]
+
+
+def label_packed_scenes(scene_numbers, meshes, execute, seed=0, size=0.3, batch=32, grasps_per_scene=120, num_rotations=6, device=None):
+    """`candidates.label_scenes` on scene meshes (objects plus table): per batch of scenes the six views of
+    `candidates.scene_views(seed, scene)` are rendered in one launch and fused at resolution 120 in another.  Returns one
+    `label_scenes` entry per scene."""
+    from . import candidates, perception
+    intrinsic = render.sim_intrinsic()
+    out = []
+    for at in range(0, len(meshes), int(batch)):
+        numbers = list(scene_numbers[at:at + int(batch)])
+        views = [candidates.scene_views(seed, s, size) for s in numbers]
+        depth, offs = render.render_depth_batch(meshes[at:at + int(batch)], intrinsic, views, device=device)
+        tsdf, weight, _ = perception.fuse_scenes(size, candidates.LABEL_RESOLUTION, [depth[offs[b]:offs[b + 1]] for b in range(len(numbers))],
+                                                 intrinsic, views, depth.device)
+        out += candidates.label_scenes(tsdf, weight, size, numbers, execute, table_height=TABLE_HEIGHT,
+                                       grasps_per_scene=grasps_per_scene, num_rotations=num_rotations, seed=seed,
+                                       finger_depth=FINGER_DEPTH, max_opening_width=MAX_OPENING_WIDTH)
+    return out

@@ -437,7 +437,24 @@ int giga_tsdf_scatter(const int32_t* voxel_index, const float* voxel_value, cons
  * the workspace (giga_tsdf_cloud_workspace_bytes(B, R)), which must reach emit unchanged together with the same state; emit
  * writes points [cap][3] float32, scenes back to back, in cell order and then axis order inside a scene.  Nothing is written at or
  * beyond cap; shortfall [1] int32 (device, may be NULL) receives the number of points that did not fit.
- * Errors: -1 as above or null state / workspace / counts; -4; -6 null points with cap > 0; -7. */
+ * Errors: -1 as above or null state / workspace / counts; -4; -6 null points with cap > 0; -7.
+ *
+ * giga_tsdf_cloud_emit_oriented (added within ABI 3): giga_tsdf_cloud_emit plus normals [cap][3] float32 (device), one per point.
+ * It reads the workspace that giga_tsdf_cloud_count filled and writes the same points in the same order (bit for bit), with the
+ * same cap / shortfall rule for both arrays; -6 also for null normals with cap > 0.  The normal of a point restates Open3D's
+ * UniformTSDFVolume::GetNormalAt (agreement with Open3D itself is unverified, as for the points).  All of it in float64, one
+ * rounding per operation, no fused multiply-add.  p is the point in float64 BEFORE it is rounded to float32 (p0 with component i
+ * replaced by the quotient above), v = voxel_length = length / R, g = 0.99 v.
+ *     T(q)   s_c = q_c / v - 0.5, i_c = floor(s_c), r_c = s_c - i_c for c = x, y, z.  With w_c(0) = 1 - r_c and w_c(1) = r_c, T is
+ *            the sum over (dx, dy, dz) in the order 000, 001, 010, 011, 100, 101, 110, 111 (dz fastest) of
+ *                ((w_x(dx) w_y(dy)) w_z(dz)) double(tsdf[i_x + dx][i_y + dy][i_z + dz]),
+ *            the first term taken as it is and the others added to it from left to right.  The weight array is NOT consulted: an
+ *            unobserved voxel contributes its stored value (0 in a volume that integrate built).  A voxel with an index outside
+ *            [0, R) on any axis contributes the value 0.0: this library's choice -- Open3D reads out of bounds there.
+ *     n_c    = T(p + g e_c) - T(p - g e_c), c = x, y, z (only component c of p changes: p_c + g, p_c - g)
+ *     z      = (n_x n_x + n_y n_y) + n_z n_z;  normal = n / sqrt(z) per component if z > 0, else (0, 0, 0) (Eigen's normalized());
+ *            every component is rounded once to float32.
+ * One lane per cell as in giga_tsdf_cloud_emit; 48 four-byte reads per normal. */
 #define GIGA_TSDF_MAX_R 512
 #define GIGA_TSDF_MAX_IMAGE 16384
 size_t giga_tsdf_integrate_workspace_bytes(int B, int n_views);
@@ -449,6 +466,8 @@ int giga_tsdf_cloud_count(const float* tsdf, const float* weight, int B, int R, 
                           int32_t* counts, void* stream);
 int giga_tsdf_cloud_emit(const float* tsdf, const float* weight, int B, int R, double length, const void* workspace,
                          size_t workspace_bytes, float* points, size_t cap, int32_t* shortfall, void* stream);
+int giga_tsdf_cloud_emit_oriented(const float* tsdf, const float* weight, int B, int R, double length, const void* workspace,
+                                  size_t workspace_bytes, float* points, float* normals, size_t cap, int32_t* shortfall, void* stream);
 
 /* ---- input side: depth images of posed triangle meshes (the depth half of btsim.Camera.render, src/vgn/utils/btsim.py:276-337,
  * which the reference hands to PyBullet) -----
@@ -973,6 +992,55 @@ int giga_roi_points(const double* grasps, const int32_t* point_offsets, const in
 size_t giga_occ_confusion_workspace_bytes(int B);
 int giga_occ_confusion(const float* logits, const uint8_t* pred, double logit_threshold, const uint8_t* target,
                        const int32_t* offsets, int B, uint64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- grasp candidates from the oriented cloud (scripts/generate_data_parallel.py:133-161: sample_grasp_point and the frame and yaw
+ * angles of evaluate_grasp_point; added within ABI 3) -----
+ * giga_grasp_candidates draws K candidates for each of B scenes.  points, normals [n][3] float32 (device) are what
+ * giga_tsdf_cloud_emit_oriented wrote, scenes back to back.  HOST arrays, validated before the first HIP call and copied into the
+ * workspace before the call returns: offsets [B + 1] int32 (start at 0, never decrease; n = offsets[B]), scene_ids [B] uint32,
+ * lower [3] and upper [3] float64, yaw_table [Y][2] float64 with row j = (sin(yaw_j / 2), cos(yaw_j / 2)), 1 <= Y <= 32: the caller
+ * computes it (the reference's angles are np.linspace(0, pi, Y)), so that no sine or cosine is evaluated on the device.
+ * Everything below is float64 with one rounding per operation and no fused multiply-add; P and N are a point and its normal widened
+ * to float64.
+ *
+ * Eligible points.  A point is eligible when lower_c <= P_c <= upper_c for c = x, y, z (both ends included, Open3D's crop),
+ * N_z > -0.1 (generate_data_parallel.py:141), d = (N_x N_x + N_y N_y) + N_z N_z > 0, and all six numbers are finite.  The eligible
+ * points of a scene are counted and listed in ascending point order by prefix sums, without atomics; counts [B] int32 (device)
+ * receives the number E_b.
+ *
+ * Draw of candidate k of scene b: one Philox-4x32-10 block with counter (k, scene_ids[b], 0, 0x47525350) and key
+ * (seed & 0xffffffff, seed >> 32).  e = (uint64(word 0) E_b) >> 32 picks the e-th eligible point; index [B][K] int32 (device)
+ * receives its index inside the scene.  u = words (2, 3) as 53 bits in (0, 1): ((w2 >> 5) << 26 | w3 >> 6) 2^-53, 2^-54 in place
+ * of 0.  lo = -(eps finger_depth), hi = (1 + eps) finger_depth, depth = lo + (hi - lo) u, pos [B][K][3] float64 (device) =
+ * P + N depth per component.  The reference redraws until N_z > -0.1; a uniform draw over the eligible points has the same
+ * distribution and always ends.  A scene with E_b = 0 gets counts[b] = 0 and its rows of pos, quat and index are left as they were.
+ * A candidate depends on (seed, scene id, k) and on the scene's own cloud alone, not on the batch or the launch.
+ *
+ * Frame (generate_data_parallel.py:149-155).  z = (-N) / sqrt(d) per component.  x = (1, 0, 0); if
+ * | |x . z| - 1 | <= 1e-8 + 1e-4 (np.isclose(.., 1.0, 1e-4); x . z = (x_0 z_0 + x_1 z_1) + x_2 z_2), x = (0, 1, 0).  y = z cross x,
+ * then x = y cross z, a cross b = (a_1 b_2 - a_2 b_1, a_2 b_0 - a_0 b_2, a_0 b_1 - a_1 b_0).  The reference hands the matrix with the
+ * columns (x, y, z) to scipy's Rotation.from_matrix although x and y are orthogonal but not of unit length; scipy (1.15.3) returns
+ * the rotation of the matrix with every column normalised, so x and y are each divided by sqrt((a_0 a_0 + a_1 a_1) + a_2 a_2) here
+ * and the grasp's z axis is -N / |N|.  With M[r][0] = x_r, M[r][1] = y_r, M[r][2] = z_r and t = (M00 + M11) + M22, the
+ * quaternion (xyzw) takes the branch of the first largest of (M00, M11, M22, t):
+ *     M00:  ((1 - t) + 2 M00,  M10 + M01,  M20 + M02,  M21 - M12)
+ *     M11:  (M01 + M10,  (1 - t) + 2 M11,  M21 + M12,  M02 - M20)
+ *     M22:  (M02 + M20,  M12 + M21,  (1 - t) + 2 M22,  M10 - M01)
+ *     t:    (M21 - M12,  M02 - M20,  M10 - M01,  1 + t)
+ * and is divided by sqrt(((q_0 q_0 + q_1 q_1) + q_2 q_2) + q_3 q_3).  Its sign is not canonicalised.
+ * Yaw j with (s, c) = yaw_table[j]:  quat [B][K][Y][4] float64 (device) =
+ *     (q_0 c + q_1 s,  q_1 c - q_0 s,  q_2 c + q_3 s,  q_3 c - q_2 s)          the product q (0, 0, s, c).
+ *
+ * One workgroup per scene; caller-owned buffers, asynchronous on `stream`, equal input gives equal bytes.  workspace:
+ * giga_grasp_candidates_workspace_bytes(B, offsets[B], Y).  Errors: -1 negative B or K, Y outside 1 .. 32, a bound, finger_depth,
+ * eps or table entry that is not finite, offsets that do not start at 0 or decrease, null host array, null points or normals with
+ * n > 0, null workspace; -4 workspace too small; -6 null output; -7 B > GIGA_MAX_SCENES.  B = 0 or K = 0 returns 0. */
+#define GIGA_CANDIDATES_MAX_ROTATIONS 32
+size_t giga_grasp_candidates_workspace_bytes(int B, int n_points, int n_rotations);
+int giga_grasp_candidates(const float* points, const float* normals, const int32_t* offsets, const uint32_t* scene_ids, int B, int K,
+                          const double* lower, const double* upper, double finger_depth, double eps, const double* yaw_table,
+                          int n_rotations, uint64_t seed, double* pos, double* quat, int32_t* index, int32_t* counts, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 /* ---- output side: grasp affordance of a scene mesh (src/vgn/utils/visual.py:22-98, affordance_visual; added within ABI 3) -----
  * Colours every face of B scene meshes by the grasp quality predicted near it.  qual [B][R^3] float32 is the volume after process
